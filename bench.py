@@ -2,6 +2,7 @@
 """bench.py — graphs/sec, forward + loss + backward, of the MI355X DiffPool path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dd|enzymes|er] [--linkpred] [--no-graph]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): graphs/sec fwd+bwd on a DD-shaped padded batch (B=20 per GPU, N_max=500, F=89,
 H=E=20, K=50, 3 GCN layers, 1 pooling level, C=2; synthetic seeded data, reference-style init).
@@ -12,7 +13,12 @@ For N > 1 the driver launches this file under torch.distributed.run, one rank pe
 sharded by graph (weak scaling: 20 graphs per GPU), and the only collective is one all-reduce of the
 flat gradient buffer per step.
 
-Rank 0 prints ONE JSON line with the driver's fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the driver's fields: metric,
+value, unit, higher_is_better, dtype, ms_per_step, ...  --dump-outputs DIR then also writes what the last timed step
+handed its caller (ypred, loss, every parameter's gradient, the level-0 assignment; predict()'s classes with --eval)
+as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
+
+--full adds, after the timed steps, the measurements that take runs of their own (single GPU, training step):
   "roofline":     the step's dominant kernel: for the DD-shaped workload the persistent level-0 backward kernel
                   (k_level0_bwd; its forward twin under "roofline_fwd", the stand-alone aggregation kernel the other
                   plans use under "roofline_aggregate"), for ER the MFMA-bound pooling product.  Algorithmic bytes
@@ -362,6 +368,33 @@ def mfma_probe(w, device, iters=50):
     return r
 
 
+DUMP_LIMIT_BYTES = 64 << 20       # all of --dump-outputs together
+DUMP_SAMPLE_ELEMS = 1 << 20       # an output larger than this is written as a fixed, seeded strided sample
+
+
+def dump_outputs(out_dir, named):
+    """Write each (name, tensor) as out_dir/<name>.npy: floating outputs as float32, integer ones as float64.  A tensor
+    of more than DUMP_SAMPLE_ELEMS elements is written as `<name>.sample`: DUMP_SAMPLE_ELEMS elements of its flattened
+    form at a fixed stride from a seeded offset (the ER shape's level-0 assignment is 268 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(0)
+    arrays = []
+    for name, t in named:
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE_ELEMS:
+            stride = t.numel() // DUMP_SAMPLE_ELEMS
+            t = t.reshape(-1)[int(rng.integers(stride))::stride][:DUMP_SAMPLE_ELEMS]
+            name += ".sample"
+        a = t.cpu().numpy()
+        arrays.append((name, a.astype(np.float32 if a.dtype.kind == "f" else np.float64)))
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget")
+    for name, a in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -379,7 +412,14 @@ def main():
                          "train.py:30-58) instead of forward + loss + backward")
     ap.add_argument("--probe-only", action="store_true",
                     help="run only the roofline probe (used to profile the dominant kernel in isolation)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline probes and the CPU baseline (single GPU, "
+                         "training step)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -432,9 +472,12 @@ def main():
             print(f"[bench] gradient all-reduce {'inside' if graph_allreduce else 'outside'} the hipGraph",
                   file=sys.stderr)
 
+    outputs = {}        # what the latest fwd_bwd handed back (under a hipGraph: the tensors every replay rewrites)
+
     def fwd_bwd():
         if args.eval:
-            return model.predict(batch["x"], batch["adj"], batch["nn"], assign_x=batch["x"])
+            outputs["pred_class"] = model.predict(batch["x"], batch["adj"], batch["nn"], assign_x=batch["x"])
+            return outputs["pred_class"]
         model.zero_grad(set_to_none=True)
         ypred = model(batch["x"], batch["adj"], batch["nn"], assign_x=batch["x"])
         if args.linkpred:
@@ -444,6 +487,8 @@ def main():
         loss.backward()
         if graph_allreduce:
             dp.reduce_gradients()
+        # detached views: same storage, without the autograd history that would keep the step's save buffer alive
+        outputs["ypred"], outputs["loss"] = ypred.detach(), loss.detach()
         return loss
 
     # ---- optional hipGraph capture of the whole fwd+loss+bwd launch sequence
@@ -500,6 +545,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        named = list(outputs.items())
+        if getattr(model, "assign_tensor", None) is not None:
+            named.append(("assign_tensor", model.assign_tensor))
+        if not args.eval:
+            named += [("grad." + k, p.grad) for k, p in model.named_parameters() if p.grad is not None]
+        nbytes = dump_outputs(args.dump_outputs, named)
+        print(f"[bench] wrote {len(named)} outputs of the last timed step ({nbytes} bytes) to {args.dump_outputs}",
+              file=sys.stderr)
+
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = w["B"] * world * args.steps / dt
@@ -517,7 +572,7 @@ def main():
                        **({"allreduce_in_graph": bool(graph_allreduce and graph is not None),
                            "batchnorm": "sync" if args.sync_bn else "local"} if world > 1 else {})},
         }
-        if world == 1 and not args.eval:
+        if args.full and world == 1 and not args.eval:
             if w.get("roofline") == "mfma":
                 # the ER workload is the MFMA-bound one: its dominant kernel is the wide pooling product
                 out["roofline"] = mfma_probe(w, device)

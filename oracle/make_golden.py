@@ -26,9 +26,13 @@ import os
 import random
 import sys
 
-import numpy as np
-import torch
-import torch.nn as nn
+# the fixtures are written under MKL's COMPATIBLE code path, the one tests/_g1_oracle_worker.py runs the oracle under:
+# the G1 outputs are checked bit for bit, and MKL's float32 GEMM rounds differently on other code paths
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)

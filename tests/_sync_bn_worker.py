@@ -46,10 +46,25 @@ def main():
     dp = DataParallelEncoder(model, sync_bn=sync_bn)
     sl = slice(rank * Bl, (rank + 1) * Bl)
     xd, ad, nd, ld = x[sl].cuda(), adj[sl].cuda(), nn_[sl], label[sl].cuda()
-    ypred = dp(xd, ad, nd, assign_x=xd)
-    win_local = gpu_winners(model, 2)
-    loss = model.loss(ypred, ld, ad, nd) if linkpred else model.loss(ypred, ld)
-    loss.backward()
+
+    def step():
+        ypred = dp(xd, ad, nd, assign_x=xd)
+        win_local = gpu_winners(model, 2)
+        loss = model.loss(ypred, ld, ad, nd) if linkpred else model.loss(ypred, ld)
+        loss.backward()
+        torch.cuda.synchronize()
+        return ypred, win_local, loss
+
+    if sync_bn:                 # the BatchNorm exchange inside the step needs every rank at once
+        ypred, win_local, loss = step()
+    else:
+        # nothing crosses ranks before the gradient all-reduce, so the ranks take turns on the GPU they share: the
+        # persistent level-0 kernels of the DD shard shape need all their workgroups resident, which two processes
+        # launching at once on one device do not guarantee (each rank of a real run has a GPU of its own)
+        for turn in range(world):
+            if turn == rank:
+                ypred, win_local, loss = step()
+            dist.barrier()
     dp.reduce_gradients()
     torch.cuda.synchronize()
     if sync_bn:

@@ -1,11 +1,15 @@
 """Pin the CPU oracle (oracle/diffpool_oracle.py) against golden vectors produced by the
 reference's own classes (oracle/make_golden.py).  CPU only."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import diffpool_oracle as O
-from tests.conftest import load_golden
+from tests.conftest import ROOT, load_golden
 
 T = torch.from_numpy
 
@@ -24,22 +28,31 @@ def req(params):
 G1_CASES = [f"g1_graphconv_s{s}b{b}n{n}" for s in (0, 1) for b in (0, 1) for n in (1, 0)]
 
 
+@pytest.fixture(scope="module")
+def g1_oracle(tmp_path_factory):
+    """The oracle's forward / backward on every G1 case, from tests/_g1_oracle_worker.py in a child process under MKL's
+    COMPATIBLE code path (the fixtures' own: oracle/make_golden.py).  MKL fixes its float32 GEMM kernels by host CPU
+    when it initialises, so only a fresh process with the path pinned rounds like the fixtures on every x86-64 host."""
+    out = str(tmp_path_factory.mktemp("g1") / "oracle.npz")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_g1_oracle_worker.py"), out] + G1_CASES,
+                       env=dict(os.environ, MKL_CBWR="COMPATIBLE"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
+    z = np.load(out, allow_pickle=False)
+    return {k: z[k] for k in z.files}
+
+
 @pytest.mark.parametrize("name", G1_CASES)
-def test_g1_graphconv_reference_text(name):
+def test_g1_graphconv_reference_text(name, g1_oracle):
     """A1 pinned by the reference's own (commented-out) GraphConv text, encoders.py:944-974 — see make_golden.py P2."""
     a, p, g = load_golden(name)
     add_self, bias, normalize = [bool(v) for v in a["cfg"]]
     assert bias == ("bias" in p)
-    x = T(a["x"]).requires_grad_(True)
-    adj = T(a["adj"]).requires_grad_(True)
-    P = req(p)
-    y = O.graph_conv(x, adj, P["weight"], P.get("bias"), add_self, normalize)
-    close(y, a["y"], 0, 0)               # same torch ops in the same order: bit-identical
-    (y * T(a["gy"])).sum().backward()
-    close(x.grad, a["gx"], 1e-6, 1e-7)
-    close(adj.grad, a["gadj"], 1e-6, 1e-7)
+    o = {k[len(name) + 2:]: v for k, v in g1_oracle.items() if k.startswith(name + "__")}
+    close(o["y"], a["y"], 0, 0)          # same torch ops in the same order: bit-identical
+    close(o["gx"], a["gx"], 1e-6, 1e-7)
+    close(o["gadj"], a["gadj"], 1e-6, 1e-7)
     for k in g:
-        close(P[k].grad, g[k], 1e-6, 1e-7)
+        close(o["grad." + k], g[k], 1e-6, 1e-7)
 
 
 def test_g2_apply_bn():
