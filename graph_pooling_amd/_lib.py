@@ -130,6 +130,11 @@ _PROTOS = {
     "dp_loss_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "dp_loss_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dp_loss_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    # packed-adjacency link-prediction loss
+    "dp_linkpred_loss_fwd_packed": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "dp_linkpred_loss_bwd_packed": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_loss_forward_packed": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_loss_backward_packed": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())

@@ -278,21 +278,24 @@ void pool_bwd_seq(Seq& q, const float* S, const float* Z, int ldz, const float* 
     }
 }
 
+// pk != null: the link loss reads the packed adjacency (bf16 rows of A in pk, of A^T in pkt) instead of adj, with the
+// same workspace carve-up, so the sizing below covers both
 void loss_fwd_seq(Seq& q, const float* ypred, const long long* label, const float* S, const float* adj,
                   const int* num_nodes, const float* norm, float* loss_out, float* prob, float* dunit, int B, int C,
-                  int N, int K, int linkpred);
+                  int N, int K, int linkpred, const unsigned short* pk = nullptr);
 void loss_bwd_seq(Seq& q, const float* prob, const long long* label, const float* S, const float* adj,
                   const int* num_nodes, const float* norm, const float* dloss, float* d_ypred, float* dS, int B, int C,
-                  int N, int K, int linkpred) {
+                  int N, int K, int linkpred, const unsigned short* pk = nullptr, const unsigned short* pkt = nullptr) {
     if (d_ypred) ce_bwd(q, prob, label, dloss, 1.f, d_ypred, B, C);
-    if (linkpred) linkpred_bwd(q, S, K, adj, num_nodes, dloss, dS, K, B, N, K, 0, norm);
+    if (linkpred && pk) linkpred_bwd_packed(q, S, K, pk, pkt, num_nodes, dloss, dS, K, B, N, K, 0, norm);
+    else if (linkpred) linkpred_bwd(q, S, K, adj, num_nodes, dloss, dS, K, B, N, K, 0, norm);
 }
 
 __global__ void k_add2(float* out, const float* a, const float* b) { out[0] = a[0] + b[0]; out[1] = b[0]; }
 
 void loss_fwd_seq(Seq& q, const float* ypred, const long long* label, const float* S, const float* adj,
                   const int* num_nodes, const float* norm, float* loss_out, float* prob, float* dunit, int B, int C,
-                  int N, int K, int linkpred) {
+                  int N, int K, int linkpred, const unsigned short* pk) {
     float* tmp = q.alloc<float>(64);
     if (q.err) return;
     if (!linkpred) {                       // loss_out = (CE, 0): one launch
@@ -301,7 +304,8 @@ void loss_fwd_seq(Seq& q, const float* ypred, const long long* label, const floa
     }
     ce_fwd(q, ypred, label, tmp, prob, B, C, nullptr, dunit);
     if (linkpred) {
-        linkpred_fwd(q, S, K, adj, num_nodes, tmp + 1, B, N, K, norm);
+        if (pk) linkpred_fwd_packed(q, S, K, pk, num_nodes, tmp + 1, B, N, K, norm);
+        else linkpred_fwd(q, S, K, adj, num_nodes, tmp + 1, B, N, K, norm);
         if (q.ok()) {
             hipLaunchKernelGGL(k_add2, dim3(1), dim3(1), 0, q.stream, loss_out, tmp, tmp + 1);
             q.check_launch("loss_add");
@@ -324,6 +328,7 @@ using namespace dp;
 #define STREAM(s) ((hipStream_t)(s))
 #define NONNEG(v) DP_CHECK_ARG((v) > 0, #v "=%d must be positive", (int)(v))
 #define NOTNULL(p) DP_CHECK_ARG((p) != nullptr, #p " is NULL")
+#define ALIGNED16(p) DP_CHECK_ARG(((uintptr_t)(p) & 15) == 0, #p " is not 16-byte aligned")
 
 extern "C" {
 
@@ -520,6 +525,26 @@ int dp_linkpred_loss_bwd(const float* S, const float* adj, const int* num_nodes,
     NONNEG(B); NONNEG(n); NONNEG(K);
     Seq q(STREAM(stream), workspace, workspace_bytes);
     linkpred_bwd(q, S, K, adj, num_nodes, dloss, dS, K, B, n, K, accumulate);
+    return q.err;
+}
+int dp_linkpred_loss_fwd_packed(const float* S, const void* adj_pk, const int* num_nodes, float* loss_out, int B,
+                                int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(adj_pk); NOTNULL(loss_out);
+    NONNEG(B); NONNEG(n); NONNEG(K);
+    ALIGNED16(adj_pk);
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    linkpred_fwd_packed(q, S, K, static_cast<const unsigned short*>(adj_pk), num_nodes, loss_out, B, n, K);
+    return q.err;
+}
+int dp_linkpred_loss_bwd_packed(const float* S, const void* adj_pk, const void* adj_pkt, const int* num_nodes,
+                                const float* dloss, float* dS, int accumulate, int B, int n, int K, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(adj_pk); NOTNULL(adj_pkt); NOTNULL(dS);
+    NONNEG(B); NONNEG(n); NONNEG(K);
+    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    linkpred_bwd_packed(q, S, K, static_cast<const unsigned short*>(adj_pk),
+                        static_cast<const unsigned short*>(adj_pkt), num_nodes, dloss, dS, K, B, n, K, accumulate);
     return q.err;
 }
 
@@ -790,6 +815,35 @@ int dp_loss_backward(const float* prob, const long long* label, const float* S, 
     DEVICE_GATE("dp_loss_backward");
     Seq q(STREAM(stream), workspace, workspace_bytes);
     loss_bwd_seq(q, prob, label, S, adj, num_nodes, link_norm, dloss, d_ypred, dS, B, C, N, K, linkpred);
+    return q.err;
+}
+int dp_loss_forward_packed(const float* ypred, const long long* label, const float* S, const void* adj_pk,
+                           const void* adj_pkt, const int* num_nodes, const float* link_norm, float* loss_out,
+                           float* prob, float* d_ypred_unit, int B, int C, int N, int K, int linkpred, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    NOTNULL(ypred); NOTNULL(label); NOTNULL(loss_out); NOTNULL(prob);
+    NONNEG(B); NONNEG(C);
+    DP_CHECK_ARG(!linkpred || (S && adj_pk && adj_pkt && N > 0 && K > 0), "linkpred needs S, adj_pk, adj_pkt, N, K");
+    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
+    DEVICE_GATE("dp_loss_forward_packed");
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    loss_fwd_seq(q, ypred, label, S, nullptr, num_nodes, link_norm, loss_out, prob, d_ypred_unit, B, C, N, K, linkpred,
+                 static_cast<const unsigned short*>(adj_pk));
+    return q.err;
+}
+int dp_loss_backward_packed(const float* prob, const long long* label, const float* S, const void* adj_pk,
+                            const void* adj_pkt, const int* num_nodes, const float* link_norm, const float* dloss,
+                            float* d_ypred, float* dS, int B, int C, int N, int K, int linkpred, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    NOTNULL(prob); NOTNULL(label);
+    NONNEG(B); NONNEG(C);
+    DP_CHECK_ARG(!linkpred || (S && adj_pk && adj_pkt && dS && N > 0 && K > 0),
+                 "linkpred needs S, adj_pk, adj_pkt, dS, N, K");
+    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
+    DEVICE_GATE("dp_loss_backward_packed");
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    loss_bwd_seq(q, prob, label, S, nullptr, num_nodes, link_norm, dloss, d_ypred, dS, B, C, N, K, linkpred,
+                 static_cast<const unsigned short*>(adj_pk), static_cast<const unsigned short*>(adj_pkt));
     return q.err;
 }
 

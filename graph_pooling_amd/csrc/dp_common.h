@@ -584,5 +584,11 @@ void linkpred_fwd(Seq& q, const float* S, int lds, const float* adj, const int* 
                   int B, int n, int K, const float* norm = nullptr /*device scalar replacing sum n_b^2*/);
 void linkpred_bwd(Seq& q, const float* S, int lds, const float* adj, const int* num_nodes, const float* dloss,
                   float* dS, int ldds, int B, int n, int K, int accumulate, const float* norm = nullptr);
+// the same on the packed adjacency (bf16 rows [B, n, adj_pack_ld(n)] of A and A^T, 16-byte aligned; pkt may be pk)
+void linkpred_fwd_packed(Seq& q, const float* S, int lds, const unsigned short* pk, const int* num_nodes,
+                         float* loss_out, int B, int n, int K, const float* norm = nullptr);
+void linkpred_bwd_packed(Seq& q, const float* S, int lds, const unsigned short* pk, const unsigned short* pkt,
+                         const int* num_nodes, const float* dloss, float* dS, int ldds, int B, int n, int K,
+                         int accumulate, const float* norm = nullptr);
 
 }  // namespace dp

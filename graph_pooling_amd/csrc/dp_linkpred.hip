@@ -10,6 +10,9 @@
 //   backward: one workgroup per 64-row block of dS walks the column tiles, RECOMPUTES each P tile, forms
 //             E = dl/dP(r,c) + dl/dP(c,r) (the A^T tile comes through LDS so both reads are coalesced) and
 //             accumulates dS_r += E S_c on the MFMA — dS = (D + D^T) S without ever storing D.
+// Both kernels are written once over an adjacency reader: the dense fp32 batch, or the packed bf16 rows of A and A^T
+// that dp_adj_pack / dp_build_batch_packed write (the captured training step holds nothing else).  The tile walk is
+// the same for both, so on a bf16-exact (0/1) adjacency the two give bit-identical loss and dS.
 #include "dp_common.h"
 
 namespace dp {
@@ -71,9 +74,135 @@ __device__ __forceinline__ void lk_ptile(const float* Sr, const float* Sc, int K
     }
 }
 
+// ------------------------------------------------------------------ adjacency readers
+// graph(b, n) is the reader of graph b; get() returns the raw element (clamped indices only) and value() decodes it at
+// its use, so the wait for a load sits where the value is needed.  The backward's tiles at column offset c0 of row
+// block r0 (CW columns):
+//   rows : A[r0 + i][c0 + j], fetched into registers and put into the LDS image Ar [64][CW + 4] (as fp32);
+//   cols : A[c0 + j][r0 + i]; put_cols() keeps the fetched tile (an LDS image, or the lane's own registers, since the
+//          next tile's fetch overwrites `at`) and col_value() returns the value at MFMA fragment position (ri, cj).
+struct LkAdjF32 {                     // dense fp32 adj [B, n, n]
+    typedef float Raw;
+    typedef float RowReg;
+    const float* a;
+    int ld;                           // row stride: n (set by graph())
+    static constexpr bool kColLds = true;                  // A^T tile: column reads transposed through LDS [CW][65]
+    template <int CW> static constexpr int row_regs() { return CW / 4; }
+    __device__ __forceinline__ static float value(Raw v) { return v; }
+    __device__ __forceinline__ LkAdjF32 graph(int b, int n) const { return LkAdjF32{a + (long)b * n * n, n}; }
+    __device__ __forceinline__ Raw get(int row, int col) const { return a[(long)row * ld + col]; }
+    template <int CW>
+    __device__ __forceinline__ void fetch_rows(RowReg* ar, int n, int r0, int c0) const {
+#pragma unroll
+        for (int m = 0; m < CW / 4; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            ar[m] = get(min(r0 + e / CW, n - 1), min(c0 + e % CW, n - 1));
+        }
+    }
+    template <int CW, int SA>
+    __device__ __forceinline__ static void put_rows(const RowReg* ar, float* Ar) {
+#pragma unroll
+        for (int m = 0; m < CW / 4; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            Ar[(e / CW) * SA + e % CW] = ar[m];
+        }
+    }
+    template <int CW, int NJ>
+    __device__ __forceinline__ void fetch_cols(Raw* at, int n, int r0, int c0, int, int, int, int) const {
+#pragma unroll
+        for (int m = 0; m < CW / 4; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            at[m] = get(min(c0 + (e >> 6), n - 1), min(r0 + (e & 63), n - 1));
+        }
+    }
+    template <int CW>
+    __device__ __forceinline__ static void put_cols(const Raw* at, float* At, Raw*) {
+#pragma unroll
+        for (int m = 0; m < CW / 4; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            At[(e >> 6) * 65 + (e & 63)] = at[m];
+        }
+    }
+    template <int NJ>
+    __device__ __forceinline__ static float col_value(const float* At, const Raw*, int, int, int, int ri, int cj) {
+        return At[cj * 65 + ri];
+    }
+};
+
+struct LkAdjBf16 {                    // packed: bf16 rows pk [B, n, ld] of A, pkt of A^T (pk == pkt: symmetric)
+    typedef unsigned Raw;             // one bf16 in the low half
+    typedef uint4 RowReg;             // 8 bf16 of one row
+    const unsigned short* pk;
+    const unsigned short* pkt;
+    int ld;                           // adj_pack_ld(n): a multiple of 8, so every 8-column chunk is 16-byte aligned
+    static constexpr bool kColLds = false;                 // A^T comes row-wise from pkt: no transposing LDS image
+    template <int CW> static constexpr int row_regs() { return CW / 32; }
+    __device__ __forceinline__ static float value(Raw v) { return __uint_as_float(v << 16); }   // exact
+    __device__ __forceinline__ LkAdjBf16 graph(int b, int n) const {
+        return LkAdjBf16{pk + (long)b * n * ld, pkt + (long)b * n * ld, ld};
+    }
+    __device__ __forceinline__ Raw get(int row, int col) const { return pk[(long)row * ld + col]; }
+    // 16-byte loads: chunk q = 8 columns; a chunk past the padded row is clamped to the row's last one — its columns
+    // are >= n, so (like the fp32 reader's clamped columns) they only ever meet the nb mask
+    template <int CW>
+    __device__ __forceinline__ void fetch_rows(RowReg* ar, int n, int r0, int c0) const {
+        constexpr int QR = CW / 8;
+#pragma unroll
+        for (int m = 0; m < CW / 32; ++m) {
+            const int q = threadIdx.x + 256 * m;
+            const int row = min(r0 + q / QR, n - 1), col = min(c0 + (q % QR) * 8, ld - 8);
+            ar[m] = *reinterpret_cast<const uint4*>(pk + (long)row * ld + col);
+        }
+    }
+    template <int CW, int SA>
+    __device__ __forceinline__ static void put_rows(const RowReg* ar, float* Ar) {
+        constexpr int QR = CW / 8;
+#pragma unroll
+        for (int m = 0; m < CW / 32; ++m) {
+            const int q = threadIdx.x + 256 * m;
+            float* d = Ar + (q / QR) * SA + (q % QR) * 8;
+            const unsigned w[4] = {ar[m].x, ar[m].y, ar[m].z, ar[m].w};
+            float v[8];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                v[2 * t] = __uint_as_float(w[t] << 16);
+                v[2 * t + 1] = __uint_as_float(w[t] & 0xffff0000u);
+            }
+            *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+            *reinterpret_cast<float4*>(d + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
+    }
+    // A[c0 + cj][r0 + ri] = A^T[r0 + ri][c0 + cj]: each lane loads its own fragment positions from pkt rows
+    // r0..r0+63 (16 lanes read 32 contiguous bytes of a row)
+    template <int CW, int NJ>
+    __device__ __forceinline__ void fetch_cols(Raw* at, int n, int r0, int c0, int wr, int wc, int l15, int kq) const {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = min(r0 + wr * 32 + i * 16 + kq * 4 + r, n - 1);
+                    const int col = min(c0 + wc * 16 * NJ + j * 16 + l15, n - 1);
+                    at[(i * NJ + j) * 4 + r] = pkt[(long)row * ld + col];
+                }
+    }
+    template <int CW>
+    __device__ __forceinline__ static void put_cols(const Raw* at, float*, Raw* cur) {
+#pragma unroll
+        for (int m = 0; m < CW / 4; ++m) cur[m] = at[m];
+    }
+    template <int NJ>
+    __device__ __forceinline__ static float col_value(const float*, const Raw* cur, int i, int j, int r, int, int) {
+        return value(cur[(i * NJ + j) * 4 + r]);
+    }
+};
+
 // ------------------------------------------------------------------ forward
-template <int KT>
-__global__ __launch_bounds__(256) void k_link_fwd(const float* S, int lds_ld, const float* adj, const int* num_nodes,
+// The A values of a lane sit at its MFMA fragment positions (one column per lane per row), so they are read one
+// element per load: 2 bytes each for the packed reader, 16 lanes covering 32 contiguous bytes of a row.
+template <int KT, class Adj>
+__global__ __launch_bounds__(256) void k_link_fwd(const float* S, int lds_ld, Adj adj, const int* num_nodes,
                                                   int n, int K, int tiles, float* partial) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int KP = KT * 16 + 2;
@@ -88,8 +217,8 @@ __global__ __launch_bounds__(256) void k_link_fwd(const float* S, int lds_ld, co
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, kq = lane >> 4;
     // the A values this thread needs, issued first (clamped addresses, no branches) so they fly under the staging
-    const float* Ab = adj + (long)b * n * n;
-    float av[2][2][4];
+    const Adj Ab = adj.graph(b, n);
+    typename Adj::Raw av[2][2][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -98,7 +227,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(const float* S, int lds_ld, co
             for (int r = 0; r < 4; ++r) {
                 const int row = min(r0 + wr * 32 + i * 16 + kq * 4 + r, n - 1);
                 const int c = min(c0 + wc * 32 + j * 16 + l15, n - 1);
-                av[i][j][r] = Ab[(long)row * n + c];
+                av[i][j][r] = Ab.get(row, c);
             }
     float* Sr = lds;
     float* Sc = lds + 64 * KP;
@@ -119,7 +248,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(const float* S, int lds_ld, co
             for (int r = 0; r < 4; ++r) {
                 const int row = r0 + wr * 32 + i * 16 + kq * 4 + r;
                 const float pv = fminf(acc[i][j][r], 1.f);
-                const float a = av[i][j][r];
+                const float a = Adj::value(av[i][j][r]);
                 const float l = -a * logf(pv + LINK_EPS) - (1.f - a) * logf(1.f - pv + LINK_EPS);
                 sum += (row < nb && c < nb) ? l : 0.f;
             }
@@ -160,8 +289,8 @@ __device__ inline float lk_dldp(float av, float raw) {
 
 // KT = ceil(K / 16) output column tiles per row block; the column tiles walked are CW = 32 NJ wide.
 // The next column tile's S rows and both A tiles are fetched into registers while the current one is computed on.
-template <int KT, int NJ>
-__global__ __launch_bounds__(256) void k_link_bwd(const float* S, int lds_ld, const float* adj, const int* num_nodes,
+template <int KT, int NJ, class Adj>
+__global__ __launch_bounds__(256) void k_link_bwd(const float* S, int lds_ld, Adj adj, const int* num_nodes,
                                                   const float* scale_ptr, float* dS, int ldds, int n, int K,
                                                   int accumulate, float* part, int split_tiles) {
     // part != null: blockIdx.z walks only `split_tiles` column tiles and stores its partial row block to
@@ -170,8 +299,7 @@ __global__ __launch_bounds__(256) void k_link_bwd(const float* S, int lds_ld, co
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int CW = 32 * NJ, KW = KT * 16, KP = KW + 2;
     constexpr int SA = CW + 4;      // E / A tile row stride: 4 SA = 16 mod 32, so (4 kq + r) rows x 16 cols spread over banks
-    constexpr int ST = 65;          // transposed A tile
-    constexpr int NS = CW * KW / 256, NA = CW / 4;
+    constexpr int NS = CW * KW / 256, NA = CW / 4, NR = Adj::template row_regs<CW>();
     const int b = blockIdx.y;
     const int r0 = blockIdx.x * 64;
     const int nb = num_nodes ? min(num_nodes[b], n) : n;
@@ -190,12 +318,14 @@ __global__ __launch_bounds__(256) void k_link_bwd(const float* S, int lds_ld, co
     float* Sr = lds;                 // [64][KP]
     float* Sc = Sr + 64 * KP;        // [CW][KP]
     float* Ar = Sc + CW * KP;        // [64][SA]   A[r0 + i][c0 + j], overwritten in place by E[i][j]
-    float* At = Ar + 64 * SA;        // [CW][ST]   A[c0 + j][r0 + i]
+    float* At = Ar + 64 * SA;        // [CW][65]   A[c0 + j][r0 + i]  (fp32 reader only)
     const float* Sb = S + (long)b * n * lds_ld;
-    const float* Ab = adj + (long)b * n * n;
+    const Adj Ab = adj.graph(b, n);
     const float scale = scale_ptr[0];
 
-    float sc[NS], ar[NA], at[NA];
+    float sc[NS];
+    typename Adj::RowReg ar[NR];
+    typename Adj::Raw at[NA], atc[NA];           // atc: the current tile's A^T values (packed reader only)
     auto fetch = [&](int c0) {
 #pragma unroll
         for (int m = 0; m < NS; ++m) {
@@ -203,12 +333,8 @@ __global__ __launch_bounds__(256) void k_link_bwd(const float* S, int lds_ld, co
             const int i = e / KW, k = e % KW;
             sc[m] = Sb[(long)min(c0 + i, n - 1) * lds_ld + min(k, K - 1)];    // raw: zeroed when it is written to LDS
         }
-#pragma unroll
-        for (int m = 0; m < NA; ++m) {
-            const int e = threadIdx.x + 256 * m;
-            ar[m] = Ab[(long)min(r0 + e / CW, n - 1) * n + min(c0 + e % CW, n - 1)];
-            at[m] = Ab[(long)min(c0 + (e >> 6), n - 1) * n + min(r0 + (e & 63), n - 1)];
-        }
+        Ab.template fetch_rows<CW>(ar, n, r0, c0);
+        Ab.template fetch_cols<CW, NJ>(at, n, r0, c0, wr, wc, l15, kq);
     };
     const int cbeg = part ? (int)blockIdx.z * split_tiles * CW : 0;
     const int cend = part ? min(nb, cbeg + split_tiles * CW) : nb;
@@ -220,19 +346,15 @@ __global__ __launch_bounds__(256) void k_link_bwd(const float* S, int lds_ld, co
     for (int t = 0; t < KT; ++t) out[t] = (lk_f32x4){0.f, 0.f, 0.f, 0.f};
 
     for (int c0 = cbeg; c0 < cend; c0 += CW) {
-        __syncthreads();                              // previous iteration's readers of Sc / Ar / At are done
+        __syncthreads();                              // previous iteration's readers of Sc / Ar (/ At) are done
 #pragma unroll
         for (int m = 0; m < NS; ++m) {
             const int e = threadIdx.x + 256 * m;
             const int i = e / KW, k = e % KW;
             Sc[i * KP + k] = (c0 + i < n && k < K) ? sc[m] : 0.f;
         }
-#pragma unroll
-        for (int m = 0; m < NA; ++m) {
-            const int e = threadIdx.x + 256 * m;
-            Ar[(e / CW) * SA + e % CW] = ar[m];
-            At[(e >> 6) * ST + (e & 63)] = at[m];
-        }
+        Adj::template put_rows<CW, SA>(ar, Ar);
+        Adj::template put_cols<CW>(at, At, atc);
         __syncthreads();
         if (c0 + CW < cend) fetch(c0 + CW);
         lk_f32x4 acc[2][NJ];
@@ -246,7 +368,8 @@ __global__ __launch_bounds__(256) void k_link_bwd(const float* S, int lds_ld, co
                 for (int r = 0; r < 4; ++r) {
                     const int ri = wr * 32 + i * 16 + kq * 4 + r;
                     const float raw = acc[i][j][r];
-                    const float e = scale * (lk_dldp(Ar[ri * SA + cj], raw) + lk_dldp(At[cj * ST + ri], raw));
+                    const float e = scale * (lk_dldp(Ar[ri * SA + cj], raw) +
+                                             lk_dldp(Adj::template col_value<NJ>(At, atc, i, j, r, ri, cj), raw));
                     Ar[ri * SA + cj] = (r0 + ri < nb && c0 + cj < nb) ? e : 0.f;
                 }
             }
@@ -306,19 +429,21 @@ static int lk_kt(int K) {
 
 // every instantiation is raised once per device to what it can ever need (static + dynamic LDS stay within 160 KiB)
 
-template <int KT>
-static void launch_link_fwd(Seq& q, const float* S, int lds_ld, const float* adj, const int* num_nodes, int B, int n,
-                            int K, int tiles, float* partial) {
+template <int KT, class Adj>
+static void launch_link_fwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num_nodes, int B, int n, int K,
+                            int tiles, float* partial) {
     constexpr size_t bytes = ((size_t)2 * 64 * (KT * 16 + 2) + 4) * sizeof(float);
     static DynLdsOnce attr;
-    if (bytes > 64 * 1024) ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_link_fwd<KT>), (int)bytes, "k_link_fwd");
+    if (bytes > 64 * 1024)
+        ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_link_fwd<KT, Adj>), (int)bytes, "k_link_fwd");
     if (!q.ok()) return;
-    hipLaunchKernelGGL((k_link_fwd<KT>), dim3(tiles * tiles, B), dim3(256), bytes, q.stream, S, lds_ld, adj, num_nodes,
-                       n, K, tiles, partial);
+    hipLaunchKernelGGL((k_link_fwd<KT, Adj>), dim3(tiles * tiles, B), dim3(256), bytes, q.stream, S, lds_ld, adj,
+                       num_nodes, n, K, tiles, partial);
 }
 
-void linkpred_fwd(Seq& q, const float* S, int lds_ld, const float* adj, const int* num_nodes, float* loss_out, int B,
-                  int n, int K, const float* norm) {
+template <class Adj>
+static void link_fwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num_nodes, float* loss_out, int B, int n,
+                     int K, const float* norm) {
     if (q.err) return;
     const int tiles = (n + 63) / 64;
     float* partial = q.alloc<float>((size_t)B * tiles * tiles);
@@ -339,23 +464,24 @@ void linkpred_fwd(Seq& q, const float* S, int lds_ld, const float* adj, const in
     q.check_launch("link_final");
 }
 
-template <int KT, int NJ>
-static void launch_link_bwd(Seq& q, const float* S, int lds_ld, const float* adj, const int* num_nodes,
-                            const float* scale, float* dS, int ldds, int B, int n, int K, int accumulate, float* part,
-                            int splits, int split_tiles) {
+template <int KT, int NJ, class Adj>
+static void launch_link_bwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num_nodes, const float* scale,
+                            float* dS, int ldds, int B, int n, int K, int accumulate, float* part, int splits,
+                            int split_tiles) {
     constexpr int CW = 32 * NJ, KP = KT * 16 + 2;
-    constexpr size_t bytes = ((size_t)(64 + CW) * KP + 64 * (CW + 4) + CW * 65) * sizeof(float);
+    constexpr size_t bytes = ((size_t)(64 + CW) * KP + 64 * (CW + 4) + (Adj::kColLds ? CW * 65 : 0)) * sizeof(float);
     static_assert(bytes <= 160 * 1024, "link_bwd LDS");
     static DynLdsOnce attr;
     if (bytes > 64 * 1024)
-        ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_link_bwd<KT, NJ>), (int)bytes, "k_link_bwd");
+        ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_link_bwd<KT, NJ, Adj>), (int)bytes, "k_link_bwd");
     if (!q.ok()) return;
-    hipLaunchKernelGGL((k_link_bwd<KT, NJ>), dim3((n + 63) / 64, B, part ? splits : 1), dim3(256), bytes, q.stream, S,
-                       lds_ld, adj, num_nodes, scale, dS, ldds, n, K, accumulate, part, split_tiles);
+    hipLaunchKernelGGL((k_link_bwd<KT, NJ, Adj>), dim3((n + 63) / 64, B, part ? splits : 1), dim3(256), bytes, q.stream,
+                       S, lds_ld, adj, num_nodes, scale, dS, ldds, n, K, accumulate, part, split_tiles);
 }
 
-void linkpred_bwd(Seq& q, const float* S, int lds_ld, const float* adj, const int* num_nodes, const float* dloss,
-                  float* dS, int ldds, int B, int n, int K, int accumulate, const float* norm) {
+template <class Adj>
+static void link_bwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num_nodes, const float* dloss, float* dS,
+                     int ldds, int B, int n, int K, int accumulate, const float* norm) {
     if (q.err) return;
     float* scale = q.alloc<float>(64);
     const int kt = lk_kt(K);
@@ -393,6 +519,24 @@ void linkpred_bwd(Seq& q, const float* S, int lds_ld, const float* adj, const in
                            n, K, accumulate);
         q.check_launch("link_reduce");
     }
+}
+
+void linkpred_fwd(Seq& q, const float* S, int lds_ld, const float* adj, const int* num_nodes, float* loss_out, int B,
+                  int n, int K, const float* norm) {
+    link_fwd(q, S, lds_ld, LkAdjF32{adj, n}, num_nodes, loss_out, B, n, K, norm);
+}
+void linkpred_bwd(Seq& q, const float* S, int lds_ld, const float* adj, const int* num_nodes, const float* dloss,
+                  float* dS, int ldds, int B, int n, int K, int accumulate, const float* norm) {
+    link_bwd(q, S, lds_ld, LkAdjF32{adj, n}, num_nodes, dloss, dS, ldds, B, n, K, accumulate, norm);
+}
+void linkpred_fwd_packed(Seq& q, const float* S, int lds_ld, const unsigned short* pk, const int* num_nodes,
+                         float* loss_out, int B, int n, int K, const float* norm) {
+    link_fwd(q, S, lds_ld, LkAdjBf16{pk, pk, adj_pack_ld(n)}, num_nodes, loss_out, B, n, K, norm);
+}
+void linkpred_bwd_packed(Seq& q, const float* S, int lds_ld, const unsigned short* pk, const unsigned short* pkt,
+                         const int* num_nodes, const float* dloss, float* dS, int ldds, int B, int n, int K,
+                         int accumulate, const float* norm) {
+    link_bwd(q, S, lds_ld, LkAdjBf16{pk, pkt, adj_pack_ld(n)}, num_nodes, dloss, dS, ldds, B, n, K, accumulate, norm);
 }
 
 }  // namespace dp

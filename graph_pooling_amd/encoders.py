@@ -34,8 +34,9 @@ class PackedAdjacency:
     of A^T (ld = dp_adj_pack_ld(N); the same tensor for a symmetric adjacency), int16 storage.  Written by
     `DeviceBatchBuilder.build(..., packed=True)` (dp_build_batch_packed) or `PackedAdjacency.from_dense`; accepted in
     place of the fp32 `adj` by the encoders' forward when the configuration takes the persistent level-0 plan
-    (dp_encoder_forward_packed raises DP_ERR_UNSUPPORTED otherwise).  The reference has no counterpart: its adjacency
-    is always the dense fp32 batch (train.py:197)."""
+    (dp_encoder_forward_packed raises DP_ERR_UNSUPPORTED otherwise), and by SoftPoolingGcnEncoder.loss for the
+    link-prediction term (dp_loss_forward_packed).  The reference has no counterpart: its adjacency is always the
+    dense fp32 batch (train.py:197)."""
 
     def __init__(self, pk: torch.Tensor, pkt: torch.Tensor, num_nodes_padded: int):
         if pk.dtype != torch.int16 or pkt.dtype != torch.int16 or pk.dim() != 3 or pk.shape != pkt.shape:
@@ -641,21 +642,32 @@ class _LossFn(torch.autograd.Function):
         label = label.contiguous().to(device=pred.device, dtype=torch.int64)
         B, Cc = pred.shape
         N = K = 0
+        packed = linkpred and isinstance(adj, PackedAdjacency)
         if linkpred:
             S = S.contiguous()
-            adj = adj.contiguous().float()
             N, K = S.shape[1], S.shape[2]
-        wsb = lib.dp_loss_workspace_bytes(B, max(N, 1), max(K, 1), int(linkpred))
+            if packed:
+                if adj.B != S.shape[0] or adj.N != N:
+                    raise ValueError(f"packed adjacency [B={adj.B}, N={adj.N}] does not match the assignment S "
+                                     f"{tuple(S.shape)}")
+                adj = (adj.pk, adj.pkt)
+            else:
+                adj = adj.contiguous().float()
+        wsb = lib.dp_loss_workspace_bytes(B, max(N, 1), max(K, 1), int(linkpred))   # covers the packed entries too
         ws = torch.empty(wsb, device=pred.device, dtype=torch.uint8)
         out = torch.empty(2, device=pred.device, dtype=torch.float32)
         prob = torch.empty(B, Cc, device=pred.device, dtype=torch.float32)
         dunit = torch.empty(B, Cc, device=pred.device, dtype=torch.float32)
-        _lib.check(lib.dp_loss_forward(pred.data_ptr(), label.data_ptr(), _lib.ptr(S) if linkpred else None,
-                                       _lib.ptr(adj) if linkpred else None, _lib.ptr(num_nodes),
-                                       _lib.ptr(link_norm) if linkpred else None,
-                                       out.data_ptr(), prob.data_ptr(), dunit.data_ptr(), B, Cc, N, K, int(linkpred),
-                                       ws.data_ptr(), wsb, _lib.current_stream()), "dp_loss_forward")
+        head = (pred.data_ptr(), label.data_ptr(), _lib.ptr(S) if linkpred else None)
+        tail = (_lib.ptr(num_nodes), _lib.ptr(link_norm) if linkpred else None, out.data_ptr(), prob.data_ptr(),
+                dunit.data_ptr(), B, Cc, N, K, int(linkpred), ws.data_ptr(), wsb, _lib.current_stream())
+        if packed:
+            _lib.check(lib.dp_loss_forward_packed(*head, adj[0].data_ptr(), adj[1].data_ptr(), *tail),
+                       "dp_loss_forward_packed")
+        else:
+            _lib.check(lib.dp_loss_forward(*head, _lib.ptr(adj) if linkpred else None, *tail), "dp_loss_forward")
         ctx.saved = (prob, dunit, label, S if linkpred else None, adj if linkpred else None, num_nodes, ws)
+        ctx.packed = packed
         ctx.link_norm = link_norm if linkpred else None
         ctx.dims = (B, Cc, N, K, bool(linkpred))
         total, link = out[0], out[1]
@@ -676,12 +688,15 @@ class _LossFn(torch.autograd.Function):
         dtotal = dtotal.contiguous().float()
         dpred = dunit if unit else torch.empty(B, Cc, device=prob.device, dtype=torch.float32)
         dS = torch.empty_like(S) if linkpred else None
-        _lib.check(lib.dp_loss_backward(prob.data_ptr(), label.data_ptr(), _lib.ptr(S), _lib.ptr(adj),
-                                        _lib.ptr(num_nodes), _lib.ptr(ctx.link_norm),
-                                        None if unit else dtotal.data_ptr(),
-                                        None if unit else dpred.data_ptr(), _lib.ptr(dS),
-                                        B, Cc, N, K, int(linkpred), ws.data_ptr(), ws.numel(),
-                                        _lib.current_stream()), "dp_loss_backward")
+        tail = (_lib.ptr(num_nodes), _lib.ptr(ctx.link_norm), None if unit else dtotal.data_ptr(),
+                None if unit else dpred.data_ptr(), _lib.ptr(dS), B, Cc, N, K, int(linkpred), ws.data_ptr(), ws.numel(),
+                _lib.current_stream())
+        if ctx.packed:
+            _lib.check(lib.dp_loss_backward_packed(prob.data_ptr(), label.data_ptr(), _lib.ptr(S), adj[0].data_ptr(),
+                                                   adj[1].data_ptr(), *tail), "dp_loss_backward_packed")
+        else:
+            _lib.check(lib.dp_loss_backward(prob.data_ptr(), label.data_ptr(), _lib.ptr(S), _lib.ptr(adj), *tail),
+                       "dp_loss_backward")
         return dpred, None, dS, None, None, None, None
 
 
@@ -880,7 +895,6 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
         if self.linkpred:
             if adj is None:
                 raise ValueError("linkpred=True: loss() needs adj (train.py:207 passes it)")
-            if isinstance(adj, PackedAdjacency):
-                raise TypeError("the link-prediction loss reads the dense fp32 adjacency; it has no packed form")
+            # adj: the dense fp32 batch or the PackedAdjacency the forward ran on (dp_loss_forward_packed)
             return _loss(self, pred, label, self.assign_tensor, adj, batch_num_nodes, True)
         return _loss(self, pred, label, None, None, None, False)

@@ -8,6 +8,9 @@ captured once:
     -> dp_gather_labels -> dp_encoder_forward_packed -> dp_loss_forward -> dp_encoder_backward_packed
     -> dp_clip_adam_step_counted (Adam's step count lives on the device)
 
+(a model with the link-prediction loss is captured with CapturedTrainStep(..., linkpred=True): dp_loss_forward /
+_backward are then their _packed forms, which read the same bf16 adjacency rows as the encoder entries)
+
 and a step is: write the batch's edge lists into a pinned slot, `graph.replay()`.  Two slots / two graphs alternate, so
 the host prepares step i + 1 while the GPU runs step i.
 
@@ -48,19 +51,28 @@ class _Slot:
         self.event = torch.cuda.Event()
         self.graph = None
         self.loss = None
+        self.link = None                                  # the link-prediction term of `loss` (linkpred models)
         self.errors = None
 
 
 class CapturedTrainStep:
-    """build -> forward -> loss -> backward -> clip + Adam of a SoftPoolingGcnEncoder (linkpred=False) as one graph
-    launch per step.  `optimizer` must be a FusedClipAdam(device_step_counter=True); every batch has `batch_size`
-    graphs (the reference's DataLoader drops nothing but its last batch may be short: run that one eagerly)."""
+    """build -> forward -> loss -> backward -> clip + Adam of a SoftPoolingGcnEncoder as one graph launch per step.
+    `optimizer` must be a FusedClipAdam(device_step_counter=True); every batch has `batch_size` graphs (the
+    reference's DataLoader drops nothing but its last batch may be short: run that one eagerly).
 
-    def __init__(self, model, optimizer: FusedClipAdam, builder: DeviceBatchBuilder, batch_size: int, slots: int = 2):
+    linkpred=True captures the link-prediction loss of a linkpred model too (train.py:207's loss(ypred, label, adj,
+    batch_num_nodes), on the packed adjacency); after each step `model.link_loss` is that step's link term, as
+    train.py:224-225 reads it.  The flag must match the model's: the objective in the graph is stated where it is
+    captured, and a linkpred model without it is refused as before."""
+
+    def __init__(self, model, optimizer: FusedClipAdam, builder: DeviceBatchBuilder, batch_size: int, slots: int = 2,
+                 linkpred: bool = False):
         if not optimizer.device_step_counter:
             raise ValueError("CapturedTrainStep needs FusedClipAdam(device_step_counter=True)")
-        if getattr(model, "linkpred", False):
-            raise ValueError("the packed-adjacency step has no link-prediction loss (it reads the fp32 adjacency)")
+        if bool(getattr(model, "linkpred", False)) != bool(linkpred):
+            raise ValueError("the model's link-prediction loss and CapturedTrainStep(linkpred=...) disagree: capture a "
+                             "linkpred model with linkpred=True (the link term then reads the packed adjacency)")
+        self.linkpred = bool(linkpred)
         self.model, self.opt, self.builder, self.B = model, optimizer, builder, int(batch_size)
         ds = builder.ds
         ecount = np.diff(ds.edge_ptr)
@@ -100,10 +112,15 @@ class CapturedTrainStep:
                    "dp_gather_labels")
         self.model.zero_grad(set_to_none=True)
         ypred = self.model(batch["feats"], batch["adj"], batch["num_nodes_device"], assign_x=batch["assign_feats"])
-        loss = self.model.loss(ypred, label)
+        if self.linkpred:
+            loss = self.model.loss(ypred, label, batch["adj"], batch["num_nodes_device"])
+        else:
+            loss = self.model.loss(ypred, label)
         loss.backward()
         self.opt.step()
-        return loss.detach(), batch["errors"]
+        # the link term is a non-differentiable output of the loss node: it keeps no autograd graph alive
+        link = self.model.link_loss if self.linkpred else None
+        return loss.detach(), link, batch["errors"]
 
     def _capture(self):
         model, opt = self.model, self.opt
@@ -120,13 +137,15 @@ class CapturedTrainStep:
         with torch.cuda.stream(side):
             for _ in range(3):
                 self._body(self.slots[0])
+        if self.linkpred:
+            model.link_loss = None                        # the warm-up's link term
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         model.zero_grad(set_to_none=True)
         for s in self.slots:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                s.loss, s.errors = self._body(s)
+                s.loss, s.link, s.errors = self._body(s)
             s.graph = g
             model.zero_grad(set_to_none=True)
         torch.cuda.synchronize(dev)
@@ -142,6 +161,8 @@ class CapturedTrainStep:
         slot.graph.replay()
         slot.event.record(torch.cuda.current_stream(self.builder.device))
         self.opt.step_count += 1
+        if slot.link is not None:
+            self.model.link_loss = slot.link              # train.py:224-225 logs the link term of the step just run
         return slot.loss
 
     def skipped_entries(self) -> int:

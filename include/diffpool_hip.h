@@ -60,9 +60,9 @@ const char* dp_last_error_string(void);
  *                             statistics with NaN, so the step's outputs and gradients are NaN, never plausible.
  *   DP_DEVERR_NONFINITE_GRAD  dp_clip_adam_step met a non-finite gradient norm and SKIPPED the update (parameters and
  *                             moments untouched) — which is also what keeps a poisoned backward from ruining them.
- * The NEXT model-level entry on that device (dp_encoder_forward / _backward, dp_loss_forward / _backward,
- * dp_clip_adam_step) finds the word set, clears it, returns DP_ERR_DEVICE before launching anything and describes it
- * in dp_last_error_string().  dp_device_error(clear) reads the current device's word directly (after a stream or
+ * The NEXT model-level entry on that device (dp_encoder_forward / _backward, dp_loss_forward / _backward, their
+ * _packed forms, dp_clip_adam_step) finds the word set, clears it, returns DP_ERR_DEVICE before launching anything and
+ * describes it in dp_last_error_string().  dp_device_error(clear) reads the current device's word directly (after a stream or
  * device synchronisation it is up to date); dp_device_error_describe(mask) is the text for a mask.  Escape hatch for
  * shared devices: DP_NO_LEVEL_FUSION=1 (no kernel with a grid barrier is used). */
 #define DP_DEVERR_BARRIER 1
@@ -183,7 +183,11 @@ int dp_masked_max_bwd(const float* dout, int ldo, const int* argmax, float* dZ, 
 
 /* ------------------------------------------------------------------ A8  link-prediction loss
  * loss = sum_{n,m < n_b} [-A log(P+1e-7) - (1-A) log(1-P+1e-7)] / sum_b n_b^2,
- * P = min(S S^T, 1) — encoders.py:1309-1331 (adj_hop = 1).  loss_out: 1 float. */
+ * P = min(S S^T, 1) — encoders.py:1309-1331 (adj_hop = 1).  loss_out: 1 float.  K <= 256 (DP_ERR_UNSUPPORTED above).
+ * The adjacency comes either as the dense fp32 batch adj [B,n,n] or, in the _packed entries, in the packed form of
+ * dp_adj_pack / dp_build_batch_packed: bf16 rows [B, n, dp_adj_pack_ld(n)] of A (adj_pk) and of A^T (adj_pkt; the same
+ * buffer for a symmetric adjacency), both 16-byte aligned.  The two forms run the same tile walk, so on a bf16-exact
+ * adjacency (0/1) they give bit-identical loss and dS.  dp_linkpred_workspace_bytes covers both forms. */
 size_t dp_linkpred_workspace_bytes(int B, int n, int K);
 int dp_linkpred_loss_fwd(const float* S, const float* adj, const int* num_nodes, float* loss_out, int B,
                          int n, int K, void* workspace, size_t workspace_bytes, void* stream);
@@ -191,6 +195,11 @@ int dp_linkpred_loss_fwd(const float* S, const float* adj, const int* num_nodes,
 int dp_linkpred_loss_bwd(const float* S, const float* adj, const int* num_nodes, const float* dloss,
                          float* dS, int accumulate, int B, int n, int K, void* workspace,
                          size_t workspace_bytes, void* stream);
+int dp_linkpred_loss_fwd_packed(const float* S, const void* adj_pk, const int* num_nodes, float* loss_out, int B,
+                                int n, int K, void* workspace, size_t workspace_bytes, void* stream);
+int dp_linkpred_loss_bwd_packed(const float* S, const void* adj_pk, const void* adj_pkt, const int* num_nodes,
+                                const float* dloss, float* dS, int accumulate, int B, int n, int K, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ softmax cross entropy
  * loss = mean_b CE(logits_b, label_b) — F.cross_entropy, encoders.py:1127.  prob [B,C] is saved
@@ -350,8 +359,8 @@ int dp_encoder_backward(const dp_encoder_cfg* cfg, const float* params, const fl
  * by dp_build_batch_packed or dp_adj_pack: no fp32 [B,N,N] batch is written, read or converted (the
  * end-to-end training step).  The bf16 values ARE the adjacency (nothing to round).  Only configurations that take the
  * persistent level-0 plan accept it (N >= 64, N % 4 == 0, B * ceil(N / RB) <= CUs, no sync-BN, no add_self):
- * DP_ERR_UNSUPPORTED otherwise — the fp32 entries above serve every configuration and train.py.  The link-prediction
- * loss (dp_loss_forward with linkpred) reads the fp32 adjacency and has no packed form. */
+ * DP_ERR_UNSUPPORTED otherwise — the fp32 entries above serve every configuration and train.py.  The loss of such a
+ * step, link prediction included, takes the same packed rows: dp_loss_forward_packed / dp_loss_backward_packed. */
 int dp_encoder_forward_packed(const dp_encoder_cfg* cfg, const float* params, const float* x, const void* adj_pk,
                               const void* adj_pkt, const float* assign_x, const int* num_nodes, const float* dropout,
                               float* ypred, float* assign_out, long long* labels_out, void* save, size_t save_bytes,
@@ -366,7 +375,7 @@ int dp_encoder_backward_packed(const dp_encoder_cfg* cfg, const float* params, c
  * d_ypred_unit [B,C] (may be NULL): d loss / d ypred for an upstream gradient of 1, (softmax - onehot) / B, written by
  * the same launch — `loss.backward()` (train.py:208) sends exactly that down, so the caller can hand it to
  * dp_encoder_backward without a gradient launch of its own. */
-size_t dp_loss_workspace_bytes(int B, int N, int K, int linkpred);
+size_t dp_loss_workspace_bytes(int B, int N, int K, int linkpred);   /* also covers the _packed entries below */
 /* link_norm (device scalar or NULL): replaces the link loss's normaliser sum_b n_b^2 (encoders.py:1326,1331).  Under
  * data parallelism every rank passes (sum over ALL ranks' graphs) / world_size, so that the mean over ranks of the
  * per-rank losses and gradients is the loss of the concatenated batch. */
@@ -378,6 +387,17 @@ int dp_loss_forward(const float* ypred, const long long* label, const float* S, 
 int dp_loss_backward(const float* prob, const long long* label, const float* S, const float* adj,
                      const int* num_nodes, const float* link_norm, const float* dloss, float* d_ypred, float* dS,
                      int B, int C, int N, int K, int linkpred, void* workspace, size_t workspace_bytes, void* stream);
+/* The same two calls with the link loss reading the packed adjacency (adj_pk / adj_pkt as in A8 above, N rows of
+ * dp_adj_pack_ld(N)) in place of adj: the loss of the step that dp_encoder_forward_packed / _backward_packed run.
+ * adj_pk / adj_pkt may be NULL when linkpred == 0. */
+int dp_loss_forward_packed(const float* ypred, const long long* label, const float* S, const void* adj_pk,
+                           const void* adj_pkt, const int* num_nodes, const float* link_norm, float* loss_out,
+                           float* prob, float* d_ypred_unit, int B, int C, int N, int K, int linkpred, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int dp_loss_backward_packed(const float* prob, const long long* label, const float* S, const void* adj_pk,
+                            const void* adj_pkt, const int* num_nodes, const float* link_norm, const float* dloss,
+                            float* d_ypred, float* dS, int B, int C, int N, int K, int linkpred, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ N1  on-device batch builder
  * Replaces GraphSampler.__getitem__ + collate + H2D of the dense batch (graph_sampler.py:97-109, train.py:197-201):
@@ -422,8 +442,8 @@ int dp_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_av
 /* The same update with the step count kept ON THE DEVICE: step_counter (device int, the number of updates done so far;
  * zero it once) is incremented by the call and the bias corrections of the new count are computed by the kernel (in
  * double, as above).  No argument changes from step to step, so the call can sit inside a captured hipGraph together
- * with dp_build_batch_packed, dp_encoder_forward_packed, dp_loss_forward and dp_encoder_backward_packed: one graph
- * launch per training step (train.py:197-210). */
+ * with dp_build_batch_packed, dp_encoder_forward_packed, dp_loss_forward (dp_loss_forward_packed with the
+ * link-prediction loss) and dp_encoder_backward_packed: one graph launch per training step (train.py:197-210). */
 int dp_clip_adam_step_counted(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, int* step_counter,
                               float lr, float beta1, float beta2, float eps, float max_norm, float* total_norm_out,
                               void* workspace, size_t workspace_bytes, void* stream);
