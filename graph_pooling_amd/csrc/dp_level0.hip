@@ -301,10 +301,13 @@ __device__ inline void l0_write_split(ScBuf vsb, const float* PT, int ct, int CT
 template <int MI, int CTH>
 __device__ __forceinline__ void l0_agg_bf16(const unsigned short* Alds, int ldp, const unsigned short* vsp, int CTt, int K8,
                                             int steps, int rot, int cb0, f32x4 (&acc)[MI][CTH]) {
-    const int lane = threadIdx.x & 63;
+    // The lane's fragment addresses are recomputed at every pass: the empty asm keeps the compiler from hoisting them
+    // out of the kernel's layer loop, where a dozen of them stayed live across every phase and were spilled to
+    // scratch (reloaded one wait at a time at the start of each pass).
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
     const int kh = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3;
     const int l15 = lane & 15, kq = lane >> 4;
-    s16x8 f0[3][CTH], f1[3][CTH];
     // The blocks of a graph walk the k-steps from different starting points (`rot`): the operand was just written
     // through to memory, so the first block to touch a line pays the miss and the others find it in the XCD's L2 —
     // started together on the same lines, every block would sit at the per-CU miss rate (~10 B / cycle) for the whole
@@ -339,48 +342,44 @@ __device__ __forceinline__ void l0_agg_bf16(const unsigned short* Alds, int ldp,
                                                                            __builtin_bit_cast(bf16x8, bf[p][cbi]),
                                                                            acc[rb][cbi], 0, 0, 0);
     };
-    if constexpr (CTH <= 2) {
-        // narrow halves: the fragments of FOUR k-steps (all of a DD-sized graph's share) are requested before the first
-        // multiply — the pass is a chain of memory round trips, not of MFMAs
-        s16x8 f2[3][CTH], f3[3][CTH];
-        for (int step = kh; step < steps; step += 16) {
-            load_b(step, f0);
-            load_b(step + 4, f1);
-            load_b(step + 8, f2);
-            load_b(step + 12, f3);
-            mma(step, f0);
-            if (step + 4 < steps) mma(step + 4, f1);
-            if (step + 8 < steps) mma(step + 8, f2);
-            if (step + 12 < steps) mma(step + 12, f3);
-        }
-    } else {
-        load_b(kh, f0);
-        load_b(kh + 4, f1);
-        for (int step = kh; step < steps; step += 8) {
-            mma(step, f0);
-            if (step + 4 < steps) {
-                load_b(step + 8, f0);
-                mma(step + 4, f1);
-                load_b(step + 12, f1);
-            }
-        }
+    // the fragments of FOUR k-steps (all of a DD-sized graph's share) are requested before the first multiply — the
+    // pass is a chain of memory round trips, not of MFMAs
+    s16x8 f0[3][CTH], f1[3][CTH], f2[3][CTH], f3[3][CTH];
+    for (int step = kh; step < steps; step += 16) {
+        load_b(step, f0);
+        load_b(step + 4, f1);
+        load_b(step + 8, f2);
+        load_b(step + 12, f3);
+        mma(step, f0);
+        if (step + 4 < steps) mma(step + 4, f1);
+        if (step + 8 < steps) mma(step + 8, f2);
+        if (step + 12 < steps) mma(step + 12, f3);
     }
 }
 
-// The same product for a graph whose adjacency is not bf16-exact: fp32 MFMA, op(A) rows straight from the fp32 input
+// The same pass for a graph whose adjacency is not bf16-exact: fp32 MFMA, op(A) rows straight from the fp32 input
 // in global memory (element (i, k) at Ag[i * rs + k * ks]: rs = N, ks = 1 for A; rs = 1, ks = N for A^T), V rebuilt
-// exactly from its planes (hi + mid + lo == v).  Slow; only weighted adjacency ever comes here.
-template <int MI, int CTH>
-__device__ __forceinline__ void l0_agg_f32(const float* Ag, long rs, long ks, int nrows, int N, const unsigned short* vsp,
-                                           int CTt, int K8, int steps, int cb0, f32x4 (&acc)[MI][CTH]) {
+// exactly from its planes (hi + mid + lo == v).  Slow; only weighted adjacency ever comes here, so it is kept compact
+// (one column tile at a time in a loop that is not unrolled: the code it adds to the kernel stays small) and writes the
+// k-quarter slots itself.  Out of line: exact graphs do not carry its code through the kernel's hot phases.  Per
+// output element the products are summed k-step by k-step, 8 terms per step.
+template <int MI>
+__device__ __attribute__((noinline)) void l0_agg_f32_pass(const float* Ag, long rs, long ks, int nrows, int N,
+                                                          const unsigned short* vsp, int CTt, int K8, int steps, int cb0,
+                                                          int ncb, float* red, int ctp) {
+    constexpr int RB = MI * 16;
     const int lane = threadIdx.x & 63;
     const int kh = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3;
     const int l15 = lane & 15, kq = lane >> 4;
-    for (int step = kh; step < steps; step += 4) {
-        float bv[CTH][8];
+#pragma unroll 1
+    for (int cbi = 0; cbi < ncb; ++cbi) {
+        const int cb = cb0 + cbi;
+        f32x4 acc[MI];
 #pragma unroll
-        for (int cbi = 0; cbi < CTH; ++cbi) {
-            const int cb = min(cb0 + cbi, CTt - 1);
+        for (int i = 0; i < MI; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int step = kh; step < steps; step += 4) {
+            float bv[8];
             u16x8 pl3[3];
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
@@ -389,49 +388,45 @@ __device__ __forceinline__ void l0_agg_f32(const float* Ag, long rs, long ks, in
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                bv[cbi][j] = (__uint_as_float((unsigned)pl3[0][j] << 16) + __uint_as_float((unsigned)pl3[1][j] << 16)) +
-                             __uint_as_float((unsigned)pl3[2][j] << 16);
-        }
+                bv[j] = (__uint_as_float((unsigned)pl3[0][j] << 16) + __uint_as_float((unsigned)pl3[1][j] << 16)) +
+                        __uint_as_float((unsigned)pl3[2][j] << 16);
 #pragma unroll
-        for (int rb = 0; rb < MI; ++rb) {
-            const int i = rb * 16 + l15;
-            float av[8];
+            for (int rb = 0; rb < MI; ++rb) {
+                const int i = rb * 16 + l15;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = step * 32 + kq * 8 + j;
-                const float t = Ag[(long)min(i, nrows - 1) * rs + (long)min(k, N - 1) * ks];
-                av[j] = (i < nrows && k < N) ? t : 0.f;
+                for (int j = 0; j < 8; ++j) {
+                    const int k = step * 32 + kq * 8 + j;
+                    const float t = Ag[(long)min(i, nrows - 1) * rs + (long)min(k, N - 1) * ks];
+                    acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32((i < nrows && k < N) ? t : 0.f, bv[j], acc[rb], 0, 0, 0);
+                }
             }
+        }
+        if (cb * 16 + l15 < ctp) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
+            for (int rb = 0; rb < MI; ++rb)
 #pragma unroll
-                for (int cbi = 0; cbi < CTH; ++cbi)
-                    acc[rb][cbi] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[cbi][j], acc[rb][cbi], 0, 0, 0);
+                for (int r = 0; r < 4; ++r) red[(kh * RB + rb * 16 + kq * 4 + r) * ctp + cb * 16 + l15] = acc[rb][r];
         }
     }
 }
 
 // One aggregation pass into the k-quarter slots red[kh][RB][ctp] (the caller sums the four quarters).
-template <int MI, int CTH, typename Args>
-__device__ __forceinline__ void l0_aggregate_pass(const Args& a, const unsigned short* Alds, bool exact, const float* Ag,
-                                                  long rs, long ks, int nrows, const unsigned short* vsb, int CTt, float* red,
-                                                  int ctp, int rot) {
+template <int MI, int CTH>
+__device__ __forceinline__ void l0_aggregate_pass(const unsigned short* Alds, int ldp, const unsigned short* vsb, int CTt,
+                                                  int K8, int steps, float* red, int ctp, int rot, int sub0 = 0) {
     constexpr int RB = MI * 16;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int kh = wave & 3, ch = wave >> 2;
     const int l15 = lane & 15, kq = lane >> 4;
     const int cta = (CTt + 1) >> 1;                        // column tiles of half 0
-    const int cb0 = ch ? cta : 0, ncb = ch ? CTt - cta : cta;
+    const int cb0 = (ch ? cta : 0) + sub0, ncb = (ch ? CTt - cta : cta) - sub0;
     f32x4 acc[MI][CTH];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < CTH; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (ncb > 0) {
-        if (exact) l0_agg_bf16<MI, CTH>(Alds, a.ldp, vsb, CTt, a.K8, a.steps, rot, cb0, acc);
-        else l0_agg_f32<MI, CTH>(Ag, rs, ks, nrows, a.f.N, vsb, CTt, a.K8, a.steps, cb0, acc);
-    }
+    if (ncb > 0) l0_agg_bf16<MI, CTH>(Alds, ldp, vsb, CTt, K8, steps, rot, cb0, acc);
 #pragma unroll
     for (int rb = 0; rb < MI; ++rb)
 #pragma unroll
@@ -444,16 +439,29 @@ __device__ __forceinline__ void l0_aggregate_pass(const Args& a, const unsigned 
                 }
             }
 }
+// The bf16 pass: two bodies, a pair of column tiles and a single one.  A half of three tiles runs the pair, then the
+// single tile (each accumulator takes the same k-steps in the same order either way): a three-tile body held 36 more
+// fragment and accumulator registers at once than the pair's, and at the kernels' 256-register cap that was paid in
+// spills around every aggregation; it was also a third unrolled body at every call site.
+template <int MI>
+__device__ __forceinline__ void l0_agg_bf16_pass(const unsigned short* Alds, int ldp, const unsigned short* vsb, int CTt,
+                                                 int K8, int steps, float* red, int ctp, int rot) {
+    // tiles of THIS wave's column half (wave-uniform; <= 3: the launcher takes <= 96 columns)
+    const int cta = (CTt + 1) >> 1;
+    const int cth = (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >> 2) ? CTt - cta : cta;
+    if (cth >= 2) l0_aggregate_pass<MI, 2>(Alds, ldp, vsb, CTt, K8, steps, red, ctp, rot);
+    if (cth != 2) l0_aggregate_pass<MI, 1>(Alds, ldp, vsb, CTt, K8, steps, red, ctp, rot, cth == 3 ? 2 : 0);
+}
 template <int MI, typename Args>
 __device__ __forceinline__ void l0_aggregate(const Args& a, const unsigned short* Alds, bool exact, const float* Ag, long rs,
                                              long ks, int nrows, const unsigned short* vsb, int CTt, float* red, int ctp, int rot) {
-    // tiles of THIS wave's column half (wave-uniform): the narrower half of an odd tile count takes the narrower
-    // instantiation instead of multiplying a clamped duplicate of the last tile
-    const int cta_ = (CTt + 1) >> 1;
-    const int cth = (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >> 2) ? CTt - cta_ : cta_;
-    if (cth <= 1) l0_aggregate_pass<MI, 1>(a, Alds, exact, Ag, rs, ks, nrows, vsb, CTt, red, ctp, rot);
-    else if (cth == 2) l0_aggregate_pass<MI, 2>(a, Alds, exact, Ag, rs, ks, nrows, vsb, CTt, red, ctp, rot);
-    else l0_aggregate_pass<MI, 3>(a, Alds, exact, Ag, rs, ks, nrows, vsb, CTt, red, ctp, rot);
+    if (exact) {
+        l0_agg_bf16_pass<MI>(Alds, a.ldp, vsb, CTt, a.K8, a.steps, red, ctp, rot);
+    } else {
+        const int cta = (CTt + 1) >> 1;
+        const int ch = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >> 2;
+        l0_agg_f32_pass<MI>(Ag, rs, ks, nrows, a.f.N, vsb, CTt, a.K8, a.steps, ch ? cta : 0, ch ? CTt - cta : cta, red, ctp);
+    }
 }
 
 // 16-byte-quad staging of RB rows of a bf16 operand [*, ld] into the LDS adjacency block (columns >= ld and
@@ -465,7 +473,10 @@ struct L0RowStage {
 };
 template <int MI>
 __device__ __forceinline__ void l0_stage_issue(L0RowStage<MI>& s, const unsigned short* rows, int ld, int nrows, int seg) {
-    const int tq = threadIdx.x & 63, tr = threadIdx.x >> 6;
+    int tq = threadIdx.x;
+    asm volatile("" : "+v"(tq));                           // (recomputed per call, as in l0_agg_bf16)
+    const int tr = tq >> 6;
+    tq &= 63;
     const int c8 = seg * 64 + tq;
 #pragma unroll
     for (int u = 0; u < L0RowStage<MI>::NQ; ++u) {
@@ -476,7 +487,10 @@ __device__ __forceinline__ void l0_stage_issue(L0RowStage<MI>& s, const unsigned
 }
 template <int MI>
 __device__ __forceinline__ void l0_stage_commit(const L0RowStage<MI>& s, unsigned short* Alds, int ldp, int ld, int nrows, int seg) {
-    const int tq = threadIdx.x & 63, tr = threadIdx.x >> 6;
+    int tq = threadIdx.x;
+    asm volatile("" : "+v"(tq));
+    const int tr = tq >> 6;
+    tq &= 63;
     const int c8 = seg * 64 + tq;
 #pragma unroll
     for (int u = 0; u < L0RowStage<MI>::NQ; ++u) {
