@@ -38,6 +38,7 @@ const Knobs& knobs() {
         k.node_ksplit = (int)num("DP_NODE_KSPLIT", 0);
         k.no_head_fusion = getenv("DP_NO_HEAD_FUSION") != nullptr;
         k.no_level_fusion = getenv("DP_NO_LEVEL_FUSION") != nullptr;
+        k.no_head_fold = getenv("DP_NO_HEAD_FOLD") != nullptr;
         k.no_split_gemm = getenv("DP_NO_SPLIT_GEMM") != nullptr;
         k.split_gemm_w4 = getenv("DP_SPLIT_GEMM_W4") != nullptr;
         k.no_agg_first = getenv("DP_NO_AGG_FIRST") != nullptr;

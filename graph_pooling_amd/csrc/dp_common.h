@@ -195,6 +195,7 @@ struct Knobs {
     int node_ksplit;       // DP_NODE_KSPLIT: 0 heuristic, 1..8 forced split-K of the node-index contractions
     bool no_head_fusion;   // DP_NO_HEAD_FUSION: pred_model on the generic GEMM
     bool no_level_fusion;  // DP_NO_LEVEL_FUSION: pooled-level GCN stacks one launch per layer
+    bool no_head_fold;     // DP_NO_HEAD_FOLD: the prediction-head backward in a launch of its own (k_head_bwd)
     bool no_split_gemm;    // DP_NO_SPLIT_GEMM: fp32 MFMA for every GEMM (no split-bf16 products)
     bool split_gemm_w4;    // DP_SPLIT_GEMM_W4: the 4-wave form of the split GEMM instead of the 8-wave one
     bool no_row_quads;     // DP_NO_ROW_QUADS: wide row kernels with 4-byte lanes (the pre-quad form)
@@ -426,11 +427,6 @@ struct SmallLevelIO {
     float* part;                   // exchange scratch, small_level_part_floats() floats
     int* bar;                      // [0] spare, [1] error word, [2] finish ticket (zeroed in stream order before the launch)
 };
-bool small_level_fused_ok(int B, int n, const int* dims, int L, bool dadj);
-size_t small_level_part_floats(int B, int n, int L);
-void small_level_fwd(Seq& q, const SmallLevelIO& io, int B, int n, const int* dims, int L, int add_self, int bn);
-void small_level_bwd(Seq& q, const SmallLevelIO& io, const float* dZe, float* dX0, float* dadj, float* slabs,
-                     long slab_stride, int B, int n, const int* dims, int L, int add_self, int bn);
 
 // (dp_level0.hip) the whole level-0 forward — adjacency pack, every GraphConv layer of the embed + assign stacks with
 // BatchNorm, max readout, assign head + softmax, T = A^T S, X' = S^T Z, A' = T^T S — as ONE persistent launch: a
@@ -560,6 +556,25 @@ struct HeadBwdArgs {
 bool head_supported(const HeadArgs& a);
 void head_fwd(Seq& q, const HeadArgs& a);
 void head_bwd(Seq& q, const HeadBwdArgs& a);
+
+bool small_level_fused_ok(int B, int n, const int* dims, int L, bool dadj);
+size_t small_level_part_floats(int B, int n, int L);
+void small_level_fwd(Seq& q, const SmallLevelIO& io, int B, int n, const int* dims, int L, int add_self, int bn);
+// The prediction-head backward folded into the LAST level's whole-level backward (dp_small.hip): each workgroup runs
+// its graph's pred_model backward and max-readout scatter in a prologue (this level's slice straight into its LDS
+// gradient totals, the other levels' slices into their dZe), publishes the graph's hidden-layer gradients as tagged
+// entries, and at the end sums a fixed slice of the head's weight / bias gradients over the batch into `grads`.
+struct SmallHeadFold {
+    HeadBwdArgs hb;          // what k_head_bwd would get; hb.lv[level].dZ is not written (that slice stays in LDS)
+    int level;               // the entry of hb.lv that is this kernel's level
+    int zcol;                // column of that level's readout in its concat buffer
+    float* part;             // exchange region of small_head_fold_part_floats(hb.h) floats (alloc_exchange)
+};
+size_t small_head_fold_part_floats(const HeadArgs& h);
+bool small_head_fold_fits(int B, int n, const int* dims, int L, bool dadj, const HeadArgs& h);
+void small_level_bwd(Seq& q, const SmallLevelIO& io, const float* dZe, float* dX0, float* dadj, float* slabs,
+                     long slab_stride, int B, int n, const int* dims, int L, int add_self, int bn,
+                     const SmallHeadFold* hf = nullptr);
 
 // (dp_batch.hip)
 void build_batch(Seq& q, const int* src, const int* dst, const int* edge_ptr, const int* label, const int* node_ptr,

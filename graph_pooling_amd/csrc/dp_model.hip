@@ -546,7 +546,7 @@ void level_forward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const L
 void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const LevelSave& lv, const LevelIO& io,
                     const float* params, const LevelGrad& gr, float* slabs, long slab_stride, int KS, float* Pj,
                     float* dUj, float* Gj, float* part, float* part_b, const PackedAdj* pk, unsigned short* vs,
-                    float* const dxm[2], float* lvl_part, int* bar, float* part_all) {
+                    float* const dxm[2], float* lvl_part, int* bar, float* part_all, const SmallHeadFold* hf = nullptr) {
     const int B = c.B, n = li.n;
     const int W = bn_world(c);
     const long gstride = slab_stride * KS;     // slab rows of one graph: KS split-K partials
@@ -555,7 +555,12 @@ void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const 
     const bool add_self = c.flags & DP_F_ADD_SELF;
     if (!bn_sync(c) && lvl_part && bar && level_is_fused(c, li, io, true)) {
         small_level_bwd(q, small_level_io(li, lv, io, params, lvl_part, bar), gr.dZe, gr.dX0, gr.dAdj, slabs, gstride,
-                        B, n, li.e->dims, li.L, add_self ? 1 : 0, bn ? 1 : 0);
+                        B, n, li.e->dims, li.L, add_self ? 1 : 0, bn ? 1 : 0, hf);
+        return;
+    }
+    if (hf) {      // (head_fold() decides with the same test: never reached)
+        set_error("level_backward: the head fold needs the whole-level backward kernel");
+        q.err = DP_ERR_UNSUPPORTED;
         return;
     }
     if (!bn_sync(c) && level_is_small(B, li) && !level_has_dropout(li, io)) {
@@ -885,14 +890,30 @@ bool level0_persistent(const dp_encoder_cfg& c) {
 // they sit right behind the barrier block, at the same offsets in the forward and the backward walk, and are never
 // handed out as scratch — they only ever hold zeros (the workspace's one-time fill) or entries of earlier launches.
 struct ExchangeRegions {
-    float *l0_fwd, *l0_bwd, *lvl;
+    float *l0_fwd, *l0_bwd, *lvl, *head;
 };
 ExchangeRegions alloc_exchange(Seq& q, const dp_encoder_cfg& c) {
     ExchangeRegions x{};
     x.l0_fwd = q.alloc<float>(level0_persistent(c) ? level0_part_floats(level0_desc(c)) : 4);
     x.l0_bwd = q.alloc<float>(level0_bwd_persistent(c) ? level0_bwd_part_floats(level0_bwd_desc(c)) : 4);
     x.lvl = q.alloc<float>(level_part_floats(c));
+    // the head fold's hidden-layer gradients (small_level_bwd with a SmallHeadFold)
+    x.head = q.alloc<float>(head_usable(c) && c.num_pooling >= 1 ? small_head_fold_part_floats(head_args(c, SaveLayout{}, nullptr,
+                                                                                                          nullptr))
+                                                                  : 4);
     return x;
+}
+
+// The prediction-head backward runs inside the last level's whole-level backward kernel (SmallHeadFold) when that
+// level takes the kernel (the test of level_backward) and the head's operands fit its LDS; else k_head_bwd.
+bool head_fold(const dp_encoder_cfg& c, const float* dropout) {
+    const int P = c.num_pooling;
+    if (knobs().no_head_fold || P < 1 || bn_sync(c) || !head_usable(c)) return false;
+    const LevelInfo li = level_info(c, P);
+    LevelIO io{};
+    io.drop = dropout;
+    return level_is_fused(c, li, io, true) &&
+           small_head_fold_fits(c.B, li.n, li.e->dims, li.L, true, head_args(c, SaveLayout{}, nullptr, nullptr));
 }
 
 // shared allocation walk for the forward (also used for sizing)
@@ -1189,8 +1210,10 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
     // (a training forward with this workspace already cleared it on the side of its adjacency pack: prezeroed)
     if (!prezeroed) zero_fill(q, q.ws + zero_begin, zero_end - zero_begin);
     const bool fused_head = head_usable(c);
+    const bool fold = head_fold(c, dropout);
+    SmallHeadFold hf{};
     if (fused_head) {
-        // pred_model backward + the max-readout scatter of every level in one launch
+        // pred_model backward + the max-readout scatter of every level in one launch (or folded into the last level's)
         HeadBwdArgs hb{};
         hb.h = head_args(c, sv, params, nullptr);
         hb.d_ypred = d_ypred;
@@ -1205,7 +1228,15 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
             s.lda = rw; s.n = li.n; s.ldz = li.D; s.rw = rw; s.featoff = featoff;
             featoff += rw;
         }
-        head_bwd(q, hb);
+        if (fold) {
+            const LevelInfo li = level_info(c, P);
+            hf.hb = hb;
+            hf.level = P;
+            hf.zcol = (c.flags & DP_F_LAST_ONLY) ? li.coff_e[li.L - 1] : 0;
+            hf.part = xr.head;
+        } else {
+            head_bwd(q, hb);
+        }
     } else {
         // ---- pred_model backward
         for (int i = c.n_pred - 1; i >= 0; --i) {
@@ -1336,7 +1367,8 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
             }
         }
         level_backward(q, c, li, lv, io, params, gr[j], slabs, slab_stride, KS, Pj, dUj, Gj, part, part_b,
-                       j == 0 ? pkp : nullptr, vs, dxm, lvl_part, bz.bar + 64 * j, part_all);
+                       j == 0 ? pkp : nullptr, vs, dxm, lvl_part, bz.bar + 64 * j, part_all,
+                       fold && j == P ? &hf : nullptr);
     }
     reduce_slabs(q, slabs, slab_stride, B * KS, grads, c.n_graph_params, 0);
     return q.err;

@@ -739,7 +739,31 @@ struct SmallLevelBwdArgs {
     int omax, wtot, D;                 // max layer output width, total weight floats, concat width
     SmDiv qd0, qD;
     SmDiv qdout[DP_MAX_LAYERS];
+    // the prediction-head backward folded in (fold != 0; see SmallHeadFold): hb as k_head_bwd gets it, hlevel / zcol
+    // this level's entry of hb.lv and its readout column, hpart the exchange of the hidden-layer gradients
+    int fold, hlevel, zcol, htot;      // htot: head weight + bias gradient entries (B * htot < 2^31)
+    HeadBwdArgs hb;
+    float* hpart;
 };
+
+// Head-fold sizes: widths of pred_model, its hidden-layer widths hup = dims[1] + .. + dims[n_pred - 1] (the per-graph
+// gradients that are exchanged, two floats per tagged entry) and the LDS it stages
+struct SmHead {
+    int nP, d0, d1, C, wup, hup, E;
+    __host__ __device__ SmHead(const HeadArgs& h) : nP(h.n_pred), d0(h.dims[0]), d1(h.dims[1]), C(h.dims[h.n_pred]) {
+        wup = hup = 0;
+        for (int i = 1; i < nP; ++i) {
+            wup += h.dims[i] * h.dims[i + 1];
+            hup += h.dims[i];
+        }
+        E = (hup + 1) / 2;
+    }
+    // W0 [d1][d0], upper weights, hid[1..nP-1] and their gradients [B][dims[i]] each, features [B][d0], d_ypred [B][C]
+    __host__ __device__ size_t lds_floats(int B) const {
+        return (size_t)d1 * d0 + wup + 2 * (size_t)B * hup + (size_t)B * d0 + (size_t)B * C;
+    }
+};
+constexpr unsigned SM_HEAD_TAG = 15u;     // tag low bits of the head-gradient entries (BN entries use 1..L)
 
 __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -764,6 +788,37 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     float* DBW = DB + a.omax;              // [16 waves][omax] per-wave partials of the bias sums
     const int tl = tid & 15, team = tid >> 4;
     const int NT = blockDim.x, NTEAMS = blockDim.x >> 4;
+    // head fold (a.fold): its operands behind the level's
+    const SmHead hz(a.hb.h);
+    const int B = a.B;
+    float* HW0 = DBW + 16 * a.omax;        // [d1][d0] first Linear's weight
+    float* HWU = HW0 + hz.d1 * hz.d0;      // the upper Linears' weights, layer 1 first
+    float* HH = HWU + hz.wup;              // hid[i] of every graph, i = 1..nP-1: [B][dims[i]] blocks
+    float* HG = HH + B * hz.hup;           // gradients w.r.t. hid[i], same layout (this graph's, then every graph's)
+    float* HF = HG + B * hz.hup;           // features hid[0] of every graph [B][d0]
+    float* HY = HF + B * hz.d0;            // d_ypred [B][C]
+    SM_STAMP(1, 16);
+    int win = -1;                          // max-readout winner row of feature tid (first pass of the scatter)
+    if (a.fold) {
+        if (tid < hz.d0) {
+            for (int lv = 0; lv < a.hb.n_levels; ++lv) {
+                const int f = tid - a.hb.lv[lv].featoff;
+                if (f >= 0 && f < a.hb.lv[lv].rw) win = a.hb.lv[lv].argmax[(long)b * a.hb.lv[lv].lda + f];
+            }
+        }
+        const HeadArgs& h = a.hb.h;
+        sm_dma(HY, B * hz.C, [&](int e) { return a.hb.d_ypred + e; });
+        sm_dma(HW0, hz.d1 * hz.d0, [&](int e) { return h.params + h.w_off[0] + e; });
+        int wo = 0, ho = 0;
+        for (int i = 1; i < hz.nP; ++i) {
+            const int cnt = h.dims[i] * h.dims[i + 1];
+            sm_dma(HWU + wo, cnt, [&](int e) { return h.params + h.w_off[i] + e; });
+            sm_dma(HH + ho, B * h.dims[i], [&](int e) { return h.hid[i] + e; });
+            wo += cnt;
+            ho += B * h.dims[i];
+        }
+        sm_dma(HF, B * hz.d0, [&](int e) { return h.hid[0] + e; });
+    }
 
     // ---- one burst
     sm_dma(A, n * n, [&](int e) { return a.adj + (long)b * n * n + e; });
@@ -793,8 +848,66 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     }
     if (a.dadj)
         for (int i = tid; i < n * n; i += NT) DA[i] = 0.f;
+    SM_STAMP(1, 17);
     __syncthreads();                       // (drains the LDS-DMA burst: vmcnt)
+    SM_STAMP(1, 18);
 
+    if (a.fold) {
+        // ---- head prologue: this graph's pred_model backward, in k_head_bwd's expression order (bit-identical)
+        const HeadArgs& h = a.hb.h;
+        int ho = B * hz.hup, wo = hz.wup;
+        for (int i = hz.nP - 1; i >= 1; --i) {
+            const int din = h.dims[i], dout = h.dims[i + 1];
+            wo -= din * dout;
+            ho -= B * din;
+            const float* go = i == hz.nP - 1 ? HY + b * dout : HG + ho + B * din + b * dout;
+            const float* W = HWU + wo;
+            for (int k = tid; k < din; k += NT) {
+                float s = 0.f;
+#pragma unroll 8
+                for (int j = 0; j < dout; ++j) s += go[j] * W[j * din + k];
+                HG[ho + b * din + k] = HH[ho + b * din + k] > 0.f ? s : 0.f;     // relu': hid = relu(.)
+            }
+            __syncthreads();
+        }
+        // publish this graph's hidden-layer gradients: entry e = values 2e, 2e + 1 of [grad hid[1] | grad hid[2] | ..]
+        const ScBuf hp = sc_buf(a.hpart, (size_t)B * hz.E * 16);
+        for (int e = tid; e < hz.E; e += NT) {
+            float v[2] = {0.f, 0.f};
+            for (int u = 0; u < 2; ++u) {
+                int t = 2 * e + u, blk = 0;
+                for (int i = 1; i < hz.nP && t >= 0; ++i) {
+                    if (t < h.dims[i]) v[u] = HG[blk + b * h.dims[i] + t];
+                    t -= h.dims[i];
+                    blk += B * h.dims[i];
+                }
+            }
+            sc_st16(hp, (unsigned)(((long)b * hz.E + e) * 16), sc_tagged(v[0], v[1], (seq << 4) | SM_HEAD_TAG));
+        }
+        // d features = g1 W0, and the max-readout scatter: this level's slice into the LDS running totals, the other
+        // levels' into their dZe (zero on entry: the caller's contract; the kernel boundary publishes them)
+        const float* g1 = hz.nP == 1 ? HY + b * hz.C : HG + b * hz.d1;
+        for (int k = tid, it = 0; k < hz.d0; k += NT, ++it) {
+            float s = 0.f;
+#pragma unroll 8
+            for (int j = 0; j < hz.d1; ++j) s += g1[j] * HW0[j * hz.d0 + k];
+            for (int lv = 0; lv < a.hb.n_levels; ++lv) {
+                const HeadBwdArgs::Level& t = a.hb.lv[lv];
+                const int f = k - t.featoff;
+                if (f >= 0 && f < t.rw) {
+                    const int r = it == 0 ? win : t.argmax[(long)b * t.lda + f];
+                    if (r < 0) continue;
+                    if (lv == a.hlevel) DZ[r * D + a.zcol + f] += s;
+                    else t.dZ[((long)b * t.n + r) * t.ldz + f] = s;
+                }
+            }
+        }
+        SM_STAMP(1, 19);
+    }
+
+    // first probe of the head-gradient poll, issued before the first layer's row backward (below) and checked at the end
+    u32x4 hprobe = (u32x4){0u, 0u, 0u, 0u};
+    const unsigned htag = ((seq << 4) | SM_HEAD_TAG) ^ (a.target_bias ? 0x40000000u : 0u);   // (what the poll wants)
     int wo_end = a.wtot;
     for (int l = L - 1; l >= 0; --l) {
         const int din = a.dims[l], dout = a.dims[l + 1];
@@ -844,6 +957,9 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
                 }
             }
         }
+        // behind the last BatchNorm exchange (its poll loads have landed, so the vmcnt waits of the layer do not drain
+        // the probe): its round trip hides behind the first layer's work
+        if (a.fold && l == 0 && tid < B * hz.E) hprobe = sc_ld16(sc_buf(a.hpart, (size_t)B * hz.E * 16), (unsigned)tid * 16u);
         lds_barrier();
         // ---- dU = normalise^T relu^T bn^T dx, one team per row (uniform trip count: the bias sums reduce across
         // the four row teams of a wave)
@@ -924,6 +1040,69 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     }
     if (a.dadj)
         for (int i = tid; i < n * n; i += NT) a.dadj[(long)b * n * n + i] = DA[i];
+    SM_STAMP(1, 20);
+    if (a.fold) {
+        // ---- head parameter gradients: every graph's hidden-layer gradients, then this workgroup's fixed slice of the
+        // dW / db entries, each the b-ascending chain of k_head_bwd (bit-identical), written straight to grads.  The
+        // entries were published in the prologues; with BatchNorm the exchanges above have already waited for every
+        // workgroup, without it this poll is the level's one cross-workgroup wait (co-residency: small_level_fused_ok;
+        // bounded like sm_poll_row: on give-up the error word is raised and these gradients are NaN)
+        const HeadArgs& h = a.hb.h;
+        const ScBuf hp = sc_buf(a.hpart, (size_t)B * hz.E * 16);
+        bool ok = true;
+        for (int t = tid; t < B * hz.E; t += NT) {
+            const int bb = t / hz.E, e = t - bb * hz.E;
+            u32x4 q = hprobe;                      // (t == tid: the probe issued before layer 0)
+            for (int it = 0;; ++it) {
+                if (t != tid || it > 0) q = sc_ld16(hp, (unsigned)t * 16u);
+                if (q[1] == htag && q[3] == htag) break;
+                if (it > a.spin_limit) {
+                    __hip_atomic_store(a.bar + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    dev_err_raise(a.dev_err, DP_DEVERR_BARRIER);
+                    ok = false;
+                    break;
+                }
+                if (t != tid || it > 0) __builtin_amdgcn_s_sleep(2);
+            }
+            for (int u = 0; u < 2; ++u) {
+                int x = 2 * e + u, blk = 0;
+                for (int i = 1; i < hz.nP && x >= 0; ++i) {
+                    if (x < h.dims[i]) HG[blk + bb * h.dims[i] + x] = __uint_as_float(q[2 * u]);
+                    x -= h.dims[i];
+                    blk += B * h.dims[i];
+                }
+            }
+        }
+        ok = __syncthreads_and(ok);
+        SM_STAMP(1, 21);
+        const int lo = a.htot * b / B, hi = a.htot * (b + 1) / B;
+        for (int e = lo + tid; e < hi; e += NT) {
+            int i = 0, r = e, ho = 0;
+            for (; i < hz.nP - 1; ++i) {
+                const int seg = h.dims[i + 1] * (h.dims[i] + (h.b_off[i] >= 0 ? 1 : 0));
+                if (r < seg) break;
+                r -= seg;
+                if (i > 0) ho += B * h.dims[i];
+            }
+            const int din = h.dims[i], dout = h.dims[i + 1];
+            // go[bb][j]: d_ypred for the last Linear, else the gradient w.r.t. hid[i + 1];  hin[bb][k]: hid[i]
+            const float* go = i == hz.nP - 1 ? HY : HG + (i > 0 ? ho + B * din : 0);
+            const float* hin = i == 0 ? HF : HH + ho;
+            float s = 0.f;
+            if (r < dout * din) {
+                const int j = r / din, k = r - j * din;
+#pragma unroll 8
+                for (int bb = 0; bb < B; ++bb) s += go[bb * dout + j] * hin[bb * din + k];
+                a.hb.grads[h.w_off[i] + r] = ok ? s : __builtin_nanf("");
+            } else {
+                const int j = r - dout * din;
+#pragma unroll 8
+                for (int bb = 0; bb < B; ++bb) s += go[bb * dout + j];
+                a.hb.grads[h.b_off[i] + j] = ok ? s : __builtin_nanf("");
+            }
+        }
+        SM_STAMP(1, 22);
+    }
     sm_finish(a.bar, a.seq, seq, a.B);
 }
 
@@ -1051,6 +1230,20 @@ bool small_level_fused_ok(int B, int n, const int* dims, int L, bool dadj) {
     return cus > 0 && B <= cus / 2 && B <= 16 * SM_BMAX16 && level_kernels_admitted();
 }
 size_t small_level_part_floats(int B, int n, int L) { return (size_t)(L > 1 ? L - 1 : 1) * B * n * 4; }
+static int head_grad_entries(const HeadArgs& h) {
+    int tot = 0;
+    for (int i = 0; i < h.n_pred; ++i) tot += h.dims[i + 1] * (h.dims[i] + (h.b_off[i] >= 0 ? 1 : 0));
+    return tot;
+}
+size_t small_head_fold_part_floats(const HeadArgs& h) {
+    const SmHead z(h);
+    return (size_t)h.B * (z.E > 0 ? z.E : 1) * 4;
+}
+// the fused level's LDS with the head's operands added still fits (else the plan keeps k_head_bwd)
+bool small_head_fold_fits(int B, int n, const int* dims, int L, bool dadj, const HeadArgs& h) {
+    if (h.n_pred < 1 || h.B != B || (long)head_grad_entries(h) * B >= (1L << 31)) return false;
+    return (small_level_lds_bwd(B, n, dims, L, dadj) + SmHead(h).lds_floats(B)) * sizeof(float) <= 150 * 1024;
+}
 
 void small_level_fwd(Seq& q, const SmallLevelIO& io, int B, int n, const int* dims, int L, int add_self, int bn) {
     if (!q.ok()) return;
@@ -1081,7 +1274,8 @@ void small_level_fwd(Seq& q, const SmallLevelIO& io, int B, int n, const int* di
 }
 
 void small_level_bwd(Seq& q, const SmallLevelIO& io, const float* dZe, float* dX0, float* dadj, float* slabs,
-                     long slab_stride, int B, int n, const int* dims, int L, int add_self, int bn) {
+                     long slab_stride, int B, int n, const int* dims, int L, int add_self, int bn,
+                     const SmallHeadFold* hf) {
     if (!q.ok()) return;
     static DynLdsOnce attr;
     ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_small_level_bwd), 159 * 1024, "k_small_level_bwd");
@@ -1106,8 +1300,17 @@ void small_level_bwd(Seq& q, const SmallLevelIO& io, const float* dZe, float* dX
     a.dev_err = device_error_word();
     a.spin_limit = knobs().test_barrier_fail ? 64 : SM_SPIN_LIMIT;
     a.target_bias = knobs().test_barrier_fail ? 1 : 0;
-    hipLaunchKernelGGL(k_small_level_bwd, dim3(B), dim3(1024),
-                       small_level_lds_bwd(B, n, dims, L, dadj != nullptr) * sizeof(float), q.stream, a);
+    size_t lds = small_level_lds_bwd(B, n, dims, L, dadj != nullptr);
+    if (hf) {
+        a.fold = 1;
+        a.hb = hf->hb;
+        a.hlevel = hf->level;
+        a.zcol = hf->zcol;
+        a.hpart = hf->part;
+        a.htot = head_grad_entries(hf->hb.h);
+        lds += SmHead(hf->hb.h).lds_floats(B);
+    }
+    hipLaunchKernelGGL(k_small_level_bwd, dim3(B), dim3(1024), lds * sizeof(float), q.stream, a);
     q.check_launch("small_level_bwd");
 }
 
