@@ -88,10 +88,12 @@ int device_error_take(bool clear) {
 static const char* device_error_text(int mask) {
     if ((mask & DP_DEVERR_BARRIER) && (mask & DP_DEVERR_NONFINITE_GRAD))
         return "a whole-level kernel's grid barrier gave up (its workgroups were not co-resident: is the device shared? "
-               "set DP_NO_LEVEL_FUSION=1) and dp_clip_adam_step refused the resulting non-finite gradients";
+               "set DP_NO_L0_PERSIST=1 DP_NO_LEVEL_FUSION=1) and dp_clip_adam_step refused the resulting non-finite "
+               "gradients";
     if (mask & DP_DEVERR_BARRIER)
         return "a whole-level kernel's grid barrier gave up: its workgroups were not co-resident (is the device shared "
-               "with another process or stream? set DP_NO_LEVEL_FUSION=1); that step's outputs are NaN";
+               "with another process or stream? set DP_NO_L0_PERSIST=1 DP_NO_LEVEL_FUSION=1); that step's outputs are "
+               "NaN";
     if (mask & DP_DEVERR_NONFINITE_GRAD)
         return "dp_clip_adam_step met a non-finite gradient norm and skipped the update (parameters untouched)";
     return mask ? "unknown device error bits" : "no device error";

@@ -64,7 +64,8 @@ const char* dp_last_error_string(void);
  * _packed forms, dp_clip_adam_step) finds the word set, clears it, returns DP_ERR_DEVICE before launching anything and
  * describes it in dp_last_error_string().  dp_device_error(clear) reads the current device's word directly (after a stream or
  * device synchronisation it is up to date); dp_device_error_describe(mask) is the text for a mask.  Escape hatch for
- * shared devices: DP_NO_LEVEL_FUSION=1 (no kernel with a grid barrier is used). */
+ * shared devices: DP_NO_L0_PERSIST=1 DP_NO_LEVEL_FUSION=1 together (no kernel with a grid barrier is used; either one
+ * alone leaves the level-0 or the pooled-level whole-level kernels in place). */
 #define DP_DEVERR_BARRIER 1
 #define DP_DEVERR_NONFINITE_GRAD 2
 int dp_device_error(int clear);

@@ -11,6 +11,8 @@ against the oracle therefore run the oracle with the winners the HIP forward rec
 forward comparison has shown that those winners hold the maximum up to rounding (the readout features agree)."""
 import torch
 
+from oracle import diffpool_oracle as O
+
 
 def close(a, b, rtol=1e-4, atol=1e-5):
     a = a.detach().cpu() if isinstance(a, torch.Tensor) else torch.as_tensor(a)
@@ -35,3 +37,11 @@ def grads_close(model, ref_grads, rtol=1e-3, atol_rel=2e-5):
 def gpu_winners(model, levels):
     """Rows the HIP forward's max readout picked, per level: int32 [B, D] (-1: a masked zero row holds the maximum)."""
     return [model.saved_activation(j, "readout_argmax").clone().cpu() for j in range(levels)]
+
+
+def _oracle_run(params, x, adj, nn_, label, linkpred, num_pooling=1, winners=None):
+    P = {k: v.clone().requires_grad_(True) for k, v in params.items()}
+    yo, inter = O.softpool_forward(P, x, adj, nn_, x, num_pooling=num_pooling, winners=winners)
+    lo, link = O.softpool_loss(yo, label, inter["assign_0"], adj, nn_, linkpred)
+    lo.backward()
+    return yo, inter, lo, {k: v.grad for k, v in P.items()}

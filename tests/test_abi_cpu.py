@@ -83,6 +83,10 @@ def test_device_error_word_decode(lib):
     assert b"grid barrier gave up" in bar and b"DP_NO_LEVEL_FUSION" in bar and b"non-finite" not in bar
     assert b"non-finite gradient norm" in nonf and b"skipped the update" in nonf and b"barrier" not in nonf
     assert b"grid barrier gave up" in both and b"non-finite" in both
+    # the escape hatch names BOTH knobs: DP_NO_LEVEL_FUSION alone leaves the persistent level-0 kernels and their
+    # barriers in place (tests/test_gpu_plan_matrix.py runs the pair and finds no barrier kernel)
+    for text in (bar, both):
+        assert b"DP_NO_L0_PERSIST=1" in text and b"DP_NO_LEVEL_FUSION=1" in text, text
     assert b"unknown" in lib.dp_device_error_describe(64)
 
 

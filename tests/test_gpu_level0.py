@@ -38,7 +38,7 @@ class _Counted:
 
 
 def _run_case(B, N, F_, H, Cc, ratio, p, linkpred, *, seed=1, n_min=None, sizes=None, weighted=False, masked=True,
-              onehot=True):
+              onehot=True, launches=(1, 1)):
     x, adj, nn_, label = O.make_batch(B, N, F_, n_min=n_min or max(1, N // 10), p=p, seed=seed, n_classes=Cc,
                                       sizes=sizes, onehot=onehot)
     if weighted:        # edge weights that bf16 cannot hold: the kernels must notice and multiply in fp32
@@ -56,7 +56,8 @@ def _run_case(B, N, F_, H, Cc, ratio, p, linkpred, *, seed=1, n_min=None, sizes=
         win = gpu_winners(model, 2)
         loss = model.loss(ypred, label.cuda(), ad, nn_arg) if linkpred else model.loss(ypred, label.cuda())
         loss.backward()
-    assert cnt.n == [1, 1], f"persistent level-0 kernels launched {cnt.n} times (forward, backward): the plan fell back"
+    assert cnt.n == list(launches), \
+        f"persistent level-0 kernels launched {cnt.n} times (forward, backward): expected {list(launches)}"
     P = {k: v.clone().requires_grad_(True) for k, v in params.items()}
     yo, inter = O.softpool_forward(P, x, adj, nn_arg, x, winners=win)
     lo, _ = O.softpool_loss(yo, label, inter["assign_0"], adj, nn_arg, linkpred)
@@ -80,6 +81,13 @@ def _run_case(B, N, F_, H, Cc, ratio, p, linkpred, *, seed=1, n_min=None, sizes=
 ])
 def test_persistent_level0_geometries_against_the_oracle(B, N, F_, H, Cc, ratio, p, linkpred, tag):
     _run_case(B, N, F_, H, Cc, ratio, p, linkpred)
+
+
+def test_persistent_forward_with_the_per_phase_backward():
+    """The mixed plan, taken without any knob: K = 56 clusters at N = 64 fit the persistent forward (32-row blocks) but
+    not the persistent backward, whose staged rows 2*32*K + 32*D + K^2 = 8640 floats (D = 60) exceed the block's 8320
+    (dp_level0.hip l0b_geometry).  The per-phase backward then reads the Y / invn / stats the persistent forward saved."""
+    _run_case(4, 64, 5, 20, 3, 0.875, 0.15, False, launches=(1, 0))
 
 
 def test_persistent_level0_with_tiny_and_full_graphs():

@@ -13,7 +13,7 @@ import torch
 from graph_pooling_amd.encoders import GcnEncoderGraph, GcnSet2SetEncoder, SoftPoolingGcnEncoder
 from graph_pooling_amd.set2set import Set2Set
 from oracle import diffpool_oracle as O
-from tests.parity import close, grads_close, gpu_winners
+from tests.parity import _oracle_run, close, grads_close, gpu_winners
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -116,14 +116,6 @@ def test_base_encoder_against_reference_golden(tag, golden):
     close(loss, a["loss"], 1e-5, 1e-6)
     loss.backward()
     grads_close(model, grads)
-
-
-def _oracle_run(params, x, adj, nn_, label, linkpred, num_pooling=1, winners=None):
-    P = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-    yo, inter = O.softpool_forward(P, x, adj, nn_, x, num_pooling=num_pooling, winners=winners)
-    lo, link = O.softpool_loss(yo, label, inter["assign_0"], adj, nn_, linkpred)
-    lo.backward()
-    return yo, inter, lo, {k: v.grad for k, v in P.items()}
 
 
 @pytest.mark.parametrize("B,N,F_,H,Cc,ratio,p,linkpred,tag", [
