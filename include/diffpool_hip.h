@@ -255,6 +255,23 @@ int dp_sparse_gcn_layer_bwd(const float* ax, const int* indptr, const int* indic
                             const float* dy, int lddy, float* dx, int lddx, float* dW, float* db, int n, int Fin,
                             int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ N4  level-0 pooling on a CSR graph
+ * Xp = S^T Z [K,D], Ap = S^T A S [K,K] — encoders.py:1278-1279 on ONE graph whose 0/1 adjacency A is given as CSR
+ * (row i lists the j with A[i,j] = 1).  S [n,K] (lds), Z [n,D] (ldz).  Xp / Ap OVERWRITTEN.  The forward gathers
+ * (A S)_i into LDS row slab by row slab and multiplies S_slab^T [A S | Z]_slab on the fp32 matrix cores; the slabs'
+ * partial K x (K+D) blocks are summed in slab order by a second launch: deterministic, no float atomics, and A S is
+ * never written to memory.  1 <= K <= 256, 1 <= D <= 512 (DP_ERR_UNSUPPORTED outside), lds >= K, ldz >= D. */
+size_t dp_csr_pool_workspace_bytes(int n, int K, int D);
+int dp_csr_pool_fwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                    float* Xp, float* Ap, int n, int K, int D, void* workspace, size_t workspace_bytes, void* stream);
+/* dS [n,K] OVERWRITTEN = (A S) dAp^T + (A^T S) dAp + Z dXp^T;  dZ [n,D] ACCUMULATED INTO += S dXp (dp_pool_bwd's
+ * contract).  indptr_t / indices_t: CSR of A^T; pass the forward's arrays for an undirected graph (the A^T S gather is
+ * then skipped).  Row-local: no atomics, bit-reproducible. */
+int dp_csr_pool_bwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                    const int* indptr_t, const int* indices_t, const float* dXp, const float* dAp,
+                    float* dS, int ldds, float* dZ, int lddz, int n, int K, int D,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ================================================================== model-level entry points
  * One call enqueues the whole forward (or backward) of an encoder, so the Python host pays one
  * FFI crossing per pass instead of ~100.  Parameters live in ONE flat fp32 buffer; the cfg gives
