@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 from torch.nn import init
 
-from . import _lib
+from . import _lib, ops
 from .set2set import Set2Set
 
 
@@ -63,49 +63,6 @@ class PackedAdjacency:
         return cls(pk, pkt, N)
 
 
-class _GraphConvFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, adj, weight, bias, flags):
-        lib = _lib.load()
-        _lib.require_gpu_tensor(x, "x")
-        x = x.contiguous().float()
-        adj = adj.contiguous().float()
-        B, n, fin = x.shape
-        fout = weight.shape[1]
-        y = torch.empty(B, n, fout, device=x.device, dtype=torch.float32)
-        invn = torch.empty(B, n, device=x.device, dtype=torch.float32)
-        wsb = lib.dp_gcn_layer_workspace_bytes(B, n, fin, fout)
-        ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
-        w = weight.contiguous()
-        _lib.check(lib.dp_gcn_layer_fwd(x.data_ptr(), fin, adj.data_ptr(), w.data_ptr(), _lib.ptr(bias),
-                                        y.data_ptr(), fout, invn.data_ptr(), B, n, fin, fout, flags,
-                                        ws.data_ptr(), wsb, _lib.current_stream()), "dp_gcn_layer_fwd")
-        ctx.save_for_backward(x, adj, w, y, invn)
-        ctx.flags = flags
-        ctx.has_bias = bias is not None
-        ctx.ws = ws
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, adj, w, y, invn = ctx.saved_tensors
-        B, n, fin = x.shape
-        fout = w.shape[1]
-        dy = dy.contiguous()
-        need_dx, need_dadj = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dx = torch.empty_like(x) if need_dx else None
-        dadj = torch.empty_like(adj) if need_dadj else None
-        dw = torch.empty_like(w)
-        db = torch.empty(fout, device=x.device, dtype=torch.float32) if ctx.has_bias else None
-        ws = ctx.ws
-        _lib.check(lib.dp_gcn_layer_bwd(x.data_ptr(), fin, adj.data_ptr(), w.data_ptr(), y.data_ptr(), fout,
-                                        invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin, dw.data_ptr(),
-                                        _lib.ptr(db), _lib.ptr(dadj), B, n, fin, fout, ctx.flags,
-                                        ws.data_ptr(), ws.numel(), _lib.current_stream()), "dp_gcn_layer_bwd")
-        return dx, dadj, dw, db, None
-
-
 class GraphConv(nn.Module):
     """y = l2norm((adj @ x [+ x]) @ W + b) — the DiffPool GraphConv (encoders.py:945-974)."""
 
@@ -125,7 +82,7 @@ class GraphConv(nn.Module):
     def forward(self, x, adj):
         if self.dropout > 0.001:
             x = nn.functional.dropout(x, self.dropout, self.training)
-        return _GraphConvFn.apply(x, adj, self.weight, self.bias, self._flags())
+        return ops.graph_conv(x, adj, self.weight, self.bias, self._flags())
 
 
 # ----------------------------------------------------------------------------- helpers

@@ -36,7 +36,7 @@ class SupervisedGraphSage(nn.Module):
 
     def forward(self, nodes) -> Tensor:
         from . import _lib
-        from .sparse import hip_linear
+        from .ops import hip_linear
         emb = self.enc(nodes)
         _lib.require_gpu_tensor(emb, "enc(nodes)")            # no CPU path, like every other module of the package
         return hip_linear(emb, self.weight.t())               # the library's fp32 MFMA GEMM (scores = emb @ weight)

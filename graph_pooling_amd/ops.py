@@ -1,0 +1,388 @@
+"""The per-op layer: one autograd wrapper per dp_*_fwd / dp_*_bwd pair of libdiffpool_hip.so that the package calls
+outside the whole-model entries (dp_encoder_* / dp_loss_*, encoders.py), each exposed as a plain function.
+
+Sits below `encoders`, `sparse` and `graphsage`: it imports only `_lib` and torch.  Every wrapper makes its inputs
+contiguous, allocates the outputs and the workspace the C entry asks for, and keeps for the backward what the forward
+wrote (the workspace included, where the backward entry reads it).  No torch arithmetic, no CPU path.  Line numbers
+cite the reference's encoders.py.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+
+
+def _f32(like, *shape):
+    """A fresh, uninitialised fp32 tensor on `like`'s device."""
+    return torch.empty(*shape, device=like.device, dtype=torch.float32)
+
+
+def _workspace(nbytes, like):
+    """The buffer a dp_*_workspace_bytes call asked for, on `like`'s device."""
+    return torch.empty(nbytes, device=like.device, dtype=torch.uint8)
+
+
+# ----------------------------------------------------------------------------- Linear on the HIP GEMM
+class _LinearFn(torch.autograd.Function):
+    """y = x W^T + b (nn.Linear layout, W [out, in]) on dp_bgemm_f32 — forward and both gradients."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(x, "x")
+        x = x.contiguous().float()
+        w = weight.contiguous()
+        rows, fin = x.shape
+        fout = w.shape[0]
+        y = _f32(x, rows, fout)
+        st = _lib.current_stream()
+        _lib.check(lib.dp_bgemm_f32(x.data_ptr(), w.data_ptr(), y.data_ptr(), _lib.ptr(bias), 1, rows, fout, fin, fin, fin,
+                                    fout, 0, 0, 0, 0, 1, 1.0, 0.0, 0, st), "dp_bgemm_f32")
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        rows, fin = x.shape
+        fout = w.shape[0]
+        st = _lib.current_stream()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)          # dx = dy W
+            _lib.check(lib.dp_bgemm_f32(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), None, 1, rows, fin, fout, fout, fin,
+                                        fin, 0, 0, 0, 0, 0, 1.0, 0.0, 0, st), "dp_bgemm_f32")
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(w)          # dW = dy^T x
+            _lib.check(lib.dp_bgemm_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), None, 1, fout, fin, rows, fout, fin,
+                                        fin, 0, 0, 0, 1, 0, 1.0, 0.0, 0, st), "dp_bgemm_f32")
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            ones = torch.ones(1, rows, device=x.device, dtype=torch.float32)      # db = 1^T dy
+            db = _f32(x, fout)
+            _lib.check(lib.dp_bgemm_f32(ones.data_ptr(), dy.data_ptr(), db.data_ptr(), None, 1, 1, fout, rows, rows,
+                                        fout, fout, 0, 0, 0, 0, 0, 1.0, 0.0, 0, st), "dp_bgemm_f32")
+        return dx, dw, db
+
+
+def hip_linear(x, weight, bias=None):
+    """nn.Linear's arithmetic (x @ weight.T + bias) on the library's fp32 MFMA GEMM; x [rows, in]."""
+    return _LinearFn.apply(x, weight, bias)
+
+
+def mlp_head(feat, linears):
+    """pred_model (encoders.py:1295-1299) on `hip_linear`: ReLU between the Linear layers, none after the last."""
+    for i, lin in enumerate(linears):
+        feat = hip_linear(feat, lin.weight, lin.bias)
+        if i < len(linears) - 1:
+            feat = torch.relu(feat)
+    return feat
+
+
+# ----------------------------------------------------------------------------- GraphConv, dense and CSR
+class _GraphConvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, adj, weight, bias, flags):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(x, "x")
+        x = x.contiguous().float()
+        adj = adj.contiguous().float()
+        B, n, fin = x.shape
+        fout = weight.shape[1]
+        y, invn = _f32(x, B, n, fout), _f32(x, B, n)
+        wsb = lib.dp_gcn_layer_workspace_bytes(B, n, fin, fout)
+        ws = _workspace(wsb, x)
+        w = weight.contiguous()
+        _lib.check(lib.dp_gcn_layer_fwd(x.data_ptr(), fin, adj.data_ptr(), w.data_ptr(), _lib.ptr(bias),
+                                        y.data_ptr(), fout, invn.data_ptr(), B, n, fin, fout, flags,
+                                        ws.data_ptr(), wsb, _lib.current_stream()), "dp_gcn_layer_fwd")
+        ctx.save_for_backward(x, adj, w, y, invn)
+        ctx.flags, ctx.ws, ctx.has_bias = flags, ws, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, adj, w, y, invn = ctx.saved_tensors
+        B, n, fin = x.shape
+        fout = w.shape[1]
+        dy = dy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dadj = torch.empty_like(adj) if ctx.needs_input_grad[1] else None
+        dw = torch.empty_like(w)
+        db = _f32(x, fout) if ctx.has_bias else None
+        _lib.check(lib.dp_gcn_layer_bwd(x.data_ptr(), fin, adj.data_ptr(), w.data_ptr(), y.data_ptr(), fout,
+                                        invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin, dw.data_ptr(),
+                                        _lib.ptr(db), _lib.ptr(dadj), B, n, fin, fout, ctx.flags,
+                                        ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream()), "dp_gcn_layer_bwd")
+        return dx, dadj, dw, db, None
+
+
+def graph_conv(x, adj, weight, bias, flags):
+    """y = l2norm((adj @ x [+ x]) @ W + b) (encoders.py:945-974) on a dense batch: x [B, n, F], adj [B, n, n],
+    W [F, F']; `flags` is `GraphConv._flags()`."""
+    return _GraphConvFn.apply(x, adj, weight, bias, flags)
+
+
+class _CsrGraphConvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, g, flags):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(x, "x")
+        x = x.contiguous().float()
+        w = weight.contiguous()
+        n, fin = x.shape
+        fout = w.shape[1]
+        y, ax, invn = _f32(x, n, fout), _f32(x, n, fin), _f32(x, n)
+        wsb = lib.dp_sparse_gcn_layer_workspace_bytes(n, fin, fout)
+        ws = _workspace(wsb, x)
+        _lib.check(lib.dp_sparse_gcn_layer_fwd(x.data_ptr(), fin, g.indptr.data_ptr(), g.indices.data_ptr(), w.data_ptr(),
+                                               _lib.ptr(bias), y.data_ptr(), fout, ax.data_ptr(), invn.data_ptr(), n,
+                                               fin, fout, flags, ws.data_ptr(), wsb, _lib.current_stream()),
+                   "dp_sparse_gcn_layer_fwd")
+        ctx.save_for_backward(ax, w, y, invn)
+        ctx.g, ctx.flags, ctx.ws, ctx.has_bias = g, flags, ws, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        ax, w, y, invn = ctx.saved_tensors
+        g = ctx.g
+        n, fin = ax.shape
+        fout = w.shape[1]
+        dy = dy.contiguous()
+        dx = torch.empty_like(ax) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w)
+        db = _f32(ax, fout) if ctx.has_bias else None
+        _lib.check(lib.dp_sparse_gcn_layer_bwd(ax.data_ptr(), g.indptr.data_ptr(), g.indices.data_ptr(),
+                                               g.indptr_t.data_ptr(), g.indices_t.data_ptr(), w.data_ptr(), y.data_ptr(),
+                                               fout, invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin,
+                                               dw.data_ptr(), _lib.ptr(db), n, fin, fout, ctx.flags, ctx.ws.data_ptr(),
+                                               ctx.ws.numel(), _lib.current_stream()), "dp_sparse_gcn_layer_bwd")
+        return dx, dw, db, None, None
+
+
+def csr_graph_conv(x, weight, bias, graph, flags):
+    """`graph_conv` on ONE graph given as CSR: x [n, F]; `graph` carries int32 indptr / indices of A and of A^T (the
+    neighbour sum A x is the gather of dp_csr_aggregate, the backward gathers over A^T)."""
+    return _CsrGraphConvFn.apply(x, weight, bias, graph, flags)
+
+
+# ----------------------------------------------------------------------------- row ops on one graph (B = 1)
+class _BnReluNodesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        x = x.contiguous()
+        n, f = x.shape
+        y = torch.empty_like(x)
+        stats = _f32(x, n, 2)
+        wsb = lib.dp_bn_node_workspace_bytes(1, n, f)
+        ws = _workspace(wsb, x)
+        _lib.check(lib.dp_bn_node_fwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), 1, n, f, 1, ws.data_ptr(), wsb,
+                                      _lib.current_stream()), "dp_bn_node_fwd")
+        ctx.save_for_backward(x, y, stats)
+        ctx.ws = ws
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, y, stats = ctx.saved_tensors
+        n, f = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        _lib.check(lib.dp_bn_node_bwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), dy.data_ptr(), f, dx.data_ptr(),
+                                      f, 1, n, f, 1, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream()),
+                   "dp_bn_node_bwd")
+        return dx
+
+
+def bn_relu_nodes(x):
+    """apply_bn (encoders.py:1048-1052) after ReLU on ONE graph, x [n, f]: dp_bn_node_* with a batch of one, the ReLU
+    fused into the kernel."""
+    return _BnReluNodesFn.apply(x)
+
+
+class _RowMaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        x = x.contiguous()
+        n, f = x.shape
+        out = _f32(x, 1, f)
+        arg = torch.empty(1, f, device=x.device, dtype=torch.int32)
+        _lib.check(lib.dp_masked_max_fwd(x.data_ptr(), f, None, out.data_ptr(), f, arg.data_ptr(), 1, n, f,
+                                         _lib.current_stream()), "dp_masked_max_fwd")
+        ctx.save_for_backward(arg)
+        ctx.shape = (n, f)
+        ctx.mark_non_differentiable(arg)
+        ctx.set_materialize_grads(False)      # no zero-fill launch for the unused gradient of `arg`
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        lib = _lib.load()
+        (arg,) = ctx.saved_tensors
+        n, f = ctx.shape
+        dx = torch.zeros(n, f, device=dout.device, dtype=torch.float32)
+        dout = dout.contiguous()
+        _lib.check(lib.dp_masked_max_bwd(dout.data_ptr(), f, arg.data_ptr(), dx.data_ptr(), f, 1, n, f,
+                                         _lib.current_stream()), "dp_masked_max_bwd")
+        return dx
+
+
+def row_max(x):
+    """Max over the node rows of x [n, f] (torch.max(x, dim=1), encoders.py:1093; the readouts :1257, :1287) through
+    dp_masked_max_* with B = 1 and no mask -> (out [1, f], arg-max rows int32 [1, f], not differentiable)."""
+    return _RowMaxFn.apply(x)
+
+
+# ----------------------------------------------------------------------------- DiffPool's assignment and pooling
+class _AssignFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, weight, bias):
+        lib = _lib.load()
+        z = z.contiguous()
+        n, din = z.shape
+        k = weight.shape[0]
+        w = weight.contiguous()
+        s = _f32(z, n, k)
+        wsb = lib.dp_assign_workspace_bytes(1, n, din, k)
+        ws = _workspace(wsb, z)
+        _lib.check(lib.dp_assign_softmax_mask_fwd(z.data_ptr(), din, w.data_ptr(), bias.data_ptr(), None, s.data_ptr(),
+                                                  1, n, din, k, ws.data_ptr(), wsb, _lib.current_stream()),
+                   "dp_assign_softmax_mask_fwd")
+        ctx.save_for_backward(z, w, s)
+        ctx.ws = ws
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        lib = _lib.load()
+        z, w, s = ctx.saved_tensors
+        n, din = z.shape
+        k = w.shape[0]
+        ds = ds.contiguous()
+        dz, dw, db = torch.empty_like(z), torch.empty_like(w), _f32(z, k)
+        _lib.check(lib.dp_assign_softmax_mask_bwd(z.data_ptr(), din, w.data_ptr(), s.data_ptr(), ds.data_ptr(), None,
+                                                  dz.data_ptr(), din, dw.data_ptr(), db.data_ptr(), 1, n, din, k,
+                                                  ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream()),
+                   "dp_assign_softmax_mask_bwd")
+        return dz, dw, db
+
+
+def assign_softmax(z, weight, bias):
+    """S = softmax(z Wp^T + bp) (encoders.py:1273) on one graph, z [n, d]: dp_assign_softmax_mask_* with B = 1 and no
+    mask (every row is a node)."""
+    return _AssignFn.apply(z, weight, bias)
+
+
+class _CsrPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, z, g):
+        lib = _lib.load()
+        s, z = s.contiguous(), z.contiguous()
+        n, k = s.shape
+        d = z.shape[1]
+        xp, ap = _f32(s, k, d), _f32(s, k, k)
+        wsb = lib.dp_csr_pool_workspace_bytes(n, k, d)
+        ws = _workspace(wsb, s)
+        _lib.check(lib.dp_csr_pool_fwd(s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr(),
+                                       xp.data_ptr(), ap.data_ptr(), n, k, d, ws.data_ptr(), wsb,
+                                       _lib.current_stream()), "dp_csr_pool_fwd")
+        ctx.save_for_backward(s, z)
+        ctx.g, ctx.ws = g, ws
+        return xp, ap
+
+    @staticmethod
+    def backward(ctx, dxp, dap):
+        lib = _lib.load()
+        s, z = ctx.saved_tensors
+        g = ctx.g
+        n, k = s.shape
+        d = z.shape[1]
+        dxp, dap = dxp.contiguous(), dap.contiguous()
+        ds = torch.empty_like(s)
+        dz = torch.zeros_like(z)
+        _lib.check(lib.dp_csr_pool_bwd(s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr(),
+                                       g.indptr_t.data_ptr(), g.indices_t.data_ptr(), dxp.data_ptr(), dap.data_ptr(),
+                                       ds.data_ptr(), k, dz.data_ptr(), d, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(),
+                                       _lib.current_stream()), "dp_csr_pool_bwd")
+        return ds, dz, None
+
+
+def csr_pool(s, z, graph):
+    """Level-0 pooling X' = S^T Z [k, d], A' = S^T A S [k, k] (encoders.py:1278-1279) with A as CSR: dp_csr_pool_*."""
+    return _CsrPoolFn.apply(s, z, graph)
+
+
+class _DensePoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, z, adj):
+        lib = _lib.load()
+        s, z, adj = s.contiguous(), z.contiguous(), adj.contiguous()
+        n, k = s.shape
+        d = z.shape[1]
+        xp, ap, t = _f32(s, k, d), _f32(s, k, k), _f32(s, k, n)
+        _lib.check(lib.dp_pool_fwd(s.data_ptr(), z.data_ptr(), d, adj.data_ptr(), xp.data_ptr(), ap.data_ptr(),
+                                   t.data_ptr(), 1, n, k, d, _lib.current_stream()), "dp_pool_fwd")
+        ctx.save_for_backward(s, z, adj, t)
+        return xp, ap
+
+    @staticmethod
+    def backward(ctx, dxp, dap):
+        lib = _lib.load()
+        s, z, adj, t = ctx.saved_tensors
+        n, k = s.shape
+        d = z.shape[1]
+        dxp, dap = dxp.contiguous(), dap.contiguous()
+        ds, dz = torch.empty_like(s), torch.zeros_like(z)
+        dadj = torch.zeros_like(adj) if ctx.needs_input_grad[2] else None
+        wsb = lib.dp_pool_bwd_workspace_bytes(1, n, k, d)
+        ws = _workspace(wsb, s)
+        _lib.check(lib.dp_pool_bwd(s.data_ptr(), z.data_ptr(), d, adj.data_ptr(), t.data_ptr(), dxp.data_ptr(),
+                                   dap.data_ptr(), ds.data_ptr(), dz.data_ptr(), d, _lib.ptr(dadj), 1, n, k, d,
+                                   ws.data_ptr(), wsb, _lib.current_stream()), "dp_pool_bwd")
+        return ds, dz, dadj
+
+
+def dense_pool(s, z, adj):
+    """The same pooling on a pooled level (dense n x n adjacency): dp_pool_* with B = 1."""
+    return _DensePoolFn.apply(s, z, adj)
+
+
+# ----------------------------------------------------------------------------- loss
+class _CrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, label):
+        lib = _lib.load()
+        logits = logits.contiguous()
+        b, c = logits.shape
+        label = label.to(device=logits.device, dtype=torch.int64).contiguous()
+        loss = _f32(logits, ())
+        prob = torch.empty_like(logits)
+        _lib.check(lib.dp_cross_entropy_fwd(logits.data_ptr(), label.data_ptr(), loss.data_ptr(), prob.data_ptr(), b, c,
+                                            _lib.current_stream()), "dp_cross_entropy_fwd")
+        ctx.save_for_backward(prob, label)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        prob, label = ctx.saved_tensors
+        b, c = prob.shape
+        dloss = dloss.contiguous().float()
+        dlogits = torch.empty_like(prob)
+        _lib.check(lib.dp_cross_entropy_bwd(prob.data_ptr(), label.data_ptr(), dloss.data_ptr(), dlogits.data_ptr(), b,
+                                            c, _lib.current_stream()), "dp_cross_entropy_bwd")
+        return dlogits, None
+
+
+def cross_entropy(logits, label):
+    """F.cross_entropy with mean reduction (encoders.py:1127) on dp_cross_entropy_fwd / bwd; logits [b, c]."""
+    return _CrossEntropyFn.apply(logits, label)

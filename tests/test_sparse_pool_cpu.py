@@ -3,11 +3,14 @@ SoftPoolingGcnEncoder, refuses what it does not run, and the dp_csr_pool kernels
 (read offline from the gfx950 code object, as test_kernel_resources_cpu.py does)."""
 import importlib.util
 import os
+import subprocess
+import sys
 
 import pytest
+import torch
 
-from graph_pooling_amd.encoders import SoftPoolingGcnEncoder
-from graph_pooling_amd.sparse import SparseSoftPoolingGcnEncoder
+from graph_pooling_amd.encoders import GcnEncoderGraph, SoftPoolingGcnEncoder
+from graph_pooling_amd.sparse import SparseGcnEncoderGraph, SparseSoftPoolingGcnEncoder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "graph_pooling_amd", "libdiffpool_hip.so")
@@ -51,6 +54,37 @@ def test_csr_path_refusals_name_the_reason():
         m.saved_activation(0, "assign")
     with pytest.raises(TypeError, match="CsrGraph"):
         m.forward(None, None)
+
+
+@pytest.mark.parametrize("bn", [True, False])
+@pytest.mark.parametrize("concat", [True, False])
+@pytest.mark.parametrize("hidden", [[], [50], [20, 10]])
+def test_base_encoder_state_dict_equals_the_dense_class_under_one_seed(hidden, concat, bn):
+    """SparseGcnEncoderGraph's contract: the dense class's keys, in its order, and its initial values."""
+    kw = dict(pred_hidden_dims=hidden, concat=concat, bn=bn)
+    torch.manual_seed(11)
+    dense = GcnEncoderGraph(7, 12, 9, 3, 3, **kw).state_dict()
+    torch.manual_seed(11)
+    sparse = SparseGcnEncoderGraph(7, 12, 9, 3, 3, **kw).state_dict()
+    assert list(sparse) == list(dense)
+    for k, v in dense.items():
+        assert torch.equal(sparse[k], v), k
+
+
+def test_base_encoder_refusals():
+    with pytest.raises(NotImplementedError, match="dropout on the CSR path"):
+        SparseGcnEncoderGraph(7, 12, 9, 3, 3, dropout=0.5)
+    m = SparseGcnEncoderGraph(7, 12, 9, 3, 3)
+    with pytest.raises(TypeError, match="GcnEncoderGraph's"):         # the dense call form is not inherited
+        m.forward(torch.zeros(2, 5, 7), torch.zeros(2, 5, 5))
+
+
+def test_ops_sits_below_encoders_and_sparse():
+    code = ("import sys, graph_pooling_amd.ops\n"
+            "bad = [m for m in ('encoders', 'sparse', 'set2set') if 'graph_pooling_amd.' + m in sys.modules]\n"
+            "assert not bad, bad")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
 
 
 # ------------------------------------------------------------------ kernel resources
