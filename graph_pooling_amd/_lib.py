@@ -101,6 +101,7 @@ _PROTOS = {
     "dp_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dp_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dp_set2set_save_bytes": (_Z, [_I, _I, _I]),
+    "dp_set2set_plan": (_I, [_I, _I]),
     "dp_set2set_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_set2set_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_set2set_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P,

@@ -142,6 +142,7 @@ void set2set_bwd(Seq& q, const float* emb, int lde, const float* w_ih, const flo
                  float* demb, int ldde, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, float* dWp,
                  float* dbp, int B, int n, int d, const void* save);
 size_t set2set_save_bytes(int B, int n, int d);
+int set2set_plan(int n, int d);
 // dp_meanagg.hip
 void mean_aggregate_fwd(Seq& q, const float* table, int ldt, const int* indptr, const int* indices, float* out,
                         int ldo, int n_rows, int feat);
@@ -569,12 +570,15 @@ int dp_cross_entropy_bwd(const float* prob, const long long* label, const float*
 }
 
 size_t dp_set2set_save_bytes(int B, int n, int d) { return set2set_save_bytes(B, n, d); }
+int dp_set2set_plan(int n, int d) { return set2set_plan(n, d); }
 int dp_set2set_fwd(const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
                    const float* b_hh, const float* Wp, const float* bp, float* out, int B, int n, int d, void* save,
                    size_t save_bytes, void* stream) {
     NOTNULL(emb); NOTNULL(w_ih); NOTNULL(w_hh); NOTNULL(b_ih); NOTNULL(b_hh); NOTNULL(Wp); NOTNULL(bp); NOTNULL(out);
     NOTNULL(save);
-    NONNEG(B); NONNEG(n); NONNEG(d);
+    DP_CHECK_ARG(B >= 0, "B=%d must not be negative", B);      // B == 0: DP_OK, nothing is launched
+    NONNEG(n); NONNEG(d);
+    DP_CHECK_ARG(lde >= d, "lde=%d smaller than the row width d=%d", lde, d);
     DP_CHECK_ARG(save_bytes >= set2set_save_bytes(B, n, d), "set2set save buffer too small: %zu < %zu",
                  save_bytes, set2set_save_bytes(B, n, d));
     Seq q(STREAM(stream), nullptr, 0);
@@ -593,7 +597,9 @@ int dp_set2set_bwd(const float* emb, int lde, const float* w_ih, const float* w_
                    size_t workspace_bytes, void* stream) {
     NOTNULL(emb); NOTNULL(w_ih); NOTNULL(w_hh); NOTNULL(Wp); NOTNULL(out); NOTNULL(dout); NOTNULL(demb);
     NOTNULL(dw_ih); NOTNULL(dw_hh); NOTNULL(db_ih); NOTNULL(db_hh); NOTNULL(dWp); NOTNULL(dbp); NOTNULL(save);
-    NONNEG(B); NONNEG(n); NONNEG(d);
+    DP_CHECK_ARG(B >= 0, "B=%d must not be negative", B);      // B == 0: DP_OK, the parameter gradients are zeroed
+    NONNEG(n); NONNEG(d);
+    DP_CHECK_ARG(lde >= d && ldde >= d, "lde=%d / ldde=%d smaller than the row width d=%d", lde, ldde, d);
     DP_CHECK_ARG(save_bytes >= set2set_save_bytes(B, n, d), "set2set save buffer too small");
     Seq q(STREAM(stream), workspace, workspace_bytes);
     set2set_bwd(q, emb, lde, w_ih, w_hh, b_ih, b_hh, Wp, bp, out, dout, demb, ldde, dw_ih, dw_hh, db_ih, db_hh, dWp,

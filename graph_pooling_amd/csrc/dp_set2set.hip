@@ -284,11 +284,15 @@ __global__ __launch_bounds__(S2S_NT) void k_set2set_fwd(S2SFwdArgs a) {
     }
     // ---- out = relu(Wp [h, r] + bp)
     if (a.QN && tid < 2 * d) a.QN[(long)b * 2 * d + tid] = h[tid];
-    for (int j = tid; j < d; j += S2S_NT) {
-        float acc = a.bp[j];
+    // One sixteen-lane team per output, the bias added last: as ONE serial chain that starts from the bias the 2d-term
+    // sum rounded at the size of its partial sums — 1.5e-6 of the largest output at d = 256, 7 x the error of an fp32
+    // CPU run, while every other tensor sat within 1.7 x (profiles/set2set_fp64_anchor.txt).
+    for (int j = team; j < d; j += 64) {
         const float* wr = a.Wp + (long)j * 2 * d;
-        for (int k = 0; k < 2 * d; ++k) acc += wr[k] * h[k];
-        a.out[(long)b * d + j] = fmaxf(acc, 0.f);
+        float s = 0.f;
+        for (int k = tl; k < 2 * d; k += 16) s += wr[k] * h[k];
+        s = team16_sum(s);
+        if (tl == 0) a.out[(long)b * d + j] = fmaxf(s + a.bp[j], 0.f);
     }
 }
 
@@ -498,22 +502,42 @@ size_t s2s_dyn_lds(int n, int d, bool w_in_lds, bool emb_in_lds = false) {
 bool s2s_w_fits(int n, int d) { return s2s_dyn_lds(n, d, true) <= 158 * 1024; }
 // the lanes of a gate / output team keep their weights in registers for the whole recurrence (k_set2set_*: WF)
 bool s2s_w_in_regs(int d) { return 4 * d <= 256 && ((2 * d + 3) >> 2) <= 32 && ((4 * d + 7) >> 3) <= 32; }
-bool s2s_emb_fits(int n, int d) { return s2s_dyn_lds(n, d, s2s_w_fits(n, d), true) <= 158 * 1024; }
+
+constexpr int S2S_WL = 1, S2S_EL = 2, S2S_WF = 4;      // bits of set2set_plan (diffpool_hip.h: dp_set2set_plan)
 
 }  // namespace
 
 size_t set2set_save_bytes(int B, int n, int d) { return s2s_layout(B, n, d).total * sizeof(float) + 256; }
+
+// The ONE place that picks the k_set2set_* variant, for the forward and the backward alike (host only, no GPU call).
+// The embedding is staged in LDS only beside weights that sit in registers or in LDS: no instance of the kernels
+// combines it with weights read from global memory, so d >= 70 never asks for that LDS.
+int set2set_plan(int n, int d) {
+    if (n < 1 || d < 1 || d > 256 || n > 1024 || s2s_dyn_lds(n, d, false) > 158 * 1024) return DP_ERR_UNSUPPORTED;
+    const bool wf = s2s_w_in_regs(d);
+    const bool wl = !wf && s2s_w_fits(n, d);
+    const bool el = (wf || wl) && s2s_dyn_lds(n, d, wl, true) <= 158 * 1024;
+    return (wl ? S2S_WL : 0) | (el ? S2S_EL : 0) | (wf ? S2S_WF : 0);
+}
+
+namespace {
+int s2s_plan_or_error(Seq& q, int n, int d) {
+    const int plan = set2set_plan(n, d);
+    if (plan < 0) {
+        set_error("Set2Set: n=%d / d=%d outside the persistent kernel's limits (1 <= n <= 1024, 1 <= d <= 256)", n, d);
+        q.err = DP_ERR_UNSUPPORTED;
+    }
+    return plan;
+}
+}  // namespace
 
 void set2set_fwd(Seq& q, const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
                  const float* b_hh, const float* Wp, const float* bp, float* out, int B, int n, int d, void* save) {
     if (q.err) return;
     const S2SLayout L = s2s_layout(B, n, d);
     if (!q.ok()) return;
-    if (s2s_dyn_lds(n, d, false) > 158 * 1024 || d > 256 || n > 1024) {
-        set_error("Set2Set: n=%d / d=%d outside the persistent kernel's limits (n <= 1024, d <= 256)", n, d);
-        q.err = DP_ERR_UNSUPPORTED;
-        return;
-    }
+    const int plan = s2s_plan_or_error(q, n, d);
+    if (plan < 0 || B == 0) return;                    // (an empty batch has no output row: nothing to launch)
     float* sv = (float*)save;
     float* wt = sv + L.wt;
     hipLaunchKernelGGL(k_s2s_prep, dim3((8 * d * d + 255) / 256), dim3(256), 0, q.stream, w_ih, w_hh, wt, d, L.GS);
@@ -522,9 +546,8 @@ void set2set_fwd(Seq& q, const float* emb, int lde, const float* w_ih, const flo
     a.emb = emb; a.lde = lde; a.wt = wt; a.b_ih = b_ih; a.b_hh = b_hh; a.Wp = Wp; a.bp = bp; a.out = out;
     a.QP = sv + L.qp; a.H = sv + L.h; a.Cs = sv + L.c; a.G = sv + L.g; a.Aw = sv + L.a; a.QN = sv + L.qn;
     a.n = n; a.d = d; a.GS = L.GS;
-    const bool wf = s2s_w_in_regs(d);
-    a.w_in_lds = !wf && s2s_w_fits(n, d) ? 1 : 0;
-    a.emb_in_lds = s2s_dyn_lds(n, d, a.w_in_lds, true) <= 158 * 1024 ? 1 : 0;
+    a.w_in_lds = plan & S2S_WL ? 1 : 0;
+    a.emb_in_lds = plan & S2S_EL ? 1 : 0;
     const size_t ldsb = s2s_dyn_lds(n, d, a.w_in_lds, a.emb_in_lds);
     auto go = [&](auto kern, DynLdsOnce& at) {
         ensure_dyn_lds(q, at, reinterpret_cast<const void*>(kern), 160 * 1024, "k_set2set_fwd");
@@ -532,11 +555,13 @@ void set2set_fwd(Seq& q, const float* emb, int lde, const float* w_ih, const flo
         hipLaunchKernelGGL(kern, dim3(B), dim3(S2S_NT), ldsb, q.stream, a);
     };
     static DynLdsOnce at00, at10, at11, af0, af1;
-    if (wf && a.emb_in_lds) go(&k_set2set_fwd<false, true, true>, af1);
-    else if (wf) go(&k_set2set_fwd<false, false, true>, af0);
-    else if (a.w_in_lds && a.emb_in_lds) go(&k_set2set_fwd<true, true, false>, at11);
-    else if (a.w_in_lds) go(&k_set2set_fwd<true, false, false>, at10);
-    else go(&k_set2set_fwd<false, false, false>, at00);
+    switch (plan) {
+        case S2S_WF | S2S_EL: go(&k_set2set_fwd<false, true, true>, af1); break;
+        case S2S_WF: go(&k_set2set_fwd<false, false, true>, af0); break;
+        case S2S_WL | S2S_EL: go(&k_set2set_fwd<true, true, false>, at11); break;
+        case S2S_WL: go(&k_set2set_fwd<true, false, false>, at10); break;
+        default: go(&k_set2set_fwd<false, false, false>, at00); break;
+    }
     q.check_launch("set2set_fwd");
 }
 
@@ -551,15 +576,31 @@ void set2set_bwd(Seq& q, const float* emb, int lde, const float* w_ih, const flo
     float* DE = q.alloc<float>((size_t)B * n * n);
     float* DPRE = q.alloc<float>((size_t)B * d);
     if (!q.ok()) return;
+    const int plan = s2s_plan_or_error(q, n, d);
+    if (plan < 0) return;
+    if (B == 0) {
+        // an empty batch: demb is empty and every parameter gradient is a sum over no graph — zero.  Decided here, on
+        // the host: a grid of zero workgroups is not a valid launch.
+        struct { float* p; size_t cnt; } z[6] = {{dw_ih, (size_t)8 * d * d}, {dw_hh, (size_t)4 * d * d},
+                                                  {db_ih, (size_t)4 * d},     {db_hh, (size_t)4 * d},
+                                                  {dWp, (size_t)2 * d * d},   {dbp, (size_t)d}};
+        for (auto& e : z) {
+            const hipError_t er = hipMemsetAsync(e.p, 0, e.cnt * sizeof(float), q.stream);
+            if (er != hipSuccess && !q.err) {
+                set_error("set2set_bwd: hipMemsetAsync: %s", hipGetErrorString(er));
+                q.err = (int)er;
+            }
+        }
+        return;
+    }
     const float* sv = (const float*)save;
     S2SBwdArgs a{};
     a.emb = emb; a.lde = lde; a.wt = sv + L.wt; a.Wp = Wp; a.out = out; a.dout = dout;
     a.H = sv + L.h; a.Cs = sv + L.c; a.G = sv + L.g; a.Aw = sv + L.a;
     a.DG = DG; a.DR = DR; a.DE = DE; a.DPRE = DPRE;
     a.n = n; a.d = d; a.GS = L.GS;
-    const bool wf = s2s_w_in_regs(d);
-    a.w_in_lds = !wf && s2s_w_fits(n, d) ? 1 : 0;
-    a.emb_in_lds = s2s_dyn_lds(n, d, a.w_in_lds, true) <= 158 * 1024 ? 1 : 0;
+    a.w_in_lds = plan & S2S_WL ? 1 : 0;
+    a.emb_in_lds = plan & S2S_EL ? 1 : 0;
     const size_t ldsb = s2s_dyn_lds(n, d, a.w_in_lds, a.emb_in_lds);
     auto go = [&](auto kern, DynLdsOnce& at) {
         ensure_dyn_lds(q, at, reinterpret_cast<const void*>(kern), 160 * 1024, "k_set2set_bwd");
@@ -567,11 +608,13 @@ void set2set_bwd(Seq& q, const float* emb, int lde, const float* w_ih, const flo
         hipLaunchKernelGGL(kern, dim3(B), dim3(S2S_NT), ldsb, q.stream, a);
     };
     static DynLdsOnce at00, at10, at11, af0, af1;
-    if (wf && a.emb_in_lds) go(&k_set2set_bwd<false, true, true>, af1);
-    else if (wf) go(&k_set2set_bwd<false, false, true>, af0);
-    else if (a.w_in_lds && a.emb_in_lds) go(&k_set2set_bwd<true, true, false>, at11);
-    else if (a.w_in_lds) go(&k_set2set_bwd<true, false, false>, at10);
-    else go(&k_set2set_bwd<false, false, false>, at00);
+    switch (plan) {
+        case S2S_WF | S2S_EL: go(&k_set2set_bwd<false, true, true>, af1); break;
+        case S2S_WF: go(&k_set2set_bwd<false, false, true>, af0); break;
+        case S2S_WL | S2S_EL: go(&k_set2set_bwd<true, true, false>, at11); break;
+        case S2S_WL: go(&k_set2set_bwd<true, false, false>, at10); break;
+        default: go(&k_set2set_bwd<false, false, false>, at00); break;
+    }
     q.check_launch("set2set_bwd");
     const float* QP = sv + L.qp;
     const float* QN = sv + L.qn;

@@ -213,8 +213,19 @@ int dp_cross_entropy_bwd(const float* prob, const long long* label, const float*
 /* ------------------------------------------------------------------ A10  Set2Set
  * Set2Set.forward, set2set.py:32-57: n LSTM-attention steps over emb [B,n,d] -> out [B,d].
  * Weights in nn.LSTM layout: w_ih [4d,2d], w_hh [4d,d], b_ih [4d], b_hh [4d] (gates i,f,g,o);
- * pred: Wp [d,2d], bp [d].  `save` (dp_set2set_save_bytes) keeps per-step state for backward. */
+ * pred: Wp [d,2d], bp [d].  `save` (dp_set2set_save_bytes) keeps per-step state for backward.
+ * Limits: 1 <= n <= 1024 and 1 <= d <= 256 (one persistent workgroup per graph holds the recurrence); outside them
+ * both calls return DP_ERR_UNSUPPORTED before any launch and touch no buffer.  n = 0 or d = 0 is DP_ERR_INVALID_ARG.
+ * B = 0 is DP_OK without a kernel launch: the forward writes nothing, the backward zero-fills the six parameter
+ * gradients (sums over no graph).
+ * Strides: `lde` is the row stride of emb (graph b starts at emb + b*n*lde) and `ldde` that of demb, in elements, each
+ * >= d.  Only the first d columns of a row are read / written; the columns beyond d are never touched, so emb and
+ * demb may be column blocks of wider buffers.  out, dout and every parameter / parameter gradient are dense.
+ * dp_set2set_plan(n, d): which k_set2set_* variant that shape runs (the forward and the backward take the same one) —
+ * bit 0 weights in LDS, bit 1 embedding in LDS, bit 2 weights in registers; no bit set: both are read from global
+ * memory.  DP_ERR_UNSUPPORTED (negative) outside the kernels' limits.  Host only: no GPU call, no error string. */
 size_t dp_set2set_save_bytes(int B, int n, int d);
+int dp_set2set_plan(int n, int d);
 int dp_set2set_fwd(const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
                    const float* b_hh, const float* Wp, const float* bp, float* out, int B, int n, int d,
                    void* save, size_t save_bytes, void* stream);
