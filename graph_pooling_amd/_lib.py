@@ -116,6 +116,9 @@ _PROTOS = {
     "dp_csr_pool_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_csr_pool_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_csr_pool_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_linkpred_workspace_bytes": (_Z, [_I, _I]),
+    "dp_csr_linkpred_loss_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _Z, _P]),
+    "dp_csr_linkpred_loss_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -1,0 +1,546 @@
+// Link-prediction loss of DiffPool (SoftPoolingGcnEncoder.loss, encoders.py:1309-1331, adj_hop = 1) on ONE graph whose
+// 0/1 adjacency is given as CSR (N4).  With p_ij = min(<S_i, S_j>, 1) and eps = 1e-7 the n^2 sum splits into
+//     sum_ij [ -A_ij log(p_ij + eps) - (1 - A_ij) log(1 - p_ij + eps) ]
+//       =  sum_ij        -log(1 - p_ij + eps)                            dense term: reads S only, symmetric in (i, j)
+//       +  sum_(i,j) in E [ -log(p_ij + eps) + log(1 - p_ij + eps) ]     edge term: nnz dot products of S rows
+// so no n x n adjacency is ever read or built; memory is O(n K).  loss = sum / n^2 and the backward scale dloss / n^2
+// are formed in double, as k_link_final does (dp_linkpred.hip).
+//
+// CSR contract: 0/1 adjacency, every (i, j) listed at most once.  Self loops are allowed (their term comes from the edge
+// kernels like any other edge); so are isolated nodes and empty rows.
+//
+// Dense forward : the P-tile walk of dp_linkpred.hip without an adjacency, over the upper triangle only (tiles with
+//                 tr <= tc; off-diagonal tiles count twice).  A workgroup owns the row-block PAIR (p, T-1-p) — T+1
+//                 tiles, the same for every pair — keeps the row block's S in LDS and walks every Z-th column tile
+//                 (Z column splits fill the chip at small n); the next column block is fetched into registers while the
+//                 current tile is computed.  Sums leave each thread as double; one double partial per workgroup.
+// Dense backward: k_link_bwd's walk without either adjacency tile: recompute P, E = 2 scale g'(P),
+//                 g'(p) = gate / (1 - min(p, 1) + eps), accumulate E S_c on the MFMA; column splits are combined in
+//                 split order by k_csr_link_reduce.
+// Edge forward  : a 16-lane team per row; neighbour ids and rows are fetched four at a time, 16-byte loads when
+//                 K % 4 == 0 and the stride allows; the dot products are reduced on DPP inside the team.
+// Edge backward : row-local gather in both directions, dS_i += scale [ sum_{j in N(i)} c_ij S_j + sum_{j in N^T(i)}
+//                 c_ji S_j ], c = gate (-1 / (p + eps) - 1 / (1 - p + eps)); one gather and a factor 2 when the
+//                 transposed CSR is the forward's.  It runs after the dense backward and adds into dS: one writer per
+//                 row.
+// No float atomics anywhere and every reduction has a fixed order: loss and dS are bit-reproducible run to run.
+#include <algorithm>
+
+#include "dp_link_tiles.h"
+
+namespace dp {
+namespace {
+
+constexpr int LK_FWD_TARGET_WGS = 1024;   // dense forward: workgroups wanted (4 per CU) before column splits stop
+constexpr int LK_BWD_TARGET_WGS = 512;    // dense backward: as link_bwd (dp_linkpred.hip)
+constexpr int LK_TEAM_ROWS = 16;          // edge kernels: rows (16-lane teams) per 256-thread workgroup
+
+inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// fixed tree over the 256 threads of the workgroup
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// ------------------------------------------------------------------ dense term
+template <int KT>
+__global__ __launch_bounds__(256) void k_csr_link_dense_fwd(const float* S, int lds_ld, int n, int K, int T,
+                                                            double* partial) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ double red[256];
+    constexpr int KW = KT * 16, KP = KW + 2, NS = 64 * KW / 256;
+    const int Z = gridDim.x, z = blockIdx.x, p = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, kq = lane >> 4;
+    float* Sr = lds;                 // [64][KP]
+    float* Sc = lds + 64 * KP;       // [64][KP]
+    float sc[NS];
+    auto fetch = [&](int c0) {
+#pragma unroll
+        for (int m = 0; m < NS; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            const int i = e / KW, k = e % KW;
+            sc[m] = S[(long)min(c0 + i, n - 1) * lds_ld + min(k, K - 1)];     // raw: zeroed when it is written to LDS
+        }
+    };
+    double tot = 0.0;
+    for (int half = 0; half < 2; ++half) {
+        const int tr = half ? T - 1 - p : p;
+        if (half && tr == p) break;                   // odd T: the middle row block is its own partner
+        int tc = tr + z;
+        if (tc >= T) continue;
+        const int r0 = tr * 64;
+        __syncthreads();                              // the previous half's readers of Sr are done
+        fetch(tc * 64);
+        lk_stage<KT, 64>(S, lds_ld, r0, n, K, Sr);
+        for (; tc < T; tc += Z) {
+            const int c0 = tc * 64;
+            __syncthreads();                          // previous tile's readers of Sc are done
+#pragma unroll
+            for (int m = 0; m < NS; ++m) {
+                const int e = threadIdx.x + 256 * m;
+                const int i = e / KW, k = e % KW;
+                Sc[i * KP + k] = (c0 + i < n && k < K) ? sc[m] : 0.f;
+            }
+            __syncthreads();
+            if (tc + Z < T) fetch((tc + Z) * 64);
+            lk_f32x4 acc[2][2];
+            lk_ptile<KT, 2>(Sr, Sc, K, wr, wc, l15, kq, acc);
+            float sum = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int c = c0 + wc * 32 + j * 16 + l15;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = r0 + wr * 32 + i * 16 + kq * 4 + r;
+                        const float pv = fminf(acc[i][j][r], 1.f);
+                        const float l = -logf(1.f - pv + LINK_EPS);
+                        sum += (row < n && c < n) ? l : 0.f;
+                    }
+                }
+            tot += (double)(tc == tr ? sum : 2.f * sum);      // P is symmetric: tile (tc, tr) holds the same terms
+        }
+    }
+    const double s = block_sum_f64(tot, red);
+    if (threadIdx.x == 0) partial[(long)p * Z + z] = s;
+}
+
+// loss = sum(partials) / n^2 (one workgroup, double, fixed order); also the backward scale dloss / n^2
+__global__ __launch_bounds__(256) void k_csr_link_final(const double* partial, int count, int n, float* out,
+                                                        float* scale_out, const float* dloss) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < count; i += 256) acc += partial[i];
+    const double s = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) {
+        const double nn = (double)n * (double)n;
+        if (out) out[0] = (float)(s / nn);
+        if (scale_out) scale_out[0] = (float)((dloss ? (double)dloss[0] : 1.0) / nn);
+    }
+}
+
+// KT = ceil(K / 16) output column tiles per row block; the column tiles walked are CW = 32 NJ wide
+template <int KT, int NJ>
+__global__ __launch_bounds__(256) void k_csr_link_dense_bwd(const float* S, int lds_ld, const float* scale_ptr,
+                                                            float* dS, int ldds, int n, int K, int accumulate,
+                                                            float* part, int split_tiles) {
+    // part != null: blockIdx.z walks only `split_tiles` column tiles and stores its partial row block to
+    // part[z][row][K]; k_csr_link_reduce sums the splits in split order
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int CW = 32 * NJ, KW = KT * 16, KP = KW + 2;
+    constexpr int SA = CW + 4;      // E tile row stride: 4 SA = 16 mod 32, so (4 kq + r) rows x 16 cols spread over banks
+    constexpr int NS = CW * KW / 256;
+    const int r0 = blockIdx.x * 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, kq = lane >> 4;
+    float* Sr = lds;                 // [64][KP]
+    float* Sc = Sr + 64 * KP;        // [CW][KP]
+    float* Et = Sc + CW * KP;        // [64][SA]   E[i][j] = 2 scale g'(P[r0 + i][c0 + j])
+    const float scale = scale_ptr[0];
+
+    float sc[NS];
+    auto fetch = [&](int c0) {
+#pragma unroll
+        for (int m = 0; m < NS; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            const int i = e / KW, k = e % KW;
+            sc[m] = S[(long)min(c0 + i, n - 1) * lds_ld + min(k, K - 1)];
+        }
+    };
+    const int cbeg = part ? (int)blockIdx.z * split_tiles * CW : 0;
+    const int cend = part ? min(n, cbeg + split_tiles * CW) : n;
+    fetch(min(cbeg, n - 1));
+    lk_stage<KT, 64>(S, lds_ld, r0, n, K, Sr);
+    // this wave's share of the output block: rows wave*16.., all KT column tiles
+    lk_f32x4 out[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) out[t] = (lk_f32x4){0.f, 0.f, 0.f, 0.f};
+
+    for (int c0 = cbeg; c0 < cend; c0 += CW) {
+        __syncthreads();                              // previous iteration's readers of Sc / Et are done
+#pragma unroll
+        for (int m = 0; m < NS; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            const int i = e / KW, k = e % KW;
+            Sc[i * KP + k] = (c0 + i < n && k < K) ? sc[m] : 0.f;
+        }
+        __syncthreads();
+        if (c0 + CW < cend) fetch(c0 + CW);
+        lk_f32x4 acc[2][NJ];
+        lk_ptile<KT, NJ>(Sr, Sc, K, wr, wc, l15, kq, acc);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int cj = wc * 16 * NJ + j * 16 + l15;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ri = wr * 32 + i * 16 + kq * 4 + r;
+                    const float raw = acc[i][j][r];
+                    const float g = lk_min_gate(raw) / (1.f - fminf(raw, 1.f) + LINK_EPS);
+                    Et[ri * SA + cj] = (r0 + ri < n && c0 + cj < n) ? scale * (g + g) : 0.f;   // d/dP(r,c) + d/dP(c,r)
+                }
+            }
+        __syncthreads();
+        // out[16 rows of this wave][K] += E[rows][CW] · Sc[CW][K]
+#pragma unroll 4
+        for (int k0 = 0; k0 < CW; k0 += 4) {
+            const float ev = Et[(wave * 16 + l15) * SA + k0 + kq];
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+                out[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ev, Sc[(k0 + kq) * KP + t * 16 + l15], out[t], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        const int col = t * 16 + l15;
+        if (col >= K) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = r0 + wave * 16 + kq * 4 + r;
+            if (row < n) {
+                if (part) {
+                    part[((long)blockIdx.z * n + row) * K + col] = out[t][r];
+                } else {
+                    float* q = dS + (long)row * ldds + col;
+                    *q = accumulate ? *q + out[t][r] : out[t][r];
+                }
+            }
+        }
+    }
+}
+
+// dS[row, :] = (accumulate ? dS : 0) + sum_z part[z][row][:]
+__global__ __launch_bounds__(256) void k_csr_link_reduce(const float* part, int splits, float* dS, int ldds, int n,
+                                                         int K, int accumulate) {
+    const long total = (long)n * K;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        float v = 0.f;
+        for (int z = 0; z < splits; ++z) v += part[(long)z * total + e];
+        float* q = dS + (e / K) * ldds + e % K;
+        *q = accumulate ? *q + v : v;
+    }
+}
+
+// ------------------------------------------------------------------ edge term
+template <int VEC> struct RowVec;
+template <> struct RowVec<1> {
+    typedef float T;
+    static __device__ __forceinline__ T zero() { return 0.f; }
+    static __device__ __forceinline__ float dot(T a, T b) { return a * b; }
+};
+template <> struct RowVec<4> {
+    typedef lk_f32x4 T;
+    static __device__ __forceinline__ T zero() { return (lk_f32x4){0.f, 0.f, 0.f, 0.f}; }
+    static __device__ __forceinline__ float dot(T a, T b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+};
+
+// A row of S spread over a 16-lane team: lane l15 holds columns (16 m + l15) VEC .. + VEC - 1 for m < NCH
+// (NCH * 16 * VEC >= K).  Chunks past K are loaded from a clamped address; mask_row() zeroes them in ONE operand of the
+// dot product, which is enough (the other operand's duplicates are finite).
+template <int VEC, int NCH>
+struct TeamRow {
+    typename RowVec<VEC>::T v[NCH];
+    __device__ __forceinline__ void load(const float* S, long lds, long row, int l15, int K) {
+#pragma unroll
+        for (int m = 0; m < NCH; ++m) {
+            const int col = min((m * 16 + l15) * VEC, K - VEC);
+            v[m] = *reinterpret_cast<const typename RowVec<VEC>::T*>(S + row * lds + col);
+        }
+    }
+    __device__ __forceinline__ void mask(int l15, int K) {
+#pragma unroll
+        for (int m = 0; m < NCH; ++m)
+            if ((m * 16 + l15) * VEC >= K) v[m] = RowVec<VEC>::zero();
+    }
+    __device__ __forceinline__ float dot(const TeamRow& o) const {     // the team's total, in all 16 lanes
+        float d = 0.f;
+#pragma unroll
+        for (int m = 0; m < NCH; ++m) d += RowVec<VEC>::dot(v[m], o.v[m]);
+        return row16_sum(d);
+    }
+};
+
+__device__ __forceinline__ float edge_term(float raw) {
+    const float pv = fminf(raw, 1.f);
+    return -logf(pv + LINK_EPS) + logf(1.f - pv + LINK_EPS);
+}
+__device__ __forceinline__ float edge_coef(float raw) {
+    const float pv = fminf(raw, 1.f);
+    return lk_min_gate(raw) * (-1.f / (pv + LINK_EPS) - 1.f / (1.f - pv + LINK_EPS));
+}
+
+template <int VEC, int NCH>
+__global__ __launch_bounds__(256) void k_csr_link_edge_fwd(const float* S, int lds_ld, const int* indptr,
+                                                           const int* indices, int n, int K, double* partial) {
+    __shared__ double red[256];
+    const int l15 = threadIdx.x & 15;
+    const int row = blockIdx.x * LK_TEAM_ROWS + (threadIdx.x >> 4);
+    const long lds = lds_ld;
+    double tot = 0.0;
+    if (row < n) {
+        TeamRow<VEC, NCH> si;
+        si.load(S, lds, row, l15, K);
+        si.mask(l15, K);
+        const int beg = indptr[row], end = indptr[row + 1];
+        int e = beg;
+        for (; e + 4 <= end; e += 4) {            // four neighbour rows in flight before the first dot product
+            const long j0 = indices[e], j1 = indices[e + 1], j2 = indices[e + 2], j3 = indices[e + 3];
+            TeamRow<VEC, NCH> a0, a1, a2, a3;
+            a0.load(S, lds, j0, l15, K);
+            a1.load(S, lds, j1, l15, K);
+            a2.load(S, lds, j2, l15, K);
+            a3.load(S, lds, j3, l15, K);
+            const float t0 = edge_term(si.dot(a0)), t1 = edge_term(si.dot(a1));
+            const float t2 = edge_term(si.dot(a2)), t3 = edge_term(si.dot(a3));
+            tot += (double)((t0 + t1) + (t2 + t3));
+        }
+        for (; e < end; ++e) {
+            TeamRow<VEC, NCH> a0;
+            a0.load(S, lds, indices[e], l15, K);
+            tot += (double)edge_term(si.dot(a0));
+        }
+        if (l15 != 0) tot = 0.0;                  // every lane of the team holds the row's sum: count it once
+    }
+    const double s = block_sum_f64(tot, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+template <int VEC, int NCH>
+__global__ __launch_bounds__(256) void k_csr_link_edge_bwd(const float* S, int lds_ld, const int* indptr,
+                                                           const int* indices, const int* indptr_t,
+                                                           const int* indices_t, const float* scale_ptr, float* dS,
+                                                           int ldds, int n, int K, int directed) {
+    const int l15 = threadIdx.x & 15;
+    const int row = blockIdx.x * LK_TEAM_ROWS + (threadIdx.x >> 4);
+    if (row >= n) return;
+    const long lds = lds_ld;
+    typedef typename RowVec<VEC>::T V;
+    TeamRow<VEC, NCH> si;
+    si.load(S, lds, row, l15, K);
+    si.mask(l15, K);
+    V acc[NCH];
+#pragma unroll
+    for (int m = 0; m < NCH; ++m) acc[m] = RowVec<VEC>::zero();
+    // p_ij = p_ji bit for bit (the same products in the same order), so both lists take c(<S_i, S_j>)
+    auto walk = [&](const int* ip, const int* ix) {
+        const int beg = ip[row], end = ip[row + 1];
+        int e = beg;
+        for (; e + 4 <= end; e += 4) {
+            const long j0 = ix[e], j1 = ix[e + 1], j2 = ix[e + 2], j3 = ix[e + 3];
+            TeamRow<VEC, NCH> a0, a1, a2, a3;
+            a0.load(S, lds, j0, l15, K);
+            a1.load(S, lds, j1, l15, K);
+            a2.load(S, lds, j2, l15, K);
+            a3.load(S, lds, j3, l15, K);
+            const float c0 = edge_coef(si.dot(a0)), c1 = edge_coef(si.dot(a1));
+            const float c2 = edge_coef(si.dot(a2)), c3 = edge_coef(si.dot(a3));
+#pragma unroll
+            for (int m = 0; m < NCH; ++m) acc[m] += (c0 * a0.v[m] + c1 * a1.v[m]) + (c2 * a2.v[m] + c3 * a3.v[m]);
+        }
+        for (; e < end; ++e) {
+            TeamRow<VEC, NCH> a0;
+            a0.load(S, lds, ix[e], l15, K);
+            const float c0 = edge_coef(si.dot(a0));
+#pragma unroll
+            for (int m = 0; m < NCH; ++m) acc[m] += c0 * a0.v[m];
+        }
+    };
+    walk(indptr, indices);
+    if (directed) walk(indptr_t, indices_t);
+    const float f = directed ? scale_ptr[0] : 2.f * scale_ptr[0];
+#pragma unroll
+    for (int m = 0; m < NCH; ++m) {
+        const int col = (m * 16 + l15) * VEC;
+        if (col < K) {
+            V* q = reinterpret_cast<V*>(dS + (long)row * ldds + col);
+            *q = *q + f * acc[m];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ launch sequences
+int fwd_splits(int T) {
+    const int pairs = (T + 1) / 2;
+    return std::max(1, std::min(T, cdiv(LK_FWD_TARGET_WGS, pairs)));
+}
+
+template <int KT>
+void launch_dense_fwd(Seq& q, const float* S, int lds, int n, int K, int T, int Z, double* partial) {
+    constexpr size_t bytes = (size_t)2 * 64 * (KT * 16 + 2) * sizeof(float);
+    static_assert(bytes + 256 * sizeof(double) <= 160 * 1024, "csr_link_dense_fwd LDS");
+    static DynLdsOnce attr;
+    if (bytes > 64 * 1024)
+        ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_csr_link_dense_fwd<KT>), (int)bytes,
+                       "k_csr_link_dense_fwd");
+    if (!q.ok()) return;
+    hipLaunchKernelGGL((k_csr_link_dense_fwd<KT>), dim3(Z, (T + 1) / 2), dim3(256), bytes, q.stream, S, lds, n, K, T,
+                       partial);
+}
+
+// (VEC, NCH) of the edge kernels: 16-byte lanes cover 64 columns per chunk, 4-byte lanes 16
+#define LK_EDGE_DISPATCH(KERNEL, v4, K, ...)                                                                \
+    do {                                                                                                    \
+        const dim3 grid_(cdiv(n, LK_TEAM_ROWS));                                                            \
+        if (v4) {                                                                                           \
+            if (K <= 64) hipLaunchKernelGGL((KERNEL<4, 1>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);    \
+            else if (K <= 128) hipLaunchKernelGGL((KERNEL<4, 2>), grid_, dim3(256), 0, q.stream, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL<4, 4>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);            \
+        } else {                                                                                            \
+            if (K <= 16) hipLaunchKernelGGL((KERNEL<1, 1>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);    \
+            else if (K <= 64) hipLaunchKernelGGL((KERNEL<1, 4>), grid_, dim3(256), 0, q.stream, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL<1, 16>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);           \
+        }                                                                                                   \
+    } while (0)
+
+void csr_link_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
+                      int K) {
+    const int T = cdiv(n, 64), Z = fwd_splits(T);
+    const int n_dense = ((T + 1) / 2) * Z, n_edge = cdiv(n, LK_TEAM_ROWS);
+    double* partial = q.alloc<double>((size_t)n_dense + n_edge);
+    if (!q.ok()) return;
+#define LK_FWD(KT_) \
+    case KT_: launch_dense_fwd<KT_>(q, S, lds, n, K, T, Z, partial); break;
+    switch (lk_kt(K)) { LK_FWD(1) LK_FWD(2) LK_FWD(3) LK_FWD(4) LK_FWD(6) LK_FWD(8) LK_FWD(12) LK_FWD(16) }
+#undef LK_FWD
+    q.check_launch("csr_link_dense_fwd");
+    if (!q.ok()) return;
+    const bool v4 = K % 4 == 0 && lds % 4 == 0 && aligned16(S);
+    LK_EDGE_DISPATCH(k_csr_link_edge_fwd, v4, K, S, lds, indptr, indices, n, K, partial + n_dense);
+    q.check_launch("csr_link_edge_fwd");
+    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)partial, n_dense + n_edge, n,
+                       loss_out, (float*)nullptr, (const float*)nullptr);
+    q.check_launch("csr_link_final");
+}
+
+template <int KT, int NJ>
+void launch_dense_bwd(Seq& q, const float* S, int lds, const float* scale, float* dS, int ldds, int n, int K,
+                      int accumulate, float* part, int splits, int split_tiles) {
+    constexpr int CW = 32 * NJ, KP = KT * 16 + 2;
+    constexpr size_t bytes = ((size_t)(64 + CW) * KP + 64 * (CW + 4)) * sizeof(float);
+    static_assert(bytes <= 160 * 1024, "csr_link_dense_bwd LDS");
+    static DynLdsOnce attr;
+    if (bytes > 64 * 1024)
+        ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_csr_link_dense_bwd<KT, NJ>), (int)bytes,
+                       "k_csr_link_dense_bwd");
+    if (!q.ok()) return;
+    hipLaunchKernelGGL((k_csr_link_dense_bwd<KT, NJ>), dim3(cdiv(n, 64), 1, part ? splits : 1), dim3(256), bytes,
+                       q.stream, S, lds, scale, dS, ldds, n, K, accumulate, part, split_tiles);
+}
+
+void csr_link_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                      const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n, int K) {
+    float* scale = q.alloc<float>(64);
+    const int kt = lk_kt(K);
+    // few row blocks: split the column tiles over extra workgroups and sum the partials afterwards (link_bwd's rule)
+    const int cw = kt >= 12 ? 32 : 64;
+    const int col_tiles = cdiv(n, cw), row_blocks = cdiv(n, 64);
+    int splits = std::max(1, std::min(col_tiles, cdiv(LK_BWD_TARGET_WGS, row_blocks)));
+    const int split_tiles = cdiv(col_tiles, splits);
+    splits = cdiv(col_tiles, split_tiles);
+    float* part = splits > 1 ? q.alloc<float>((size_t)splits * n * K) : nullptr;
+    if (!q.ok()) return;
+    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)nullptr, 0, n, (float*)nullptr,
+                       scale, dloss);
+    q.check_launch("csr_link_scale");
+#define LK_BWD(KT_, NJ_)                                                                                      \
+    case KT_:                                                                                                 \
+        launch_dense_bwd<KT_, NJ_>(q, S, lds, scale, dS, ldds, n, K, accumulate, part, splits, split_tiles);  \
+        break;
+    switch (kt) { LK_BWD(1, 2) LK_BWD(2, 2) LK_BWD(3, 2) LK_BWD(4, 2) LK_BWD(6, 2) LK_BWD(8, 2) LK_BWD(12, 1) LK_BWD(16, 1) }
+#undef LK_BWD
+    q.check_launch("csr_link_dense_bwd");
+    if (!q.ok()) return;
+    if (part) {
+        const int blocks = std::min(cdiv((long)n * K, 256), 2048);
+        hipLaunchKernelGGL(k_csr_link_reduce, dim3(blocks), dim3(256), 0, q.stream, (const float*)part, splits, dS, ldds,
+                           n, K, accumulate);
+        q.check_launch("csr_link_reduce");
+    }
+    const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
+    const bool v4 = K % 4 == 0 && lds % 4 == 0 && ldds % 4 == 0 && aligned16(S) && aligned16(dS);
+    LK_EDGE_DISPATCH(k_csr_link_edge_bwd, v4, K, S, lds, indptr, indices, indptr_t, indices_t, (const float*)scale, dS,
+                     ldds, n, K, directed);
+    q.check_launch("csr_link_edge_bwd");
+}
+
+size_t sized_bytes(int n, int K) {
+    Seq f = Seq::sizing();
+    csr_link_fwd_seq(f, nullptr, K, nullptr, nullptr, nullptr, n, K);
+    Seq b = Seq::sizing();
+    csr_link_bwd_seq(b, nullptr, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, K, 0, n, K);
+    return std::max(f.ws_off, b.ws_off);
+}
+
+}  // namespace
+}  // namespace dp
+
+using namespace dp;
+
+#define CL_CHECK(cond, code, ...)        \
+    do {                                 \
+        if (!(cond)) {                   \
+            ::dp::set_error(__VA_ARGS__); \
+            return code;                 \
+        }                                \
+    } while (0)
+#define CL_PTR(p)                                                                    \
+    do {                                                                             \
+        CL_CHECK((p) != nullptr, DP_ERR_INVALID_ARG, #p " is NULL");                 \
+        CL_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, #p " is not 4-byte aligned"); \
+    } while (0)
+
+namespace {
+int check_call(const char* entry, int n, int K, int lds, const void* workspace, size_t workspace_bytes) {
+    CL_CHECK(n >= 1, DP_ERR_INVALID_ARG, "%s: n=%d must be positive", entry, n);
+    CL_CHECK(K >= 1, DP_ERR_INVALID_ARG, "%s: K=%d must be positive", entry, K);
+    CL_CHECK(K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d clusters exceed the fused tile kernel (max 256)", entry, K);
+    CL_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", entry, lds, K);
+    CL_CHECK(workspace != nullptr && ((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG,
+             "%s: workspace is NULL or not 16-byte aligned", entry);
+    const size_t need = sized_bytes(n, K);
+    CL_CHECK(workspace_bytes >= need, DP_ERR_INVALID_ARG, "%s: workspace too small: need >= %zu bytes, have %zu", entry,
+             need, workspace_bytes);
+    return DP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t dp_csr_linkpred_workspace_bytes(int n, int K) {
+    if (n < 1 || K < 1 || K > 256) return 0;
+    return sized_bytes(n, K);
+}
+
+int dp_csr_linkpred_loss_fwd(const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
+                             int K, void* workspace, size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(loss_out);
+    if (int rc = check_call("dp_csr_linkpred_loss_fwd", n, K, lds, workspace, workspace_bytes)) return rc;
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_fwd_seq(q, S, lds, indptr, indices, loss_out, n, K);
+    return q.err;
+}
+
+int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                             const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n,
+                             int K, void* workspace, size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(indptr_t); CL_PTR(indices_t); CL_PTR(dS);
+    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
+    if (int rc = check_call("dp_csr_linkpred_loss_bwd", n, K, lds, workspace, workspace_bytes)) return rc;
+    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "dp_csr_linkpred_loss_bwd: ldds=%d smaller than K=%d", ldds, K);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_bwd_seq(q, S, lds, indptr, indices, indptr_t, indices_t, dloss, dS, ldds, accumulate, n, K);
+    return q.err;
+}
+
+}  // extern "C"

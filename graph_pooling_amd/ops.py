@@ -386,3 +386,42 @@ class _CrossEntropyFn(torch.autograd.Function):
 def cross_entropy(logits, label):
     """F.cross_entropy with mean reduction (encoders.py:1127) on dp_cross_entropy_fwd / bwd; logits [b, c]."""
     return _CrossEntropyFn.apply(logits, label)
+
+
+class _CsrLinkLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, g):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(s, "s")
+        s = s.contiguous().float()
+        n, k = s.shape
+        loss = _f32(s, ())
+        wsb = lib.dp_csr_linkpred_workspace_bytes(n, k)
+        ws = _workspace(wsb, s)
+        _lib.check(lib.dp_csr_linkpred_loss_fwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(),
+                                                loss.data_ptr(), n, k, ws.data_ptr(), wsb, _lib.current_stream()),
+                   "dp_csr_linkpred_loss_fwd")
+        ctx.save_for_backward(s)
+        ctx.g, ctx.ws = g, ws
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        (s,) = ctx.saved_tensors
+        g = ctx.g
+        n, k = s.shape
+        dloss = dloss.contiguous().float()
+        ds = torch.empty_like(s)
+        _lib.check(lib.dp_csr_linkpred_loss_bwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(),
+                                                g.indptr_t.data_ptr(), g.indices_t.data_ptr(), dloss.data_ptr(),
+                                                ds.data_ptr(), k, 0, n, k, ctx.ws.data_ptr(), ctx.ws.numel(),
+                                                _lib.current_stream()), "dp_csr_linkpred_loss_bwd")
+        return ds, None
+
+
+def csr_link_loss(s, graph):
+    """DiffPool's link-prediction loss (encoders.py:1309-1331) of the assignment s [n, k] on ONE graph given as CSR
+    (0/1 adjacency, each edge listed once): dp_csr_linkpred_loss_* — a tile walk over s for the n^2 term that does not
+    depend on the adjacency plus a gather over the edges, O(n k) memory.  Returns the device scalar."""
+    return _CsrLinkLossFn.apply(s, graph)

@@ -15,7 +15,8 @@ entries live in `ops.py`; this module holds the CSR container and the two model 
 
 `SparseSoftPoolingGcnEncoder` does the same for DiffPool (`SoftPoolingGcnEncoder`): level 0 on the CSR ops above plus
 dp_csr_pool_fwd / bwd for the pooling S^T Z, S^T A S (encoders.py:1278-1279), the small pooled levels on the dense
-per-op entries with B = 1.
+per-op entries with B = 1, and the link-prediction loss (encoders.py:1309-1331) on dp_csr_linkpred_loss_fwd / bwd,
+which never forms an n x n adjacency.
 """
 from __future__ import annotations
 
@@ -127,8 +128,12 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     with B = 1 (dp_gcn_layer_*, dp_bn_node_*, dp_assign_softmax_mask_*, dp_pool_*); readouts on dp_masked_max_*,
     pred_model on `hip_linear`, the loss on dp_cross_entropy_*.
 
-    Not on this path: dropout, the link-prediction loss (an n^2 term; `loss` refuses it, forward / predict work for a
-    linkpred model), K_0 > 256 or a concatenated embedding wider than 512 (dp_csr_pool's limits)."""
+    A linkpred=True model (the constructor default, train.py --linkpred) trains here too: `loss(pred, label, graph)`
+    adds the link-prediction term on dp_csr_linkpred_loss_* — the n^2 part of the sum does not depend on the adjacency
+    and is a tile walk over S, the rest a gather over the edges; O(n K_0) memory, no dense adjacency.
+
+    Not on this path: dropout, adj_hop > 1, batches of graphs, K_0 > 256 or a concatenated embedding wider than 512
+    (dp_csr_pool's limits)."""
 
     def __init__(self, max_num_nodes, input_dim, hidden_dim, embedding_dim, label_dim, num_layers,
                  assign_hidden_dim, assign_ratio=0.25, assign_num_layers=-1, num_pooling=1,
@@ -205,15 +210,30 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         return self.forward(x, graph, assign_x=assign_x).argmax(dim=1)
 
     def loss(self, pred, label, adj=None, batch_num_nodes=None, adj_hop=1):
-        """Cross entropy of the prediction (encoders.py:1124-1127).  The link-prediction term (encoders.py:1309-1331)
-        is an n^2 pass over the graph and is not offered on the CSR path: a linkpred=True model refuses."""
+        """Cross entropy of the prediction (encoders.py:1124-1127), plus — for a linkpred=True model — the
+        link-prediction term of the level-0 assignment (encoders.py:1309-1331) on dp_csr_linkpred_loss_*.  `adj` is
+        then the CsrGraph the forward ran on, in the position where train.py:207 passes the dense batch:
+        loss(pred, label, graph).  The link term is kept in `self.link_loss`, as the dense class does."""
         if self.linkpred:
-            raise NotImplementedError("SparseSoftPoolingGcnEncoder.loss: the link-prediction loss (linkpred=True) is an "
-                                      "n^2 term over the CSR graph and is not supported on this path; build the model "
-                                      "with linkpred=False to train on CSR graphs (forward / predict work either way)")
+            call = "SparseSoftPoolingGcnEncoder.loss(pred, label, graph)"
+            if adj is None:
+                raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the CsrGraph the "
+                                          "forward ran on; it cannot be formed from the prediction alone")
+            if not isinstance(adj, CsrGraph):
+                raise TypeError(f"{call}: graph must be the CsrGraph of the last forward, got {type(adj).__name__} "
+                                "(the dense (pred, label, adj, batch_num_nodes) form is SoftPoolingGcnEncoder's)")
         if adj_hop != 1:
             raise NotImplementedError("adj_hop > 1 is never used by the reference's callers (train.py:207)")
-        return ops.cross_entropy(pred, label)
+        if not self.linkpred:
+            return ops.cross_entropy(pred, label)
+        if self._saved is None:
+            raise ValueError(f"{call}: no forward pass has run yet, so there is no assignment to score")
+        s0 = self._saved["assign"][0]                # attached: dS of the link term and of the pooling add up
+        if adj.n != s0.shape[0]:
+            raise ValueError(f"{call}: graph has n = {adj.n} nodes but the last forward ran on n = {s0.shape[0]}; "
+                             "pass the graph of that forward")
+        self.link_loss = ops.csr_link_loss(s0, adj)
+        return ops.cross_entropy(pred, label) + self.link_loss
 
     def saved_activation(self, level, what):
         """One activation of the LAST forward call, shaped as the dense class returns it with B = 1: 'assign' [1, n_j,

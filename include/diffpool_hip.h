@@ -283,6 +283,28 @@ int dp_csr_pool_bwd(const float* S, int lds, const float* Z, int ldz, const int*
                     float* dS, int ldds, float* dZ, int lddz, int n, int K, int D,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ N4  link-prediction loss on a CSR graph
+ * The loss of A8 — loss = sum_ij [-A log(P+1e-7) - (1-A) log(1-P+1e-7)] / n^2, P = min(S S^T, 1), encoders.py:1309-1331
+ * (adj_hop = 1) — on ONE graph whose adjacency is given as CSR, for any n.  No n x n adjacency is read or built: for a
+ * 0/1 adjacency the sum decomposes into
+ *     sum_ij -log(1 - p_ij + eps)                                   (dense term: a P-tile walk over S alone, upper
+ *                                                                    triangle, off-diagonal tiles counted twice)
+ *   + sum_{(i,j) in E} [ -log(p_ij + eps) + log(1 - p_ij + eps) ]   (edge term: nnz dot products of S rows, a gather)
+ * and the backward likewise into a tile walk plus a row-local gather over A and A^T.  S [n,K] (lds >= K), 1 <= K <= 256
+ * (DP_ERR_UNSUPPORTED above), n >= 1.  CSR contract: 0/1 adjacency, each (i,j) listed at most once; self loops,
+ * isolated nodes and empty rows are allowed.  Sums are taken in double in a fixed order and there are no float atomics:
+ * loss and dS are bit-reproducible.  They agree with the dense entries of A8 to fp32 rounding, not bit for bit (the
+ * summation is decomposed).  The workspace is O(n K): dp_csr_linkpred_workspace_bytes covers both directions; a short
+ * or NULL workspace, n < 1, lds < K and NULL pointers are DP_ERR_INVALID_ARG before any launch. */
+size_t dp_csr_linkpred_workspace_bytes(int n, int K);
+int dp_csr_linkpred_loss_fwd(const float* S, int lds, const int* indptr, const int* indices, float* loss_out,
+                             int n, int K, void* workspace, size_t workspace_bytes, void* stream);
+/* dS (+)= dloss * dloss/dS; dloss: device scalar or NULL = 1; indptr_t/indices_t: CSR of A^T (the forward's arrays
+   for an undirected graph: one gather and a factor 2) */
+int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                             const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate,
+                             int n, int K, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ================================================================== model-level entry points
  * One call enqueues the whole forward (or backward) of an encoder, so the Python host pays one
  * FFI crossing per pass instead of ~100.  Parameters live in ONE flat fp32 buffer; the cfg gives
