@@ -119,6 +119,23 @@ _PROTOS = {
     "dp_csr_linkpred_workspace_bytes": (_Z, [_I, _I]),
     "dp_csr_linkpred_loss_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _Z, _P]),
     "dp_csr_linkpred_loss_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    # ragged batches of CSR graphs (host pointers — node_off_host, the plan's tables — are passed as addresses too)
+    "dp_bn_ragged_workspace_bytes": (_Z, [_I, _I]),
+    "dp_bn_ragged_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dp_bn_ragged_bwd": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_gcn_pad_const_fwd": (_I, [_P, _P, _I, _I, _P]),
+    "dp_gcn_pad_const_bwd": (_I, [_P, _P, _P, _I, _I, _P]),
+    "dp_segment_max_workspace_bytes": (_Z, [_I, _I]),
+    "dp_segment_max_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _Z, _P]),
+    "dp_segment_max_bwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "dp_csr_pool_batch_plan": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "dp_csr_pool_batch_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "dp_csr_pool_batch_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_pool_batch_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P,
+                                   _Z, _P]),
+    "dp_csr_linkpred_batch_workspace_bytes": (_Z, [_P, _I, _I]),
+    "dp_csr_linkpred_batch_loss_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _Z, _P]),
+    "dp_csr_linkpred_batch_loss_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -116,14 +116,14 @@ __global__ __launch_bounds__(256) void k_csr_link_dense_fwd(const float* S, int 
 }
 
 // loss = sum(partials) / n^2 (one workgroup, double, fixed order); also the backward scale dloss / n^2
-__global__ __launch_bounds__(256) void k_csr_link_final(const double* partial, int count, int n, float* out,
+// (nn: n^2 of the graph, or sum_b n_b^2 of a batch)
+__global__ __launch_bounds__(256) void k_csr_link_final(const double* partial, int count, double nn, float* out,
                                                         float* scale_out, const float* dloss) {
     __shared__ double red[256];
     double acc = 0.0;
     for (int i = threadIdx.x; i < count; i += 256) acc += partial[i];
     const double s = block_sum_f64(acc, red);
     if (threadIdx.x == 0) {
-        const double nn = (double)n * (double)n;
         if (out) out[0] = (float)(s / nn);
         if (scale_out) scale_out[0] = (float)((dloss ? (double)dloss[0] : 1.0) / nn);
     }
@@ -403,11 +403,15 @@ void launch_dense_fwd(Seq& q, const float* S, int lds, int n, int K, int T, int 
         }                                                                                                   \
     } while (0)
 
-void csr_link_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
-                      int K) {
+int fwd_partials(int n) {
+    const int T = cdiv(n, 64);
+    return ((T + 1) / 2) * fwd_splits(T) + cdiv(n, LK_TEAM_ROWS);
+}
+// the dense and the edge partials of one graph -> partial[0 .. fwd_partials(n) - 1]
+void csr_link_fwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, int n, int K,
+                        double* partial) {
     const int T = cdiv(n, 64), Z = fwd_splits(T);
-    const int n_dense = ((T + 1) / 2) * Z, n_edge = cdiv(n, LK_TEAM_ROWS);
-    double* partial = q.alloc<double>((size_t)n_dense + n_edge);
+    const int n_dense = ((T + 1) / 2) * Z;
     if (!q.ok()) return;
 #define LK_FWD(KT_) \
     case KT_: launch_dense_fwd<KT_>(q, S, lds, n, K, T, Z, partial); break;
@@ -418,8 +422,16 @@ void csr_link_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const 
     const bool v4 = K % 4 == 0 && lds % 4 == 0 && aligned16(S);
     LK_EDGE_DISPATCH(k_csr_link_edge_fwd, v4, K, S, lds, indptr, indices, n, K, partial + n_dense);
     q.check_launch("csr_link_edge_fwd");
-    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)partial, n_dense + n_edge, n,
-                       loss_out, (float*)nullptr, (const float*)nullptr);
+}
+void csr_link_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
+                      int K) {
+    const int count = fwd_partials(n);
+    double* partial = q.alloc<double>((size_t)count);
+    if (!q.ok()) return;
+    csr_link_fwd_graph(q, S, lds, indptr, indices, n, K, partial);
+    if (!q.ok()) return;
+    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)partial, count,
+                       (double)n * (double)n, loss_out, (float*)nullptr, (const float*)nullptr);
     q.check_launch("csr_link_final");
 }
 
@@ -438,21 +450,43 @@ void launch_dense_bwd(Seq& q, const float* S, int lds, const float* scale, float
                        q.stream, S, lds, scale, dS, ldds, n, K, accumulate, part, split_tiles);
 }
 
-void csr_link_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
-                      const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n, int K) {
-    float* scale = q.alloc<float>(64);
-    const int kt = lk_kt(K);
-    // few row blocks: split the column tiles over extra workgroups and sum the partials afterwards (link_bwd's rule)
-    const int cw = kt >= 12 ? 32 : 64;
+// column splits of the dense backward and their partial buffer (floats; 0: no split)
+size_t bwd_part_floats(int n, int K, int* splits_out, int* split_tiles_out) {
+    const int cw = lk_kt(K) >= 12 ? 32 : 64;
     const int col_tiles = cdiv(n, cw), row_blocks = cdiv(n, 64);
     int splits = std::max(1, std::min(col_tiles, cdiv(LK_BWD_TARGET_WGS, row_blocks)));
     const int split_tiles = cdiv(col_tiles, splits);
     splits = cdiv(col_tiles, split_tiles);
-    float* part = splits > 1 ? q.alloc<float>((size_t)splits * n * K) : nullptr;
+    if (splits_out) *splits_out = splits;
+    if (split_tiles_out) *split_tiles_out = split_tiles;
+    return splits > 1 ? (size_t)splits * n * K : 0;
+}
+void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                        const int* indices_t, const float* scale, float* part, float* dS, int ldds, int accumulate,
+                        int n, int K, int directed);
+void csr_link_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                      const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n, int K) {
+    float* scale = q.alloc<float>(64);
+    float* part = nullptr;
+    if (const size_t pf = bwd_part_floats(n, K, nullptr, nullptr)) part = q.alloc<float>(pf);
     if (!q.ok()) return;
-    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)nullptr, 0, n, (float*)nullptr,
-                       scale, dloss);
+    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)nullptr, 0,
+                       (double)n * (double)n, (float*)nullptr, scale, dloss);
     q.check_launch("csr_link_scale");
+    const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
+    csr_link_bwd_graph(q, S, lds, indptr, indices, indptr_t, indices_t, scale, part, dS, ldds, accumulate, n, K,
+                       directed);
+}
+// one graph's dS from the ready scale; `part`: bwd_part_floats(n, K) floats (null when that is 0)
+void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                        const int* indices_t, const float* scale, float* part, float* dS, int ldds, int accumulate,
+                        int n, int K, int directed) {
+    const int kt = lk_kt(K);
+    int splits, split_tiles;
+    if (!bwd_part_floats(n, K, &splits, &split_tiles)) part = nullptr;
+    if (!q.ok()) return;
+    // few row blocks: the column tiles are split over extra workgroups and the partials summed afterwards (link_bwd's
+    // rule, bwd_part_floats)
 #define LK_BWD(KT_, NJ_)                                                                                      \
     case KT_:                                                                                                 \
         launch_dense_bwd<KT_, NJ_>(q, S, lds, scale, dS, ldds, n, K, accumulate, part, splits, split_tiles);  \
@@ -467,7 +501,6 @@ void csr_link_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const 
                            n, K, accumulate);
         q.check_launch("csr_link_reduce");
     }
-    const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
     const bool v4 = K % 4 == 0 && lds % 4 == 0 && ldds % 4 == 0 && aligned16(S) && aligned16(dS);
     LK_EDGE_DISPATCH(k_csr_link_edge_bwd, v4, K, S, lds, indptr, indices, indptr_t, indices_t, (const float*)scale, dS,
                      ldds, n, K, directed);
@@ -479,6 +512,56 @@ size_t sized_bytes(int n, int K) {
     csr_link_fwd_seq(f, nullptr, K, nullptr, nullptr, nullptr, n, K);
     Seq b = Seq::sizing();
     csr_link_bwd_seq(b, nullptr, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, K, 0, n, K);
+    return std::max(f.ws_off, b.ws_off);
+}
+
+// ---- a ragged batch: loss = sum_b (graph b's sum) / sum_b n_b^2 (encoders.py:1326-1331).  Per-graph launches of the
+// kernels above — the tile walk is n_b^2 work per graph anyway — into one partial array, one final launch for the
+// batch; the backward forms the scale once.  indptr is the batch's (row node_off[b] + i, GLOBAL edge offsets), the
+// column indices are graph-LOCAL.  Launch count grows with B (a batched tile table is the open item).
+double batch_norm(const int* off, int B) {
+    double nn = 0.0;
+    for (int b = 0; b < B; ++b) nn += (double)(off[b + 1] - off[b]) * (double)(off[b + 1] - off[b]);
+    return nn;
+}
+void csr_link_batch_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* off,
+                            int B, float* loss_out, int K) {
+    size_t count = 0;
+    for (int b = 0; b < B; ++b) count += fwd_partials(off[b + 1] - off[b]);
+    double* partial = q.alloc<double>(count);
+    if (!q.ok()) return;
+    size_t at = 0;
+    for (int b = 0; b < B && q.ok(); ++b) {
+        const int n = off[b + 1] - off[b];
+        csr_link_fwd_graph(q, S + (long)off[b] * lds, lds, indptr + off[b], indices, n, K, partial + at);
+        at += fwd_partials(n);
+    }
+    if (!q.ok()) return;
+    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)partial, (int)count,
+                       batch_norm(off, B), loss_out, (float*)nullptr, (const float*)nullptr);
+    q.check_launch("csr_link_final");
+}
+void csr_link_batch_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                            const int* indices_t, const int* off, int B, const float* dloss, float* dS, int ldds,
+                            int accumulate, int K) {
+    float* scale = q.alloc<float>(64);
+    size_t pf = 0;
+    for (int b = 0; b < B; ++b) pf = std::max(pf, bwd_part_floats(off[b + 1] - off[b], K, nullptr, nullptr));
+    float* part = pf ? q.alloc<float>(pf) : nullptr;       // reused graph after graph: the launches are stream-ordered
+    if (!q.ok()) return;
+    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)nullptr, 0, batch_norm(off, B),
+                       (float*)nullptr, scale, dloss);
+    q.check_launch("csr_link_scale");
+    const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
+    for (int b = 0; b < B && q.ok(); ++b)
+        csr_link_bwd_graph(q, S + (long)off[b] * lds, lds, indptr + off[b], indices, indptr_t + off[b], indices_t, scale,
+                           part, dS + (long)off[b] * ldds, ldds, accumulate, off[b + 1] - off[b], K, directed);
+}
+size_t batch_sized_bytes(const int* off, int B, int K) {
+    Seq f = Seq::sizing();
+    csr_link_batch_fwd_seq(f, nullptr, K, nullptr, nullptr, off, B, nullptr, K);
+    Seq b = Seq::sizing();
+    csr_link_batch_bwd_seq(b, nullptr, K, nullptr, nullptr, nullptr, nullptr, off, B, nullptr, nullptr, K, 0, K);
     return std::max(f.ws_off, b.ws_off);
 }
 
@@ -540,6 +623,58 @@ int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const i
     CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "dp_csr_linkpred_loss_bwd: ldds=%d smaller than K=%d", ldds, K);
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     csr_link_bwd_seq(q, S, lds, indptr, indices, indptr_t, indices_t, dloss, dS, ldds, accumulate, n, K);
+    return q.err;
+}
+
+// ---- the same loss on a ragged batch (node_off_host: int32 [B + 1] on the HOST)
+static int check_batch(const char* entry, const int* off, int B, int K, int lds, const void* workspace,
+                       size_t workspace_bytes) {
+    CL_CHECK(off != nullptr, DP_ERR_INVALID_ARG, "%s: node_off_host is NULL", entry);
+    CL_CHECK(B >= 1, DP_ERR_INVALID_ARG, "%s: B=%d must be positive", entry, B);
+    CL_CHECK(K >= 1, DP_ERR_INVALID_ARG, "%s: K=%d must be positive", entry, K);
+    CL_CHECK(K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d clusters exceed the fused tile kernel (max 256)", entry, K);
+    CL_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", entry, lds, K);
+    CL_CHECK(off[0] == 0, DP_ERR_INVALID_ARG, "%s: node_off[0] must be 0", entry);
+    for (int b = 0; b < B; ++b)
+        CL_CHECK(off[b + 1] > off[b], DP_ERR_INVALID_ARG, "%s: graph %d has no node (node_off must increase)", entry, b);
+    CL_CHECK(workspace != nullptr && ((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG,
+             "%s: workspace is NULL or not 16-byte aligned", entry);
+    const size_t need = batch_sized_bytes(off, B, K);
+    CL_CHECK(workspace_bytes >= need, DP_ERR_INVALID_ARG, "%s: workspace too small: need >= %zu bytes, have %zu", entry,
+             need, workspace_bytes);
+    return DP_OK;
+}
+
+size_t dp_csr_linkpred_batch_workspace_bytes(const int* node_off_host, int B, int K) {
+    if (!node_off_host || B < 1 || K < 1 || K > 256 || node_off_host[0] != 0) return 0;
+    for (int b = 0; b < B; ++b)
+        if (node_off_host[b + 1] <= node_off_host[b]) return 0;
+    return batch_sized_bytes(node_off_host, B, K);
+}
+
+int dp_csr_linkpred_batch_loss_fwd(const float* S, int lds, const int* indptr, const int* indices_local,
+                                   const int* node_off_host, int B, float* loss_out, int K, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(loss_out);
+    if (int rc = check_batch("dp_csr_linkpred_batch_loss_fwd", node_off_host, B, K, lds, workspace, workspace_bytes))
+        return rc;
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_batch_fwd_seq(q, S, lds, indptr, indices_local, node_off_host, B, loss_out, K);
+    return q.err;
+}
+
+int dp_csr_linkpred_batch_loss_bwd(const float* S, int lds, const int* indptr, const int* indices_local,
+                                   const int* indptr_t, const int* indices_t_local, const int* node_off_host, int B,
+                                   const float* dloss, float* dS, int ldds, int accumulate, int K, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(indptr_t); CL_PTR(indices_t_local); CL_PTR(dS);
+    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
+    if (int rc = check_batch("dp_csr_linkpred_batch_loss_bwd", node_off_host, B, K, lds, workspace, workspace_bytes))
+        return rc;
+    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "dp_csr_linkpred_batch_loss_bwd: ldds=%d smaller than K=%d", ldds, K);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_batch_bwd_seq(q, S, lds, indptr, indices_local, indptr_t, indices_t_local, node_off_host, B, dloss, dS, ldds,
+                           accumulate, K);
     return q.err;
 }
 

@@ -75,6 +75,7 @@ struct PoolFwdArgs {
     const int* indices;
     float* part;            // [nslab][K][K+D]
     int lds, ldz, n, K, D, rows_per_slab;
+    const int* tab;         // batch: slab table {first row, end row, graph, 0} per slab (rows global); null: one graph
 };
 
 // MI / NI: 16x16 MFMA tiles per wave along the K result rows / the 64 output columns; WM waves along the rows
@@ -94,8 +95,12 @@ __global__ __launch_bounds__(256) void k_csr_pool_fwd(PoolFwdArgs a) {
     const int wm = wave / WN, wn = wave % WN;
     const int n0 = blockIdx.x * FWD_TN;
     const int KD = a.K + a.D;
-    const int rbeg = blockIdx.y * a.rows_per_slab;
-    const int rend = min(a.n, rbeg + a.rows_per_slab);
+    int rbeg = blockIdx.y * a.rows_per_slab;
+    int rend = min(a.n, rbeg + a.rows_per_slab);
+    if (a.tab) {                                      // a slab of the batch: never crosses a graph boundary
+        rbeg = a.tab[blockIdx.y * 4];
+        rend = a.tab[blockIdx.y * 4 + 1];
+    }
     const long lds = a.lds, ldz = a.ldz;
 
     f32x4 acc[MI][NI];
@@ -161,17 +166,26 @@ __global__ __launch_bounds__(256) void k_csr_pool_fwd(PoolFwdArgs a) {
 
 // [Ap | Xp] = sum over slabs of the partials, in slab order.  A workgroup sums 64 entries: wave w takes the slabs
 // w, w + 4, ... and the four wave sums are added in wave order (a fixed tree: deterministic).
+// Batch (slab_off != null): blockIdx.y is the graph, its slabs are slab_off[b] .. slab_off[b + 1] - 1 — the same tree
+// per graph, so a graph's result has the bits of a single-graph call.
 __global__ __launch_bounds__(256) void k_csr_pool_reduce(const float* part, int nslab, int K, int D, float* Xp,
-                                                         float* Ap) {
+                                                         float* Ap, const int* slab_off) {
     __shared__ float red[4][64];
     const int KD = K + D;
     const long total = (long)K * KD;
     const long e = (long)blockIdx.x * 64 + (threadIdx.x & 63);
     const int wave = threadIdx.x >> 6;
+    int s0 = 0, s1 = nslab;
+    if (slab_off) {
+        s0 = slab_off[blockIdx.y];
+        s1 = slab_off[blockIdx.y + 1];
+        Xp += (long)blockIdx.y * K * D;
+        Ap += (long)blockIdx.y * K * K;
+    }
     float s = 0.f;
     if (e < total) {
 #pragma unroll 4
-        for (int sl = wave; sl < nslab; sl += 4) s += part[(long)sl * total + e];
+        for (int sl = s0 + wave; sl < s1; sl += 4) s += part[(long)sl * total + e];
     }
     red[wave][threadIdx.x & 63] = s;
     __syncthreads();
@@ -184,11 +198,16 @@ __global__ __launch_bounds__(256) void k_csr_pool_reduce(const float* part, int 
 }
 
 // Backward prologue: Wcat [KXp x WLD] and dXpP [Kp x Dp], zero-padded row-major copies the main kernel copies into LDS
-// with 16-byte loads.  KX = K + D (undirected) or 2K + D.
+// with 16-byte loads.  KX = K + D (undirected) or 2K + D.  blockIdx.y is the graph of a batch (its own dXp / dAp and
+// its own copies).
 __global__ __launch_bounds__(256) void k_csr_pool_bwd_prep(const float* dXp, const float* dAp, float* W, int KXp,
                                                            int WLD, float* dXpP, int Kp, int Dp, int K, int D,
                                                            int directed) {
     const long nw = (long)KXp * WLD, total = nw + (long)Kp * Dp;
+    dXp += (long)blockIdx.y * K * D;
+    dAp += (long)blockIdx.y * K * K;
+    W += (long)blockIdx.y * nw;
+    dXpP += (long)blockIdx.y * Kp * Dp;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         if (e < nw) {
             const int k = (int)(e / WLD), c = (int)(e % WLD);
@@ -219,6 +238,7 @@ struct PoolBwdArgs {
     float* dS;
     float* dZ;
     int lds, ldz, ldds, lddz, n, K, D, KX, KXp, Kp, Dp, directed;
+    const int* tab;         // batch: row-block table {first row, end row, graph, 0} (rows global); null: one graph
 };
 
 // NI: 16-column MFMA tiles per wave (NI * 16 >= K; also the dZ column block).  Wave w owns rows 16w .. 16w + 15 of the
@@ -233,7 +253,16 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    const int row0 = blockIdx.x * BWD_ROWS;
+    int row0 = blockIdx.x * BWD_ROWS, rend = a.n;
+    const float* Wg = a.W;
+    const float* dXg = a.dXpP;
+    if (a.tab) {                                      // a row block of the batch: rows of one graph, its own Wcat / dXp
+        row0 = a.tab[blockIdx.x * 4];
+        rend = a.tab[blockIdx.x * 4 + 1];
+        const long g = a.tab[blockIdx.x * 4 + 2];
+        Wg += g * a.KXp * TN;
+        dXg += g * a.Kp * a.Dp;
+    }
     const long lds = a.lds, ldz = a.ldz;
     const int koff = a.directed ? 2 * a.K : a.K;      // first X column of Z
 
@@ -270,14 +299,14 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
         for (int r = wave * 16 + lane / LPR; r < wave * 16 + 16; r += RPP) {
             const int row = row0 + r;
             typename Vec<VEC>::T v = Vec<VEC>::zero();
-            if (row < a.n) {
+            if (row < rend) {
                 if (c < a.K) v = gather_row<VEC>(a.S, lds, a.indptr, a.indices, row, c);
                 else if (c < koff) v = gather_row<VEC>(a.S, lds, a.indptr_t, a.indices_t, row, c - a.K);
                 else if (c < a.KX) v = vload<VEC>(a.Z + (long)row * ldz + (c - koff));
             }
             Vec<VEC>::put(&Ximg[r * XP + ac], v);
         }
-        fill_b(a.W, TN, c0, 0);
+        fill_b(Wg, TN, c0, 0);
         __syncthreads();
         mfma_chunk();
     }
@@ -287,7 +316,7 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = row0 + wave * 16 + l4 * 4 + r;
-            if (row < a.n && col < a.K) a.dS[(long)row * a.ldds + col] = acc[j][r];
+            if (row < rend && col < a.K) a.dS[(long)row * a.ldds + col] = acc[j][r];
         }
     }
 
@@ -301,10 +330,10 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
             for (int r = wave * 16 + lane / LPR; r < wave * 16 + 16; r += RPP) {
                 const int row = row0 + r;
                 typename Vec<VEC>::T v = Vec<VEC>::zero();
-                if (row < a.n && c < a.K) v = vload<VEC>(a.S + (long)row * lds + c);
+                if (row < rend && c < a.K) v = vload<VEC>(a.S + (long)row * lds + c);
                 Vec<VEC>::put(&Ximg[r * XP + ac], v);
             }
-            fill_b(a.dXpP, a.Dp, c0, nb);
+            fill_b(dXg, a.Dp, c0, nb);
             __syncthreads();
             mfma_chunk();
         }
@@ -314,7 +343,7 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = row0 + wave * 16 + l4 * 4 + r;
-                if (row < a.n && col < a.D) {
+                if (row < rend && col < a.D) {
                     float* p = a.dZ + (long)row * a.lddz + col;
                     *p = *p + acc[j][r];
                 }
@@ -338,14 +367,17 @@ int bwd_ni(int K) { return K <= 64 ? 4 : (K <= 128 ? 8 : 16); }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// tab / slab_off / nslab_batch / B: the slab table of a batch (dp_csr_pool_batch_plan); null / 0: one graph of n rows
 void csr_pool_fwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
-                      float* Xp, float* Ap, int n, int K, int D) {
+                      float* Xp, float* Ap, int n, int K, int D, const int* tab = nullptr,
+                      const int* slab_off = nullptr, int nslab_batch = 0, int B = 1) {
     int nslab, rows;
     fwd_slabs(n, K, D, &nslab, &rows);
+    if (nslab_batch) nslab = nslab_batch;
     float* part = q.alloc<float>((size_t)nslab * K * (K + D));
     if (!q.ok()) return;
     const bool v4 = K % 4 == 0 && D % 4 == 0 && lds % 4 == 0 && ldz % 4 == 0 && aligned16(S) && aligned16(Z);
-    PoolFwdArgs a{S, Z, indptr, indices, part, lds, ldz, n, K, D, rows};
+    PoolFwdArgs a{S, Z, indptr, indices, part, lds, ldz, n, K, D, rows, tab};
     const dim3 grid(cdiv(K + D, FWD_TN), nslab);
 #define DP_POOL_FWD(MI, NI, WM)                                                                        \
     do {                                                                                               \
@@ -357,29 +389,30 @@ void csr_pool_fwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, 
     else DP_POOL_FWD(4, 4, 4);
 #undef DP_POOL_FWD
     q.check_launch("csr_pool_fwd");
-    hipLaunchKernelGGL(k_csr_pool_reduce, dim3(cdiv((long)K * (K + D), 64)), dim3(256), 0, q.stream, part, nslab, K, D,
-                       Xp, Ap);
+    hipLaunchKernelGGL(k_csr_pool_reduce, dim3(cdiv((long)K * (K + D), 64), B), dim3(256), 0, q.stream, part, nslab, K,
+                       D, Xp, Ap, slab_off);
     q.check_launch("csr_pool_reduce");
 }
 
 void csr_pool_bwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                       const int* indptr_t, const int* indices_t, const float* dXp, const float* dAp, float* dS,
-                      int ldds, float* dZ, int lddz, int n, int K, int D) {
+                      int ldds, float* dZ, int lddz, int n, int K, int D, const int* tab = nullptr, int nblk_batch = 0,
+                      int B = 1) {
     const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
     const int NI = bwd_ni(K), TN = NI * 16;
     const int KX = (directed ? 2 * K : K) + D;
     const int KXp = cdiv(KX, BWD_KC) * BWD_KC, Kp = cdiv(K, BWD_KC) * BWD_KC, Dp = cdiv(D, TN) * TN;
-    float* W = q.alloc<float>((size_t)KXp * TN);
-    float* dXpP = q.alloc<float>((size_t)Kp * Dp);
+    float* W = q.alloc<float>((size_t)B * KXp * TN);
+    float* dXpP = q.alloc<float>((size_t)B * Kp * Dp);
     if (!q.ok()) return;
     const long prep = (long)KXp * TN + (long)Kp * Dp;
-    hipLaunchKernelGGL(k_csr_pool_bwd_prep, dim3(std::min(cdiv(prep, 256), 1024)), dim3(256), 0, q.stream, dXp, dAp, W,
+    hipLaunchKernelGGL(k_csr_pool_bwd_prep, dim3(std::min(cdiv(prep, 256), 1024), B), dim3(256), 0, q.stream, dXp, dAp, W,
                        KXp, TN, dXpP, Kp, Dp, K, D, directed);
     q.check_launch("csr_pool_bwd_prep");
     const bool v4 = K % 4 == 0 && D % 4 == 0 && lds % 4 == 0 && ldz % 4 == 0 && aligned16(S) && aligned16(Z);
     PoolBwdArgs a{S, Z, indptr, indices, indptr_t, indices_t, W, dXpP, dS, dZ, lds, ldz, ldds, lddz, n, K, D, KX, KXp,
-                  Kp, Dp, directed};
-    const dim3 grid(cdiv(n, BWD_ROWS));
+                  Kp, Dp, directed, tab};
+    const dim3 grid(nblk_batch ? nblk_batch : cdiv(n, BWD_ROWS));
 #define DP_POOL_BWD(NI_)                                                                           \
     do {                                                                                           \
         if (v4) hipLaunchKernelGGL((k_csr_pool_bwd<NI_, 4>), grid, dim3(256), 0, q.stream, a);    \
@@ -400,6 +433,43 @@ size_t sized_bytes(int n, int K, int D) {
     csr_pool_bwd_seq(b, nullptr, K, nullptr, D, nullptr, nullptr, (const int*)1, nullptr, nullptr, nullptr, nullptr, K,
                      nullptr, D, n, K, D);
     return std::max(f, b.ws_off);
+}
+
+// Slab / row-block tables of a batch, on the host: graph b keeps the partition fwd_slabs(n_b) and the 64-row backward
+// blocks a single-graph call would use, shifted to its first row.  Null tables: count only.
+void batch_plan(const int* off, int B, int K, int D, int* ftab, int* soff, int* btab, int* counts) {
+    int ns = 0, nb = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = off[b + 1] - off[b];
+        int s, rows;
+        fwd_slabs(n, K, D, &s, &rows);
+        if (soff) soff[b] = ns;
+        for (int i = 0; i < s; ++i, ++ns)
+            if (ftab) {
+                ftab[4 * ns] = off[b] + i * rows;
+                ftab[4 * ns + 1] = std::min(off[b + 1], off[b] + (i + 1) * rows);
+                ftab[4 * ns + 2] = b;
+                ftab[4 * ns + 3] = 0;
+            }
+        for (int r = 0; r < n; r += BWD_ROWS, ++nb)
+            if (btab) {
+                btab[4 * nb] = off[b] + r;
+                btab[4 * nb + 1] = std::min(off[b + 1], off[b] + r + BWD_ROWS);
+                btab[4 * nb + 2] = b;
+                btab[4 * nb + 3] = 0;
+            }
+    }
+    if (soff) soff[B] = ns;
+    counts[0] = ns;
+    counts[1] = nb;
+}
+
+size_t batch_sized_bytes(int nslab, int B, int K, int D) {
+    const size_t f = align256((size_t)nslab * K * (K + D) * sizeof(float));
+    const int TN = bwd_ni(K) * 16;
+    const int KXp = cdiv(2 * K + D, BWD_KC) * BWD_KC, Kp = cdiv(K, BWD_KC) * BWD_KC, Dp = cdiv(D, TN) * TN;
+    const size_t b = align256((size_t)B * KXp * TN * sizeof(float)) + align256((size_t)B * Kp * Dp * sizeof(float));
+    return std::max(f, b);
 }
 
 }  // namespace
@@ -459,6 +529,62 @@ int dp_csr_pool_bwd(const float* S, int lds, const float* Z, int ldz, const int*
     CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_bwd: workspace is not 16-byte aligned");
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n, K, D);
+    return q.err;
+}
+
+// ---- the same on a ragged batch of B graphs (rows concatenated, block-diagonal CSR with GLOBAL column indices)
+int dp_csr_pool_batch_plan(const int* node_off_host, int B, int K, int D, int* fwd_tab_host, int* slab_off_host,
+                           int* bwd_tab_host, int* counts_host) {
+    CP_NOTNULL(node_off_host); CP_NOTNULL(counts_host);
+    CP_CHECK(B >= 1, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_plan: B=%d must be positive", B);
+    CP_CHECK(K >= 1 && K <= 256 && D >= 1 && D <= 512, DP_ERR_UNSUPPORTED,
+             "dp_csr_pool_batch_plan: K=%d / D=%d outside the supported 1..256 / 1..512", K, D);
+    CP_CHECK(node_off_host[0] == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_plan: node_off[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        CP_CHECK(node_off_host[b + 1] > node_off_host[b], DP_ERR_INVALID_ARG,
+                 "dp_csr_pool_batch_plan: graph %d has no node (node_off must increase)", b);
+    batch_plan(node_off_host, B, K, D, fwd_tab_host, slab_off_host, bwd_tab_host, counts_host);
+    return DP_OK;
+}
+
+size_t dp_csr_pool_batch_workspace_bytes(int n_slabs, int B, int K, int D) {
+    if (n_slabs < 1 || B < 1 || K < 1 || K > 256 || D < 1 || D > 512) return 0;
+    return batch_sized_bytes(n_slabs, B, K, D);
+}
+
+int dp_csr_pool_batch_fwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                          const int* fwd_tab, const int* slab_off, int n_slabs, float* Xp, float* Ap, int B,
+                          int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
+    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(fwd_tab); CP_NOTNULL(slab_off);
+    CP_NOTNULL(Xp); CP_NOTNULL(Ap);
+    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(fwd_tab); CP_ALIGNED(slab_off);
+    CP_ALIGNED(Xp); CP_ALIGNED(Ap);
+    if (int rc = check_shape("dp_csr_pool_batch_fwd", n_total, K, D, lds, ldz)) return rc;
+    CP_CHECK(B >= 1 && B <= 65535 && n_slabs >= B && n_slabs <= 65535, DP_ERR_INVALID_ARG,
+             "dp_csr_pool_batch_fwd: B=%d / n_slabs=%d outside 1..65535 (every graph has a slab)", B, n_slabs);
+    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_fwd: workspace is not 16-byte aligned");
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n_total, K, D, fwd_tab, slab_off, n_slabs, B);
+    return q.err;
+}
+
+int dp_csr_pool_batch_bwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                          const int* indptr_t, const int* indices_t, const int* bwd_tab, int n_blocks,
+                          const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int B,
+                          int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
+    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(indptr_t); CP_NOTNULL(indices_t);
+    CP_NOTNULL(bwd_tab); CP_NOTNULL(dXp); CP_NOTNULL(dAp); CP_NOTNULL(dS); CP_NOTNULL(dZ);
+    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(indptr_t); CP_ALIGNED(indices_t);
+    CP_ALIGNED(bwd_tab); CP_ALIGNED(dXp); CP_ALIGNED(dAp); CP_ALIGNED(dS); CP_ALIGNED(dZ);
+    if (int rc = check_shape("dp_csr_pool_batch_bwd", n_total, K, D, lds, ldz)) return rc;
+    CP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG,
+             "dp_csr_pool_batch_bwd: ldds=%d / lddz=%d smaller than K=%d / D=%d", ldds, lddz, K, D);
+    CP_CHECK(B >= 1 && B <= 65535 && n_blocks >= B, DP_ERR_INVALID_ARG,
+             "dp_csr_pool_batch_bwd: B=%d / n_blocks=%d (every graph has a row block)", B, n_blocks);
+    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_bwd: workspace is not 16-byte aligned");
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n_total, K,
+                     D, bwd_tab, n_blocks, B);
     return q.err;
 }
 

@@ -173,17 +173,22 @@ def csr_graph_conv(x, weight, bias, graph, flags):
 
 
 # ----------------------------------------------------------------------------- row ops on one graph (B = 1)
+def _bnf(x):
+    """(B, n, f) of x [n, f] (one graph) or x [B, n, f] (a dense batch)."""
+    return (1,) + tuple(x.shape) if x.dim() == 2 else tuple(x.shape)
+
+
 class _BnReluNodesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         lib = _lib.load()
         x = x.contiguous()
-        n, f = x.shape
+        b, n, f = _bnf(x)
         y = torch.empty_like(x)
         stats = _f32(x, n, 2)
-        wsb = lib.dp_bn_node_workspace_bytes(1, n, f)
+        wsb = lib.dp_bn_node_workspace_bytes(b, n, f)
         ws = _workspace(wsb, x)
-        _lib.check(lib.dp_bn_node_fwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), 1, n, f, 1, ws.data_ptr(), wsb,
+        _lib.check(lib.dp_bn_node_fwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), b, n, f, 1, ws.data_ptr(), wsb,
                                       _lib.current_stream()), "dp_bn_node_fwd")
         ctx.save_for_backward(x, y, stats)
         ctx.ws = ws
@@ -193,18 +198,18 @@ class _BnReluNodesFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, y, stats = ctx.saved_tensors
-        n, f = x.shape
+        b, n, f = _bnf(x)
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         _lib.check(lib.dp_bn_node_bwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), dy.data_ptr(), f, dx.data_ptr(),
-                                      f, 1, n, f, 1, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream()),
+                                      f, b, n, f, 1, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream()),
                    "dp_bn_node_bwd")
         return dx
 
 
 def bn_relu_nodes(x):
     """apply_bn (encoders.py:1048-1052) after ReLU on ONE graph, x [n, f]: dp_bn_node_* with a batch of one, the ReLU
-    fused into the kernel."""
+    fused into the kernel.  x [B, n, f]: the same on a dense batch (the pooled levels of a CsrBatch)."""
     return _BnReluNodesFn.apply(x)
 
 
@@ -213,13 +218,13 @@ class _RowMaxFn(torch.autograd.Function):
     def forward(ctx, x):
         lib = _lib.load()
         x = x.contiguous()
-        n, f = x.shape
-        out = _f32(x, 1, f)
-        arg = torch.empty(1, f, device=x.device, dtype=torch.int32)
-        _lib.check(lib.dp_masked_max_fwd(x.data_ptr(), f, None, out.data_ptr(), f, arg.data_ptr(), 1, n, f,
+        b, n, f = _bnf(x)
+        out = _f32(x, b, f)
+        arg = torch.empty(b, f, device=x.device, dtype=torch.int32)
+        _lib.check(lib.dp_masked_max_fwd(x.data_ptr(), f, None, out.data_ptr(), f, arg.data_ptr(), b, n, f,
                                          _lib.current_stream()), "dp_masked_max_fwd")
         ctx.save_for_backward(arg)
-        ctx.shape = (n, f)
+        ctx.shape = tuple(x.shape)
         ctx.mark_non_differentiable(arg)
         ctx.set_materialize_grads(False)      # no zero-fill launch for the unused gradient of `arg`
         return out, arg
@@ -228,17 +233,18 @@ class _RowMaxFn(torch.autograd.Function):
     def backward(ctx, dout, _darg):
         lib = _lib.load()
         (arg,) = ctx.saved_tensors
-        n, f = ctx.shape
-        dx = torch.zeros(n, f, device=dout.device, dtype=torch.float32)
+        b, n, f = (1,) + ctx.shape if len(ctx.shape) == 2 else ctx.shape
+        dx = torch.zeros(ctx.shape, device=dout.device, dtype=torch.float32)
         dout = dout.contiguous()
-        _lib.check(lib.dp_masked_max_bwd(dout.data_ptr(), f, arg.data_ptr(), dx.data_ptr(), f, 1, n, f,
+        _lib.check(lib.dp_masked_max_bwd(dout.data_ptr(), f, arg.data_ptr(), dx.data_ptr(), f, b, n, f,
                                          _lib.current_stream()), "dp_masked_max_bwd")
         return dx
 
 
 def row_max(x):
     """Max over the node rows of x [n, f] (torch.max(x, dim=1), encoders.py:1093; the readouts :1257, :1287) through
-    dp_masked_max_* with B = 1 and no mask -> (out [1, f], arg-max rows int32 [1, f], not differentiable)."""
+    dp_masked_max_* with B = 1 and no mask -> (out [1, f], arg-max rows int32 [1, f], not differentiable).  x [B, n, f]:
+    per graph of a dense batch -> (out [B, f], arg-max [B, f])."""
     return _RowMaxFn.apply(x)
 
 
@@ -248,14 +254,14 @@ class _AssignFn(torch.autograd.Function):
     def forward(ctx, z, weight, bias):
         lib = _lib.load()
         z = z.contiguous()
-        n, din = z.shape
+        b, n, din = _bnf(z)
         k = weight.shape[0]
         w = weight.contiguous()
-        s = _f32(z, n, k)
-        wsb = lib.dp_assign_workspace_bytes(1, n, din, k)
+        s = _f32(z, *z.shape[:-1], k)
+        wsb = lib.dp_assign_workspace_bytes(b, n, din, k)
         ws = _workspace(wsb, z)
         _lib.check(lib.dp_assign_softmax_mask_fwd(z.data_ptr(), din, w.data_ptr(), bias.data_ptr(), None, s.data_ptr(),
-                                                  1, n, din, k, ws.data_ptr(), wsb, _lib.current_stream()),
+                                                  b, n, din, k, ws.data_ptr(), wsb, _lib.current_stream()),
                    "dp_assign_softmax_mask_fwd")
         ctx.save_for_backward(z, w, s)
         ctx.ws = ws
@@ -265,12 +271,12 @@ class _AssignFn(torch.autograd.Function):
     def backward(ctx, ds):
         lib = _lib.load()
         z, w, s = ctx.saved_tensors
-        n, din = z.shape
+        b, n, din = _bnf(z)
         k = w.shape[0]
         ds = ds.contiguous()
         dz, dw, db = torch.empty_like(z), torch.empty_like(w), _f32(z, k)
         _lib.check(lib.dp_assign_softmax_mask_bwd(z.data_ptr(), din, w.data_ptr(), s.data_ptr(), ds.data_ptr(), None,
-                                                  dz.data_ptr(), din, dw.data_ptr(), db.data_ptr(), 1, n, din, k,
+                                                  dz.data_ptr(), din, dw.data_ptr(), db.data_ptr(), b, n, din, k,
                                                   ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream()),
                    "dp_assign_softmax_mask_bwd")
         return dz, dw, db
@@ -278,7 +284,8 @@ class _AssignFn(torch.autograd.Function):
 
 def assign_softmax(z, weight, bias):
     """S = softmax(z Wp^T + bp) (encoders.py:1273) on one graph, z [n, d]: dp_assign_softmax_mask_* with B = 1 and no
-    mask (every row is a node)."""
+    mask (every row is a node).  z [B, n, d]: a dense batch (pooled levels), the real B.  The ragged rows of a
+    CsrBatch are the first form with n = n_total."""
     return _AssignFn.apply(z, weight, bias)
 
 
@@ -326,11 +333,12 @@ class _DensePoolFn(torch.autograd.Function):
     def forward(ctx, s, z, adj):
         lib = _lib.load()
         s, z, adj = s.contiguous(), z.contiguous(), adj.contiguous()
-        n, k = s.shape
-        d = z.shape[1]
-        xp, ap, t = _f32(s, k, d), _f32(s, k, k), _f32(s, k, n)
+        b, n, k = _bnf(s)
+        d = z.shape[-1]
+        lead = s.shape[:-2]
+        xp, ap, t = _f32(s, *lead, k, d), _f32(s, *lead, k, k), _f32(s, *lead, k, n)
         _lib.check(lib.dp_pool_fwd(s.data_ptr(), z.data_ptr(), d, adj.data_ptr(), xp.data_ptr(), ap.data_ptr(),
-                                   t.data_ptr(), 1, n, k, d, _lib.current_stream()), "dp_pool_fwd")
+                                   t.data_ptr(), b, n, k, d, _lib.current_stream()), "dp_pool_fwd")
         ctx.save_for_backward(s, z, adj, t)
         return xp, ap
 
@@ -338,22 +346,223 @@ class _DensePoolFn(torch.autograd.Function):
     def backward(ctx, dxp, dap):
         lib = _lib.load()
         s, z, adj, t = ctx.saved_tensors
-        n, k = s.shape
-        d = z.shape[1]
+        b, n, k = _bnf(s)
+        d = z.shape[-1]
         dxp, dap = dxp.contiguous(), dap.contiguous()
         ds, dz = torch.empty_like(s), torch.zeros_like(z)
         dadj = torch.zeros_like(adj) if ctx.needs_input_grad[2] else None
-        wsb = lib.dp_pool_bwd_workspace_bytes(1, n, k, d)
+        wsb = lib.dp_pool_bwd_workspace_bytes(b, n, k, d)
         ws = _workspace(wsb, s)
         _lib.check(lib.dp_pool_bwd(s.data_ptr(), z.data_ptr(), d, adj.data_ptr(), t.data_ptr(), dxp.data_ptr(),
-                                   dap.data_ptr(), ds.data_ptr(), dz.data_ptr(), d, _lib.ptr(dadj), 1, n, k, d,
+                                   dap.data_ptr(), ds.data_ptr(), dz.data_ptr(), d, _lib.ptr(dadj), b, n, k, d,
                                    ws.data_ptr(), wsb, _lib.current_stream()), "dp_pool_bwd")
         return ds, dz, dadj
 
 
 def dense_pool(s, z, adj):
-    """The same pooling on a pooled level (dense n x n adjacency): dp_pool_* with B = 1."""
+    """The same pooling on a pooled level (dense n x n adjacency): dp_pool_* with B = 1; with a leading batch
+    dimension on all three, on a dense batch."""
     return _DensePoolFn.apply(s, z, adj)
+
+
+# ----------------------------------------------------------------------------- ragged batch of CSR graphs
+class _PadConstFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bias, flags):
+        lib = _lib.load()
+        bias = bias.contiguous()
+        f = bias.numel()
+        pad = _f32(bias, f)
+        _lib.check(lib.dp_gcn_pad_const_fwd(bias.data_ptr(), pad.data_ptr(), f, flags, _lib.current_stream()),
+                   "dp_gcn_pad_const_fwd")
+        ctx.save_for_backward(bias)
+        ctx.flags = flags
+        return pad
+
+    @staticmethod
+    def backward(ctx, dpad):
+        lib = _lib.load()
+        (bias,) = ctx.saved_tensors
+        f = bias.numel()
+        dpad = dpad.contiguous()
+        dbias = torch.empty_like(bias)
+        _lib.check(lib.dp_gcn_pad_const_bwd(bias.data_ptr(), dpad.data_ptr(), dbias.data_ptr(), f, ctx.flags,
+                                            _lib.current_stream()), "dp_gcn_pad_const_bwd")
+        return dbias, None
+
+
+def gcn_pad_const(bias, flags):
+    """relu(l2norm(bias)) [F]: what a padded row of the dense batch holds after a GraphConv layer and its ReLU (its
+    adjacency row is zero, encoders.py:962-972) — dp_gcn_pad_const_*; the backward returns the bias gradient."""
+    return _PadConstFn.apply(bias, flags)
+
+
+class _BnReluRaggedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pad, batch):
+        lib = _lib.load()
+        x = x.contiguous()
+        n, f = x.shape
+        pad = None if pad is None else pad.contiguous()
+        y = torch.empty_like(x)
+        stats = _f32(x, batch.max_n, 2)
+        _lib.check(lib.dp_bn_ragged_fwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), batch.node_off.data_ptr(),
+                                        batch.order.data_ptr(), batch.cnt.data_ptr(), _lib.ptr(pad), batch.num_graphs,
+                                        batch.max_n, f, 1, _lib.current_stream()), "dp_bn_ragged_fwd")
+        ctx.save_for_backward(x, y, stats, pad)
+        ctx.batch = batch
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, y, stats, pad = ctx.saved_tensors
+        batch = ctx.batch
+        n, f = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        dpad = torch.empty_like(pad) if pad is not None and ctx.needs_input_grad[1] else None
+        wsb = lib.dp_bn_ragged_workspace_bytes(batch.max_n, f)
+        ws = _workspace(wsb, x)
+        _lib.check(lib.dp_bn_ragged_bwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), dy.data_ptr(), f,
+                                        dx.data_ptr(), f, _lib.ptr(dpad), batch.node_off.data_ptr(),
+                                        batch.order.data_ptr(), batch.cnt.data_ptr(), _lib.ptr(pad), batch.num_graphs,
+                                        batch.max_n, f, 1, ws.data_ptr(), wsb, _lib.current_stream()),
+                   "dp_bn_ragged_bwd")
+        return dx, dpad, None
+
+
+def bn_relu_ragged(x, pad, batch):
+    """apply_bn after ReLU per node index over a ragged batch, x [n_total, f]: what `bn_relu_nodes` gives on the dense
+    batch padded to max_b n_b, whose padded rows all hold `pad` [f] (None: zeros) — dp_bn_ragged_*.  `batch` carries
+    node_off, the size order and the owner counts (CsrBatch)."""
+    return _BnReluRaggedFn.apply(x, pad, batch)
+
+
+class _SegmentMaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, batch):
+        lib = _lib.load()
+        z = z.contiguous()
+        n, f = z.shape
+        b = batch.num_graphs
+        out = _f32(z, b, f)
+        arg = torch.empty(b, f, device=z.device, dtype=torch.int32)
+        nch = batch.seg_chunks
+        wsb = lib.dp_segment_max_workspace_bytes(nch, f)
+        ws = _workspace(wsb, z)
+        _lib.check(lib.dp_segment_max_fwd(z.data_ptr(), f, batch.node_off.data_ptr(), batch.seg_tab.data_ptr(),
+                                          batch.seg_off.data_ptr(), nch, batch.floor_flag.data_ptr(), out.data_ptr(), f,
+                                          arg.data_ptr(), b, f, ws.data_ptr(), wsb, _lib.current_stream()),
+                   "dp_segment_max_fwd")
+        ctx.save_for_backward(arg)
+        ctx.batch, ctx.shape = batch, (n, f)
+        ctx.mark_non_differentiable(arg)
+        ctx.set_materialize_grads(False)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        lib = _lib.load()
+        (arg,) = ctx.saved_tensors
+        n, f = ctx.shape
+        batch = ctx.batch
+        dz = torch.zeros(n, f, device=dout.device, dtype=torch.float32)
+        dout = dout.contiguous()
+        _lib.check(lib.dp_segment_max_bwd(dout.data_ptr(), f, arg.data_ptr(), batch.node_off.data_ptr(), dz.data_ptr(),
+                                          f, batch.num_graphs, f, _lib.current_stream()), "dp_segment_max_bwd")
+        return dz, None
+
+
+def segment_max(z, batch):
+    """Max readout per graph of a ragged batch, z [n_total, f] -> (out [B, f], graph-local arg-max rows int32 [B, f]):
+    graphs with padded rows in the dense batch the CsrBatch stands for (n_b < pad_to) are floored at 0, arg-max -1
+    where the zero wins — dp_segment_max_*."""
+    return _SegmentMaxFn.apply(z, batch)
+
+
+class _CsrPoolBatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, z, batch):
+        lib = _lib.load()
+        s, z = s.contiguous(), z.contiguous()
+        n, k = s.shape
+        d = z.shape[1]
+        b = batch.num_graphs
+        plan = batch.pool_plan(k, d)
+        xp, ap = _f32(s, b, k, d), _f32(s, b, k, k)
+        wsb = lib.dp_csr_pool_batch_workspace_bytes(plan.n_slabs, b, k, d)
+        ws = _workspace(wsb, s)
+        _lib.check(lib.dp_csr_pool_batch_fwd(s.data_ptr(), k, z.data_ptr(), d, batch.indptr.data_ptr(),
+                                             batch.indices.data_ptr(), plan.fwd_tab.data_ptr(),
+                                             plan.slab_off.data_ptr(), plan.n_slabs, xp.data_ptr(), ap.data_ptr(), b, n,
+                                             k, d, ws.data_ptr(), wsb, _lib.current_stream()), "dp_csr_pool_batch_fwd")
+        ctx.save_for_backward(s, z)
+        ctx.batch, ctx.plan, ctx.ws = batch, plan, ws
+        return xp, ap
+
+    @staticmethod
+    def backward(ctx, dxp, dap):
+        lib = _lib.load()
+        s, z = ctx.saved_tensors
+        g, plan = ctx.batch, ctx.plan
+        n, k = s.shape
+        d = z.shape[1]
+        dxp, dap = dxp.contiguous(), dap.contiguous()
+        ds = torch.empty_like(s)
+        dz = torch.zeros_like(z)
+        _lib.check(lib.dp_csr_pool_batch_bwd(s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr(),
+                                             g.indptr_t.data_ptr(), g.indices_t.data_ptr(), plan.bwd_tab.data_ptr(),
+                                             plan.n_blocks, dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k,
+                                             dz.data_ptr(), d, g.num_graphs, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(),
+                                             _lib.current_stream()), "dp_csr_pool_batch_bwd")
+        return ds, dz, None
+
+
+def csr_pool_batch(s, z, batch):
+    """`csr_pool` for every graph of a ragged batch: X' [B, k, d], A' [B, k, k] from s [n_total, k], z [n_total, d] —
+    dp_csr_pool_batch_*, two launches per direction whatever B."""
+    return _CsrPoolBatchFn.apply(s, z, batch)
+
+
+class _CsrLinkLossBatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, g):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(s, "s")
+        s = s.contiguous().float()
+        n, k = s.shape
+        off = g.node_off_host.ctypes.data
+        loss = _f32(s, ())
+        wsb = lib.dp_csr_linkpred_batch_workspace_bytes(off, g.num_graphs, k)
+        ws = _workspace(wsb, s)
+        _lib.check(lib.dp_csr_linkpred_batch_loss_fwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr(),
+                                                      off, g.num_graphs, loss.data_ptr(), k, ws.data_ptr(), wsb,
+                                                      _lib.current_stream()), "dp_csr_linkpred_batch_loss_fwd")
+        ctx.save_for_backward(s)
+        ctx.g, ctx.ws = g, ws
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        (s,) = ctx.saved_tensors
+        g = ctx.g
+        n, k = s.shape
+        dloss = dloss.contiguous().float()
+        ds = torch.empty_like(s)
+        _lib.check(lib.dp_csr_linkpred_batch_loss_bwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr(),
+                                                      g.indptr_t.data_ptr(), g.indices_t_local.data_ptr(),
+                                                      g.node_off_host.ctypes.data, g.num_graphs, dloss.data_ptr(),
+                                                      ds.data_ptr(), k, 0, k, ctx.ws.data_ptr(), ctx.ws.numel(),
+                                                      _lib.current_stream()), "dp_csr_linkpred_batch_loss_bwd")
+        return ds, None
+
+
+def csr_link_loss_batch(s, batch):
+    """The link-prediction loss of a ragged batch, sum_b sum_{i,j < n_b} l_ij / sum_b n_b^2 (encoders.py:1326-1331), of
+    s [n_total, k]: dp_csr_linkpred_batch_* (per-graph launches of the single-graph kernels, one final launch)."""
+    return _CsrLinkLossBatchFn.apply(s, batch)
 
 
 # ----------------------------------------------------------------------------- loss

@@ -70,6 +70,169 @@ class CsrGraph:
         return CsrGraph.from_edges(a.shape[0], r, c, adj.device, symmetric=False)
 
 
+class _PoolPlan:
+    """Device tables of dp_csr_pool_batch_* for one (K, D): see dp_csr_pool_batch_plan."""
+
+    def __init__(self, node_off_host, k, d, device):
+        lib = _lib.load()
+        b = node_off_host.size - 1
+        counts = np.zeros(2, dtype=np.int32)
+        off = node_off_host.ctypes.data
+        _lib.check(lib.dp_csr_pool_batch_plan(off, b, k, d, None, None, None, counts.ctypes.data),
+                   "dp_csr_pool_batch_plan")
+        self.n_slabs, self.n_blocks = int(counts[0]), int(counts[1])
+        fwd = np.zeros((self.n_slabs, 4), dtype=np.int32)
+        soff = np.zeros(b + 1, dtype=np.int32)
+        bwd = np.zeros((self.n_blocks, 4), dtype=np.int32)
+        _lib.check(lib.dp_csr_pool_batch_plan(off, b, k, d, fwd.ctypes.data, soff.ctypes.data, bwd.ctypes.data,
+                                              counts.ctypes.data), "dp_csr_pool_batch_plan")
+        self.fwd_tab = torch.from_numpy(fwd).to(device)
+        self.slab_off = torch.from_numpy(soff).to(device)
+        self.bwd_tab = torch.from_numpy(bwd).to(device)
+
+
+class CsrBatch:
+    """A RAGGED batch of B graphs on the device: node rows concatenated without padding (graph b owns rows
+    node_off[b] .. node_off[b+1]-1 of every [n_total, .] tensor), standing for the dense batch of the same graphs padded
+    to `pad_to` nodes (default: max_b n_b).
+
+    Fields: `num_graphs`, `num_nodes` (host int array [B]), `node_off` (int32 [B+1] on the device) / `node_off_host`,
+    `n_total`, `max_n`, `pad_to`.  The adjacency is one block-diagonal CSR: `indptr` [n_total+1] with `indices` holding
+    GLOBAL columns (rows of the concatenated tensors: GraphConv, pooling) and `indices_local` graph-local ones (link
+    loss); `indptr_t` / `indices_t` / `indices_t_local` the CSR of A^T — the same tensors unless a graph is directed.
+
+    `pad_to` only decides which graphs get the max readout's zero floor (n_b < pad_to: the dense batch has a masked
+    zero row for them); host code that knows `max_num_nodes` reproduces a dense run at that padding with it.  Everything
+    the kernels need is laid out here, once: the size order and owner counts of the node-index BatchNorm, the row
+    chunks of the segmented max, the floor flags, and (on first use per (K, D), then cached) the pooling's slab tables."""
+
+    SEG_ROWS = 128          # rows per chunk of the segmented max readout
+
+    def __init__(self, sizes, parts, device, pad_to=None):
+        """`parts`: per graph (indptr, indices, indptr_t, indices_t) as host int arrays with graph-local columns, the
+        transposed pair None for an undirected graph.  Use the from_* constructors."""
+        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+        if sizes.size == 0:
+            raise ValueError("CsrBatch: no graph")
+        if (sizes < 1).any():
+            raise ValueError(f"CsrBatch: every graph needs at least one node, got sizes {sizes.tolist()}")
+        if len(parts) != sizes.size:
+            raise ValueError(f"CsrBatch: {sizes.size} sizes but {len(parts)} graphs")
+        if int(sizes.sum()) >= 2 ** 31:
+            raise ValueError("CsrBatch: more than 2^31 - 1 nodes in one batch")
+        self.num_graphs = int(sizes.size)
+        self.num_nodes = sizes.astype(np.int64)
+        self.max_n = int(sizes.max())
+        self.pad_to = self.max_n if pad_to is None else int(pad_to)
+        if self.pad_to < self.max_n:
+            raise ValueError(f"CsrBatch: pad_to = {self.pad_to} is below the largest graph ({self.max_n} nodes)")
+        self.node_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        self.n_total = self.n = int(self.node_off_host[-1])
+        self.device = torch.device(device)
+        directed = any(p[2] is not None for p in parts)
+
+        def stack(which):
+            ips, loc, glob, e0 = [], [], [], 0
+            for b, p in enumerate(parts):
+                ip = np.asarray(p[which] if p[which] is not None else p[0], dtype=np.int64)
+                ix = np.asarray(p[which + 1] if p[which] is not None else p[1], dtype=np.int64)
+                n = int(sizes[b])
+                if ip.size != n + 1 or ip[0] != 0 or ip[-1] != ix.size or (np.diff(ip) < 0).any():
+                    raise ValueError(f"CsrBatch: graph {b}: indptr does not describe {n} rows over {ix.size} entries")
+                if ix.size and (ix.min() < 0 or ix.max() >= n):
+                    raise ValueError(f"CsrBatch: graph {b}: column index outside 0..{n - 1}")
+                ips.append(ip[:-1] + e0)
+                loc.append(ix)
+                glob.append(ix + int(self.node_off_host[b]))
+                e0 += ix.size
+            if e0 >= 2 ** 31:
+                raise ValueError("CsrBatch: more than 2^31 - 1 edges in one batch")
+            ips.append(np.array([e0]))
+            pad = [np.zeros(1, dtype=np.int64)] if e0 == 0 else []      # the kernels want non-NULL index arrays
+            dev = lambda a: torch.from_numpy(np.concatenate(a).astype(np.int32)).to(self.device)
+            return dev(ips), dev(glob + pad), dev(loc + pad)
+
+        self.indptr, self.indices, self.indices_local = stack(0)
+        if directed:
+            self.indptr_t, self.indices_t, self.indices_t_local = stack(2)
+        else:
+            self.indptr_t, self.indices_t, self.indices_t_local = self.indptr, self.indices, self.indices_local
+        self.node_off = torch.from_numpy(self.node_off_host).to(self.device)
+        # node-index BatchNorm: graphs by size, largest first; cnt[i] = graphs with n_b > i
+        order = np.argsort(-sizes, kind="stable")
+        asc = np.sort(sizes)
+        cnt = self.num_graphs - np.searchsorted(asc, np.arange(self.max_n), side="right")
+        self.order = torch.from_numpy(order.astype(np.int32)).to(self.device)
+        self.cnt = torch.from_numpy(cnt.astype(np.int32)).to(self.device)
+        self.has_padding = bool((sizes < self.max_n).any())
+        self.floor_flag = torch.from_numpy((sizes < self.pad_to).astype(np.int32)).to(self.device)
+        # segmented max: row chunks that never cross a graph boundary
+        tab, seg_off = [], [0]
+        for b in range(self.num_graphs):
+            lo, hi = int(self.node_off_host[b]), int(self.node_off_host[b + 1])
+            for r in range(lo, hi, self.SEG_ROWS):
+                tab.append((b, r, min(hi, r + self.SEG_ROWS), 0))
+            seg_off.append(len(tab))
+        self.seg_chunks = len(tab)
+        self.seg_tab = torch.from_numpy(np.asarray(tab, dtype=np.int32)).to(self.device)
+        self.seg_off = torch.from_numpy(np.asarray(seg_off, dtype=np.int32)).to(self.device)
+        self._pool_plans = {}
+
+    def pool_plan(self, k, d):
+        """Slab / row-block tables of the batched pooling for cluster count k and embedding width d (built once)."""
+        plan = self._pool_plans.get((k, d))
+        if plan is None:
+            plan = self._pool_plans[(k, d)] = _PoolPlan(self.node_off_host, k, d, self.device)
+        return plan
+
+    @staticmethod
+    def from_graphs(graphs, pad_to=None):
+        """A batch of existing `CsrGraph`s (their arrays are read back to the host once)."""
+        graphs = list(graphs)
+        if not graphs:
+            raise ValueError("CsrBatch: no graph")
+        parts = []
+        for g in graphs:
+            if not isinstance(g, CsrGraph):
+                raise TypeError(f"CsrBatch.from_graphs: expected CsrGraph, got {type(g).__name__}")
+            ip, ix = g.indptr.cpu().numpy(), g.indices.cpu().numpy()
+            if g.indptr_t is g.indptr and g.indices_t is g.indices:
+                parts.append((ip, ix[:ip[-1]], None, None))
+            else:
+                ipt, ixt = g.indptr_t.cpu().numpy(), g.indices_t.cpu().numpy()
+                parts.append((ip, ix[:ip[-1]], ipt, ixt[:ipt[-1]]))
+        return CsrBatch([g.n for g in graphs], parts, graphs[0].indptr.device, pad_to=pad_to)
+
+    @staticmethod
+    def from_edge_lists(sizes, srcs, dsts, device, symmetric=True, pad_to=None):
+        """Per graph an edge list (graph-local node ids) -> the batch; `symmetric` as in `CsrGraph.from_edges`."""
+        if not (len(sizes) == len(srcs) == len(dsts)):
+            raise ValueError("CsrBatch.from_edge_lists: sizes, srcs and dsts must have one entry per graph")
+        parts = []
+        for n, src, dst in zip(sizes, srcs, dsts):
+            g = CsrGraph.from_edges(int(n), src, dst, "cpu", symmetric=symmetric)
+            ip, ix = g.indptr.numpy(), g.indices.numpy()
+            parts.append((ip, ix, None, None) if symmetric else (ip, ix, g.indptr_t.numpy(), g.indices_t.numpy()))
+        return CsrBatch(sizes, parts, device, pad_to=pad_to)
+
+    @staticmethod
+    def from_dense(adj, num_nodes, pad_to=None):
+        """[B, N, N] tensor (any device) + node counts -> the batch on adj's device, reading only the leading
+        n_b x n_b block of each graph (testing aid, like `CsrGraph.from_dense`)."""
+        a = adj.detach().cpu().numpy() != 0
+        nn_ = np.asarray(num_nodes, dtype=np.int64).reshape(-1)
+        if a.ndim != 3 or a.shape[0] != nn_.size or a.shape[1] != a.shape[2]:
+            raise ValueError(f"CsrBatch.from_dense: adj {tuple(a.shape)} does not match {nn_.size} node counts")
+        if (nn_ > a.shape[1]).any():
+            raise ValueError("CsrBatch.from_dense: a node count exceeds the padded size")
+        srcs, dsts = [], []
+        for b, n in enumerate(nn_):
+            r, c = np.nonzero(a[b, :n, :n])
+            srcs.append(r)
+            dsts.append(c)
+        return CsrBatch.from_edge_lists(nn_, srcs, dsts, adj.device, symmetric=False, pad_to=pad_to)
+
+
 def _gcn_stack(mods, h, graph, bn=True):
     """gcn_forward (encoders.py:1054-1081) on one graph: GraphConv -> ReLU -> apply_bn for every layer but the last;
     yields each layer's output as soon as it is enqueued.  `graph` is a CsrGraph, or a pooled level's dense K x K
@@ -81,6 +244,30 @@ def _gcn_stack(mods, h, graph, bn=True):
             h = ops.graph_conv(h.unsqueeze(0), graph.unsqueeze(0), m.weight, m.bias, m._flags())[0]
         if i < len(mods) - 1:
             h = ops.bn_relu_nodes(h) if bn else torch.relu(h)      # ReLU is fused into the BN kernel
+        yield h
+
+
+def _gcn_stack_ragged(mods, h, batch):
+    """`_gcn_stack` on the ragged rows of a CsrBatch, h [n_total, F]: the CSR GraphConv on the block-diagonal adjacency,
+    then apply_bn per node index over the batch — the padded rows of the dense batch enter its statistics as the layer's
+    constant relu(l2norm(bias)) (dp_bn_ragged_*), whose gradient flows back into the bias."""
+    for i, m in enumerate(mods):
+        if m.add_self:
+            raise NotImplementedError("add_self GraphConv layers (concat=False) on a CsrBatch: a padded row of the dense "
+                                      "batch is then not a constant of the layer")
+        h = ops.csr_graph_conv(h, m.weight, m.bias, batch, m._flags())
+        if i < len(mods) - 1:
+            pad = ops.gcn_pad_const(m.bias, m._flags()) if batch.has_padding and m.bias is not None else None
+            h = ops.bn_relu_ragged(h, pad, batch)
+        yield h
+
+
+def _gcn_stack_dense(mods, h, adj):
+    """`_gcn_stack` on a dense batch h [B, n, F], adj [B, n, n] (the pooled levels of a CsrBatch)."""
+    for i, m in enumerate(mods):
+        h = ops.graph_conv(h, adj, m.weight, m.bias, m._flags())
+        if i < len(mods) - 1:
+            h = ops.bn_relu_nodes(h)
         yield h
 
 
@@ -98,6 +285,10 @@ class SparseGcnEncoderGraph(GcnEncoderGraph):
                          concat=concat, bn=bn, dropout=dropout, args=args)
 
     def forward(self, x, graph: CsrGraph):
+        if isinstance(graph, CsrBatch):
+            raise TypeError("SparseGcnEncoderGraph takes one CsrGraph per call: its max readout is unmasked, so on a "
+                            "batch the padded rows' post-BatchNorm values enter the maximum (a suffix-max over node "
+                            "indices), which is not built; SparseSoftPoolingGcnEncoder accepts a CsrBatch")
         if not isinstance(graph, CsrGraph):
             raise TypeError("SparseGcnEncoderGraph.forward(x [n, F], graph: CsrGraph): the dense (x [B, N, F], adj, "
                             "batch_num_nodes) form is GcnEncoderGraph's")
@@ -132,8 +323,16 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     adds the link-prediction term on dp_csr_linkpred_loss_* — the n^2 part of the sum does not depend on the adjacency
     and is a tile walk over S, the rest a gather over the edges; O(n K_0) memory, no dense adjacency.
 
-    Not on this path: dropout, adj_hop > 1, batches of graphs, K_0 > 256 or a concatenated embedding wider than 512
-    (dp_csr_pool's limits)."""
+    A `CsrBatch` (B graphs, rows concatenated) in place of the CsrGraph runs the batch: forward(x [n_total, F], batch)
+    -> ypred [B, label_dim], computing what the dense class computes on the same graphs padded to max_b n_b — the
+    BatchNorm statistics per node index include the padded rows' constants (dp_bn_ragged_*), the level-0 readout has the
+    zero floor of a graph with padded rows (dp_segment_max_*), pooling and link loss are taken per graph
+    (dp_csr_pool_batch_*, dp_csr_linkpred_batch_*) and the pooled levels run on the dense entries with the real B.
+    Differences from the dense class's saved tensors: level-0 'assign' / 'embedding' and `assign_tensor` stay RAGGED,
+    [n_total, .] (dense: [B, N, .]); level-0 'readout_argmax' rows are graph-local.
+
+    Not on this path: dropout, adj_hop > 1, weighted adjacencies, K_0 > 256 or a concatenated embedding wider than 512
+    (dp_csr_pool's limits); on a CsrBatch also concat=False."""
 
     def __init__(self, max_num_nodes, input_dim, hidden_dim, embedding_dim, label_dim, num_layers,
                  assign_hidden_dim, assign_ratio=0.25, assign_num_layers=-1, num_pooling=1,
@@ -158,7 +357,60 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         return torch.cat(list(_gcn_stack(self._stack_modules(first, block, last), h, graph)), dim=1)
 
     # -- public surface
+    def _forward_batch(self, x, batch, assign_x):
+        x_a = x if assign_x is None else assign_x
+        for t, name in ((x, "x"), (x_a, "assign_x")):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != batch.n_total:
+                got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"expected {name} [n_total, F] with n_total = {batch.n_total} (the batch's graphs "
+                                 f"concatenated), got {got}")
+        if x.shape[1] != self.input_dim or x_a.shape[1] != self.assign_input_dim:
+            raise ValueError(f"feature widths {x.shape[1]}/{x_a.shape[1]} do not match the model "
+                             f"({self.input_dim}/{self.assign_input_dim})")
+        if not self.concat:
+            raise NotImplementedError("concat=False (add_self GraphConv layers) on a CsrBatch")
+        _lib.require_gpu_tensor(x, "x")
+        _lib.require_gpu_tensor(x_a, "assign_x")
+        x, x_a = x.contiguous().float(), x_a.contiguous().float()
+        saved = {"assign": [], "xpool": [], "adjpool": [], "embedding": [], "graph": batch}
+        cat = lambda gen, dim: torch.cat(list(gen), dim=dim)
+        z = cat(_gcn_stack_ragged(self._stack_modules(self.conv_first, self.conv_block, self.conv_last), x, batch), 1)
+        saved["embedding"].append(z)
+        out, arg = ops.segment_max(z, batch)                                                              # :1257
+        outs, argmax = [out], [arg]
+        adj, s0 = None, None
+        for i in range(self.num_pooling):                                                                 # :1263
+            pred = self.assign_pred_modules[i]
+            amods = self._stack_modules(self.assign_conv_first_modules[i], self.assign_conv_block_modules[i],
+                                        self.assign_conv_last_modules[i])
+            if i == 0:
+                za = cat(_gcn_stack_ragged(amods, x_a, batch), 1)
+                s = s0 = ops.assign_softmax(za, pred.weight, pred.bias)           # ragged rows: every row is a node
+                xp, adj = ops.csr_pool_batch(s, z, batch)                                                 # :1278-1279
+            else:
+                za = cat(_gcn_stack_dense(amods, x_a, adj), 2)
+                s = ops.assign_softmax(za, pred.weight, pred.bias)
+                xp, adj = ops.dense_pool(s, z, adj)
+            x_a = xp                                                                                      # :1280
+            z = cat(_gcn_stack_dense(self._stack_modules(self.conv_first_after_pool[i], self.conv_block_after_pool[i],
+                                                         self.conv_last_after_pool[i]), xp, adj), 2)
+            out, arg = ops.row_max(z)                                                                     # :1287
+            outs.append(out)
+            argmax.append(arg)
+            saved["assign"].append(s)
+            saved["xpool"].append(xp)
+            saved["adjpool"].append(adj)
+            saved["embedding"].append(z)
+        ypred = ops.mlp_head(torch.cat(outs, dim=1), self._pred_linears())                                # :1295-1299
+        saved["readout_argmax"] = argmax
+        self._saved = saved
+        self.assign_tensor = s0                      # RAGGED [n_total, K_0] (the dense class keeps [B, N, K_0])
+        return ypred
+
     def forward(self, x, graph: CsrGraph, assign_x=None):
+        """x [n, F] and a CsrGraph -> ypred [1, label_dim]; x [n_total, F] and a CsrBatch -> ypred [B, label_dim]."""
+        if isinstance(graph, CsrBatch):
+            return self._forward_batch(x, graph, assign_x)
         if not isinstance(graph, CsrGraph):
             raise TypeError("SparseSoftPoolingGcnEncoder.forward(x [n, F], graph: CsrGraph[, assign_x]): the dense "
                             "(x [B, N, F], adj, batch_num_nodes) form is SoftPoolingGcnEncoder's")
@@ -206,7 +458,7 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
 
     @torch.no_grad()
     def predict(self, x, graph: CsrGraph, assign_x=None):
-        """Arg-max class of the graph: int64 [1] on the device."""
+        """Arg-max class of the graph: int64 [1] on the device ([B] for a CsrBatch)."""
         return self.forward(x, graph, assign_x=assign_x).argmax(dim=1)
 
     def loss(self, pred, label, adj=None, batch_num_nodes=None, adj_hop=1):
@@ -214,6 +466,8 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         link-prediction term of the level-0 assignment (encoders.py:1309-1331) on dp_csr_linkpred_loss_*.  `adj` is
         then the CsrGraph the forward ran on, in the position where train.py:207 passes the dense batch:
         loss(pred, label, graph).  The link term is kept in `self.link_loss`, as the dense class does."""
+        if isinstance(adj, CsrBatch) or (self._saved is not None and isinstance(self._saved.get("graph"), CsrBatch)):
+            return self._loss_batch(pred, label, adj, adj_hop)
         if self.linkpred:
             call = "SparseSoftPoolingGcnEncoder.loss(pred, label, graph)"
             if adj is None:
@@ -235,10 +489,40 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         self.link_loss = ops.csr_link_loss(s0, adj)
         return ops.cross_entropy(pred, label) + self.link_loss
 
+    def _loss_batch(self, pred, label, batch, adj_hop):
+        """`loss` for a CsrBatch forward: label [B]; the link term is sum_b sum_{i,j<n_b} l_ij / sum_b n_b^2."""
+        call = "SparseSoftPoolingGcnEncoder.loss(pred, label, batch)"
+        if batch is not None and not isinstance(batch, CsrBatch):
+            raise TypeError(f"{call}: the last forward ran on a CsrBatch, got {type(batch).__name__}")
+        nb = batch.num_graphs if batch is not None else self._saved["graph"].num_graphs
+        if pred.dim() != 2 or pred.shape[0] != nb:
+            raise ValueError(f"{call}: pred {tuple(pred.shape)} does not hold one row per graph of the batch ({nb})")
+        if not isinstance(label, torch.Tensor) or label.numel() != nb:
+            got = label.numel() if isinstance(label, torch.Tensor) else type(label).__name__
+            raise ValueError(f"{call}: label must hold one class per graph of the batch ({nb}), got {got}")
+        if adj_hop != 1:
+            raise NotImplementedError("adj_hop > 1 is never used by the reference's callers (train.py:207)")
+        if not self.linkpred:
+            return ops.cross_entropy(pred, label.reshape(-1))
+        if batch is None:
+            raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the CsrBatch the "
+                                      "forward ran on; it cannot be formed from the prediction alone")
+        if self._saved is None:
+            raise ValueError(f"{call}: no forward pass has run yet, so there is no assignment to score")
+        if self._saved.get("graph") is not batch:
+            raise ValueError(f"{call}: this is not the batch the last forward ran on; pass the batch of that forward")
+        self.link_loss = ops.csr_link_loss_batch(self._saved["assign"][0], batch)
+        return ops.cross_entropy(pred, label.reshape(-1)) + self.link_loss
+
     def saved_activation(self, level, what):
         """One activation of the LAST forward call, shaped as the dense class returns it with B = 1: 'assign' [1, n_j,
         K_j], 'xpool' [1, K_j, D], 'adjpool' [1, K_j, K_j], 'embedding' [1, n_j, D] (levels 0 .. num_pooling) and
-        'readout_argmax' int32 [1, D] (levels 0 .. num_pooling).  Detached views: clone to keep them."""
+        'readout_argmax' int32 [1, D] (levels 0 .. num_pooling).  Detached views: clone to keep them.
+
+        After a CsrBatch forward: 'xpool' [B, K_j, D], 'adjpool' [B, K_j, K_j], pooled-level 'assign' / 'embedding'
+        [B, K_j, .] and 'readout_argmax' [B, D] as the dense class returns them; the level-0 'assign' / 'embedding' stay
+        ragged, [n_total, .], and the level-0 arg-max rows are graph-local (-1: the zero floor of a graph with padded
+        rows holds the maximum)."""
         if self._saved is None:
             raise RuntimeError("saved_activation(): no forward pass has run yet")
         if what not in ("assign", "xpool", "adjpool", "embedding", "readout_argmax"):
@@ -246,4 +530,6 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         seq = self._saved[what]
         if not 0 <= level < len(seq):
             raise IndexError(f"saved_activation(): level {level} out of range for {what!r} ({len(seq)} levels)")
-        return seq[level].detach() if what == "readout_argmax" else seq[level].detach().unsqueeze(0)
+        if what == "readout_argmax" or isinstance(self._saved.get("graph"), CsrBatch):
+            return seq[level].detach()
+        return seq[level].detach().unsqueeze(0)

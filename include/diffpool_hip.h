@@ -305,6 +305,85 @@ int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const i
                              const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate,
                              int n, int K, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ N4  ragged batches of CSR graphs
+ * B graphs with their node rows CONCATENATED, no padding: graph b owns rows node_off[b] .. node_off[b+1]-1 of every
+ * [n_total, .] tensor (node_off: int32 [B+1] on the device, node_off[0] = 0, every graph has >= 1 node).  The entries
+ * below compute what the dense entries compute on the same graphs padded to N = max_b n_b, without storing a padded
+ * row.  The CSR of the batch is block diagonal: indptr [n_total+1] with GLOBAL edge offsets; column indices GLOBAL
+ * (rows of the concatenated tensors) for GraphConv (dp_sparse_gcn_layer_* with n = n_total) and the pooling, graph-LOCAL
+ * for the link loss.  No float atomics, every reduction in a fixed order: all results are bit-reproducible.
+ *
+ * dp_bn_ragged_*: apply_bn (A3) per NODE INDEX i < max_n = max_b n_b.  The statistics of index i run over the rows
+ * node_off[b] + i of the cnt[i] graphs with n_b > i plus (B - cnt[i]) copies of pad [F] (NULL = zeros) — the value a
+ * padded row of the dense batch has in front of the BatchNorm, relu(l2norm(bias)) of the GraphConv before it — with
+ * divisor B*F, biased variance, eps 1e-5.  order: int32 [B], the graphs by size, largest first, so the owners of index
+ * i are order[0 .. cnt[i]-1]; cnt: int32 [max_n].  relu != 0 applies ReLU first.  stats [max_n,2] = (mean, rstd).  A
+ * wave owns one node index whatever its owner count.  The backward gives dx for the real rows and, when dpad != NULL,
+ * dpad [F] (OVERWRITTEN): the padded rows' own dx, rstd_i (-mean(dy) - xhat_pad mean(dy xhat)) times (B - cnt[i]),
+ * summed over i in a fixed order.  F <= 2048.  Only the backward needs a workspace. */
+size_t dp_bn_ragged_workspace_bytes(int max_n, int F);
+int dp_bn_ragged_fwd(const float* x, int ldx, float* y, int ldy, float* stats, const int* node_off, const int* order,
+                     const int* cnt, const float* pad, int B, int max_n, int F, int relu, void* stream);
+int dp_bn_ragged_bwd(const float* x, int ldx, const float* y, int ldy, const float* stats, const float* dy, int lddy,
+                     float* dx, int lddx, float* dpad, const int* node_off, const int* order, const int* cnt,
+                     const float* pad, int B, int max_n, int F, int relu, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* pad [F] = relu(bias / max(||bias||, 1e-12)) (without DP_F_NORMALIZE: relu(bias); bias NULL: zeros) — the GraphConv
+ * output of a row whose adjacency row is zero, after the ReLU; and dbias [F] (OVERWRITTEN) from dpad through the ReLU
+ * gate and the l2norm Jacobian (F.normalize's: identity / eps below eps; a zero bias gives dbias = 0 since relu'(0) = 0).
+ * One small launch each, no host synchronisation.  DP_F_ADD_SELF is DP_ERR_UNSUPPORTED (a padded row is then not a
+ * constant of the layer). */
+int dp_gcn_pad_const_fwd(const float* bias, float* pad, int F, int flags, void* stream);
+int dp_gcn_pad_const_bwd(const float* bias, const float* dpad, float* dbias, int F, int flags, void* stream);
+
+/* dp_segment_max_*: the max readout (A7) per graph of a ragged batch: out [B,F] (ldo), argmax int32 [B,F] graph-LOCAL
+ * rows, ties to the lowest row.  floor_flag: int32 [B] or NULL; where non-zero the graph has padded rows in the dense
+ * batch it stands for, so its result is max(max over its rows, 0) with argmax -1 where the zero wins (a real row holding
+ * exactly 0 keeps its index, as dp_masked_max_fwd reports it).  chunk_tab: int32 [n_chunks,4] = {graph, first row, end
+ * row, 0} (rows global), chunks of a graph consecutive and in row order, none crossing a graph boundary; chunk_off int32
+ * [B+1] = a graph's chunk range.  Two launches for the whole batch (chunk partials, then a per-graph combine in chunk
+ * order), so the parallelism comes from the rows.  The backward ACCUMULATES INTO dZ [n_total,F]; one writer per entry. */
+size_t dp_segment_max_workspace_bytes(int n_chunks, int F);
+int dp_segment_max_fwd(const float* Z, int ldz, const int* node_off, const int* chunk_tab, const int* chunk_off,
+                       int n_chunks, const int* floor_flag, float* out, int ldo, int* argmax, int B, int F,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int dp_segment_max_bwd(const float* dout, int ldo, const int* argmax, const int* node_off, float* dZ, int lddz, int B,
+                       int F, void* stream);
+
+/* dp_csr_pool_batch_*: the level-0 pooling of dp_csr_pool_* for every graph of the batch, Xp [B,K,D], Ap [B,K,K], from
+ * the ragged S [n_total,K], Z [n_total,D] and the block-diagonal CSR (GLOBAL column indices).  The kernels are those of
+ * dp_csr_pool_*, driven by tables: dp_csr_pool_batch_plan (host only, no GPU call) writes for the sizes node_off_host
+ * the forward slab table [n_slabs,4] = {first row, end row, graph, 0}, slab_off [B+1] and the backward row-block table
+ * [n_blocks,4], and counts_host[2] = {n_slabs, n_blocks}; with the table pointers NULL it only counts.  Graph b keeps
+ * the slab partition and the row blocks a dp_csr_pool_* call on it alone would use, no slab or row block crosses a graph
+ * boundary and the partials are summed per graph in slab order: every graph's result equals that call's BIT FOR BIT.
+ * The caller copies the tables to the device once.  Limits and contract of dp_csr_pool_* (K <= 256, D <= 512; dS
+ * OVERWRITTEN, dZ ACCUMULATED INTO); the launch count does not depend on B (2 forward, 2 backward). */
+int dp_csr_pool_batch_plan(const int* node_off_host, int B, int K, int D, int* fwd_tab_host, int* slab_off_host,
+                           int* bwd_tab_host, int* counts_host);
+size_t dp_csr_pool_batch_workspace_bytes(int n_slabs, int B, int K, int D);
+int dp_csr_pool_batch_fwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                          const int* fwd_tab, const int* slab_off, int n_slabs, float* Xp, float* Ap, int B,
+                          int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream);
+int dp_csr_pool_batch_bwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                          const int* indptr_t, const int* indices_t, const int* bwd_tab, int n_blocks,
+                          const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int B,
+                          int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dp_csr_linkpred_batch_*: the link loss of a batch, sum_b (graph b's sum) / sum_b n_b^2 (encoders.py:1326-1331), with
+ * O(n_total K) memory and no dense adjacency.  Built from PER-GRAPH launches of the dp_csr_linkpred_* kernels (the
+ * tile walk is n_b^2 work per graph anyway) plus one final / scale launch for the batch, so the launch count grows with
+ * B: 2B + 1 forward, up to 3B + 1 backward.  node_off_host is on the HOST; indptr is the batch's, the column indices
+ * are graph-LOCAL.  Contract of dp_csr_linkpred_* otherwise. */
+size_t dp_csr_linkpred_batch_workspace_bytes(const int* node_off_host, int B, int K);
+int dp_csr_linkpred_batch_loss_fwd(const float* S, int lds, const int* indptr, const int* indices_local,
+                                   const int* node_off_host, int B, float* loss_out, int K, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int dp_csr_linkpred_batch_loss_bwd(const float* S, int lds, const int* indptr, const int* indices_local,
+                                   const int* indptr_t, const int* indices_t_local, const int* node_off_host, int B,
+                                   const float* dloss, float* dS, int ldds, int accumulate, int K, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* ================================================================== model-level entry points
  * One call enqueues the whole forward (or backward) of an encoder, so the Python host pays one
  * FFI crossing per pass instead of ~100.  Parameters live in ONE flat fp32 buffer; the cfg gives
