@@ -54,6 +54,29 @@ class EncoderCfg(C.Structure):
                 ("exchange_user", C.c_void_p)]
 
 
+class GemmProblem(C.Structure):
+    """dp_gemm_problem (include/diffpool_hip.h): one contraction of a dp_bgemm_group_f32 / dp_bgemm_plan group."""
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("bias", C.c_void_p),
+                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("lda", C.c_int), ("ldb", C.c_int), ("ldc", C.c_int),
+                ("sA", C.c_int64), ("sB", C.c_int64), ("sC", C.c_int64),
+                ("tA", C.c_int), ("tB", C.c_int),
+                ("alpha", C.c_float), ("beta", C.c_float),
+                ("act", C.c_int),
+                ("split", C.c_int),
+                ("sK", C.c_int64)]
+
+
+GEMM_GROUP_MAX = 4
+GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
+GEMM_PLAN_NONE, GEMM_PLAN_SPLIT_BF16 = 0, 1                           # DP_GEMM_PLAN_*
+
+
+def gemm_plan_decode(plan):
+    """(BM, BN, quad, ranges) of a dp_bgemm_plan code that names a tile (DP_GEMM_PLAN_BM / _BN / _QUAD / _RANGES)."""
+    return plan >> 20, (plan >> 12) & 255, (plan >> 11) & 1, plan & 2047
+
+
 # int (*dp_exchange_fn)(void* user, const void* local, void* gathered, size_t bytes_per_rank, void* stream)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -75,6 +98,10 @@ _PROTOS = {
     "dp_sizeof_encoder_cfg": (_Z, []),
     "dp_bgemm_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _I, _I, _F, _F, _I, _P]),
     "dp_bgemm_split_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _I, _I, _F, _P]),
+    "dp_sizeof_gemm_problem": (_Z, []),
+    "dp_bgemm_plan": (_I, [C.POINTER(GemmProblem), _I, _I, _I, C.POINTER(_I)]),
+    "dp_bgemm_group_workspace_bytes": (_Z, [C.POINTER(GemmProblem), _I, _I, _I]),
+    "dp_bgemm_group_f32": (_I, [C.POINTER(GemmProblem), _I, _I, _I, _P, _Z, _P]),
     "dp_adj_aggregate": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "dp_adj_pack_ld": (_I, [_I]),
     "dp_adj_pack_bytes": (_Z, [_I, _I]),
@@ -191,6 +218,9 @@ def load():
         if lib.dp_sizeof_encoder_cfg() != C.sizeof(EncoderCfg):
             raise RuntimeError("dp_encoder_cfg layout mismatch between diffpool_hip.h and _lib.py: "
                                f"{lib.dp_sizeof_encoder_cfg()} vs {C.sizeof(EncoderCfg)}")
+        if lib.dp_sizeof_gemm_problem() != C.sizeof(GemmProblem):
+            raise RuntimeError("dp_gemm_problem layout mismatch between diffpool_hip.h and _lib.py: "
+                               f"{lib.dp_sizeof_gemm_problem()} vs {C.sizeof(GemmProblem)}")
         _lib = lib
     return _lib
 

@@ -361,6 +361,99 @@ int dp_bgemm_f32(const float* A, const float* B, float* C, const float* bias, in
     return q.err;
 }
 
+// ---- groups of contractions (dp_bgemm_plan / dp_bgemm_group_f32): dp_gemm_problem -> GemmDesc the way dp_model.hip
+// fills it for each split-K form.  split_out, the row-partial hook, Seq::pred and Seq::fold_zero_p stay unset here.
+static_assert(DP_GEMM_GROUP_MAX == GEMM_GROUP_MAX, "diffpool_hip.h and dp_common.h disagree on the group size");
+size_t dp_sizeof_gemm_problem(void) { return sizeof(dp_gemm_problem); }
+namespace {
+bool gemm_tickets(const dp_gemm_problem& p, int ksplit) { return p.split == DP_GEMM_TICKETS && ksplit > 1; }
+GemmDesc gemm_desc_of(const dp_gemm_problem& p, float* fix_part, int* fix_cnt) {
+    GemmDesc d{p.A, p.B, p.C, p.bias, p.M, p.N, p.K, p.lda, p.ldb, p.ldc, (long)p.sA, (long)p.sB, (long)p.sC,
+               p.tA != 0, p.tB != 0, p.alpha, p.beta, p.act, 0, 0, nullptr, 0, 0, 0};
+    d.nosplit = p.split == DP_GEMM_WHOLE_K ? 1 : 0;
+    d.atomic = p.split == DP_GEMM_ATOMIC ? 1 : 0;
+    d.sK = p.split == DP_GEMM_SLABS ? (long)p.sK : 0;
+    d.fix_part = fix_part;
+    d.fix_cnt = fix_cnt;
+    return d;
+}
+int gemm_group_check(const dp_gemm_problem* p, int count, int batch, int ksplit, bool pointers) {
+    NOTNULL(p);
+    DP_CHECK_ARG(count >= 1 && count <= GEMM_GROUP_MAX, "count=%d out of range [1,%d]", count, GEMM_GROUP_MAX);
+    DP_CHECK_ARG(batch >= 1 && batch <= 65535, "batch=%d out of range [1,65535]", batch);
+    DP_CHECK_ARG(ksplit >= 1 && ksplit <= DP_GEMM_MAX_KSPLIT, "ksplit=%d out of range [1,%d]", ksplit,
+                 DP_GEMM_MAX_KSPLIT);
+    for (int i = 0; i < count; ++i) {
+        const dp_gemm_problem& s = p[i];
+        DP_CHECK_ARG(s.M >= 0 && s.N >= 0 && s.K >= 0, "problem %d: M=%d N=%d K=%d must not be negative", i, s.M, s.N, s.K);
+        DP_CHECK_ARG(s.split >= DP_GEMM_WHOLE_K && s.split <= DP_GEMM_TICKETS, "problem %d: split=%d", i, s.split);
+        DP_CHECK_ARG(s.act == 0 || s.act == 1, "problem %d: act=%d (0 none, 1 relu)", i, s.act);
+        if (!pointers) continue;
+        DP_CHECK_ARG(s.lda >= (s.tA ? s.M : s.K), "problem %d: lda=%d too small", i, s.lda);
+        DP_CHECK_ARG(s.ldb >= (s.tB ? s.K : s.N), "problem %d: ldb=%d too small", i, s.ldb);
+        DP_CHECK_ARG(s.ldc >= s.N, "problem %d: ldc=%d < N=%d", i, s.ldc, s.N);
+        if (s.split == DP_GEMM_ATOMIC)
+            DP_CHECK_ARG(!s.bias && !s.act && s.beta == 0.f,
+                         "problem %d: atomic split-K accumulates into C and takes no bias, act or beta", i);
+        if (s.split == DP_GEMM_SLABS) {
+            DP_CHECK_ARG(!s.bias && !s.act, "problem %d: slab split-K takes no bias or act (the slabs are partial sums)", i);
+            DP_CHECK_ARG(s.sK > 0, "problem %d: slab split-K needs sK > 0, the distance between two slabs", i);
+        }
+        if (s.M > 0 && s.N > 0) DP_CHECK_ARG(s.A && s.B && s.C, "problem %d: A, B or C is NULL", i);
+    }
+    return DP_OK;
+}
+// carves the partials and the tickets of the ticket problems out of q's workspace and launches (or only sizes: q.dry)
+void gemm_group_seq(Seq& q, const dp_gemm_problem* p, int count, int batch, int ksplit) {
+    GemmDesc d[GEMM_GROUP_MAX];
+    size_t cnt_ints = 0;
+    for (int i = 0; i < count; ++i)
+        if (gemm_tickets(p[i], ksplit)) cnt_ints += gemm_fix_counters(batch, p[i].M, p[i].N);
+    int* cnt = cnt_ints ? q.alloc<int>(cnt_ints) : nullptr;
+    size_t off = 0;
+    for (int i = 0; i < count; ++i) {
+        float* part = nullptr;
+        int* c = nullptr;
+        if (gemm_tickets(p[i], ksplit) && p[i].M > 0 && p[i].N > 0) {
+            part = q.alloc<float>((size_t)batch * ksplit * p[i].M * p[i].N);
+            c = cnt + off;
+            off += gemm_fix_counters(batch, p[i].M, p[i].N);
+        }
+        d[i] = gemm_desc_of(p[i], part, c);
+    }
+    if (q.err) return;
+    if (cnt_ints) zero_fill(q, cnt, cnt_ints * sizeof(int));
+    bgemm_group(q, d, count, batch, ksplit);
+}
+}  // namespace
+
+int dp_bgemm_plan(const dp_gemm_problem* p, int count, int batch, int ksplit, int* plan_out) {
+    NOTNULL(plan_out);
+    const int rc = gemm_group_check(p, count, batch, ksplit, false);
+    if (rc != DP_OK) return rc;
+    GemmDesc d[GEMM_GROUP_MAX];
+    float* const some = reinterpret_cast<float*>(sizeof(float));      // "has partials": never dereferenced
+    for (int i = 0; i < count; ++i)
+        d[i] = gemm_desc_of(p[i], gemm_tickets(p[i], ksplit) ? some : nullptr, nullptr);
+    return bgemm_plan(d, count, batch, ksplit, plan_out);
+}
+
+size_t dp_bgemm_group_workspace_bytes(const dp_gemm_problem* p, int count, int batch, int ksplit) {
+    if (gemm_group_check(p, count, batch, ksplit, false) != DP_OK) return 0;
+    Seq q = Seq::sizing();
+    gemm_group_seq(q, p, count, batch, ksplit);
+    return q.ws_off;
+}
+
+int dp_bgemm_group_f32(const dp_gemm_problem* p, int count, int batch, int ksplit, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    const int rc = gemm_group_check(p, count, batch, ksplit, true);
+    if (rc != DP_OK) return rc;
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    gemm_group_seq(q, p, count, batch, ksplit);
+    return q.err;
+}
+
 int dp_adj_aggregate(const float* adj, const float* V, int ldv, float* U, int ldu, int B, int n, int C, int trans,
                      float beta, void* stream) {
     NOTNULL(adj); NOTNULL(V); NOTNULL(U);

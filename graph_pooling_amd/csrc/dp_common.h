@@ -288,6 +288,16 @@ __device__ __host__ inline long vs_index(int plane, int CTt, int K8, int cb, int
 // ksplit > 1 cuts K into ranges run by different workgroups (contractions over the node index have K = n
 // = 500 but outputs of a few KB: without it they are 40-80 workgroups walking 16 dependent k-steps).
 void bgemm_group(Seq& q, const GemmDesc* d, int count, int batch, int ksplit = 1);
+// The launch-time choices of bgemm_group, made in ONE function (dp_gemm.hip): the tile of the launch and the K ranges
+// each problem runs (indexed like `d`; 0 for a problem with M or N = 0, which is not launched).
+struct GemmPick {
+    int bm, bn;
+    int ranges[GEMM_GROUP_MAX];
+};
+GemmPick gemm_pick(const GemmDesc* d, int count, int batch, int ksplit, bool hooked, long target);
+long gemm_target_wgs();
+// per problem a DP_GEMM_PLAN_* code (diffpool_hip.h: dp_bgemm_plan); host only
+int bgemm_plan(const GemmDesc* d, int count, int batch, int ksplit, int* plan_out);
 // (dp_gemm_split.hip) the same contraction with both operands split into three bf16 planes in registers and multiplied
 // on the bf16 matrix cores (six plane products, fp32 accumulation): fp32-grade results at ~2x the fp32-MFMA rate.
 // Large shapes only, no epilogue options (bias / act / split-K / split_out).

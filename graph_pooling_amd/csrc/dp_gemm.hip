@@ -514,6 +514,101 @@ static void launch_tile(Seq& q, GemmGroupArgs& g, int batch) {
                        q.stream, g);
 }
 
+// ---- launch-time choices.  gemm_pick is the ONLY place the tile and the K ranges of a launch are decided: bgemm_group
+// launches what it answers and bgemm_plan (dp_bgemm_plan, diffpool_hip.h) reports it.
+long gemm_target_wgs() { return knobs().gemm_target_wgs > 0 ? knobs().gemm_target_wgs : 512L; }   // tuning knob
+
+// K ranges problem `s` runs in a launch cut into `ksplit`
+static int gemm_ranges(const GemmDesc& s, int ksplit) {
+    if (s.nosplit || ksplit <= 1) return 1;
+    if (s.sK != 0) return ksplit;      // slab rows: every range writes its partial, the empty ones zeros
+    // ranges that start past K have nothing to add to a shared C (atomic or ticket combine): not launched
+    const int kchunk = ((s.K + ksplit * KT - 1) / (ksplit * KT)) * KT;
+    const int eff = (s.K + kchunk - 1) / kchunk;
+    return eff < 1 ? 1 : eff;
+}
+
+// One launch has ONE tile shape: the largest that still gives >= `target` workgroups (256 CUs x 2), the smallest
+// otherwise, and never a tile taller than the tallest problem (rows of padding are MFMA time).  Problems with
+// M or N = 0 are not launched and do not count.  `hooked`: a problem carries the row-partial hook, its row must stay
+// inside ONE wave (WN >= 32).
+GemmPick gemm_pick(const GemmDesc* d, int count, int batch, int ksplit, bool hooked, long target) {
+    GemmPick pk{};
+    int maxN = 0, maxM = 0;
+    for (int i = 0; i < count; ++i) {
+        if (d[i].M <= 0 || d[i].N <= 0) continue;
+        pk.ranges[i] = gemm_ranges(d[i], ksplit);
+        if (d[i].N > maxN) maxN = d[i].N;
+        if (d[i].M > maxM) maxM = d[i].M;
+    }
+    auto wgs = [&](int bm, int bn) {
+        long t = 0;
+        for (int i = 0; i < count; ++i)
+            if (d[i].M > 0 && d[i].N > 0)
+                t += (long)((d[i].M + bm - 1) / bm) * ((d[i].N + bn - 1) / bn) * batch;   // split-K not counted:
+        // it exists to add parallelism to small-output problems, not to license bigger tiles
+        return t;
+    };
+    auto tile = [&pk](int bm, int bn) { pk.bm = bm, pk.bn = bn; };
+    if (maxN <= 16) {
+        tile(64, 16);
+    } else if (maxN <= 32) {
+        if (maxM > 64 && wgs(128, 32) >= target) tile(128, 32);
+        else if (hooked || (maxM > 32 && wgs(64, 32) >= target)) tile(64, 32);
+        else tile(32, 32);
+    } else {
+        if (hooked || (maxM > 32 && wgs(64, 64) >= target)) tile(64, 64);
+        else if (maxM > 16 && wgs(32, 64) >= target) tile(32, 64);
+        else if (maxM > 16 && maxM <= 32) tile(32, 64);
+        else tile(16, 64);
+    }
+    return pk;
+}
+
+// Big batches: a group is one launch with ONE tile shape, and a 20-row or 20-column problem in a 64 x 64 tile spends
+// 3.2x its flops on padding — at B = 256, n = 1024 that padding, not memory, set the time of the GraphConv backward
+// groups (363 us for [20x20x1024 TN] [1024x20x20 NT] [20x256x1024 TN] [1024x20x256 NT]).  When the group is worth
+// more than a few launch floors it is split by shape class (short M / narrow N / the rest), one launch per class.
+static int gemm_class(const GemmDesc& s) { return s.M <= 32 ? 0 : s.N <= 32 ? 1 : 2; }
+static bool gemm_split_by_class(const GemmDesc* d, int count, int batch) {
+    if (count <= 1) return false;
+    double flops = 0;
+    for (int i = 0; i < count; ++i) flops += 2.0 * d[i].M * d[i].N * d[i].K * batch;
+    bool mixed = false;
+    for (int i = 1; i < count; ++i) mixed = mixed || gemm_class(d[i]) != gemm_class(d[0]);
+    return mixed && flops > 0.5e9;
+}
+
+// What bgemm_group does with each problem of a group, decided by the functions it decides with and in its order
+// (diversion, class split, tile); no GPU call, no pointer is read.  Launches without a predicate or a row-partial hook.
+int bgemm_plan(const GemmDesc* d, int count, int batch, int ksplit, int* plan_out) {
+    if (ksplit < 1) ksplit = 1;
+    int idx[GEMM_GROUP_MAX], nrest = 0;
+    for (int i = 0; i < count; ++i) {
+        if (gemm_split_usable(d[i], batch, d[i].nosplit ? 1 : ksplit)) plan_out[i] = DP_GEMM_PLAN_SPLIT_BF16;
+        else idx[nrest++] = i;
+    }
+    GemmDesc rest[GEMM_GROUP_MAX];
+    for (int i = 0; i < nrest; ++i) rest[i] = d[idx[i]];
+    const bool by_class = gemm_split_by_class(rest, nrest, batch);
+    for (int c = 0; c < (by_class ? 3 : 1); ++c) {
+        GemmDesc part[GEMM_GROUP_MAX];
+        int pidx[GEMM_GROUP_MAX], np = 0;
+        for (int i = 0; i < nrest; ++i)
+            if (!by_class || gemm_class(rest[i]) == c) part[np] = rest[i], pidx[np++] = idx[i];
+        const GemmPick pk = gemm_pick(part, np, batch, ksplit, false, gemm_target_wgs());
+        for (int i = 0; i < np; ++i) {
+            const GemmDesc& s = part[i];
+            // (the loader is the kernel's own choice, bgemm_kernel `quad`: 16-byte loads need four elements along each
+            // operand's contiguous dimension)
+            const bool quad = (s.tA ? s.M : s.K) >= 4 && (s.tB ? s.K : s.N) >= 4;
+            plan_out[pidx[i]] = (s.M <= 0 || s.N <= 0) ? DP_GEMM_PLAN_NONE
+                                                      : DP_GEMM_PLAN(pk.bm, pk.bn, quad ? 1 : 0, pk.ranges[i]);
+        }
+    }
+    return DP_OK;
+}
+
 void bgemm_group(Seq& q, const GemmDesc* d_in, int count, int batch, int ksplit) {
     if (!q.ok() || batch <= 0 || count <= 0) return;
     if (ksplit < 1) ksplit = 1;
@@ -543,26 +638,15 @@ void bgemm_group(Seq& q, const GemmDesc* d_in, int count, int batch, int ksplit)
         q.err = DP_ERR_INVALID_ARG;
         return;
     }
-    // Big batches: a group is one launch with ONE tile shape, and a 20-row or 20-column problem in a 64 x 64 tile spends
-    // 3.2x its flops on padding — at B = 256, n = 1024 that padding, not memory, set the time of the GraphConv backward
-    // groups (363 us for [20x20x1024 TN] [1024x20x20 NT] [20x256x1024 TN] [1024x20x256 NT]).  When the group is worth
-    // more than a few launch floors it is split by shape class (short M / narrow N / the rest), one launch per class.
-    if (count > 1 && !q.pred) {
-        double flops = 0;
-        for (int i = 0; i < count; ++i) flops += 2.0 * d[i].M * d[i].N * d[i].K * batch;
-        auto cls = [](const GemmDesc& s) { return s.M <= 32 ? 0 : s.N <= 32 ? 1 : 2; };
-        bool mixed = false;
-        for (int i = 1; i < count; ++i) mixed = mixed || cls(d[i]) != cls(d[0]);
-        if (mixed && flops > 0.5e9) {
-            GemmDesc part[GEMM_GROUP_MAX];
-            for (int c = 0; c < 3; ++c) {
-                int np = 0;
-                for (int i = 0; i < count; ++i)
-                    if (cls(d[i]) == c) part[np++] = d[i];
-                if (np > 0) bgemm_group(q, part, np, batch, ksplit);
-            }
-            return;
+    if (!q.pred && gemm_split_by_class(d, count, batch)) {      // one launch per shape class
+        GemmDesc part[GEMM_GROUP_MAX];
+        for (int c = 0; c < 3; ++c) {
+            int np = 0;
+            for (int i = 0; i < count; ++i)
+                if (gemm_class(d[i]) == c) part[np++] = d[i];
+            if (np > 0) bgemm_group(q, part, np, batch, ksplit);
         }
+        return;
     }
     GemmGroupArgs g{};
     g.pred = q.pred;
@@ -570,11 +654,12 @@ void bgemm_group(Seq& q, const GemmDesc* d_in, int count, int batch, int ksplit)
         g.zero_p = static_cast<uint4*>(q.fold_zero_p);
         g.zero_n16 = q.fold_zero_n16;
     }
-    int maxN = 0, maxM = 0;
     bool hooked = false;      // a problem carries the row-partial hook: its row must stay inside ONE wave (WN >= 32)
+    int src[GEMM_GROUP_MAX];  // g.p[k] is problem d[src[k]]
     for (int i = 0; i < count; ++i) {
         const GemmDesc& s = d[i];
         if (s.M <= 0 || s.N <= 0) continue;
+        src[g.count] = i;
         GemmArgs& a = g.p[g.count++];
         a = GemmArgs{s.A, s.B, s.C, s.bias, s.M, s.N, s.K, s.lda, s.ldb, s.ldc, s.sA, s.sB, s.sC, s.alpha, s.beta,
                      s.act, 0, s.tA ? 1 : 0, s.tB ? 1 : 0, s.nosplit ? 1 : ksplit, ksplit, s.sK, s.atomic,
@@ -588,16 +673,10 @@ void bgemm_group(Seq& q, const GemmDesc* d_in, int count, int batch, int ksplit)
             }
             hooked = true;
         }
-        if (a.ksplit > 1 && a.sK == 0) {
-            // ranges that start past K have nothing to add to a shared C (atomic or ticket combine): not launched
-            const int kchunk = ((a.K + a.ksplit * KT - 1) / (a.ksplit * KT)) * KT;
-            const int eff = (a.K + kchunk - 1) / kchunk;
-            a.ksplit = eff < 1 ? 1 : eff;
-        }
-        if (s.N > maxN) maxN = s.N;
-        if (s.M > maxM) maxM = s.M;
     }
     if (g.count == 0) return;
+    const GemmPick pk = gemm_pick(d, count, batch, ksplit, hooked, gemm_target_wgs());
+    for (int k = 0; k < g.count; ++k) g.p[k].ksplit = pk.ranges[src[k]];
     if (g.zero_p) q.fold_zero_p = nullptr, q.fold_zero_n16 = 0;
     if (knobs().gemm_trace) {   // host-side shape log, one line per launch
         fprintf(stderr, "bgemm batch=%d ksplit=%d:", batch, ksplit);
@@ -606,27 +685,14 @@ void bgemm_group(Seq& q, const GemmDesc* d_in, int count, int batch, int ksplit)
                     g.p[i].tB ? 'T' : 'N', d[i].nosplit ? " nosplit" : "", d[i].atomic ? " atomic" : "");
         fprintf(stderr, "\n");
     }
-    // Largest tile that still gives >= TARGET workgroups (256 CUs x 2); smallest tile otherwise.
-    const long TARGET = knobs().gemm_target_wgs > 0 ? knobs().gemm_target_wgs : 512L;   // tuning knob
-    auto wgs = [&](int bm, int bn) {
-        long t = 0;
-        for (int i = 0; i < g.count; ++i)
-            t += (long)((g.p[i].M + bm - 1) / bm) * ((g.p[i].N + bn - 1) / bn) * batch;   // split-K not counted:
-        // it exists to add parallelism to small-output problems, not to license bigger tiles
-        return t;
-    };
-    // ... and never a tile taller than the tallest problem (rows of padding are MFMA time)
-    if (maxN <= 16) {
-        launch_tile<64, 16, 4, 1>(q, g, batch);
-    } else if (maxN <= 32) {
-        if (maxM > 64 && wgs(128, 32) >= TARGET) launch_tile<128, 32, 4, 1>(q, g, batch);
-        else if (hooked || (maxM > 32 && wgs(64, 32) >= TARGET)) launch_tile<64, 32, 4, 1>(q, g, batch);
-        else launch_tile<32, 32, 2, 2>(q, g, batch);
-    } else {
-        if (hooked || (maxM > 32 && wgs(64, 64) >= TARGET)) launch_tile<64, 64, 2, 2>(q, g, batch);
-        else if (maxM > 16 && wgs(32, 64) >= TARGET) launch_tile<32, 64, 1, 4>(q, g, batch);
-        else if (maxM > 16 && maxM <= 32) launch_tile<32, 64, 1, 4>(q, g, batch);
-        else launch_tile<16, 64, 1, 4>(q, g, batch);
+    switch (pk.bm * 1000 + pk.bn) {
+        case 64016: launch_tile<64, 16, 4, 1>(q, g, batch); break;
+        case 128032: launch_tile<128, 32, 4, 1>(q, g, batch); break;
+        case 64032: launch_tile<64, 32, 4, 1>(q, g, batch); break;
+        case 32032: launch_tile<32, 32, 2, 2>(q, g, batch); break;
+        case 64064: launch_tile<64, 64, 2, 2>(q, g, batch); break;
+        case 32064: launch_tile<32, 64, 1, 4>(q, g, batch); break;
+        default: launch_tile<16, 64, 1, 4>(q, g, batch); break;
     }
     q.check_launch("bgemm");
 }

@@ -86,6 +86,65 @@ int dp_bgemm_f32(const float* A, const float* B, float* C, const float* bias, in
                  int K, int lda, int ldb, int ldc, long strideA, long strideB, long strideC, int transA,
                  int transB, float alpha, float beta, int act, void* stream);
 
+/* Groups of up to DP_GEMM_GROUP_MAX contractions (same batch count) in ONE launch, optionally with K cut into `ksplit`
+ * ranges run by different workgroups — the form the encoder's backward and pooling products use.  No reference
+ * counterpart (the reference issues one torch.matmul per product).  Per problem, `split` says how the ranges combine:
+ *   DP_GEMM_WHOLE_K   this problem walks its whole K in one workgroup whatever `ksplit` is (a sibling of split ones)
+ *   DP_GEMM_ATOMIC    C += alpha * op(A) op(B) with float atomics (no bias, act or beta: C is accumulated into)
+ *   DP_GEMM_SLABS     range ks writes alpha * (its partial product) + beta * (old value) at C + ks * sK, ranges
+ *                     without any k write the beta term alone; the caller sums the slabs (no bias or act)
+ *   DP_GEMM_TICKETS   every range stores its partial to the workspace, the last to arrive adds them in range order and
+ *                     applies the full epilogue once: bit-reproducible
+ * Strides sA, sB, sC and sK are in elements.  `bias` is tested for NULL only by the plan query. */
+#define DP_GEMM_GROUP_MAX 4
+#define DP_GEMM_WHOLE_K 0
+#define DP_GEMM_ATOMIC 1
+#define DP_GEMM_SLABS 2
+#define DP_GEMM_TICKETS 3
+typedef struct {
+    const float* A;
+    const float* B;
+    float* C;
+    const float* bias;
+    int M, N, K, lda, ldb, ldc;
+    int64_t sA, sB, sC;
+    int tA, tB;
+    float alpha, beta;
+    int act;
+    int split;
+    int64_t sK;
+} dp_gemm_problem;
+size_t dp_sizeof_gemm_problem(void); /* sizeof(dp_gemm_problem): lets a binding check its struct layout */
+
+/* dp_bgemm_plan: what the launcher does with each problem of such a group (dp_bgemm_f32 is a group of one at
+ * ksplit = 1, split = DP_GEMM_WHOLE_K) — answered by the function the launcher itself decides with.  Host only: no GPU
+ * call, and no pointer of `p` is read.  plan_out[i] is
+ *   DP_GEMM_PLAN_NONE        not launched (M or N = 0)
+ *   DP_GEMM_PLAN_SPLIT_BF16  diverted to the split-bf16 kernel (dp_bgemm_split_bf16), a launch of its own
+ *   otherwise                DP_GEMM_PLAN(BM, BN, quad, ranges): the BM x BN workgroup tile of the launch the problem
+ *                            ends up in (a mixed group worth more than 0.5 GFLOP is split into one launch per shape
+ *                            class), quad = 1 for the 16-byte operand loader, 0 for the 4-byte one, and the number of
+ *                            K ranges that are launched (ranges that would start past K are not, except with slabs).
+ * Returns DP_OK, or DP_ERR_INVALID_ARG for a count, batch or ksplit out of range. */
+#define DP_GEMM_PLAN_NONE 0
+#define DP_GEMM_PLAN_SPLIT_BF16 1
+#define DP_GEMM_PLAN(bm, bn, quad, ranges) (((bm) << 20) | ((bn) << 12) | ((quad) << 11) | (ranges))
+#define DP_GEMM_PLAN_BM(plan) ((plan) >> 20)
+#define DP_GEMM_PLAN_BN(plan) (((plan) >> 12) & 255)
+#define DP_GEMM_PLAN_QUAD(plan) (((plan) >> 11) & 1)
+#define DP_GEMM_PLAN_RANGES(plan) ((plan) & 2047)
+#define DP_GEMM_MAX_KSPLIT 2047
+int dp_bgemm_plan(const dp_gemm_problem* p, int count, int batch, int ksplit, int* plan_out);
+
+/* dp_bgemm_group_f32 launches the group.  The workspace (dp_bgemm_group_workspace_bytes) holds the partials
+ * [batch][ksplit][M][N] and the tickets of the DP_GEMM_TICKETS problems; the tickets are zero-filled on the stream in
+ * front of the launch.  Refused with DP_ERR_INVALID_ARG before any launch: count > DP_GEMM_GROUP_MAX, leading
+ * dimensions smaller than the rows, bias / act / beta with DP_GEMM_ATOMIC, bias / act with DP_GEMM_SLABS, sK <= 0 with
+ * DP_GEMM_SLABS. */
+size_t dp_bgemm_group_workspace_bytes(const dp_gemm_problem* p, int count, int batch, int ksplit);
+int dp_bgemm_group_f32(const dp_gemm_problem* p, int count, int batch, int ksplit, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* The same contraction (alpha = 1, beta in {0, 1}, no bias / activation) with BOTH fp32 operands split exactly into
  * three bf16 planes on the way to LDS and multiplied on the bf16 matrix cores — six plane products, fp32 accumulation;
  * the dropped cross terms are <= 2^-23 of a product, so the result is fp32-grade (not bit-identical to dp_bgemm_f32).

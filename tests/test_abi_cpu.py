@@ -71,6 +71,7 @@ def test_version_and_error_string(lib):
     assert lib.dp_version() == 100
     assert isinstance(lib.dp_last_error_string(), bytes)
     assert lib.dp_sizeof_encoder_cfg() == C.sizeof(_lib.EncoderCfg)
+    assert lib.dp_sizeof_gemm_problem() == C.sizeof(_lib.GemmProblem) == 112
 
 
 def test_device_error_word_decode(lib):
@@ -94,6 +95,12 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     # NULL pointers / bad dims must come back as DP_ERR_INVALID_ARG with a message (no GPU needed)
     rc = lib.dp_bgemm_f32(None, None, None, None, 1, 4, 4, 4, 4, 4, 4, 0, 0, 0, 0, 0, 1.0, 0.0, 0, None)
     assert rc == -1 and b"NULL" in lib.dp_last_error_string()
+    # a group entry answers before it looks at a pointer: a bad count, then NULL operands
+    prob = (_lib.GemmProblem * 1)(_lib.GemmProblem(M=4, N=4, K=4, lda=4, ldb=4, ldc=4, alpha=1.0))
+    plan = (C.c_int * 1)()
+    assert lib.dp_bgemm_plan(prob, 5, 1, 1, plan) == -1 and b"count=5" in lib.dp_last_error_string()
+    assert lib.dp_bgemm_plan(prob, 1, 1, 1, plan) == 0 and _lib.gemm_plan_decode(plan[0]) == (64, 16, 1, 1)
+    assert lib.dp_bgemm_group_f32(prob, 1, 1, 1, None, 0, None) == -1 and b"NULL" in lib.dp_last_error_string()
     rc = lib.dp_masked_max_fwd(1, 4, None, 1, 4, 1, 0, 3, 4, None)
     assert rc == -1 and b"B=0" in lib.dp_last_error_string()
     cfg = _lib.EncoderCfg()
@@ -108,6 +115,13 @@ def test_workspace_queries_run_without_gpu(lib):
     assert 0 < lib.dp_linkpred_workspace_bytes(20, 500, 50) < 20 * 500 * 500 * 4 // 2
     assert lib.dp_linkpred_workspace_bytes(256, 1024, 256) < 1 << 20          # big batches need no split
     assert lib.dp_bn_node_workspace_bytes(4, 16, 8) > 0
+    # tickets: [batch][ksplit][M][N] partials and one counter per 16 x 16 block; no other split form needs any
+    prob = (_lib.GemmProblem * 1)(_lib.GemmProblem(M=20, N=40, K=500, lda=500, ldb=40, ldc=40, alpha=1.0,
+                                                   split=_lib.GEMM_TICKETS))
+    assert lib.dp_bgemm_group_workspace_bytes(prob, 1, 3, 4) >= 4 * (3 * 4 * 20 * 40 + 3 * 2 * 3)
+    assert lib.dp_bgemm_group_workspace_bytes(prob, 1, 3, 1) == 0
+    prob[0].split = _lib.GEMM_SLABS
+    assert lib.dp_bgemm_group_workspace_bytes(prob, 1, 3, 4) == 0
 
 
 def test_product_has_no_cpu_fallback():
