@@ -167,8 +167,9 @@ class _CsrGraphConvFn(torch.autograd.Function):
 
 
 def csr_graph_conv(x, weight, bias, graph, flags):
-    """`graph_conv` on ONE graph given as CSR: x [n, F]; `graph` carries int32 indptr / indices of A and of A^T (the
-    neighbour sum A x is the gather of dp_csr_aggregate, the backward gathers over A^T)."""
+    """`graph_conv` on node rows x [n, F] with the adjacency as CSR: `graph` (a CsrGraph, or a CsrBatch with its
+    block-diagonal CSR and n = n_total) carries int32 indptr / indices of A and of A^T (the neighbour sum A x is the
+    gather of dp_csr_aggregate, the backward gathers over A^T)."""
     return _CsrGraphConvFn.apply(x, weight, bias, graph, flags)
 
 
@@ -209,7 +210,7 @@ class _BnReluNodesFn(torch.autograd.Function):
 
 def bn_relu_nodes(x):
     """apply_bn (encoders.py:1048-1052) after ReLU on ONE graph, x [n, f]: dp_bn_node_* with a batch of one, the ReLU
-    fused into the kernel.  x [B, n, f]: the same on a dense batch (the pooled levels of a CsrBatch)."""
+    fused into the kernel.  x [B, n, f]: the same on a dense batch (the pooled levels of the CSR DiffPool model)."""
     return _BnReluNodesFn.apply(x)
 
 
@@ -361,7 +362,7 @@ class _DensePoolFn(torch.autograd.Function):
 
 def dense_pool(s, z, adj):
     """The same pooling on a pooled level (dense n x n adjacency): dp_pool_* with B = 1; with a leading batch
-    dimension on all three, on a dense batch."""
+    dimension on all three (as the CSR DiffPool model calls it, B = 1 behind a CsrGraph), on a dense batch."""
     return _DensePoolFn.apply(s, z, adj)
 
 

@@ -13,10 +13,13 @@ aggregators.py:50-62), the transform, bias, l2-normalisation and their backward 
 prediction head run on dp_bgemm_f32 (`hip_linear`).  No torch arithmetic on the path.  The autograd wrappers of these
 entries live in `ops.py`; this module holds the CSR container and the two model classes.
 
-`SparseSoftPoolingGcnEncoder` does the same for DiffPool (`SoftPoolingGcnEncoder`): level 0 on the CSR ops above plus
-dp_csr_pool_fwd / bwd for the pooling S^T Z, S^T A S (encoders.py:1278-1279), the small pooled levels on the dense
-per-op entries with B = 1, and the link-prediction loss (encoders.py:1309-1331) on dp_csr_linkpred_loss_fwd / bwd,
-which never forms an n x n adjacency.
+`SparseSoftPoolingGcnEncoder` does the same for DiffPool (`SoftPoolingGcnEncoder`) on one `CsrGraph` or on a ragged
+`CsrBatch`, in ONE forward and one loss.  The two containers differ in four steps, each a method of the container:
+`bn_relu` (dp_bn_node_* / dp_bn_ragged_*), `readout` (dp_masked_max_* / dp_segment_max_*), `pool` — S^T Z, S^T A S,
+encoders.py:1278-1279 — (dp_csr_pool_* / dp_csr_pool_batch_*) and `link_loss` — encoders.py:1309-1331, never forming
+an n x n adjacency — (dp_csr_linkpred_loss_* / dp_csr_linkpred_batch_*).  A single graph is NOT a batch of one: it
+keeps its own kernels.  The small pooled levels run on the dense per-op entries as a dense batch [B, K, .], B = 1
+behind a CsrGraph.
 """
 from __future__ import annotations
 
@@ -32,13 +35,38 @@ from .ops import hip_linear  # noqa: F401  (tests and tools import it from here)
 class CsrGraph:
     """CSR of one graph's adjacency on the device: int32 indptr [n + 1], indices [nnz] — row i lists the j with
     A[i, j] != 0 (0/1 adjacency, graph_sampler.py:26) — plus the CSR of A^T for the backward gather (the same arrays
-    for an undirected graph)."""
+    for an undirected graph).
+
+    `bn_relu`, `readout`, `pool` and `link_loss` are the four steps of the DiffPool model that differ between one graph
+    and a `CsrBatch`; `ARG` and `rows()` are how the model's messages name the container and its node rows."""
+
+    ARG = "graph"
 
     def __init__(self, indptr, indices, indptr_t=None, indices_t=None):
         self.indptr, self.indices = indptr, indices
         self.indptr_t = indptr if indptr_t is None else indptr_t
         self.indices_t = indices if indices_t is None else indices_t
         self.n = indptr.numel() - 1
+
+    def rows(self):
+        return f"[n, F] with n = {self.n}"
+
+    def bn_relu(self, h, layer):
+        """apply_bn after ReLU behind GraphConv `layer`: dp_bn_node_* with B = 1."""
+        return ops.bn_relu_nodes(h)
+
+    def readout(self, z):
+        """Max over the node rows -> (out [1, D], arg-max rows [1, D]): dp_masked_max_*."""
+        return ops.row_max(z)
+
+    def pool(self, s, z):
+        """S^T Z [1, K, D] and S^T A S [1, K, K] (dp_csr_pool_*), shaped as the one-graph dense batch the pooled
+        levels run on."""
+        xp, ap = ops.csr_pool(s, z, self)
+        return xp.unsqueeze(0), ap.unsqueeze(0)
+
+    def link_loss(self, s):
+        return ops.csr_link_loss(s, self)
 
     @staticmethod
     def from_edges(n, src, dst, device, symmetric=True):
@@ -107,6 +135,7 @@ class CsrBatch:
     chunks of the segmented max, the floor flags, and (on first use per (K, D), then cached) the pooling's slab tables."""
 
     SEG_ROWS = 128          # rows per chunk of the segmented max readout
+    ARG = "batch"
 
     def __init__(self, sizes, parts, device, pad_to=None):
         """`parts`: per graph (indptr, indices, indptr_t, indices_t) as host int arrays with graph-local columns, the
@@ -185,6 +214,32 @@ class CsrBatch:
             plan = self._pool_plans[(k, d)] = _PoolPlan(self.node_off_host, k, d, self.device)
         return plan
 
+    # -- the four steps of the DiffPool model that differ from a single CsrGraph's
+    def rows(self):
+        return f"[n_total, F] with n_total = {self.n_total} (the batch's graphs concatenated)"
+
+    def bn_relu(self, h, layer):
+        """apply_bn after ReLU behind GraphConv `layer`, per node index over the batch: the padded rows of the dense
+        batch enter the statistics as the layer's constant relu(l2norm(bias)) (dp_bn_ragged_*), whose gradient flows
+        back into the bias."""
+        if layer.add_self:
+            raise NotImplementedError("add_self GraphConv layers (concat=False) on a CsrBatch: a padded row of the dense "
+                                      "batch is then not a constant of the layer")
+        pad = ops.gcn_pad_const(layer.bias, layer._flags()) if self.has_padding and layer.bias is not None else None
+        return ops.bn_relu_ragged(h, pad, self)
+
+    def readout(self, z):
+        """Max over each graph's rows, with the zero floor of a graph that has padded rows -> (out [B, D], graph-local
+        arg-max rows [B, D]): dp_segment_max_*."""
+        return ops.segment_max(z, self)
+
+    def pool(self, s, z):
+        """Per graph S^T Z [B, K, D] and S^T A S [B, K, K]: dp_csr_pool_batch_*."""
+        return ops.csr_pool_batch(s, z, self)
+
+    def link_loss(self, s):
+        return ops.csr_link_loss_batch(s, self)
+
     @staticmethod
     def from_graphs(graphs, pad_to=None):
         """A batch of existing `CsrGraph`s (their arrays are read back to the host once)."""
@@ -234,36 +289,19 @@ class CsrBatch:
 
 
 def _gcn_stack(mods, h, graph, bn=True):
-    """gcn_forward (encoders.py:1054-1081) on one graph: GraphConv -> ReLU -> apply_bn for every layer but the last;
-    yields each layer's output as soon as it is enqueued.  `graph` is a CsrGraph, or a pooled level's dense K x K
-    adjacency (dp_gcn_layer_* with B = 1)."""
+    """gcn_forward (encoders.py:1054-1081) on the node rows h [n, F] of a CsrGraph or a CsrBatch: the CSR GraphConv, then
+    ReLU -> apply_bn as the container does it (`graph.bn_relu`) for every layer but the last; yields each layer's
+    output as soon as it is enqueued."""
     for i, m in enumerate(mods):
-        if isinstance(graph, CsrGraph):
-            h = ops.csr_graph_conv(h, m.weight, m.bias, graph, m._flags())
-        else:
-            h = ops.graph_conv(h.unsqueeze(0), graph.unsqueeze(0), m.weight, m.bias, m._flags())[0]
+        h = ops.csr_graph_conv(h, m.weight, m.bias, graph, m._flags())
         if i < len(mods) - 1:
-            h = ops.bn_relu_nodes(h) if bn else torch.relu(h)      # ReLU is fused into the BN kernel
-        yield h
-
-
-def _gcn_stack_ragged(mods, h, batch):
-    """`_gcn_stack` on the ragged rows of a CsrBatch, h [n_total, F]: the CSR GraphConv on the block-diagonal adjacency,
-    then apply_bn per node index over the batch — the padded rows of the dense batch enter its statistics as the layer's
-    constant relu(l2norm(bias)) (dp_bn_ragged_*), whose gradient flows back into the bias."""
-    for i, m in enumerate(mods):
-        if m.add_self:
-            raise NotImplementedError("add_self GraphConv layers (concat=False) on a CsrBatch: a padded row of the dense "
-                                      "batch is then not a constant of the layer")
-        h = ops.csr_graph_conv(h, m.weight, m.bias, batch, m._flags())
-        if i < len(mods) - 1:
-            pad = ops.gcn_pad_const(m.bias, m._flags()) if batch.has_padding and m.bias is not None else None
-            h = ops.bn_relu_ragged(h, pad, batch)
+            h = graph.bn_relu(h, m) if bn else torch.relu(h)      # ReLU is fused into the BN kernel
         yield h
 
 
 def _gcn_stack_dense(mods, h, adj):
-    """`_gcn_stack` on a dense batch h [B, n, F], adj [B, n, n] (the pooled levels of a CsrBatch)."""
+    """`_gcn_stack` on a dense batch h [B, n, F], adj [B, n, n]: the pooled levels (dp_gcn_layer_*, dp_bn_node_*), with
+    B = 1 behind a CsrGraph."""
     for i, m in enumerate(mods):
         h = ops.graph_conv(h, adj, m.weight, m.bias, m._flags())
         if i < len(mods) - 1:
@@ -305,31 +343,32 @@ class SparseGcnEncoderGraph(GcnEncoderGraph):
 
 # ----------------------------------------------------------------------------- DiffPool on a CSR graph
 class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
-    """`SoftPoolingGcnEncoder` (DiffPool, encoders.py:1160-1334 with the SURVEY.md Appendix B fixes D3 / D4) on ONE graph
+    """`SoftPoolingGcnEncoder` (DiffPool, encoders.py:1160-1334 with the SURVEY.md Appendix B fixes D3 / D4) on a graph
     given as CSR: forward(x [n, F], graph) -> ypred [1, label_dim], for any n — also graphs above `max_num_nodes`,
-    which the padded dense path (and the reference, load_data.py:79) cannot hold.
+    which the padded dense path (and the reference, load_data.py:79) cannot hold — or on a `CsrBatch` (B graphs, rows
+    concatenated): forward(x [n_total, F], batch) -> ypred [B, label_dim].
 
     Same constructor and `state_dict` keys / shapes as the dense class (it IS the dense class's module tree), so a
     model trained on the dense path scores large graphs after `load_state_dict`.  `max_num_nodes` only fixes the
     cluster counts K_j = int(max_num_nodes * assign_ratio^(j+1)), as in the dense class.
 
-    Level 0 runs on the CSR kernels: GraphConv as dp_sparse_gcn_layer_*, apply_bn as dp_bn_node_* with B = 1 (ReLU
-    fused), the assignment softmax as dp_assign_softmax_mask_* (no mask: every row is a node), and the pooling
-    S^T Z, S^T A S as dp_csr_pool_*.  The pooled levels are K_j x K_j dense graphs and run on the dense per-op entries
-    with B = 1 (dp_gcn_layer_*, dp_bn_node_*, dp_assign_softmax_mask_*, dp_pool_*); readouts on dp_masked_max_*,
+    One body serves both containers.  Level 0 runs on the node rows: GraphConv as dp_sparse_gcn_layer_* (for a batch on
+    the block-diagonal CSR), the assignment softmax as dp_assign_softmax_mask_* (no mask: every row is a node), and
+    apply_bn (ReLU fused), the max readout and the pooling S^T Z, S^T A S as the container does them.  A CsrGraph:
+    dp_bn_node_* with B = 1, dp_masked_max_*, dp_csr_pool_*.  A CsrBatch computes what the dense class computes on the
+    same graphs padded to max_b n_b: the BatchNorm statistics per node index include the padded rows' constants
+    (dp_bn_ragged_*), the readout has the zero floor of a graph with padded rows (dp_segment_max_*), the pooling is
+    taken per graph (dp_csr_pool_batch_*).  The pooled levels are dense [B, K_j, K_j] graphs (B = 1 behind a CsrGraph)
+    on the dense per-op entries (dp_gcn_layer_*, dp_bn_node_*, dp_assign_softmax_mask_*, dp_pool_*, dp_masked_max_*);
     pred_model on `hip_linear`, the loss on dp_cross_entropy_*.
 
     A linkpred=True model (the constructor default, train.py --linkpred) trains here too: `loss(pred, label, graph)`
-    adds the link-prediction term on dp_csr_linkpred_loss_* — the n^2 part of the sum does not depend on the adjacency
-    and is a tile walk over S, the rest a gather over the edges; O(n K_0) memory, no dense adjacency.
+    adds the link-prediction term on dp_csr_linkpred_loss_* (per graph of a batch: dp_csr_linkpred_batch_*) — the n^2
+    part of the sum does not depend on the adjacency and is a tile walk over S, the rest a gather over the edges;
+    O(n K_0) memory, no dense adjacency.
 
-    A `CsrBatch` (B graphs, rows concatenated) in place of the CsrGraph runs the batch: forward(x [n_total, F], batch)
-    -> ypred [B, label_dim], computing what the dense class computes on the same graphs padded to max_b n_b — the
-    BatchNorm statistics per node index include the padded rows' constants (dp_bn_ragged_*), the level-0 readout has the
-    zero floor of a graph with padded rows (dp_segment_max_*), pooling and link loss are taken per graph
-    (dp_csr_pool_batch_*, dp_csr_linkpred_batch_*) and the pooled levels run on the dense entries with the real B.
-    Differences from the dense class's saved tensors: level-0 'assign' / 'embedding' and `assign_tensor` stay RAGGED,
-    [n_total, .] (dense: [B, N, .]); level-0 'readout_argmax' rows are graph-local.
+    Differences of a CsrBatch forward from the dense class's saved tensors: level-0 'assign' / 'embedding' and
+    `assign_tensor` stay RAGGED, [n_total, .] (dense: [B, N, .]); level-0 'readout_argmax' rows are graph-local.
 
     Not on this path: dropout, adj_hop > 1, weighted adjacencies, K_0 > 256 or a concatenated embedding wider than 512
     (dp_csr_pool's limits); on a CsrBatch also concat=False."""
@@ -352,97 +391,42 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
                              "(dp_csr_pool) supports D <= 512")
         self._saved = None
 
-    def _embed(self, first, block, last, h, graph):
-        """One GraphConv stack's embedding: the concatenation of all its layers' outputs (encoders.py:1078)."""
-        return torch.cat(list(_gcn_stack(self._stack_modules(first, block, last), h, graph)), dim=1)
-
-    # -- public surface
-    def _forward_batch(self, x, batch, assign_x):
-        x_a = x if assign_x is None else assign_x
-        for t, name in ((x, "x"), (x_a, "assign_x")):
-            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != batch.n_total:
-                got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"expected {name} [n_total, F] with n_total = {batch.n_total} (the batch's graphs "
-                                 f"concatenated), got {got}")
-        if x.shape[1] != self.input_dim or x_a.shape[1] != self.assign_input_dim:
-            raise ValueError(f"feature widths {x.shape[1]}/{x_a.shape[1]} do not match the model "
-                             f"({self.input_dim}/{self.assign_input_dim})")
-        if not self.concat:
-            raise NotImplementedError("concat=False (add_self GraphConv layers) on a CsrBatch")
-        _lib.require_gpu_tensor(x, "x")
-        _lib.require_gpu_tensor(x_a, "assign_x")
-        x, x_a = x.contiguous().float(), x_a.contiguous().float()
-        saved = {"assign": [], "xpool": [], "adjpool": [], "embedding": [], "graph": batch}
-        cat = lambda gen, dim: torch.cat(list(gen), dim=dim)
-        z = cat(_gcn_stack_ragged(self._stack_modules(self.conv_first, self.conv_block, self.conv_last), x, batch), 1)
-        saved["embedding"].append(z)
-        out, arg = ops.segment_max(z, batch)                                                              # :1257
-        outs, argmax = [out], [arg]
-        adj, s0 = None, None
-        for i in range(self.num_pooling):                                                                 # :1263
-            pred = self.assign_pred_modules[i]
-            amods = self._stack_modules(self.assign_conv_first_modules[i], self.assign_conv_block_modules[i],
-                                        self.assign_conv_last_modules[i])
-            if i == 0:
-                za = cat(_gcn_stack_ragged(amods, x_a, batch), 1)
-                s = s0 = ops.assign_softmax(za, pred.weight, pred.bias)           # ragged rows: every row is a node
-                xp, adj = ops.csr_pool_batch(s, z, batch)                                                 # :1278-1279
-            else:
-                za = cat(_gcn_stack_dense(amods, x_a, adj), 2)
-                s = ops.assign_softmax(za, pred.weight, pred.bias)
-                xp, adj = ops.dense_pool(s, z, adj)
-            x_a = xp                                                                                      # :1280
-            z = cat(_gcn_stack_dense(self._stack_modules(self.conv_first_after_pool[i], self.conv_block_after_pool[i],
-                                                         self.conv_last_after_pool[i]), xp, adj), 2)
-            out, arg = ops.row_max(z)                                                                     # :1287
-            outs.append(out)
-            argmax.append(arg)
-            saved["assign"].append(s)
-            saved["xpool"].append(xp)
-            saved["adjpool"].append(adj)
-            saved["embedding"].append(z)
-        ypred = ops.mlp_head(torch.cat(outs, dim=1), self._pred_linears())                                # :1295-1299
-        saved["readout_argmax"] = argmax
-        self._saved = saved
-        self.assign_tensor = s0                      # RAGGED [n_total, K_0] (the dense class keeps [B, N, K_0])
-        return ypred
-
-    def forward(self, x, graph: CsrGraph, assign_x=None):
+    def forward(self, x, graph, assign_x=None):
         """x [n, F] and a CsrGraph -> ypred [1, label_dim]; x [n_total, F] and a CsrBatch -> ypred [B, label_dim]."""
-        if isinstance(graph, CsrBatch):
-            return self._forward_batch(x, graph, assign_x)
-        if not isinstance(graph, CsrGraph):
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
             raise TypeError("SparseSoftPoolingGcnEncoder.forward(x [n, F], graph: CsrGraph[, assign_x]): the dense "
                             "(x [B, N, F], adj, batch_num_nodes) form is SoftPoolingGcnEncoder's")
-        _lib.require_gpu_tensor(x, "x")
         x_a = x if assign_x is None else assign_x
-        _lib.require_gpu_tensor(x_a, "assign_x")
-        if x.dim() != 2 or x.shape[0] != graph.n or x_a.dim() != 2 or x_a.shape[0] != graph.n:
-            raise ValueError(f"expected x / assign_x [n, F] with n = {graph.n}, got {tuple(x.shape)} / "
-                             f"{tuple(x_a.shape)}")
+        for t, name in ((x, "x"), (x_a, "assign_x")):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
+                got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"expected {name} {graph.rows()}, got {got}")
         if x.shape[1] != self.input_dim or x_a.shape[1] != self.assign_input_dim:
             raise ValueError(f"feature widths {x.shape[1]}/{x_a.shape[1]} do not match the model "
                              f"({self.input_dim}/{self.assign_input_dim})")
+        _lib.require_gpu_tensor(x, "x")
+        _lib.require_gpu_tensor(x_a, "assign_x")
         x, x_a = x.contiguous().float(), x_a.contiguous().float()
-        saved = {"assign": [], "xpool": [], "adjpool": [], "embedding": []}
-        z = self._embed(self.conv_first, self.conv_block, self.conv_last, x, graph)                       # :1254
+
+        def embed(stack, first, block, last, h, adj):
+            """One GraphConv stack's embedding: the concatenation of all its layers' outputs (encoders.py:1078)."""
+            return torch.cat(list(stack(self._stack_modules(first, block, last), h, adj)), dim=-1)
+
+        saved = {"assign": [], "xpool": [], "adjpool": [], "embedding": [], "graph": graph}
+        z = embed(_gcn_stack, self.conv_first, self.conv_block, self.conv_last, x, graph)                 # :1254
         saved["embedding"].append(z)
-        out, arg = ops.row_max(z)                                                                         # :1257
+        out, arg = graph.readout(z)                                                                       # :1257
         outs, argmax = [out], [arg]
-        adj, s0 = graph, None            # the adjacency of the current level: the CSR graph, then dense K x K blocks
+        adj = graph                      # the adjacency of the current level: the container, then dense [B, K, K] blocks
         for i in range(self.num_pooling):                                                                 # :1263
             pred = self.assign_pred_modules[i]
-            za = self._embed(self.assign_conv_first_modules[i], self.assign_conv_block_modules[i],
-                             self.assign_conv_last_modules[i], x_a, adj)    # :1269-1271; D4: level >= 1 assigns from X'
-            s = ops.assign_softmax(za, pred.weight, pred.bias)                                            # :1273
-            if i == 0:
-                xp, adj = ops.csr_pool(s, z, graph)                                                       # :1278-1279
-                s0 = s
-            else:
-                xp, adj = ops.dense_pool(s, z, adj)
-            x_a = xp                                                                                      # :1280
-            z = self._embed(self.conv_first_after_pool[i], self.conv_block_after_pool[i],
-                            self.conv_last_after_pool[i], xp, adj)                                        # :1282-1284
+            za = embed(_gcn_stack if i == 0 else _gcn_stack_dense, self.assign_conv_first_modules[i],
+                       self.assign_conv_block_modules[i], self.assign_conv_last_modules[i], x_a, adj)
+            s = ops.assign_softmax(za, pred.weight, pred.bias)      # :1273; level 0: every row is a node, no mask
+            xp, adj = graph.pool(s, z) if i == 0 else ops.dense_pool(s, z, adj)                           # :1278-1279
+            x_a = xp                                                # :1280; D4: level >= 1 assigns from X'
+            z = embed(_gcn_stack_dense, self.conv_first_after_pool[i], self.conv_block_after_pool[i],
+                      self.conv_last_after_pool[i], xp, adj)                                              # :1282-1284
             out, arg = ops.row_max(z)                                                                     # :1287
             outs.append(out)
             argmax.append(arg)
@@ -453,7 +437,8 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         ypred = ops.mlp_head(torch.cat(outs, dim=1), self._pred_linears())                                # :1295-1299
         saved["readout_argmax"] = argmax
         self._saved = saved
-        self.assign_tensor = s0.unsqueeze(0)        # level-0 assignment [1, n, K_0], as the dense class keeps it
+        s0 = saved["assign"][0]          # [1, n, K_0] as the dense class keeps it; RAGGED [n_total, K_0] for a batch
+        self.assign_tensor = s0.unsqueeze(0) if isinstance(graph, CsrGraph) else s0
         return ypred
 
     @torch.no_grad()
@@ -463,56 +448,42 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
 
     def loss(self, pred, label, adj=None, batch_num_nodes=None, adj_hop=1):
         """Cross entropy of the prediction (encoders.py:1124-1127), plus — for a linkpred=True model — the
-        link-prediction term of the level-0 assignment (encoders.py:1309-1331) on dp_csr_linkpred_loss_*.  `adj` is
-        then the CsrGraph the forward ran on, in the position where train.py:207 passes the dense batch:
-        loss(pred, label, graph).  The link term is kept in `self.link_loss`, as the dense class does."""
-        if isinstance(adj, CsrBatch) or (self._saved is not None and isinstance(self._saved.get("graph"), CsrBatch)):
-            return self._loss_batch(pred, label, adj, adj_hop)
-        if self.linkpred:
-            call = "SparseSoftPoolingGcnEncoder.loss(pred, label, graph)"
-            if adj is None:
-                raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the CsrGraph the "
-                                          "forward ran on; it cannot be formed from the prediction alone")
-            if not isinstance(adj, CsrGraph):
-                raise TypeError(f"{call}: graph must be the CsrGraph of the last forward, got {type(adj).__name__} "
-                                "(the dense (pred, label, adj, batch_num_nodes) form is SoftPoolingGcnEncoder's)")
+        link-prediction term of the level-0 assignment (encoders.py:1309-1331) on dp_csr_linkpred_loss_* (for a batch
+        dp_csr_linkpred_batch_*: sum_b sum_{i,j<n_b} l_ij / sum_b n_b^2).  `adj` is then the CsrGraph or CsrBatch the
+        forward ran on, in the position where train.py:207 passes the dense batch: loss(pred, label, graph), with
+        label [B] for a batch.  The link term is kept in `self.link_loss`, as the dense class does."""
+        last = None if self._saved is None else self._saved.get("graph")
+        kind = CsrBatch if isinstance(adj, CsrBatch) or isinstance(last, CsrBatch) else CsrGraph
+        call = f"SparseSoftPoolingGcnEncoder.loss(pred, label, {kind.ARG})"
+        if kind is CsrBatch:
+            nb = (adj if isinstance(adj, CsrBatch) else last).num_graphs
+            if pred.dim() != 2 or pred.shape[0] != nb:
+                raise ValueError(f"{call}: pred {tuple(pred.shape)} does not hold one row per graph of the batch ({nb})")
+            if not isinstance(label, torch.Tensor) or label.numel() != nb:
+                got = label.numel() if isinstance(label, torch.Tensor) else type(label).__name__
+                raise ValueError(f"{call}: label must hold one class per graph of the batch ({nb}), got {got}")
+            label = label.reshape(-1)
         if adj_hop != 1:
             raise NotImplementedError("adj_hop > 1 is never used by the reference's callers (train.py:207)")
         if not self.linkpred:
             return ops.cross_entropy(pred, label)
+        if adj is None:
+            raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the {kind.__name__} the "
+                                      "forward ran on; it cannot be formed from the prediction alone")
+        if not isinstance(adj, kind):
+            raise TypeError(f"{call}: {kind.ARG} must be the {kind.__name__} of the last forward, got "
+                            f"{type(adj).__name__} (the dense (pred, label, adj, batch_num_nodes) form is "
+                            "SoftPoolingGcnEncoder's)")
         if self._saved is None:
             raise ValueError(f"{call}: no forward pass has run yet, so there is no assignment to score")
         s0 = self._saved["assign"][0]                # attached: dS of the link term and of the pooling add up
-        if adj.n != s0.shape[0]:
-            raise ValueError(f"{call}: graph has n = {adj.n} nodes but the last forward ran on n = {s0.shape[0]}; "
-                             "pass the graph of that forward")
-        self.link_loss = ops.csr_link_loss(s0, adj)
-        return ops.cross_entropy(pred, label) + self.link_loss
-
-    def _loss_batch(self, pred, label, batch, adj_hop):
-        """`loss` for a CsrBatch forward: label [B]; the link term is sum_b sum_{i,j<n_b} l_ij / sum_b n_b^2."""
-        call = "SparseSoftPoolingGcnEncoder.loss(pred, label, batch)"
-        if batch is not None and not isinstance(batch, CsrBatch):
-            raise TypeError(f"{call}: the last forward ran on a CsrBatch, got {type(batch).__name__}")
-        nb = batch.num_graphs if batch is not None else self._saved["graph"].num_graphs
-        if pred.dim() != 2 or pred.shape[0] != nb:
-            raise ValueError(f"{call}: pred {tuple(pred.shape)} does not hold one row per graph of the batch ({nb})")
-        if not isinstance(label, torch.Tensor) or label.numel() != nb:
-            got = label.numel() if isinstance(label, torch.Tensor) else type(label).__name__
-            raise ValueError(f"{call}: label must hold one class per graph of the batch ({nb}), got {got}")
-        if adj_hop != 1:
-            raise NotImplementedError("adj_hop > 1 is never used by the reference's callers (train.py:207)")
-        if not self.linkpred:
-            return ops.cross_entropy(pred, label.reshape(-1))
-        if batch is None:
-            raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the CsrBatch the "
-                                      "forward ran on; it cannot be formed from the prediction alone")
-        if self._saved is None:
-            raise ValueError(f"{call}: no forward pass has run yet, so there is no assignment to score")
-        if self._saved.get("graph") is not batch:
+        if kind is CsrBatch and last is not adj:
             raise ValueError(f"{call}: this is not the batch the last forward ran on; pass the batch of that forward")
-        self.link_loss = ops.csr_link_loss_batch(self._saved["assign"][0], batch)
-        return ops.cross_entropy(pred, label.reshape(-1)) + self.link_loss
+        if adj.n != s0.shape[0]:
+            raise ValueError(f"{call}: {kind.ARG} has n = {adj.n} nodes but the last forward ran on n = {s0.shape[0]}; "
+                             f"pass the {kind.ARG} of that forward")
+        self.link_loss = adj.link_loss(s0)
+        return ops.cross_entropy(pred, label) + self.link_loss
 
     def saved_activation(self, level, what):
         """One activation of the LAST forward call, shaped as the dense class returns it with B = 1: 'assign' [1, n_j,
@@ -530,6 +501,7 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         seq = self._saved[what]
         if not 0 <= level < len(seq):
             raise IndexError(f"saved_activation(): level {level} out of range for {what!r} ({len(seq)} levels)")
-        if what == "readout_argmax" or isinstance(self._saved.get("graph"), CsrBatch):
-            return seq[level].detach()
-        return seq[level].detach().unsqueeze(0)
+        t = seq[level].detach()
+        if not isinstance(self._saved.get("graph"), CsrBatch) and what != "readout_argmax" and t.dim() == 2:
+            return t.unsqueeze(0)                    # a single graph's level-0 'assign' / 'embedding' [n, .]
+        return t

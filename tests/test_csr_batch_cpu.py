@@ -207,12 +207,11 @@ def test_forward_and_loss_check_their_arguments_before_the_device():
 
 def test_add_self_layers_are_refused_on_a_batch():
     """With add_self (concat=False) a padded row of the dense batch is not a constant of the layer.  The DiffPool
-    constructor refuses concat=False on either path already; the ragged GraphConv stack says so itself as well."""
+    constructor refuses concat=False on either path already; the batch's BatchNorm step says so itself as well."""
     from graph_pooling_amd.encoders import GraphConv
-    from graph_pooling_amd.sparse import _gcn_stack_ragged
-    mods = [GraphConv(7, 12, add_self=True, normalize_embedding=True), GraphConv(12, 12, add_self=True)]
+    layer = GraphConv(7, 12, add_self=True, normalize_embedding=True)
     with pytest.raises(NotImplementedError, match="add_self GraphConv layers"):
-        list(_gcn_stack_ragged(mods, torch.zeros(9, 7), _three()))
+        _three().bn_relu(torch.zeros(9, 12), layer)
     with pytest.raises(ValueError, match="concat=False"):
         SparseSoftPoolingGcnEncoder(**ARGS, concat=False)
 

@@ -416,6 +416,40 @@ def test_one_graph_batch_equals_the_single_graph_call():
     grads_close(model, g1, rtol=2e-3, atol_rel=1e-4)
 
 
+def test_single_graph_run_keeps_nothing_of_a_batch_run_between():
+    """One forward body serves both containers: a single-graph run after a batch run on the same model is bit for bit
+    the single-graph run before it — ypred, loss, link loss, every parameter gradient, every saved activation."""
+    sizes, num_pooling = [300, 41, 1], 2
+    srcs, dsts = _edge_lists(sizes, 12)
+    g = CsrGraph.from_edges(sizes[0], srcs[0], dsts[0], "cuda", symmetric=True)
+    model, params, batch, _, x, label = _model_case(sizes, num_pooling, True, seed=12)
+    x1, l1 = x[:sizes[0]].cuda(), label[:1].cuda()
+
+    def single():
+        model.zero_grad(set_to_none=True)
+        ypred = model(x1, g)
+        loss = model.loss(ypred, l1, g)
+        loss.backward()
+        out = {"ypred": ypred, "loss": loss, "link_loss": model.link_loss, "assign_tensor": model.assign_tensor}
+        out.update({"grad " + k: p.grad for k, p in model.named_parameters()})
+        for what in ("assign", "xpool", "adjpool", "embedding", "readout_argmax"):
+            for j in range(num_pooling + (what in ("embedding", "readout_argmax"))):
+                out[f"{what} {j}"] = model.saved_activation(j, what)
+        return {k: v.detach().clone() for k, v in out.items()}
+
+    first = single()
+    _run(model, x, batch, label)
+    assert model.assign_tensor.shape == (sum(sizes), model.assign_dims[0])
+    third = single()
+    assert first["assign_tensor"].shape == (1, sizes[0], model.assign_dims[0])
+    assert first["embedding 0"].shape == (1, sizes[0], model.pred_input_dim)
+    assert first["xpool 1"].shape == (1, model.assign_dims[1], model.pred_input_dim)
+    assert first["readout_argmax 2"].shape == (1, model.pred_input_dim)
+    assert list(third) == list(first)
+    for k, v in first.items():
+        assert third[k].shape == v.shape and torch.equal(third[k], v), k
+
+
 def test_batch_is_bit_reproducible():
     model, params, batch, adj, x, label = _model_case([300, 41, 1, 700, 300], 2, True, seed=2)
     runs = []
