@@ -67,6 +67,24 @@ class GemmProblem(C.Structure):
                 ("sK", C.c_int64)]
 
 
+class RowGroups(C.Structure):
+    """dp_row_groups (include/diffpool_hip.h): one or two column groups of a joint buffer."""
+    _fields_ = [("G", C.c_int), ("c0", C.c_int * 2), ("w", C.c_int * 2)]
+
+
+class GroupPtrs(C.Structure):
+    """dp_group_ptrs: per group a pointer at the group's first column and its leading dimension."""
+    _fields_ = [("p", C.c_void_p * 2), ("ld", C.c_int * 2)]
+
+
+# dp_rowop_plan: DP_ROWOP_*, DP_ROWK_*, DP_ROWF_*, DP_ROWZ_*
+ROWOP_ROWNORM_FWD, ROWOP_ROWNORM_BWD, ROWOP_BN_APPLY_FWD, ROWOP_SOFTMAX_FWD, ROWOP_SOFTMAX_BWD, ROWOP_MASKED_MAX_FWD = range(6)
+(ROWK_ROWNORM_FWD, ROWK_ROWNORM_BWD, ROWK_BN_APPLY_FWD, ROWK_SOFTMAX_FWD_PLAN, ROWK_SOFTMAX_FWD, ROWK_SOFTMAX_BWD_PLAN,
+ ROWK_SOFTMAX_BWD, ROWK_MASKED_MAX_FWD) = range(8)
+ROWF_STATS, ROWF_VS, ROWF_ZERO, ROWF_ZERO_UNALIGNED, ROWF_DBIAS = 1, 2, 4, 8, 16
+ROWZ_NONE, ROWZ_FOLDED, ROWZ_APART = 0, 1, 2
+ROWOP_PLAN_INTS = 6
+
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
 GEMM_PLAN_NONE, GEMM_PLAN_SPLIT_BF16 = 0, 1                           # DP_GEMM_PLAN_*
@@ -122,6 +140,18 @@ _PROTOS = {
     "dp_pool_bwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "dp_masked_max_fwd": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _P]),
     "dp_masked_max_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "dp_sizeof_row_groups": (_Z, []),
+    "dp_sizeof_group_ptrs": (_Z, []),
+    "dp_rowop_plan": (_I, [_I, C.POINTER(RowGroups), _I, _I, _I, _I, C.POINTER(_I)]),
+    "dp_rownorm_fwd": (_I, [_P, _I, _P, C.POINTER(RowGroups), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), _P, _P, _L, _I,
+                            _I, _P]),
+    "dp_bn_apply_fwd": (_I, [_P, _I, _P, _P, C.POINTER(RowGroups), C.POINTER(GroupPtrs), _I, _I, _I, _I, _P]),
+    "dp_bn_bwd_partials": (_I, [C.POINTER(RowGroups), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), _P, _L, _P]),
+    "dp_rownorm_bwd": (_I, [C.POINTER(RowGroups), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), _P, _P,
+                            _P, _P, _I, C.POINTER(GroupPtrs), _I, _I, _I, _I, _I, _P, _I, _P]),
+    "dp_softmax_mask_fwd": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "dp_softmax_mask_bwd": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "dp_colsum_batched": (_I, [_P, _I, _L, _I, _I, _P, _L, _I, _I, _P]),
     "dp_linkpred_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_linkpred_loss_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_linkpred_loss_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
@@ -221,6 +251,8 @@ def load():
         if lib.dp_sizeof_gemm_problem() != C.sizeof(GemmProblem):
             raise RuntimeError("dp_gemm_problem layout mismatch between diffpool_hip.h and _lib.py: "
                                f"{lib.dp_sizeof_gemm_problem()} vs {C.sizeof(GemmProblem)}")
+        if lib.dp_sizeof_row_groups() != C.sizeof(RowGroups) or lib.dp_sizeof_group_ptrs() != C.sizeof(GroupPtrs):
+            raise RuntimeError("dp_row_groups / dp_group_ptrs layout mismatch between diffpool_hip.h and _lib.py")
         _lib = lib
     return _lib
 

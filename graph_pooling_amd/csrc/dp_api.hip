@@ -603,6 +603,214 @@ int dp_masked_max_bwd(const float* dout, int ldo, const int* argmax, float* dZ, 
     return q.err;
 }
 
+// ---- the row launchers as the encoder plans call them (dp_rowop_plan and the pass-through entries of diffpool_hip.h)
+size_t dp_sizeof_row_groups(void) { return sizeof(dp_row_groups); }
+size_t dp_sizeof_group_ptrs(void) { return sizeof(dp_group_ptrs); }
+namespace {
+int row_groups_check(const dp_row_groups* g) {
+    NOTNULL(g);
+    DP_CHECK_ARG(g->G >= 1 && g->G <= 2, "G=%d out of range [1,2]", g->G);
+    for (int i = 0; i < g->G; ++i) {
+        DP_CHECK_ARG(g->w[i] >= 1, "group %d: width w=%d must be >= 1", i, g->w[i]);
+        DP_CHECK_ARG(g->c0[i] >= 0, "group %d: c0=%d must not be negative", i, g->c0[i]);
+    }
+    if (g->G == 2)
+        DP_CHECK_ARG(g->c0[1] >= g->c0[0] + g->w[0], "groups overlap: group 1 starts at column %d, group 0 ends at %d",
+                     g->c0[1], g->c0[0] + g->w[0]);
+    return DP_OK;
+}
+RowGroups row_groups_of(const dp_row_groups& g) {
+    RowGroups r{};
+    r.G = g.G;
+    for (int i = 0; i < g.G; ++i) {
+        r.c0[i] = g.c0[i];
+        r.w[i] = g.w[i];
+    }
+    return r;
+}
+// need: every group's pointer must be there; otherwise a group may go without (bias, dbias)
+int group_ptrs_check(const dp_row_groups& g, const dp_group_ptrs* p, const char* name, bool need) {
+    DP_CHECK_ARG(p != nullptr, "%s is NULL", name);
+    for (int i = 0; i < g.G; ++i) {
+        DP_CHECK_ARG(!need || p->p[i], "%s: the pointer of group %d is NULL", name, i);
+        DP_CHECK_ARG(!need || p->ld[i] >= g.w[i], "%s: ld=%d of group %d smaller than its width %d", name, p->ld[i], i,
+                     g.w[i]);
+    }
+    return DP_OK;
+}
+GroupPtrs gptrs(const dp_row_groups& g, const dp_group_ptrs* p) {
+    GroupPtrs r{};
+    for (int i = 0; p && i < g.G; ++i) {
+        r.p[i] = (float*)p->p[i];
+        r.ld[i] = p->ld[i];
+    }
+    return r;
+}
+GroupCPtrs gcptrs(const dp_row_groups& g, const dp_group_ptrs* p) {
+    GroupCPtrs r{};
+    for (int i = 0; p && i < g.G; ++i) {
+        r.p[i] = (const float*)p->p[i];
+        r.ld[i] = p->ld[i];
+    }
+    return r;
+}
+int joint_width(const dp_row_groups& g) { return g.c0[g.G - 1] + g.w[g.G - 1]; }
+}  // namespace
+#define ROWS_OK(g)                                  \
+    do {                                            \
+        const int rg_rc_ = row_groups_check(g);     \
+        if (rg_rc_ != DP_OK) return rg_rc_;         \
+    } while (0)
+#define GROUP_PTRS(g, p, need)                                    \
+    do {                                                          \
+        const int gp_rc_ = group_ptrs_check(*(g), p, #p, need);   \
+        if (gp_rc_ != DP_OK) return gp_rc_;                       \
+    } while (0)
+
+int dp_rowop_plan(int op, const dp_row_groups* g, int n, int B, int Bs, int flags, int* plan_out) {
+    NOTNULL(plan_out);
+    DP_CHECK_ARG(op >= DP_ROWOP_ROWNORM_FWD && op <= DP_ROWOP_MASKED_MAX_FWD, "op=%d is no row operation", op);
+    RowPick p{};
+    if (op == DP_ROWOP_MASKED_MAX_FWD) {
+        NONNEG(n);
+        p = masked_max_fwd_pick(n);
+    } else {
+        ROWS_OK(g);
+        if (Bs <= 0) Bs = B;
+        const RowGroups r = row_groups_of(*g);
+        const bool zero = (flags & DP_ROWF_ZERO) != 0;
+        switch (op) {
+            case DP_ROWOP_ROWNORM_FWD: p = rownorm_fwd_pick(r); break;
+            case DP_ROWOP_ROWNORM_BWD: p = rownorm_bwd_pick(r, (flags & DP_ROWF_STATS) != 0, Bs); break;
+            case DP_ROWOP_BN_APPLY_FWD: p = bn_apply_fwd_pick(r, (flags & DP_ROWF_STATS) != 0, Bs); break;
+            case DP_ROWOP_SOFTMAX_FWD:
+                p = softmax_mask_fwd_pick(r.w[0], (flags & DP_ROWF_VS) != 0, zero, !(flags & DP_ROWF_ZERO_UNALIGNED));
+                break;
+            default: p = softmax_mask_bwd_pick(r.w[0], (flags & DP_ROWF_DBIAS) != 0); break;
+        }
+    }
+    const int out[DP_ROWOP_PLAN_INTS] = {p.kernel, p.nk, p.quad, p.finalize, p.generic() ? 1 : 0, p.zero};
+    for (int i = 0; i < DP_ROWOP_PLAN_INTS; ++i) plan_out[i] = out[i];
+    return DP_OK;
+}
+
+int dp_rownorm_fwd(const float* U, int ldu, const float* P, const dp_row_groups* g, const dp_group_ptrs* bias,
+                   const dp_group_ptrs* yout, float* invn, float* part, long rows, int normalize, int stats_mode,
+                   void* stream) {
+    ROWS_OK(g);
+    NOTNULL(U);
+    GROUP_PTRS(g, yout, true);
+    if (bias) GROUP_PTRS(g, bias, false);
+    NONNEG(rows);
+    DP_CHECK_ARG(ldu >= joint_width(*g), "ldu=%d smaller than the joint width %d", ldu, joint_width(*g));
+    DP_CHECK_ARG(stats_mode >= 0 && stats_mode <= 2, "stats_mode=%d (0 none, 1 of relu(y), 2 of y)", stats_mode);
+    DP_CHECK_ARG(!stats_mode || part, "part is NULL but stats_mode=%d", stats_mode);
+    Seq q(STREAM(stream), nullptr, 0);
+    rownorm_fwd(q, U, ldu, P, gcptrs(*g, bias), row_groups_of(*g), gptrs(*g, yout), invn, part, rows, normalize != 0,
+                stats_mode);
+    return q.err;
+}
+
+int dp_bn_apply_fwd(const float* Y, int ldy, const float* part, float* stats, const dp_row_groups* g,
+                    const dp_group_ptrs* xout, int B, int n, int relu, int Bs, void* stream) {
+    ROWS_OK(g);
+    NOTNULL(Y);
+    GROUP_PTRS(g, xout, true);
+    NONNEG(B); NONNEG(n);
+    DP_CHECK_ARG(Bs >= 0, "Bs=%d must not be negative (0: B)", Bs);
+    DP_CHECK_ARG(ldy >= joint_width(*g), "ldy=%d smaller than the joint width %d", ldy, joint_width(*g));
+    DP_CHECK_ARG(!part || stats, "stats is NULL but part is given");
+    Seq q(STREAM(stream), nullptr, 0);
+    bn_apply_fwd(q, Y, ldy, part, stats, row_groups_of(*g), gptrs(*g, xout), B, n, relu != 0, Bs);
+    return q.err;
+}
+
+int dp_bn_bwd_partials(const dp_row_groups* g, const dp_group_ptrs* dx, const dp_group_ptrs* xhat, float* part,
+                       long rows, void* stream) {
+    ROWS_OK(g);
+    GROUP_PTRS(g, dx, true);
+    GROUP_PTRS(g, xhat, true);
+    NOTNULL(part);
+    NONNEG(rows);
+    Seq q(STREAM(stream), nullptr, 0);
+    bn_bwd_partials(q, gcptrs(*g, dx), gcptrs(*g, xhat), row_groups_of(*g), part, rows);
+    return q.err;
+}
+
+int dp_rownorm_bwd(const dp_row_groups* g, const dp_group_ptrs* dx, const dp_group_ptrs* xhat, const dp_group_ptrs* y,
+                   const float* invn, const float* stats, float* part2, float* dU, int ldu, const dp_group_ptrs* dbias,
+                   int B, int n, int has_relu, int has_bn, int normalize, void* vs, int Bs, void* stream) {
+    ROWS_OK(g);
+    GROUP_PTRS(g, dx, true);
+    GROUP_PTRS(g, y, true);
+    if (has_bn) GROUP_PTRS(g, xhat, true);
+    if (dbias) GROUP_PTRS(g, dbias, false);
+    NOTNULL(dU);
+    NONNEG(B); NONNEG(n);
+    DP_CHECK_ARG(Bs >= 0, "Bs=%d must not be negative (0: B)", Bs);
+    DP_CHECK_ARG(B <= 65535, "B=%d exceeds the grid's second dimension (65535)", B);
+    DP_CHECK_ARG(ldu >= joint_width(*g), "ldu=%d smaller than the joint width %d", ldu, joint_width(*g));
+    DP_CHECK_ARG(!has_bn || (stats && part2), "has_bn is set but stats or part2 is NULL");
+    DP_CHECK_ARG(!normalize || invn, "normalize is set but invn is NULL");
+    const bool want = dbias && (dbias->p[0] || (g->G == 2 && dbias->p[1]));
+    const size_t lds = ((want ? 16 : 0) + (vs ? 8 : 0)) * (size_t)joint_width(*g) * sizeof(float);
+    DP_CHECK_ARG(lds <= 64 * 1024, "dbias / vs: the slabs and the split need %zu bytes of LDS at joint width %d, no form has "
+                 "more than 64 KiB", lds, joint_width(*g));
+    // (a slab's ld is the distance between the graphs' rows)
+    for (int i = 0; dbias && i < g->G; ++i)
+        DP_CHECK_ARG(!dbias->p[i] || B <= 1 || dbias->ld[i] >= g->w[i],
+                     "dbias: ld=%d of group %d, the stride between graphs, smaller than its width %d", dbias->ld[i], i,
+                     g->w[i]);
+    if (vs) ALIGNED16(vs);
+    GroupPtrs db = gptrs(*g, dbias);
+    Seq q(STREAM(stream), nullptr, 0);
+    rownorm_bwd(q, gcptrs(*g, dx), gcptrs(*g, has_bn ? xhat : nullptr), gcptrs(*g, y), invn, stats, part2,
+                row_groups_of(*g), dU, ldu, dbias ? &db : nullptr, B, n, has_relu != 0, has_bn != 0, normalize != 0,
+                (unsigned short*)vs, Bs);
+    return q.err;
+}
+
+int dp_softmax_mask_fwd(const float* logits, int ldl, float* S, int lds, const int* num_nodes, int B, int n, int K,
+                        float* S2, void* vs, void* zero_p, size_t zero_bytes, void* stream) {
+    NOTNULL(logits); NOTNULL(S);
+    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_CHECK_ARG(B <= 65535, "B=%d exceeds the grid's second dimension (65535)", B);
+    DP_CHECK_ARG(ldl >= K && lds >= K, "ldl=%d/lds=%d smaller than K=%d", ldl, lds, K);
+    DP_CHECK_ARG(!vs || !softmax_mask_fwd_pick(K, true, false, true).generic(),
+                 "vs: K=%d is past the plan forms (16 rows of K floats must fit 48 KiB), the generic kernel writes no split",
+                 K);
+    DP_CHECK_ARG(!zero_bytes || zero_p, "zero_p is NULL but zero_bytes=%zu", zero_bytes);
+    if (vs) ALIGNED16(vs);
+    Seq q(STREAM(stream), nullptr, 0);
+    softmax_mask_fwd(q, logits, ldl, S, lds, num_nodes, B, n, K, S2, (unsigned short*)vs, zero_bytes ? zero_p : nullptr,
+                     zero_bytes);
+    return q.err;
+}
+
+int dp_softmax_mask_bwd(const float* S, int lds, float* dS, int ldds, const int* num_nodes, float* dlogits, int ldl,
+                        int B, int n, int K, float* dbias, long dbias_stride, const float* dS2, void* stream) {
+    NOTNULL(S); NOTNULL(dS); NOTNULL(dlogits);
+    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_CHECK_ARG(B <= 65535, "B=%d exceeds the grid's second dimension (65535)", B);
+    DP_CHECK_ARG(lds >= K && ldds >= K && ldl >= K, "lds=%d/ldds=%d/ldl=%d smaller than K=%d", lds, ldds, ldl, K);
+    DP_CHECK_ARG(!dbias || B == 1 || dbias_stride >= K, "dbias_stride=%ld smaller than K=%d", dbias_stride, K);
+    Seq q(STREAM(stream), nullptr, 0);
+    softmax_mask_bwd(q, S, lds, dS, ldds, num_nodes, dlogits, ldl, B, n, K, dbias, dbias_stride, dS2);
+    return q.err;
+}
+
+int dp_colsum_batched(const float* X, int ldx, long strideX, int rows, int cols, float* out, long strideOut, int batch,
+                      int rowsplit, void* stream) {
+    NOTNULL(X); NOTNULL(out);
+    NONNEG(rows); NONNEG(cols); NONNEG(batch);
+    DP_CHECK_ARG(ldx >= cols, "ldx=%d smaller than cols=%d", ldx, cols);
+    DP_CHECK_ARG(rowsplit >= 1 && rowsplit <= 65535, "rowsplit=%d out of range [1,65535]", rowsplit);
+    DP_CHECK_ARG(batch <= 65535, "batch=%d exceeds the grid's second dimension (65535)", batch);
+    Seq q(STREAM(stream), nullptr, 0);
+    colsum_batched(q, X, ldx, strideX, rows, cols, out, strideOut, batch, rowsplit);
+    return q.err;
+}
+
 size_t dp_linkpred_workspace_bytes(int B, int n, int K) {
     size_t f = sized([&](Seq& q) { linkpred_fwd(q, 0, K, 0, 0, 0, B, n, K); });
     size_t b = sized([&](Seq& q) { linkpred_bwd(q, 0, K, 0, 0, 0, 0, K, B, n, K, 0); });

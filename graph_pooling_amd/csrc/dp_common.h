@@ -266,7 +266,8 @@ inline size_t gemm_fix_counters(int batch, int M, int N) {
     return (size_t)batch * ((M + 15) / 16) * ((N + 15) / 16);
 }
 
-// hi/mid/lo bf16 planes with hi + mid + lo == v exactly (round-to-nearest-even at each step)
+// hi/mid/lo bf16 planes with hi + mid + lo == v exactly (round-to-nearest-even at each step) for |v| >= 2^-110; below,
+// the low plane rounds on the bf16 denormal grid and the sum is within 2^-134 of v
 __device__ inline void bf16_split3(float v, unsigned short& h, unsigned short& m, unsigned short& l) {
     auto rn = [](float x) -> unsigned {
         unsigned u = __float_as_uint(x);
@@ -321,6 +322,22 @@ struct GroupCPtrs {
 };
 
 // (dp_rowops.hip)
+// The form a row launcher takes (which instantiation, what runs in front), decided in ONE host function per launcher:
+// the launcher launches what it answers and dp_rowop_plan (diffpool_hip.h) reports it.  Host only.
+struct RowPick {
+    int kernel;      // DP_ROWK_*
+    int nk;          // the kernel's NK template argument; 0: the any-width form
+    int quad;        // 1: 16-byte quads per lane
+    int finalize;    // 1: k_bn_finalize / k_bn_bwd_finalize runs in front (statistics over more than 32 graphs)
+    int zero;        // softmax forward: DP_ROWZ_*
+    bool generic() const { return kernel == DP_ROWK_SOFTMAX_FWD || kernel == DP_ROWK_SOFTMAX_BWD; }   // no _plan form
+};
+RowPick rownorm_fwd_pick(const RowGroups& g);
+RowPick rownorm_bwd_pick(const RowGroups& g, bool has_bn, int Bs);
+RowPick bn_apply_fwd_pick(const RowGroups& g, bool has_part, int Bs);
+RowPick softmax_mask_fwd_pick(int K, bool vs, bool zero, bool zero_aligned);
+RowPick softmax_mask_bwd_pick(int K, bool dbias);
+RowPick masked_max_fwd_pick(int n);
 void rownorm_fwd(Seq& q, const float* U, int ldu, const float* P /*add_self or null*/, GroupCPtrs bias,
                  RowGroups g, GroupPtrs yout, float* invn, float* part /*[rows,G,2] or null*/, long rows,
                  int normalize, int relu_stats);
@@ -343,12 +360,12 @@ void rownorm_bwd(Seq& q, GroupCPtrs dx, GroupCPtrs xhat /*BN output, null when n
                  int Bs = 0 /*graphs in part2 (sync-BN: B x ranks); 0 = B*/);
 int rownorm_bwd_chunks(int n);
 void colsum_batched(Seq& q, const float* X, int ldx, long strideX, int rows, int cols, float* out,
-                    long strideOut, int batch, int rowsplit = 1);
+                    long strideOut, int batch, int rowsplit = 1, bool add = false /*one row range adds, too*/);
 // vs: also emit the 3-plane bf16 split of S (dp_agg.hip layout); zero_p/zero_bytes: also zero-fill that region
 void softmax_mask_fwd(Seq& q, const float* logits, int ldl, float* S, int lds, const int* num_nodes, int B,
                       int n, int K, float* S2 = nullptr, unsigned short* vs = nullptr, void* zero_p = nullptr,
                       size_t zero_bytes = 0);
-// dbias: slab row of graph 0 for the column sums of dlogits (graphs dbias_stride floats apart, atomically added)
+// dbias: slab row of graph 0 for the column sums of dlogits (graphs dbias_stride floats apart, added on every path)
 void softmax_mask_bwd(Seq& q, const float* S, int lds, const float* dS, int ldds, const int* num_nodes,
                       float* dlogits, int ldl, int B, int n, int K, float* dbias = nullptr, long dbias_stride = 0,
                       const float* dS2 = nullptr /*second addend of dS, same leading dimension*/);

@@ -34,6 +34,70 @@ static inline int team_grid(long items) {
     return (int)blocks;
 }
 
+// ---- the form each launcher takes: ONE host function per launcher decides, the launcher launches what it answers and
+// dp_rowop_plan (diffpool_hip.h) reports it.  nk is the kernel's NK template argument (0: the any-width form).
+static inline int groups_maxw(const RowGroups& g) { return g.G == 2 && g.w[1] > g.w[0] ? g.w[1] : g.w[0]; }
+static inline int quad_nk(int maxw) { return maxw <= 256 ? 4 : maxw <= 320 ? 5 : 8; }
+// the switch key of a form: form_key(quad, NK) in the case labels, pick_key(answer) in the switch
+static constexpr int form_key(bool quad, int nk) { return (quad ? 1000 : 0) + nk; }
+static inline int pick_key(const RowPick& p) { return form_key(p.quad != 0, p.nk); }
+RowPick rownorm_fwd_pick(const RowGroups& g) {
+    const int maxw = groups_maxw(g);
+    RowPick p{DP_ROWK_ROWNORM_FWD, 0, 0, 0, DP_ROWZ_NONE};
+    if (maxw > 128 && maxw <= 512 && row_quads_ok(g)) {
+        p.quad = 1;
+        p.nk = quad_nk(maxw);
+    } else
+        p.nk = maxw <= 32 ? 2 : maxw <= 64 ? 4 : maxw <= 128 ? 8 : maxw <= 320 ? 20 : 0;
+    return p;
+}
+RowPick rownorm_bwd_pick(const RowGroups& g, bool has_bn, int Bs) {
+    const int maxw = groups_maxw(g);
+    RowPick p{DP_ROWK_ROWNORM_BWD, 0, 0, has_bn && Bs > 32 ? 1 : 0, DP_ROWZ_NONE};
+    if (maxw > 128 && maxw <= 512 && row_quads_ok(g)) {
+        p.quad = 1;
+        p.nk = quad_nk(maxw);
+    } else
+        p.nk = maxw <= 32 ? 2 : maxw <= 64 ? 4 : maxw <= 128 ? 8 : maxw <= 256 ? 16 : 0;
+    return p;
+}
+RowPick bn_apply_fwd_pick(const RowGroups& g, bool has_part, int Bs) {
+    const int maxw = groups_maxw(g);
+    RowPick p{DP_ROWK_BN_APPLY_FWD, 0, 0, has_part && Bs > 32 ? 1 : 0, DP_ROWZ_NONE};
+    p.nk = maxw <= 32 ? 2 : maxw <= 64 ? 4 : maxw <= 128 ? 8 : 0;
+    return p;
+}
+static inline void softmax_plan_form(RowPick& p, int K) {
+    if (K > 128 && K <= 512 && (K & 3) == 0 && !knobs().no_row_quads) {
+        p.quad = 1;
+        p.nk = quad_nk(K);
+    } else
+        p.nk = K <= 64 ? 4 : K <= 128 ? 8 : K <= 256 ? 16 : 0;
+}
+RowPick softmax_mask_fwd_pick(int K, bool vs, bool zero, bool zero_aligned) {
+    RowPick p{DP_ROWK_SOFTMAX_FWD, 0, 0, 0, DP_ROWZ_NONE};
+    const bool fits = (size_t)16 * K * sizeof(float) <= 48 * 1024;   // (a split is only ever asked for K <= 320)
+    if (zero) p.zero = fits && zero_aligned ? DP_ROWZ_FOLDED : DP_ROWZ_APART;
+    if (!fits || !(vs || zero)) return p;
+    p.kernel = DP_ROWK_SOFTMAX_FWD_PLAN;
+    softmax_plan_form(p, K);
+    return p;
+}
+RowPick softmax_mask_bwd_pick(int K, bool dbias) {
+    RowPick p{DP_ROWK_SOFTMAX_BWD, 0, 0, 0, DP_ROWZ_NONE};
+    if (!dbias || (size_t)16 * K * sizeof(float) > 64 * 1024) return p;
+    p.kernel = DP_ROWK_SOFTMAX_BWD_PLAN;
+    softmax_plan_form(p, K);
+    return p;
+}
+// k_masked_max_fwd chooses between its two loops itself: nk = 32, the rows of a thread in one batch of loads, up to
+// n = 512; nk = 0, the loop, above
+RowPick masked_max_fwd_pick(int n) { return RowPick{DP_ROWK_MASKED_MAX_FWD, n <= 16 * 32 ? 32 : 0, 0, 0, DP_ROWZ_NONE}; }
+static inline void pick_missing(Seq& q, const char* what, const RowPick& p) {
+    set_error("%s: no kernel form for quad=%d NK=%d", what, p.quad, p.nk);
+    q.err = DP_ERR_UNSUPPORTED;
+}
+
 // ------------------------------------------------------------------ rownorm fwd
 // u = U[row, c0+c] (+ P[row, c0+c]) (+ bias[c]);  y = u / max(||u||, 1e-12)   (encoders.py:966-972)
 // optional BN partials of relu(y): (row mean, row M2) for a Chan-combine over the batch.
@@ -206,20 +270,19 @@ void rownorm_fwd(Seq& q, const float* U, int ldu, const float* P, GroupCPtrs bia
                  float* invn, float* part, long rows, int normalize, int stats_mode) {
     if (!q.ok() || rows <= 0) return;
     RownormFwdArgs a{U, ldu, P, bias, g, yout, invn, part, rows, normalize, stats_mode};
-    const int maxw = g.G == 2 && g.w[1] > g.w[0] ? g.w[1] : g.w[0];
+    const RowPick pk = rownorm_fwd_pick(g);
     const dim3 grid(team_grid(rows * g.G));
-    if (maxw > 128 && maxw <= 512 && row_quads_ok(g)) {
-        if (maxw <= 256) hipLaunchKernelGGL((k_rownorm_fwd<4, true>), grid, dim3(256), 0, q.stream, a);
-        else if (maxw <= 320) hipLaunchKernelGGL((k_rownorm_fwd<5, true>), grid, dim3(256), 0, q.stream, a);
-        else hipLaunchKernelGGL((k_rownorm_fwd<8, true>), grid, dim3(256), 0, q.stream, a);
-        q.check_launch("rownorm_fwd");
-        return;
+    switch (pick_key(pk)) {
+        case form_key(true, 4): hipLaunchKernelGGL((k_rownorm_fwd<4, true>), grid, dim3(256), 0, q.stream, a); break;
+        case form_key(true, 5): hipLaunchKernelGGL((k_rownorm_fwd<5, true>), grid, dim3(256), 0, q.stream, a); break;
+        case form_key(true, 8): hipLaunchKernelGGL((k_rownorm_fwd<8, true>), grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 2): hipLaunchKernelGGL(k_rownorm_fwd<2>, grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 4): hipLaunchKernelGGL(k_rownorm_fwd<4>, grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 8): hipLaunchKernelGGL(k_rownorm_fwd<8>, grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 20): hipLaunchKernelGGL(k_rownorm_fwd<20>, grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 0): hipLaunchKernelGGL(k_rownorm_fwd<0>, grid, dim3(256), 0, q.stream, a); break;
+        default: pick_missing(q, "rownorm_fwd", pk); return;
     }
-    if (maxw <= 32) hipLaunchKernelGGL(k_rownorm_fwd<2>, grid, dim3(256), 0, q.stream, a);
-    else if (maxw <= 64) hipLaunchKernelGGL(k_rownorm_fwd<4>, grid, dim3(256), 0, q.stream, a);
-    else if (maxw <= 128) hipLaunchKernelGGL(k_rownorm_fwd<8>, grid, dim3(256), 0, q.stream, a);
-    else if (maxw <= 320) hipLaunchKernelGGL(k_rownorm_fwd<20>, grid, dim3(256), 0, q.stream, a);
-    else hipLaunchKernelGGL(k_rownorm_fwd<0>, grid, dim3(256), 0, q.stream, a);
     q.check_launch("rownorm_fwd");
 }
 
@@ -472,17 +535,20 @@ void bn_apply_fwd(Seq& q, const float* Y, int ldy, const float* part, float* sta
     if (!q.ok()) return;
     if (Bs <= 0) Bs = B;
     BnApplyArgs a{Y, ldy, part, stats, g, xout, B, n, relu, 0, Bs};
-    if (part && Bs > 32) {
+    const RowPick pk = bn_apply_fwd_pick(g, part != nullptr, Bs);
+    if (pk.finalize) {
         hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)(((long)n * g.G + 15) / 16)), dim3(256), 0, q.stream, a);
         q.check_launch("bn_finalize");
         a.stats_ready = 1;
     }
-    const int maxw = g.G == 2 && g.w[1] > g.w[0] ? g.w[1] : g.w[0];
     const dim3 grid(team_grid((long)B * n * g.G));
-    if (maxw <= 32) hipLaunchKernelGGL(k_bn_apply_fwd<2>, grid, dim3(256), 0, q.stream, a);
-    else if (maxw <= 64) hipLaunchKernelGGL(k_bn_apply_fwd<4>, grid, dim3(256), 0, q.stream, a);
-    else if (maxw <= 128) hipLaunchKernelGGL(k_bn_apply_fwd<8>, grid, dim3(256), 0, q.stream, a);
-    else hipLaunchKernelGGL(k_bn_apply_fwd<0>, grid, dim3(256), 0, q.stream, a);
+    switch (pick_key(pk)) {
+        case form_key(false, 2): hipLaunchKernelGGL(k_bn_apply_fwd<2>, grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 4): hipLaunchKernelGGL(k_bn_apply_fwd<4>, grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 8): hipLaunchKernelGGL(k_bn_apply_fwd<8>, grid, dim3(256), 0, q.stream, a); break;
+        case form_key(false, 0): hipLaunchKernelGGL(k_bn_apply_fwd<0>, grid, dim3(256), 0, q.stream, a); break;
+        default: pick_missing(q, "bn_apply_fwd", pk); return;
+    }
     q.check_launch("bn_apply_fwd");
 }
 
@@ -1141,28 +1207,27 @@ void rownorm_bwd(Seq& q, GroupCPtrs dx, GroupCPtrs xhat, GroupCPtrs y, const flo
     const int ct = g.c0[g.G - 1] + g.w[g.G - 1];
     RownormBwdArgs a{dx, xhat, y, invn, stats, part2, g, dU, ldu, db, want, vs, (ct + 15) / 16, ((n + 31) / 32) * 4,
                      B, n, 8, has_relu, has_bn, normalize, Bs, 0};
-    if (has_bn && Bs > 32) {
+    const RowPick pk = rownorm_bwd_pick(g, has_bn != 0, Bs);
+    if (pk.finalize) {
         // (part2 is plan scratch; the combined means go where graph 0's pair was)
         hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)(((long)n * g.G + 15) / 16)), dim3(256), 0, q.stream,
                            const_cast<float*>(part2), Bs, n, g);
         q.check_launch("bn_bwd_finalize");
         a.means_ready = 1;
     }
-    const int maxw = g.G == 2 && g.w[1] > g.w[0] ? g.w[1] : g.w[0];
     const dim3 grid(rownorm_bwd_chunks(n), B);
     const size_t lds = ((want ? 16 : 0) + (vs ? 8 : 0)) * ct * sizeof(float);
-    if (maxw > 128 && maxw <= 512 && row_quads_ok(g)) {
-        if (maxw <= 256) hipLaunchKernelGGL((k_rownorm_bwd<4, true>), grid, dim3(256), lds, q.stream, a);
-        else if (maxw <= 320) hipLaunchKernelGGL((k_rownorm_bwd<5, true>), grid, dim3(256), lds, q.stream, a);
-        else hipLaunchKernelGGL((k_rownorm_bwd<8, true>), grid, dim3(256), lds, q.stream, a);
-        q.check_launch("rownorm_bwd");
-        return;
+    switch (pick_key(pk)) {
+        case form_key(true, 4): hipLaunchKernelGGL((k_rownorm_bwd<4, true>), grid, dim3(256), lds, q.stream, a); break;
+        case form_key(true, 5): hipLaunchKernelGGL((k_rownorm_bwd<5, true>), grid, dim3(256), lds, q.stream, a); break;
+        case form_key(true, 8): hipLaunchKernelGGL((k_rownorm_bwd<8, true>), grid, dim3(256), lds, q.stream, a); break;
+        case form_key(false, 2): hipLaunchKernelGGL(k_rownorm_bwd<2>, grid, dim3(256), lds, q.stream, a); break;
+        case form_key(false, 4): hipLaunchKernelGGL(k_rownorm_bwd<4>, grid, dim3(256), lds, q.stream, a); break;
+        case form_key(false, 8): hipLaunchKernelGGL(k_rownorm_bwd<8>, grid, dim3(256), lds, q.stream, a); break;
+        case form_key(false, 16): hipLaunchKernelGGL(k_rownorm_bwd<16>, grid, dim3(256), lds, q.stream, a); break;
+        case form_key(false, 0): hipLaunchKernelGGL(k_rownorm_bwd<0>, grid, dim3(256), lds, q.stream, a); break;
+        default: pick_missing(q, "rownorm_bwd", pk); return;
     }
-    if (maxw <= 32) hipLaunchKernelGGL(k_rownorm_bwd<2>, grid, dim3(256), lds, q.stream, a);
-    else if (maxw <= 64) hipLaunchKernelGGL(k_rownorm_bwd<4>, grid, dim3(256), lds, q.stream, a);
-    else if (maxw <= 128) hipLaunchKernelGGL(k_rownorm_bwd<8>, grid, dim3(256), lds, q.stream, a);
-    else if (maxw <= 256) hipLaunchKernelGGL(k_rownorm_bwd<16>, grid, dim3(256), lds, q.stream, a);
-    else hipLaunchKernelGGL(k_rownorm_bwd<0>, grid, dim3(256), lds, q.stream, a);
     q.check_launch("rownorm_bwd");
 }
 
@@ -1242,17 +1307,19 @@ __global__ __launch_bounds__(1024) void k_colsum_batched(const float* X, int ldx
         float t = 0.f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) t += red[k][cl];
-        if (atomic) atomicAdd(out + (long)b * strideOut + c, t);
+        if (atomic == 1) atomicAdd(out + (long)b * strideOut + c, t);
+        else if (atomic == 2) out[(long)b * strideOut + c] += t;     // (one row range: this thread owns the entry)
         else out[(long)b * strideOut + c] = t;
     }
 }
-// rowsplit > 1: the rows are cut into `rowsplit` ranges that ADD into `out` with float atomics (out pre-zeroed)
+// rowsplit > 1: the rows are cut into `rowsplit` ranges that ADD into `out` with float atomics (out pre-zeroed);
+// add: one range adds into `out` too (a plain read-modify-write by the entry's only thread) instead of storing
 void colsum_batched(Seq& q, const float* X, int ldx, long strideX, int rows, int cols, float* out, long strideOut,
-                    int batch, int rowsplit) {
+                    int batch, int rowsplit, bool add) {
     if (!q.ok() || cols <= 0 || batch <= 0) return;
     if (rowsplit < 1) rowsplit = 1;
     hipLaunchKernelGGL(k_colsum_batched, dim3((cols + 63) / 64, batch, rowsplit), dim3(1024), 0, q.stream, X, ldx,
-                       strideX, rows, cols, out, strideOut, rowsplit > 1 ? 1 : 0);
+                       strideX, rows, cols, out, strideOut, rowsplit > 1 ? 1 : add ? 2 : 0);
     q.check_launch("colsum_batched");
 }
 
@@ -1429,29 +1496,28 @@ void softmax_mask_fwd(Seq& q, const float* logits, int ldl, float* S, int lds, c
                       int K, float* S2, unsigned short* vs, void* zero_p, size_t zero_bytes) {
     if (!q.ok()) return;
     const long rows = (long)B * n;
-    const bool fits = (size_t)16 * K * sizeof(float) <= 48 * 1024;   // (a split is only ever asked for K <= 320)
-    if (!fits && zero_p) {
-        zero_fill(q, zero_p, zero_bytes);
+    const bool aligned = (reinterpret_cast<uintptr_t>(zero_p) & 15) == 0 && (zero_bytes & 15) == 0;
+    const RowPick pk = softmax_mask_fwd_pick(K, vs != nullptr, zero_p != nullptr, aligned);
+    if (pk.zero == DP_ROWZ_APART) {
+        if (pk.generic()) zero_fill(q, zero_p, zero_bytes);
+        else zero_small(q, zero_p, zero_bytes);
         zero_p = nullptr;
     }
-    if (fits && (vs || zero_p)) {
-        if (zero_p && ((reinterpret_cast<uintptr_t>(zero_p) & 15) != 0 || (zero_bytes & 15) != 0)) {
-            zero_small(q, zero_p, zero_bytes);
-            zero_p = nullptr;
-        }
+    if (!pk.generic()) {
         SoftmaxFwdArgs a{logits, ldl, S, lds, S2, num_nodes, n, K, vs, (K + 15) / 16, ((n + 31) / 32) * 4,
                          (uint4*)zero_p, (long)(zero_bytes / 16)};
         const dim3 grid((n + 15) / 16, B);
         const size_t sm = (size_t)16 * K * sizeof(float);
-        if (K > 128 && K <= 512 && (K & 3) == 0 && !knobs().no_row_quads) {
-            if (K <= 256) hipLaunchKernelGGL((k_softmax_mask_fwd_plan<4, true>), grid, dim3(256), sm, q.stream, a);
-            else if (K <= 320) hipLaunchKernelGGL((k_softmax_mask_fwd_plan<5, true>), grid, dim3(256), sm, q.stream, a);
-            else hipLaunchKernelGGL((k_softmax_mask_fwd_plan<8, true>), grid, dim3(256), sm, q.stream, a);
-        } else
-        if (K <= 64) hipLaunchKernelGGL(k_softmax_mask_fwd_plan<4>, grid, dim3(256), sm, q.stream, a);
-        else if (K <= 128) hipLaunchKernelGGL(k_softmax_mask_fwd_plan<8>, grid, dim3(256), sm, q.stream, a);
-        else if (K <= 256) hipLaunchKernelGGL(k_softmax_mask_fwd_plan<16>, grid, dim3(256), sm, q.stream, a);
-        else hipLaunchKernelGGL(k_softmax_mask_fwd_plan<0>, grid, dim3(256), sm, q.stream, a);
+        switch (pick_key(pk)) {
+            case form_key(true, 4): hipLaunchKernelGGL((k_softmax_mask_fwd_plan<4, true>), grid, dim3(256), sm, q.stream, a); break;
+            case form_key(true, 5): hipLaunchKernelGGL((k_softmax_mask_fwd_plan<5, true>), grid, dim3(256), sm, q.stream, a); break;
+            case form_key(true, 8): hipLaunchKernelGGL((k_softmax_mask_fwd_plan<8, true>), grid, dim3(256), sm, q.stream, a); break;
+            case form_key(false, 4): hipLaunchKernelGGL(k_softmax_mask_fwd_plan<4>, grid, dim3(256), sm, q.stream, a); break;
+            case form_key(false, 8): hipLaunchKernelGGL(k_softmax_mask_fwd_plan<8>, grid, dim3(256), sm, q.stream, a); break;
+            case form_key(false, 16): hipLaunchKernelGGL(k_softmax_mask_fwd_plan<16>, grid, dim3(256), sm, q.stream, a); break;
+            case form_key(false, 0): hipLaunchKernelGGL(k_softmax_mask_fwd_plan<0>, grid, dim3(256), sm, q.stream, a); break;
+            default: pick_missing(q, "softmax_mask_fwd_plan", pk); return;
+        }
         q.check_launch("softmax_mask_fwd_plan");
         return;
     }
@@ -1593,25 +1659,27 @@ void softmax_mask_bwd(Seq& q, const float* S, int lds, const float* dS, int ldds
                       const float* dS2) {
     if (!q.ok()) return;
     const long rows = (long)B * n;
-    if (dbias && (size_t)16 * K * sizeof(float) <= 64 * 1024) {
+    const RowPick pk = softmax_mask_bwd_pick(K, dbias != nullptr);
+    if (!pk.generic()) {
         const dim3 grid((n + 63) / 64, B);
         const size_t sm = (size_t)16 * K * sizeof(float);
-#define DP_SMB(NK, RW)                                                                                            \
-    hipLaunchKernelGGL((k_softmax_mask_bwd_plan<NK, RW>), grid, dim3(256), sm, q.stream, S, lds, dS, ldds, dlogits, \
-                       ldl, n, K, dbias, dbias_stride, dS2)
-        if (K > 128 && K <= 512 && (K & 3) == 0 && !knobs().no_row_quads) {
-            if (K <= 256) hipLaunchKernelGGL((k_softmax_mask_bwd_plan<4, 1, true>), grid, dim3(256), sm, q.stream, S, lds,
-                                             dS, ldds, dlogits, ldl, n, K, dbias, dbias_stride, dS2);
-            else if (K <= 320) hipLaunchKernelGGL((k_softmax_mask_bwd_plan<5, 1, true>), grid, dim3(256), sm, q.stream, S,
-                                                  lds, dS, ldds, dlogits, ldl, n, K, dbias, dbias_stride, dS2);
-            else hipLaunchKernelGGL((k_softmax_mask_bwd_plan<8, 1, true>), grid, dim3(256), sm, q.stream, S, lds, dS, ldds,
-                                    dlogits, ldl, n, K, dbias, dbias_stride, dS2);
-        } else
-        if (K <= 64) DP_SMB(4, 4);
-        else if (K <= 128) DP_SMB(8, 2);
-        else if (K <= 256) DP_SMB(16, 1);
-        else DP_SMB(0, 1);
-#undef DP_SMB
+        switch (pick_key(pk)) {
+            case form_key(true, 4): hipLaunchKernelGGL((k_softmax_mask_bwd_plan<4, 1, true>), grid, dim3(256), sm, q.stream, S, lds,
+                                         dS, ldds, dlogits, ldl, n, K, dbias, dbias_stride, dS2); break;
+            case form_key(true, 5): hipLaunchKernelGGL((k_softmax_mask_bwd_plan<5, 1, true>), grid, dim3(256), sm, q.stream, S, lds,
+                                         dS, ldds, dlogits, ldl, n, K, dbias, dbias_stride, dS2); break;
+            case form_key(true, 8): hipLaunchKernelGGL((k_softmax_mask_bwd_plan<8, 1, true>), grid, dim3(256), sm, q.stream, S, lds,
+                                         dS, ldds, dlogits, ldl, n, K, dbias, dbias_stride, dS2); break;
+            case form_key(false, 4): hipLaunchKernelGGL((k_softmax_mask_bwd_plan<4, 4>), grid, dim3(256), sm, q.stream, S, lds, dS, ldds,
+                                       dlogits, ldl, n, K, dbias, dbias_stride, dS2); break;
+            case form_key(false, 8): hipLaunchKernelGGL((k_softmax_mask_bwd_plan<8, 2>), grid, dim3(256), sm, q.stream, S, lds, dS, ldds,
+                                       dlogits, ldl, n, K, dbias, dbias_stride, dS2); break;
+            case form_key(false, 16): hipLaunchKernelGGL((k_softmax_mask_bwd_plan<16, 1>), grid, dim3(256), sm, q.stream, S, lds, dS, ldds,
+                                        dlogits, ldl, n, K, dbias, dbias_stride, dS2); break;
+            case form_key(false, 0): hipLaunchKernelGGL((k_softmax_mask_bwd_plan<0, 1>), grid, dim3(256), sm, q.stream, S, lds, dS, ldds,
+                                       dlogits, ldl, n, K, dbias, dbias_stride, dS2); break;
+            default: pick_missing(q, "softmax_mask_bwd_plan", pk); return;
+        }
         q.check_launch("softmax_mask_bwd_plan");
         return;
     }
@@ -1619,7 +1687,8 @@ void softmax_mask_bwd(Seq& q, const float* S, int lds, const float* dS, int ldds
     hipLaunchKernelGGL(k_softmax_mask_bwd, dim3(team_grid(rows)), dim3(256), 0, q.stream, S, lds, dS, ldds,
                        num_nodes, dlogits, ldl, rows, n, K);
     q.check_launch("softmax_mask_bwd");
-    if (dbias) colsum_batched(q, dlogits, ldl, (long)n * ldl, n, K, dbias, dbias_stride, B, n >= 256 ? 8 : 1);
+    // (the slab is ADDED to on every path, as the plan forms do: below 256 rows the one range adds as well)
+    if (dbias) colsum_batched(q, dlogits, ldl, (long)n * ldl, n, K, dbias, dbias_stride, B, n >= 256 ? 8 : 1, true);
 }
 
 // ------------------------------------------------------------------ masked max readout

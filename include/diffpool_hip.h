@@ -241,6 +241,101 @@ int dp_masked_max_fwd(const float* Z, int ldz, const int* num_nodes, float* out,
 int dp_masked_max_bwd(const float* dout, int ldo, const int* argmax, float* dZ, int lddz, int B, int n,
                       int F, void* stream);
 
+/* ------------------------------------------------------------------ row kernels, as the encoder plans call them
+ * The row-wise launchers behind the entries above (GraphConv tail, node BatchNorm, assignment softmax, column sums),
+ * passed straight through with every optional operand: up to two column groups of a joint buffer, per-group outputs
+ * with their own leading dimensions, BatchNorm partials, bias-gradient slabs, the 3-plane bf16 split (`vs`, the
+ * layout dp_adj_aggregate_packed reads: Vs[b][plane][cb][k8][c][j], ((n + 31) / 32) * 4 k8 groups) and the folded
+ * zero-fill.  No reference counterpart; they exist so that every compiled form can be tested on its own.
+ *
+ * dp_row_groups: G = 1 or 2 groups, group i is columns c0[i] .. c0[i] + w[i] of the joint buffer (c0 ascending, no
+ * overlap).  dp_group_ptrs: per group a pointer ALREADY at the group's first column, and its leading dimension. */
+typedef struct {
+    int G;
+    int c0[2];
+    int w[2];
+} dp_row_groups;
+typedef struct {
+    void* p[2];
+    int ld[2];
+} dp_group_ptrs;
+size_t dp_sizeof_row_groups(void);
+size_t dp_sizeof_group_ptrs(void);
+
+/* dp_rowop_plan: the form a launcher takes, answered by the host function the launcher itself decides with.  Host
+ * only: no GPU call.  `g` holds the groups (softmax: K = g->w[0]; masked max: unused, may be NULL); Bs = graphs the
+ * BatchNorm statistics span (0: B).  flags: DP_ROWF_STATS (bn_apply_fwd: `part` given; rownorm_bwd: has_bn),
+ * DP_ROWF_VS, DP_ROWF_ZERO (a zero region is given), DP_ROWF_ZERO_UNALIGNED (it is not 16-byte aligned or not a
+ * multiple of 16 bytes), DP_ROWF_DBIAS (softmax_mask_bwd: a bias-gradient slab is given).
+ * plan_out[DP_ROWOP_PLAN_INTS] = { kernel (DP_ROWK_*), NK (0: the any-width form; masked max: 32 = all rows of a thread
+ * in one batch of loads, n <= 512), quad (1: 16-byte lanes), finalize (1: k_bn_finalize / k_bn_bwd_finalize runs in
+ * front), generic (1: the generic softmax kernel, no _plan form), zero (DP_ROWZ_*) }. */
+#define DP_ROWOP_ROWNORM_FWD 0
+#define DP_ROWOP_ROWNORM_BWD 1
+#define DP_ROWOP_BN_APPLY_FWD 2
+#define DP_ROWOP_SOFTMAX_FWD 3
+#define DP_ROWOP_SOFTMAX_BWD 4
+#define DP_ROWOP_MASKED_MAX_FWD 5
+#define DP_ROWK_ROWNORM_FWD 0
+#define DP_ROWK_ROWNORM_BWD 1
+#define DP_ROWK_BN_APPLY_FWD 2
+#define DP_ROWK_SOFTMAX_FWD_PLAN 3
+#define DP_ROWK_SOFTMAX_FWD 4
+#define DP_ROWK_SOFTMAX_BWD_PLAN 5
+#define DP_ROWK_SOFTMAX_BWD 6
+#define DP_ROWK_MASKED_MAX_FWD 7
+#define DP_ROWF_STATS 1
+#define DP_ROWF_VS 2
+#define DP_ROWF_ZERO 4
+#define DP_ROWF_ZERO_UNALIGNED 8
+#define DP_ROWF_DBIAS 16
+#define DP_ROWZ_NONE 0
+#define DP_ROWZ_FOLDED 1 /* the softmax kernel's own workgroups clear the region */
+#define DP_ROWZ_APART 2  /* a zero-fill launch of its own in front */
+#define DP_ROWOP_PLAN_INTS 6
+int dp_rowop_plan(int op, const dp_row_groups* g, int n, int B, int Bs, int flags, int* plan_out);
+
+/* Every entry below refuses with DP_ERR_INVALID_ARG, before any launch: G outside 1..2, a width below 1, overlapping
+ * or descending groups, a leading dimension smaller than its rows, NULL required pointers, and a `vs` request the
+ * launcher has no form for (see each entry).
+ *
+ * y_g = u / max(||u||, 1e-12), u = U[row, c0_g + c] (+ P[row, c0_g + c]) (+ bias_g[c]); normalize = 0: y = u.
+ * P (same ld as U) and bias (NULL, or per group NULL / [w_g]) are optional.  invn [rows, G] (NULL, or 1 / max(||u||, eps)
+ * out).  stats_mode 1 / 2 with part [rows, G, 2]: (row mean, row M2) of relu(y) / of y. */
+int dp_rownorm_fwd(const float* U, int ldu, const float* P, const dp_row_groups* g, const dp_group_ptrs* bias,
+                   const dp_group_ptrs* yout, float* invn, float* part, long rows, int normalize, int stats_mode,
+                   void* stream);
+/* x = (relu?(y) - mu_n) * rstd_n per node index n and group, the statistics Chan-combined from part [Bs, n, G, 2]
+ * (Bs = 0: B; Bs > B: the statistics span more graphs than the B normalised here); stats [n, G, 2] receives (mu, rstd).
+ * part = NULL: no BatchNorm (ReLU only), stats unused. */
+int dp_bn_apply_fwd(const float* Y, int ldy, const float* part, float* stats, const dp_row_groups* g,
+                    const dp_group_ptrs* xout, int B, int n, int relu, int Bs, void* stream);
+/* part [rows, G, 2] = (sum_c dx, sum_c dx * xhat) per row and group */
+int dp_bn_bwd_partials(const dp_row_groups* g, const dp_group_ptrs* dx, const dp_group_ptrs* xhat, float* part,
+                       long rows, void* stream);
+/* dx -> (BatchNorm bwd, has_bn) -> (ReLU bwd, has_relu) -> (l2-normalise bwd, normalize) -> dU [B * n, ldu] at the
+ * groups' columns.  part2 [Bs, n, G, 2] from dp_bn_bwd_partials (OVERWRITTEN when Bs > 32); dbias: NULL, or per group
+ * NULL / the slab row of graph 0, graphs ld >= w_g apart — the column sums of dU are ADDED.  vs: NULL, or the 3-plane split of
+ * dU [B, n, c0[G-1] + w[G-1]] out (16-byte aligned; refused when slabs + split need more than 64 KiB of LDS). */
+int dp_rownorm_bwd(const dp_row_groups* g, const dp_group_ptrs* dx, const dp_group_ptrs* xhat,
+                   const dp_group_ptrs* y, const float* invn, const float* stats, float* part2, float* dU, int ldu,
+                   const dp_group_ptrs* dbias, int B, int n, int has_relu, int has_bn, int normalize, void* vs, int Bs,
+                   void* stream);
+/* S = softmax_K(logits) on rows n < num_nodes[b] (NULL: all), 0 elsewhere; S2: NULL or a second copy (ld lds);
+ * vs: NULL or the 3-plane split of S out (16-byte aligned; refused for K > 768, where no plan form exists);
+ * zero_p / zero_bytes: a region to clear on the way. */
+int dp_softmax_mask_fwd(const float* logits, int ldl, float* S, int lds, const int* num_nodes, int B, int n, int K,
+                        float* S2, void* vs, void* zero_p, size_t zero_bytes, void* stream);
+/* dlogits = S * (dS (+ dS2) - <dS (+ dS2), S>).  dbias: NULL, or the slab row of graph 0 (graphs dbias_stride apart) the
+ * column sums of dlogits are ADDED to.  dS2: NULL or a second addend, ld ldds.  Without dbias (and for K > 1024) dS2 is
+ * first ADDED INTO dS, as one run of B * n * ldds floats: there both buffers must hold B * n * ldds floats — the last
+ * row its full ldds too — and the padding of dS receives the padding of dS2. */
+int dp_softmax_mask_bwd(const float* S, int lds, float* dS, int ldds, const int* num_nodes, float* dlogits, int ldl,
+                        int B, int n, int K, float* dbias, long dbias_stride, const float* dS2, void* stream);
+/* out[b, c] = sum_r X[b, r, c]; rowsplit > 1: `rowsplit` row ranges ADD into out with float atomics */
+int dp_colsum_batched(const float* X, int ldx, long strideX, int rows, int cols, float* out, long strideOut, int batch,
+                      int rowsplit, void* stream);
+
 /* ------------------------------------------------------------------ A8  link-prediction loss
  * loss = sum_{n,m < n_b} [-A log(P+1e-7) - (1-A) log(1-P+1e-7)] / sum_b n_b^2,
  * P = min(S S^T, 1) — encoders.py:1309-1331 (adj_hop = 1).  loss_out: 1 float.  K <= 256 (DP_ERR_UNSUPPORTED above).

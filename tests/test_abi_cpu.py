@@ -72,6 +72,8 @@ def test_version_and_error_string(lib):
     assert isinstance(lib.dp_last_error_string(), bytes)
     assert lib.dp_sizeof_encoder_cfg() == C.sizeof(_lib.EncoderCfg)
     assert lib.dp_sizeof_gemm_problem() == C.sizeof(_lib.GemmProblem) == 112
+    assert lib.dp_sizeof_row_groups() == C.sizeof(_lib.RowGroups) == 20
+    assert lib.dp_sizeof_group_ptrs() == C.sizeof(_lib.GroupPtrs) == 24
 
 
 def test_device_error_word_decode(lib):
@@ -101,6 +103,18 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     assert lib.dp_bgemm_plan(prob, 5, 1, 1, plan) == -1 and b"count=5" in lib.dp_last_error_string()
     assert lib.dp_bgemm_plan(prob, 1, 1, 1, plan) == 0 and _lib.gemm_plan_decode(plan[0]) == (64, 16, 1, 1)
     assert lib.dp_bgemm_group_f32(prob, 1, 1, 1, None, 0, None) == -1 and b"NULL" in lib.dp_last_error_string()
+    # the row launchers' pass-through entries and their plan query: a bad descriptor, then NULL operands
+    g = _lib.RowGroups(G=2, c0=(C.c_int * 2)(0, 4), w=(C.c_int * 2)(8, 8))
+    out = (C.c_int * _lib.ROWOP_PLAN_INTS)()
+    assert lib.dp_rowop_plan(_lib.ROWOP_ROWNORM_FWD, C.byref(g), 4, 1, 0, 0, out) == -1
+    assert b"overlap" in lib.dp_last_error_string()
+    g.c0[1] = 8
+    assert lib.dp_rowop_plan(_lib.ROWOP_ROWNORM_FWD, C.byref(g), 4, 1, 0, 0, out) == 0
+    assert tuple(out) == (_lib.ROWK_ROWNORM_FWD, 2, 0, 0, 0, 0)
+    for name in ("dp_rownorm_fwd", "dp_bn_apply_fwd", "dp_bn_bwd_partials", "dp_rownorm_bwd", "dp_softmax_mask_fwd",
+                 "dp_softmax_mask_bwd", "dp_colsum_batched"):
+        assert name in _lib.EXPORTED_SYMBOLS
+    assert lib.dp_colsum_batched(None, 8, 0, 4, 8, None, 8, 1, 1, None) == -1 and b"NULL" in lib.dp_last_error_string()
     rc = lib.dp_masked_max_fwd(1, 4, None, 1, 4, 1, 0, 3, 4, None)
     assert rc == -1 and b"B=0" in lib.dp_last_error_string()
     cfg = _lib.EncoderCfg()
