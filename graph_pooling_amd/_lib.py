@@ -85,6 +85,13 @@ ROWF_STATS, ROWF_VS, ROWF_ZERO, ROWF_ZERO_UNALIGNED, ROWF_DBIAS = 1, 2, 4, 8, 16
 ROWZ_NONE, ROWZ_FOLDED, ROWZ_APART = 0, 1, 2
 ROWOP_PLAN_INTS = 6
 
+# dp_adj_aggregate_plan: DP_AGG_FORM_*, DP_AGG_FB_*; DP_AGG_DECLINED of dp_adj_aggregate_rownorm
+(AGG_FORM_PANEL_F32, AGG_FORM_PANEL_BF16, AGG_FORM_WIDE, AGG_FORM_WIDE_DMA, AGG_FORM_GEMM_F32,
+ AGG_FORM_GEMM_SPLIT_BF16) = range(6)
+AGG_FB_NONE, AGG_FB_PANEL, AGG_FB_GEMM = 0, 1, 2
+AGG_PLAN_INTS = 14
+AGG_DECLINED = -5
+
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
 GEMM_PLAN_NONE, GEMM_PLAN_SPLIT_BF16 = 0, 1                           # DP_GEMM_PLAN_*
@@ -124,8 +131,10 @@ _PROTOS = {
     "dp_adj_pack_ld": (_I, [_I]),
     "dp_adj_pack_bytes": (_Z, [_I, _I]),
     "dp_adj_pack": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "dp_adj_pack_zero": (_I, [_P, _P, _P, _P, _I, _I, _P, _Z, _P]),
     "dp_adj_aggregate_packed_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_adj_aggregate_packed": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _Z, _P]),
+    "dp_adj_aggregate_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _F, C.POINTER(_I)]),
     "dp_gcn_layer_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "dp_gcn_layer_fwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dp_gcn_layer_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
@@ -145,6 +154,8 @@ _PROTOS = {
     "dp_rowop_plan": (_I, [_I, C.POINTER(RowGroups), _I, _I, _I, _I, C.POINTER(_I)]),
     "dp_rownorm_fwd": (_I, [_P, _I, _P, C.POINTER(RowGroups), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), _P, _P, _L, _I,
                             _I, _P]),
+    "dp_adj_aggregate_rownorm": (_I, [_P, _P, _P, _P, _P, _I, _P, C.POINTER(RowGroups), C.POINTER(GroupPtrs),
+                                      C.POINTER(GroupPtrs), _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dp_bn_apply_fwd": (_I, [_P, _I, _P, _P, C.POINTER(RowGroups), C.POINTER(GroupPtrs), _I, _I, _I, _I, _P]),
     "dp_bn_bwd_partials": (_I, [C.POINTER(RowGroups), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), _P, _L, _P]),
     "dp_rownorm_bwd": (_I, [C.POINTER(RowGroups), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), C.POINTER(GroupPtrs), _P, _P,

@@ -843,19 +843,16 @@ static int aggw_ct(int C) {
     const int ct = (C + 15) / 16;
     return ct <= 8 ? ct : (ct + 1) & ~1;
 }
-// the wide kernel pays when it fills the chip (>= 2 workgroups per CU) or when the operand is too wide for the
-// panel kernel; it needs the packed adjacency (n >= 128)
-static bool aggw_usable(const PackedAdj* pk, const unsigned short* vs, int B, int n, int C) {
-    if (!pk || !vs || n < 128 || C < 1 || C > AGGW_MAX_C) return false;
-    const int force = knobs().agg_wide;   // tests: 0 never, 1 always
-    if (force >= 0) return force != 0;
-    return C > 128 || (long)B * ((n + 127) / 128) >= 512;
+constexpr int aggw_ks(int CT) { return CT <= 4 ? DP_AGGW_KS : CT <= 8 ? 2 : 1; }
+constexpr size_t aggw_lds_bytes(int CT) { return (size_t)2 * 3 * CT * aggw_ks(CT) * 1024; }
+constexpr int aggw_dma_waves(int CT) { return CT <= 18 ? 8 : 4; }
+constexpr size_t aggw_dma_lds_bytes(int CT, int WAVES) {
+    return ((size_t)2 * 3 * CT * 512 + 3 * WAVES * 1024) * sizeof(unsigned short);
 }
 
 template <int CT>
 static void launch_aggw(Seq& q, const AggArgs& a, int B) {
-    constexpr int KS = CT <= 4 ? DP_AGGW_KS : CT <= 8 ? 2 : 1;
-    constexpr size_t lds = (size_t)2 * 3 * CT * KS * 1024;
+    constexpr size_t lds = aggw_lds_bytes(CT);
     static_assert(lds <= 160 * 1024, "wide aggregation LDS");
     static DynLdsOnce attr;
     if (lds > 64 * 1024)
@@ -868,7 +865,8 @@ static void launch_aggw(Seq& q, const AggArgs& a, int B) {
 }
 template <int CT, int WAVES>
 static void launch_aggw_dma(Seq& q, const AggArgs& a, int B) {
-    constexpr size_t lds = ((size_t)2 * 3 * CT * 512 + 3 * WAVES * 1024) * sizeof(unsigned short);
+    static_assert(WAVES == aggw_dma_waves(CT), "agg_pick reports aggw_dma_waves(CT)");
+    constexpr size_t lds = aggw_dma_lds_bytes(CT, WAVES);
     static_assert(lds <= 160 * 1024, "wide aggregation LDS");
     static DynLdsOnce attr;
     ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_aggregate_wide_dma<CT, WAVES>), (int)lds,
@@ -879,13 +877,23 @@ static void launch_aggw_dma(Seq& q, const AggArgs& a, int B) {
     aa.vs_ct = (a.C + 15) / 16;
     hipLaunchKernelGGL((k_aggregate_wide_dma<CT, WAVES>), dim3(aa.tiles * B), dim3(WAVES * 64), lds, q.stream, aa);
 }
-static void dispatch_wide(Seq& q, const AggArgs& a, int B) {
-    switch (aggw_ct(a.C)) {
-#define W(T) case T: launch_aggw<T>(q, a, B); break;
-#define D(T, WV) case T: launch_aggw_dma<T, WV>(q, a, B); break;
-        W(1) W(2) W(3) W(4) W(5) W(6) W(7) W(8) D(10, 8) D(12, 8) D(14, 8) D(16, 8) D(18, 8) D(20, 4)
-#undef W
-#undef D
+// ct: AggPick::ct of a wide form (aggw_ct(C))
+static void dispatch_wide(Seq& q, const AggArgs& a, int B, int ct) {
+    switch (ct) {
+        case 1: launch_aggw<1>(q, a, B); break;
+        case 2: launch_aggw<2>(q, a, B); break;
+        case 3: launch_aggw<3>(q, a, B); break;
+        case 4: launch_aggw<4>(q, a, B); break;
+        case 5: launch_aggw<5>(q, a, B); break;
+        case 6: launch_aggw<6>(q, a, B); break;
+        case 7: launch_aggw<7>(q, a, B); break;
+        case 8: launch_aggw<8>(q, a, B); break;
+        case 10: launch_aggw_dma<10, 8>(q, a, B); break;
+        case 12: launch_aggw_dma<12, 8>(q, a, B); break;
+        case 14: launch_aggw_dma<14, 8>(q, a, B); break;
+        case 16: launch_aggw_dma<16, 8>(q, a, B); break;
+        case 18: launch_aggw_dma<18, 8>(q, a, B); break;
+        case 20: launch_aggw_dma<20, 4>(q, a, B); break;
         default: break;
     }
 }
@@ -903,23 +911,108 @@ static size_t agg_lds_bytes(bool trans, int n, int CT, int RT, int NW = 4) {
     const size_t red = (size_t)(NW + 1) * RT * (CT * 16 + 1);
     return (panel > red ? panel : red) * sizeof(float);    // the reduction area overlays the panel
 }
-// 16-row tiles when 32-row tiles would leave CUs idle (< 1 workgroup per CU): twice the workgroups.  Otherwise 32
-// rows: every row tile re-reads the whole split V from L2 (147 KB at the DD shape against a 16-32 KB adjacency
-// panel), so halving the tile count halves the dominant on-chip traffic (DD: 0.424 -> 0.418 ms per step).
-static int agg_row_tile(int B, int n, int C, bool trans) {
-    if (agg_lds_bytes(trans, n, agg_ct(C), 32) > 160 * 1024) return 16;   // 32 rows do not fit
-    const int force = knobs().agg_rt;   // tuning knob
-    if (force == 16 || force == 32) return force;
-    return ((long)((n + 31) / 32) * B >= 256) ? 32 : 16;
+
+// the panel kernel's shapes.  C > 128 is not a panel shape: a 16/32-row panel re-reads the whole V operand per row tile
+// (25 GB of L2 traffic per pass at the ER shape).  Wide operands go to k_aggregate_wide_dma when the adjacency is packed
+// and bf16-exact, to the tiled fp32 GEMM otherwise.
+static bool agg_panel_shape(unsigned a_misalign, int n, int C, bool trans) {
+    if (n < 4 || n % 4 != 0 || C < 1 || C > 128) return false;
+    if ((a_misalign & 15) != 0) return false;
+    return agg_lds_bytes(trans, n, agg_ct(C), 16) <= 160 * 1024;
+}
+// the packed operand is worth it only for big levels; the bf16 panel of a 32-row tile must fit LDS beside the
+// reduction area
+static bool agg_pack_shape(int n, int C) {
+    if (knobs().no_pack) return false;     // ablation: fp32 adjacency passes everywhere
+    return n >= 128 && C >= 1 && C <= AGGW_MAX_C &&
+           ((size_t)16 * (((n + 511) / 512) * 512 + 8) * 2 + 5 * 16 * 129 * 4 <= 156 * 1024);
+}
+static bool agg_gemm_splits(int B, int n, int C, bool trans, float beta) {
+    GemmDesc d{nullptr, nullptr, nullptr, nullptr, n, C, n, n, C, C, (long)n * n, (long)n * C, (long)n * C, trans, false, 1.f, beta, 0};
+    return gemm_split_usable(d, B, 1);
+}
+
+// The one routing decision of this file: aggregate() and aggregate_rownorm_fwd() launch what it answers, and
+// dp_adj_aggregate_plan (diffpool_hip.h) reports it.  Host only.  `packed`: a packed adjacency and a split buffer are
+// given; `fused`: the GraphConv-tail entry (NN, no U); a_misalign: the low address bits of A.
+AggPick agg_pick(int B, int n, int C, bool trans, bool packed, bool fused, unsigned a_misalign, float beta) {
+    AggPick p{};
+    p.fallback = DP_AGG_FB_NONE;
+    if (fused) trans = false, beta = 0.f;
+    const bool panel = agg_panel_shape(a_misalign, n, C, trans);
+    const bool packed_given = packed;
+    packed = packed && agg_pack_shape(n, C);
+    // a general (pooled, weighted) adjacency at a big batch: both operands are general fp32, which is the split-bf16
+    // GEMM's case — the fp32 panel kernel ran the 84-column level-1 passes of the ER shape at 30 TFLOP/s.  Narrow
+    // operands (C < 48) stay: the pass is bound by reading A, the panel kernel's case.
+    const bool prefers_split = !packed && C >= 48 && agg_gemm_splits(B, n, C, trans, beta);
+    if (fused && (!panel || prefers_split)) {
+        // the fused entry declines: the answer is what the caller's two-launch path gets from aggregate()
+        p = agg_pick(B, n, C, false, packed_given, false, a_misalign, 0.f);
+        p.declines = true;
+        return p;
+    }
+    if (prefers_split) {
+        p.form = DP_AGG_FORM_GEMM_SPLIT_BF16;
+        return p;
+    }
+    auto panel_dims = [&](int& ct, int& rt, int& tiles, int& grid, size_t& lds) {
+        ct = agg_ct(C);
+        // 16-row tiles when 32-row tiles would leave CUs idle (< 1 workgroup per CU): twice the workgroups.  Otherwise
+        // 32 rows: every row tile re-reads the whole split V from L2 (147 KB at the DD shape against a 16-32 KB
+        // adjacency panel), so halving the tile count halves the dominant on-chip traffic (DD: 0.424 -> 0.418 ms per
+        // step).
+        const int force = knobs().agg_rt;   // tuning knob
+        if (agg_lds_bytes(trans, n, ct, 32) > 160 * 1024) rt = 16;   // 32 rows do not fit
+        else if (force == 16 || force == 32) rt = force;
+        else rt = ((long)((n + 31) / 32) * B >= 256) ? 32 : 16;
+        tiles = (n + rt - 1) / rt;
+        grid = tiles * B;
+        lds = agg_lds_bytes(trans, n, ct, rt);
+    };
+    // the wide kernels pay when they fill the chip (>= 2 workgroups per CU) or when the operand is too wide for the
+    // panel kernel; they need the packed adjacency (n >= 128)
+    bool wide = packed && n >= 128 && C >= 1 && C <= AGGW_MAX_C;
+    if (wide) {
+        const int force = knobs().agg_wide;   // tests: 0 never, 1 always
+        wide = force >= 0 ? force != 0 : (C > 128 || (long)B * ((n + 127) / 128) >= 512);
+    }
+    if (wide) {
+        p.packed = true;
+        p.ct = aggw_ct(C);
+        if (p.ct <= 8) {
+            p.form = DP_AGG_FORM_WIDE;
+            p.rt = 4;
+            p.tiles = (n + 127) / 128;
+            p.lds = aggw_lds_bytes(p.ct);
+        } else {
+            p.form = DP_AGG_FORM_WIDE_DMA;
+            p.rt = aggw_dma_waves(p.ct);
+            p.tiles = (n + 32 * p.rt - 1) / (32 * p.rt);
+            p.lds = aggw_dma_lds_bytes(p.ct, p.rt);
+        }
+        p.grid = p.tiles * B;
+        // fp32 fallback for adjacency that is not bf16-exact, gated on the device flag (no host sync)
+        if (panel) {
+            p.fallback = DP_AGG_FB_PANEL;
+            panel_dims(p.fb_ct, p.fb_rt, p.fb_tiles, p.fb_grid, p.fb_lds);
+        } else {
+            p.fallback = DP_AGG_FB_GEMM;      // (a predicated bgemm launch never diverts to the split kernel)
+        }
+        return p;
+    }
+    if (!panel) {
+        p.form = agg_gemm_splits(B, n, C, trans, beta) ? DP_AGG_FORM_GEMM_SPLIT_BF16 : DP_AGG_FORM_GEMM_F32;
+        return p;
+    }
+    p.form = packed ? DP_AGG_FORM_PANEL_BF16 : DP_AGG_FORM_PANEL_F32;
+    p.packed = packed;
+    panel_dims(p.ct, p.rt, p.tiles, p.grid, p.lds);
+    return p;
 }
 
 bool aggregate_supported(const float* A, int n, int C, bool trans) {
-    // C > 128 is not a panel shape: a 16/32-row panel re-reads the whole V operand per row tile (25 GB of L2
-    // traffic per pass at the ER shape).  Wide operands go to k_aggregate_wide_dma when the adjacency is packed and
-    // bf16-exact, to the tiled fp32 GEMM otherwise.
-    if (n < 4 || n % 4 != 0 || C < 1 || C > 128) return false;
-    if ((reinterpret_cast<uintptr_t>(A) & 15) != 0) return false;
-    return agg_lds_bytes(trans, n, agg_ct(C), 16) <= 160 * 1024;
+    return agg_panel_shape((unsigned)(reinterpret_cast<uintptr_t>(A) & 15), n, C, trans);
 }
 
 template <bool TRANS, int CT, int RT, int NW>
@@ -937,27 +1030,33 @@ static void launch_agg_rt(Seq& q, const AggArgs& a, int B) {
     aa.dbg = knobs().agg_debug;     // phase-ablation mask: DP_STAMP diagnostic builds only, 0 in the product
     hipLaunchKernelGGL((k_aggregate<TRANS, CT, RT, NW>), dim3(aa.tiles * B), dim3(NW * 64), lds, q.stream, aa);
 }
-template <bool TRANS, int CT>
-static void launch_agg(Seq& q, const AggArgs& a, int B) {
-    // (8 waves per 32-row tile, NW = 8: measured slower at DD, 9.5 vs 8.0 us per launch and 0.427 vs 0.407 ms per
-    // step -- the launch is bound by the L2 burst of V fragments, not by per-wave latency, and the extra waves only
-    // add barrier and reduction work.  64-row tiles: also slower, 9.1 us per launch, 0.412 vs 0.398 ms.)
-    if (agg_row_tile(B, a.n, a.C, TRANS) == 32) {
-        launch_agg_rt<TRANS, CT, 32, 4>(q, a, B);
-    } else launch_agg_rt<TRANS, CT, 16, 4>(q, a, B);     // (64-row tiles: measured slower at DD, 0.437 vs 0.417 ms)
-}
 
+// ct, rt: the panel dimensions agg_pick answered (CT = ceil(C / 16), the row tile).
+// (8 waves per 32-row tile, NW = 8: measured slower at DD, 9.5 vs 8.0 us per launch and 0.427 vs 0.407 ms per
+// step -- the launch is bound by the L2 burst of V fragments, not by per-wave latency, and the extra waves only
+// add barrier and reduction work.  64-row tiles in place of the 32-row ones: also slower, 9.1 us per launch, 0.412 vs
+// 0.398 ms per step.)
+// (64-row tiles in place of the 16-row ones: measured slower at DD, 0.437 vs 0.417 ms per step.)
 template <bool TRANS>
-static void dispatch_ct(Seq& q, const AggArgs& a, int B) {
-    switch (agg_ct(a.C)) {
-        case 1: launch_agg<TRANS, 1>(q, a, B); break;
-        case 2: launch_agg<TRANS, 2>(q, a, B); break;
-        case 3: launch_agg<TRANS, 3>(q, a, B); break;
-        case 4: launch_agg<TRANS, 4>(q, a, B); break;
-        case 5: launch_agg<TRANS, 5>(q, a, B); break;
-        case 6: launch_agg<TRANS, 6>(q, a, B); break;
-        case 7: launch_agg<TRANS, 7>(q, a, B); break;
-        default: launch_agg<TRANS, 8>(q, a, B); break;
+static void dispatch_ct(Seq& q, const AggArgs& a, int B, int ct, int rt) {
+    switch (ct * 100 + rt) {
+        case 116: launch_agg_rt<TRANS, 1, 16, 4>(q, a, B); break;
+        case 132: launch_agg_rt<TRANS, 1, 32, 4>(q, a, B); break;
+        case 216: launch_agg_rt<TRANS, 2, 16, 4>(q, a, B); break;
+        case 232: launch_agg_rt<TRANS, 2, 32, 4>(q, a, B); break;
+        case 316: launch_agg_rt<TRANS, 3, 16, 4>(q, a, B); break;
+        case 332: launch_agg_rt<TRANS, 3, 32, 4>(q, a, B); break;
+        case 416: launch_agg_rt<TRANS, 4, 16, 4>(q, a, B); break;
+        case 432: launch_agg_rt<TRANS, 4, 32, 4>(q, a, B); break;
+        case 516: launch_agg_rt<TRANS, 5, 16, 4>(q, a, B); break;
+        case 532: launch_agg_rt<TRANS, 5, 32, 4>(q, a, B); break;
+        case 616: launch_agg_rt<TRANS, 6, 16, 4>(q, a, B); break;
+        case 632: launch_agg_rt<TRANS, 6, 32, 4>(q, a, B); break;
+        case 716: launch_agg_rt<TRANS, 7, 16, 4>(q, a, B); break;
+        case 732: launch_agg_rt<TRANS, 7, 32, 4>(q, a, B); break;
+        case 816: launch_agg_rt<TRANS, 8, 16, 4>(q, a, B); break;
+        case 832: launch_agg_rt<TRANS, 8, 32, 4>(q, a, B); break;
+        default: break;
     }
 }
 
@@ -1073,13 +1172,7 @@ void adj_pack(Seq& q, const float* A, unsigned short* P, unsigned short* Pt, int
     q.check_launch("adj_pack");
 }
 int adj_pack_ld(int n) { return (n + 7) & ~7; }
-bool adj_pack_supported(int n, int C) {
-    const bool off = knobs().no_pack;      // ablation: fp32 adjacency passes everywhere
-    if (off) return false;
-    // worth it only for big levels; the bf16 panel of a 32-row tile must fit LDS beside the reduction area
-    return n >= 128 && C >= 1 && C <= AGGW_MAX_C &&
-           ((size_t)16 * (((n + 511) / 512) * 512 + 8) * 2 + 5 * 16 * 129 * 4 <= 156 * 1024);
-}
+bool adj_pack_supported(int n, int C) { return agg_pack_shape(n, C); }
 
 // k_split3: V [B, n, C] fp32 -> three bf16 planes hi, mid, lo with hi + mid + lo == V exactly, in the layout
 // the bf16 MFMA B-operand wants: Vs[b][plane][cb][k8][c][j] = plane(V[b][8*k8 + j][16*cb + c]), zero padded in k
@@ -1138,62 +1231,49 @@ static void fill_packed(AggArgs& a, const PackedAdj* pk, bool trans, const unsig
     a.vs_k8 = ((n + 31) / 32) * 4;
 }
 
-static bool agg_prefers_split_gemm(const float* A, const float* V, float* U, int B, int n, int C, int ldv, int ldu,
-                                  bool trans, float beta) {
-    if (C < 48) return false;                 // narrow operands: the pass is bound by reading A, the panel kernel's case
-    GemmDesc d{A, V, U, nullptr, n, C, n, n, ldv, ldu, (long)n * n, (long)n * ldv, (long)n * ldu, trans, false, 1.f, beta, 0};
-    return gemm_split_usable(d, B, 1);
-}
 // U[b] (ldu) = op(A[b]) V[b] (+ beta U[b]);  falls back to the generic GEMM for shapes the panel kernel
 // does not take (n not a multiple of 4, C > 128, unaligned A).  With `pk` (a packed copy of A from adj_pack) and a
 // scratch buffer `vs` (split3_elems) the bf16 path is taken when the device flag says A is bf16-exact.
 void aggregate(Seq& q, const float* A, const float* V, int ldv, float* U, int ldu, int B, int n, int C, bool trans,
                float beta, const PackedAdj* pk, unsigned short* vs, bool vs_ready) {
     if (!q.ok()) return;
-    const bool packed = pk && vs && adj_pack_supported(n, C);
-    const bool panel = aggregate_supported(A, n, C, trans);
-    const bool wide = packed && aggw_usable(pk, vs, B, n, C);
-    if (!packed && agg_prefers_split_gemm(A, V, U, B, n, C, ldv, ldu, trans, beta)) {
-        // a general (pooled, weighted) adjacency at a big batch: both operands are general fp32, which is the split-bf16
-        // GEMM's case — the fp32 panel kernel ran the 84-column level-1 passes of the ER shape at 30 TFLOP/s
-        bgemm(q, A, V, U, nullptr, B, n, C, n, n, ldv, ldu, (long)n * n, (long)n * ldv, (long)n * ldu, trans, false, 1.f,
-              beta, 0);
-        return;
-    }
+    const AggPick p = agg_pick(B, n, C, trans, pk && vs, false, (unsigned)(reinterpret_cast<uintptr_t>(A) & 15), beta);
     AggArgs a{};
     a.A = A; a.V = V; a.ldv = ldv; a.n = n; a.C = C; a.U = U; a.ldu = ldu; a.beta = beta;
-    if (wide) {
-        if (!vs_ready) split3(q, V, ldv, vs, B, n, C);
-        fill_packed(a, pk, trans, vs, n);
-        dispatch_wide(q, a, B);
-        q.check_launch("aggregate_wide");
-        // fp32 fallback for adjacency that is not bf16-exact, gated on the device flag (no host sync)
-        if (panel) {
-            AggArgs f{};
-            f.A = A; f.V = V; f.ldv = ldv; f.n = n; f.C = C; f.U = U; f.ldu = ldu; f.beta = beta;
-            f.run_if = pk->flag;
-            if (trans) dispatch_ct<true>(q, f, B); else dispatch_ct<false>(q, f, B);
+    switch (p.form) {
+        case DP_AGG_FORM_WIDE:
+        case DP_AGG_FORM_WIDE_DMA:
+            if (!vs_ready) split3(q, V, ldv, vs, B, n, C);
+            fill_packed(a, pk, trans, vs, n);
+            dispatch_wide(q, a, B, p.ct);
+            q.check_launch("aggregate_wide");
+            if (p.fallback == DP_AGG_FB_PANEL) {
+                AggArgs f{};
+                f.A = A; f.V = V; f.ldv = ldv; f.n = n; f.C = C; f.U = U; f.ldu = ldu; f.beta = beta;
+                f.run_if = pk->flag;
+                if (trans) dispatch_ct<true>(q, f, B, p.fb_ct, p.fb_rt); else dispatch_ct<false>(q, f, B, p.fb_ct, p.fb_rt);
+                q.check_launch("aggregate");
+            } else {
+                const int* keep = q.pred;
+                q.pred = pk->flag;
+                bgemm(q, A, V, U, nullptr, B, n, C, n, n, ldv, ldu, (long)n * n, (long)n * ldv, (long)n * ldu, trans, false,
+                      1.f, beta, 0);
+                q.pred = keep;
+            }
+            return;
+        case DP_AGG_FORM_PANEL_BF16:
+            if (!vs_ready) split3(q, V, ldv, vs, B, n, C);
+            fill_packed(a, pk, trans, vs, n);
+            [[fallthrough]];
+        case DP_AGG_FORM_PANEL_F32:
+            if (trans) dispatch_ct<true>(q, a, B, p.ct, p.rt); else dispatch_ct<false>(q, a, B, p.ct, p.rt);
             q.check_launch("aggregate");
-        } else {
-            const int* keep = q.pred;
-            q.pred = pk->flag;
+            return;
+        default:      // the GEMM forms: bgemm diverts to the split-bf16 kernel by the rule agg_pick asked
             bgemm(q, A, V, U, nullptr, B, n, C, n, n, ldv, ldu, (long)n * n, (long)n * ldv, (long)n * ldu, trans, false,
                   1.f, beta, 0);
-            q.pred = keep;
-        }
-        return;
+            return;
     }
-    if (!panel) {
-        bgemm(q, A, V, U, nullptr, B, n, C, n, n, ldv, ldu, (long)n * n, (long)n * ldv, (long)n * ldu, trans, false,
-              1.f, beta, 0);
-        return;
-    }
-    if (packed) {
-        if (!vs_ready) split3(q, V, ldv, vs, B, n, C);
-        fill_packed(a, pk, trans, vs, n);
-    }
-    if (trans) dispatch_ct<true>(q, a, B); else dispatch_ct<false>(q, a, B);
-    q.check_launch("aggregate");
 }
 
 // Fused forward GraphConv tail: y = l2norm(A V (+ P) + bias) per column group, written to yout, with the
@@ -1202,26 +1282,26 @@ bool aggregate_rownorm_fwd(Seq& q, const float* A, const float* V, int ldv, cons
                            RowGroups g, GroupPtrs yout, float* invn, float* part, int B, int n, int normalize,
                            int stats_mode, const PackedAdj* pk, unsigned short* vs, bool vs_ready) {
     const int C = g.c0[g.G - 1] + g.w[g.G - 1];
-    if (!aggregate_supported(A, n, C, false)) return false;
-    if (!(pk && vs && adj_pack_supported(n, C)) && agg_prefers_split_gemm(A, V, nullptr, B, n, C, ldv, C, false, 0.f))
-        return false;                          // (the caller's two-launch path takes the split GEMM in aggregate())
+    const AggPick p = agg_pick(B, n, C, false, pk && vs, true, (unsigned)(reinterpret_cast<uintptr_t>(A) & 15), 0.f);
+    if (p.declines) return false;
     if (!q.ok()) return true;
     AggArgs a{};
     a.A = A; a.V = V; a.ldv = ldv; a.n = n; a.C = C; a.U = nullptr;
     a.P = P; a.bias = bias; a.g = g; a.yout = yout; a.invn = invn; a.part = part;
     a.normalize = normalize; a.stats_mode = stats_mode;
-    const bool packed = pk && vs && adj_pack_supported(n, C);
-    if (packed && !vs_ready) split3(q, V, ldv, vs, B, n, C);
-    if (packed && aggw_usable(pk, vs, B, n, C)) {
+    if (p.packed && !vs_ready) split3(q, V, ldv, vs, B, n, C);
+    int ct = p.ct, rt = p.rt;
+    if (p.form == DP_AGG_FORM_WIDE || p.form == DP_AGG_FORM_WIDE_DMA) {
         AggArgs w = a;
         fill_packed(w, pk, false, vs, n);
-        dispatch_wide(q, w, B);
+        dispatch_wide(q, w, B, p.ct);
         q.check_launch("aggregate_wide_rownorm");
         a.run_if = pk->flag;               // fp32 fallback, runs only for adjacency that is not bf16-exact
-    } else if (packed) {
+        ct = p.fb_ct, rt = p.fb_rt;
+    } else if (p.form == DP_AGG_FORM_PANEL_BF16) {
         fill_packed(a, pk, false, vs, n);
     }
-    dispatch_ct<false>(q, a, B);
+    dispatch_ct<false>(q, a, B, ct, rt);
     q.check_launch("aggregate_rownorm_fwd");
     return true;
 }

@@ -473,6 +473,15 @@ int dp_adj_pack(const float* adj, void* packed, void* packed_t, int* flag, int B
     adj_pack(q, adj, (unsigned short*)packed, (unsigned short*)packed_t, flag, B, n, adj_pack_ld(n));
     return q.err;
 }
+int dp_adj_pack_zero(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, void* zero_p,
+                     size_t zero_bytes, void* stream) {
+    NOTNULL(adj); NOTNULL(packed); NOTNULL(packed_t); NOTNULL(flag); NOTNULL(zero_p);
+    NONNEG(B); NONNEG(n);
+    Seq q(STREAM(stream), nullptr, 0);
+    adj_pack(q, adj, (unsigned short*)packed, (unsigned short*)packed_t, flag, B, n, adj_pack_ld(n), false, zero_p,
+             zero_bytes);
+    return q.err;
+}
 size_t dp_adj_aggregate_packed_workspace_bytes(int B, int n, int C) {
     return split3_elems(B, n, C) * sizeof(unsigned short) + 512;
 }
@@ -488,6 +497,18 @@ int dp_adj_aggregate_packed(const float* adj, const void* packed, const void* pa
     PackedAdj pk{(const unsigned short*)packed, (const unsigned short*)packed_t, adj_pack_ld(n), flag};
     aggregate(q, adj, V, ldv, U, ldu, B, n, C, trans != 0, beta, &pk, vs, presplit != 0);
     return q.err;
+}
+
+int dp_adj_aggregate_plan(int B, int n, int C, int trans, int packed, int fused, int a_misalign, float beta,
+                          int* plan_out) {
+    NOTNULL(plan_out);
+    NONNEG(B); NONNEG(n); NONNEG(C);
+    DP_CHECK_ARG(a_misalign >= 0 && a_misalign <= 15, "a_misalign=%d is not the low four bits of an address", a_misalign);
+    const AggPick p = agg_pick(B, n, C, trans != 0, packed != 0, fused != 0, (unsigned)a_misalign, beta);
+    const int out[DP_AGG_PLAN_INTS] = {p.form, p.ct, p.rt, p.tiles, p.grid, (int)p.lds, p.fallback, p.fb_ct, p.fb_rt,
+                                       p.fb_tiles, p.fb_grid, (int)p.fb_lds, p.packed ? 1 : 0, p.declines ? 1 : 0};
+    for (int i = 0; i < DP_AGG_PLAN_INTS; ++i) plan_out[i] = out[i];
+    return DP_OK;
 }
 
 size_t dp_gcn_layer_workspace_bytes(int B, int n, int Fin, int Fout) {
@@ -708,6 +729,39 @@ int dp_rownorm_fwd(const float* U, int ldu, const float* P, const dp_row_groups*
     Seq q(STREAM(stream), nullptr, 0);
     rownorm_fwd(q, U, ldu, P, gcptrs(*g, bias), row_groups_of(*g), gptrs(*g, yout), invn, part, rows, normalize != 0,
                 stats_mode);
+    return q.err;
+}
+
+int dp_adj_aggregate_rownorm(const float* adj, const void* packed, const void* packed_t, const int* flag, const float* V,
+                             int ldv, const float* P, const dp_row_groups* g, const dp_group_ptrs* bias,
+                             const dp_group_ptrs* yout, float* invn, float* part, int B, int n, int normalize,
+                             int stats_mode, int presplit, void* workspace, size_t workspace_bytes, void* stream) {
+    ROWS_OK(g);
+    NOTNULL(adj); NOTNULL(V);
+    GROUP_PTRS(g, yout, true);
+    if (bias) GROUP_PTRS(g, bias, false);
+    NONNEG(B); NONNEG(n);
+    const int Cj = joint_width(*g);
+    // (the tail kernels take the groups as one run of columns: the wide forms norm every column below c0[1] with group 0)
+    DP_CHECK_ARG(g->c0[0] == 0 && (g->G == 1 || g->c0[1] == g->w[0]),
+                 "the groups must cover the joint width without a gap (c0 = %d, %d; w[0] = %d)", g->c0[0],
+                 g->G == 2 ? g->c0[1] : 0, g->w[0]);
+    DP_CHECK_ARG(ldv >= Cj, "ldv=%d smaller than the joint width %d", ldv, Cj);
+    DP_CHECK_ARG(stats_mode >= 0 && stats_mode <= 2, "stats_mode=%d (0 none, 1 of relu(y), 2 of y)", stats_mode);
+    DP_CHECK_ARG(!stats_mode || part, "part is NULL but stats_mode=%d", stats_mode);
+    const bool any = packed || packed_t || flag || workspace;
+    DP_CHECK_ARG(!any || (packed && packed_t && flag && workspace),
+                 "packed, packed_t, flag and workspace are given together or not at all");
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    PackedAdj pk{(const unsigned short*)packed, (const unsigned short*)packed_t, adj_pack_ld(n), flag};
+    unsigned short* vs = nullptr;
+    if (any) {
+        vs = q.alloc<unsigned short>(split3_elems(B, n, Cj));
+        if (q.err) return q.err;
+    }
+    if (!aggregate_rownorm_fwd(q, adj, V, ldv, P, gcptrs(*g, bias), row_groups_of(*g), gptrs(*g, yout), invn, part, B, n,
+                               normalize != 0, stats_mode, any ? &pk : nullptr, vs, presplit != 0))
+        return DP_AGG_DECLINED;
     return q.err;
 }
 

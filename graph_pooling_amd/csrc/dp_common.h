@@ -423,6 +423,21 @@ bool aggregate_rownorm_fwd(Seq& q, const float* A, const float* V, int ldv, cons
                            int stats_mode, const PackedAdj* pk = nullptr, unsigned short* vs = nullptr,
                            bool vs_ready = false);
 bool aggregate_packed_usable(const float* A, int n, int C);
+// What aggregate() / aggregate_rownorm_fwd() launch for a shape (dp_agg.hip: agg_pick decides it, both launchers switch
+// over its answer and dp_adj_aggregate_plan, diffpool_hip.h, reports it).  Host only.
+struct AggPick {
+    int form;            // DP_AGG_FORM_*
+    int ct;              // column tiles of the kernel's CT template argument (GEMM forms: 0)
+    int rt;              // panel forms: the row tile (16 / 32); wide forms: waves per workgroup
+    int tiles, grid;     // row tiles per graph, workgroups
+    size_t lds;          // dynamic LDS bytes of the launch
+    int fallback;        // DP_AGG_FB_*: the launch queued behind a wide form, gated on the pack flag
+    int fb_ct, fb_rt, fb_tiles, fb_grid;   // DP_AGG_FB_PANEL: the predicated panel launch
+    size_t fb_lds;
+    bool packed;         // the packed operand is used (V is split into its three bf16 planes): the bf16 and wide forms
+    bool declines;       // fused entry only: returns false, nothing launched (form = what aggregate() then takes)
+};
+AggPick agg_pick(int B, int n, int C, bool trans, bool packed, bool fused, unsigned a_misalign, float beta);
 
 // (dp_small.hip) one-workgroup-per-graph GCN layers of a pooled level (n <= 64)
 bool small_level_supported(int B, int n, int din, int dout);

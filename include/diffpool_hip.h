@@ -172,12 +172,40 @@ int dp_adj_aggregate(const float* adj, const float* V, int ldv, float* U, int ld
 int dp_adj_pack_ld(int n);
 size_t dp_adj_pack_bytes(int B, int n);            /* bytes of ONE packed copy */
 int dp_adj_pack(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, void* stream);
+/* dp_adj_pack as the encoder plans call it, with the side job: the pack launch's workgroups also clear zero_bytes bytes
+ * at zero_p between them (a region that is not 16-byte aligned or no multiple of 16 bytes gets a launch of its own).
+ * zero_p must not be NULL; zero_bytes = 0 is allowed and clears nothing. */
+int dp_adj_pack_zero(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, void* zero_p,
+                     size_t zero_bytes, void* stream);
 size_t dp_adj_aggregate_packed_workspace_bytes(int B, int n, int C);
 /* presplit != 0: the workspace already holds the 3-plane split of this V from an earlier call (skips the split
  * pass — the encoder plan gets the split from V's producer kernel the same way). */
 int dp_adj_aggregate_packed(const float* adj, const void* packed, const void* packed_t, const int* flag,
                             const float* V, int ldv, float* U, int ldu, int B, int n, int C, int trans, float beta,
                             int presplit, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dp_adj_aggregate_plan: what the two aggregation launchers (dp_adj_aggregate[_packed], dp_adj_aggregate_rownorm and
+ * the encoder plans) launch for a shape, answered by the one host function both decide with.  Host only: no GPU call.
+ * packed != 0: a packed adjacency and a workspace are given; fused != 0: the GraphConv-tail entry (trans and beta are
+ * ignored); a_misalign: the low four bits of adj's address (0: 16-byte aligned).
+ * plan_out[DP_AGG_PLAN_INTS] = { form (DP_AGG_FORM_*), CT (the kernel's column tiles; 0 for the GEMM forms), RT (panel
+ * forms: rows per workgroup, 16 / 32; wide forms: waves per workgroup, 4 / 8), row tiles per graph, workgroups, dynamic
+ * LDS bytes, fallback (DP_AGG_FB_*: the launch queued behind a wide form that runs only when the pack flag is set), the
+ * fallback panel launch's CT, RT, row tiles, workgroups and LDS bytes (0 unless DP_AGG_FB_PANEL), split (1: V is split
+ * into its three bf16 planes — the panel-bf16 and wide forms; 0 for every other form, also when a packed operand was given), declines (fused only: 1 = the entry launches nothing and the caller takes `form` through
+ * dp_adj_aggregate[_packed]) }.  The tiles of the GEMM forms are dp_bgemm_plan's to report. */
+#define DP_AGG_FORM_PANEL_F32 0       /* k_aggregate, fp32 loop */
+#define DP_AGG_FORM_PANEL_BF16 1      /* k_aggregate on the packed operand (fp32 loop in the same launch if the flag is set) */
+#define DP_AGG_FORM_WIDE 2            /* k_aggregate_wide: 128 rows x all columns, C <= 128 */
+#define DP_AGG_FORM_WIDE_DMA 3        /* k_aggregate_wide_dma: 128 < C <= 320 */
+#define DP_AGG_FORM_GEMM_F32 4        /* dp_bgemm_f32's kernel */
+#define DP_AGG_FORM_GEMM_SPLIT_BF16 5 /* dp_bgemm_split_bf16's kernel */
+#define DP_AGG_FB_NONE 0
+#define DP_AGG_FB_PANEL 1
+#define DP_AGG_FB_GEMM 2
+#define DP_AGG_PLAN_INTS 14
+int dp_adj_aggregate_plan(int B, int n, int C, int trans, int packed, int fused, int a_misalign, float beta,
+                          int* plan_out);
 
 /* ------------------------------------------------------------------ A1  GraphConv
  * y = l2norm((adj @ x [+ x]) @ W + b)   — GraphConv.forward, encoders.py:962-974.
@@ -305,6 +333,20 @@ int dp_rowop_plan(int op, const dp_row_groups* g, int n, int B, int Bs, int flag
 int dp_rownorm_fwd(const float* U, int ldu, const float* P, const dp_row_groups* g, const dp_group_ptrs* bias,
                    const dp_group_ptrs* yout, float* invn, float* part, long rows, int normalize, int stats_mode,
                    void* stream);
+/* The same tail fused behind the aggregation, as the encoder plans call it: u = adj[b] V[b] (+ P) (+ bias_g) over the
+ * joint width C = c0[G-1] + w[G-1] of V [B, n, C] (ldv; P has V's layout), one launch (plus the flag-gated fallback
+ * behind a wide form).  packed / packed_t / flag / workspace (dp_adj_aggregate_packed_workspace_bytes) are given
+ * together or not at all; presplit as in dp_adj_aggregate_packed.  Returns DP_AGG_DECLINED for the shapes
+ * dp_adj_aggregate_plan reports as declined: not an error — the arguments were accepted, nothing was launched and no
+ * error string is set; the caller then runs dp_adj_aggregate[_packed] + dp_rownorm_fwd.  The value is negative so that it
+ * can be neither DP_OK nor the hipError_t of a failed launch (> 0), and it is no DP_ERR_* code.
+ * The groups must cover the joint width without a gap (c0[0] = 0, c0[1] = w[0]), as the encoder's do. */
+#define DP_AGG_DECLINED (-5)
+int dp_adj_aggregate_rownorm(const float* adj, const void* packed, const void* packed_t, const int* flag,
+                             const float* V, int ldv, const float* P, const dp_row_groups* g,
+                             const dp_group_ptrs* bias, const dp_group_ptrs* yout, float* invn, float* part, int B, int n,
+                             int normalize, int stats_mode, int presplit, void* workspace, size_t workspace_bytes,
+                             void* stream);
 /* x = (relu?(y) - mu_n) * rstd_n per node index n and group, the statistics Chan-combined from part [Bs, n, G, 2]
  * (Bs = 0: B; Bs > B: the statistics span more graphs than the B normalised here); stats [n, G, 2] receives (mu, rstd).
  * part = NULL: no BatchNorm (ReLU only), stats unused. */

@@ -403,6 +403,8 @@ def rownorm_fwd_math(c, d, dt, drop=None):
             un = torch.cat([u, d["Ug"][1 - i].to(dt)[:, :1]], 1)
         if drop == "quad":
             un = _quad_again(u)
+        if drop == "dup":                 # a clamped duplicate of the last column counted in the norm (agg_cases.py)
+            un = torch.cat([u, u[:, -1:]], 1)
         ss = (un * un).sum(1, keepdim=True)
         inv = 1.0 / ss.sqrt().clamp_min(L2_EPS) if o["normalize"] else torch.ones_like(ss)
         y = u * inv

@@ -117,6 +117,17 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     assert lib.dp_colsum_batched(None, 8, 0, 4, 8, None, 8, 1, 1, None) == -1 and b"NULL" in lib.dp_last_error_string()
     rc = lib.dp_masked_max_fwd(1, 4, None, 1, 4, 1, 0, 3, 4, None)
     assert rc == -1 and b"B=0" in lib.dp_last_error_string()
+    # the aggregation's plan query (host only) and its fused pass-through entry
+    for name in ("dp_adj_aggregate_plan", "dp_adj_aggregate_rownorm", "dp_adj_pack_zero"):
+        assert name in _lib.EXPORTED_SYMBOLS
+    plan = (C.c_int * _lib.AGG_PLAN_INTS)()
+    assert lib.dp_adj_aggregate_plan(20, 500, 40, 0, 0, 0, 0, 0.0, plan) == 0
+    assert tuple(plan)[:6] == (_lib.AGG_FORM_PANEL_F32, 3, 32, 16, 320, 66048)
+    assert lib.dp_adj_aggregate_plan(20, 500, 40, 0, 0, 0, 0, 0.0, None) == -1 and b"NULL" in lib.dp_last_error_string()
+    yp = _lib.GroupPtrs()
+    rc = lib.dp_adj_aggregate_rownorm(None, None, None, None, None, 16, None, C.byref(g), None, C.byref(yp), None, None,
+                                      1, 4, 1, 0, 0, None, 0, None)
+    assert rc == -1 and b"NULL" in lib.dp_last_error_string()
     cfg = _lib.EncoderCfg()
     assert lib.dp_encoder_save_bytes(C.byref(cfg)) == 0          # invalid cfg -> 0 + message
     assert b"must be positive" in lib.dp_last_error_string()
