@@ -484,6 +484,7 @@ struct Level0Fwd {
     int bn, train, do_max, mask_readout;
     const float* A;                // [B, N, N] fp32 as delivered
     const float* x0[2];            // per stack: [B, N, st[g].dims[0]] contiguous
+    int x_shared;                  // both stacks read the SAME input tensor (x0[0] == x0[1], equal widths): staged once
     const int* num_nodes;          // int32[B] or null
     const float* params;
     L0Stack st[2];
@@ -526,6 +527,7 @@ struct Level0Bwd {
     int B, N, L, G, bn;
     const float* A;                // fp32 adjacency (only read when it is not bf16-exact)
     const float* x0[2];
+    int x_shared;                  // as Level0Fwd
     const float* params;
     L0Stack st[2];
     const float* Y[DP_MAX_LAYERS];

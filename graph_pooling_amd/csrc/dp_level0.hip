@@ -170,17 +170,27 @@ __device__ inline void l0_mma(const float* A, int lda, const float* B, int ldb, 
 struct L0Epoch {
     int graph;
 };
+// A crossing is two halves, so that work the consumer of the barrier does not need can run between them (the arrival
+// atomic and the release poll cross the XCD boundary through memory: 3-6 k cycles with all blocks doing equal work):
+//   l0_arrive  drains this thread's stores, joins the workgroup, thread 0 adds the arrival;
+//   l0_wait    thread 0 polls (bounded), the workgroup joins again.
+// Between the two: no other graph barrier and no tagged-entry poll; nothing another workgroup writes in this launch is
+// read; LDS the phase behind the wait overwrites or reads is left alone unless an lds_barrier separates the two; global
+// stores issued there are published by the NEXT arrive, so their first reader in another workgroup must sit behind a
+// later barrier (or the kernel boundary).  Thread 0 does its share of that work first and polls afterwards.
 template <typename Args>
-__device__ inline bool l0_barrier(const Args& a, int b, int* sflag /*LDS: [0] ok, [1] failed (sticky)*/, L0Epoch& ep) {
+__device__ __forceinline__ void l0_arrive(const Args& a, int b, int* /*sflag: the wait's*/, L0Epoch& ep) {
     ep.graph += 1;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's write-through stores are acknowledged
     __syncthreads();
+    if (threadIdx.x == 0) ag_add(a.f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE, 1);
+}
+template <typename Args>
+__device__ inline bool l0_wait(const Args& a, int b, int* sflag /*LDS: [0] ok, [1] failed (sticky)*/, const L0Epoch& ep) {
     if (threadIdx.x == 0) {
         int ok = sflag[1] ? 0 : 1;
-        int* gc = a.f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE;
-        int* pollw = gc;
+        int* pollw = a.f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE;
         const int target = ep.graph * a.T + a.target_bias;
-        ag_add(gc, 1);
         if (ok) {
             int it = 0;
             while (ag_ld(pollw) < target) {
@@ -198,6 +208,11 @@ __device__ inline bool l0_barrier(const Args& a, int b, int* sflag /*LDS: [0] ok
     }
     __syncthreads();
     return sflag[0] != 0;
+}
+template <typename Args>
+__device__ inline bool l0_barrier(const Args& a, int b, int* sflag, L0Epoch& ep) {
+    l0_arrive(a, b, sflag, ep);
+    return l0_wait(a, b, sflag, ep);
 }
 
 // ---- BatchNorm exchange without a barrier: tagged entries (the scheme of RCCL's LL protocol).
@@ -562,7 +577,8 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
         l0_copy_in<4>(X0s0, f.x0[0] + ((long)b * N + r0) * din0_0, nrows * din0_0, RB * din0_0);
         l0_copy_in<4>(W0s0, f.params + f.st[0].w_off[0], din0_0 * f.st[0].dims[1]);
         if (G == 2) {
-            l0_copy_in<4>(X0s1, f.x0[1] + ((long)b * N + r0) * din0_1, nrows * din0_1, RB * din0_1);
+            // (one tensor for both stacks — the usual call: the second product reads the first copy)
+            if (!f.x_shared) l0_copy_in<4>(X0s1, f.x0[1] + ((long)b * N + r0) * din0_1, nrows * din0_1, RB * din0_1);
             l0_copy_in<4>(W0s1, f.params + f.st[1].w_off[0], din0_1 * f.st[1].dims[1]);
         }
         // biases: one 64-float slot per (layer, stack), zeros where a layer has none
@@ -653,7 +669,8 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
     int ct = f.st[0].dims[1] + (G == 2 ? f.st[1].dims[1] : 0);
     for (int g = 0; g < G; ++g) {
         const int dout = f.st[g].dims[1], c0 = g ? f.st[0].dims[1] : 0;
-        l0_mma<false, false>(g ? X0s1 : X0s0, g ? din0_1 : din0_0, g ? W0s1 : W0s0, dout, RB, dout, g ? din0_1 : din0_0,
+        const float* xs = g && !f.x_shared ? X0s1 : X0s0;
+        l0_mma<false, false>(xs, g ? din0_1 : din0_0, g ? W0s1 : W0s0, dout, RB, dout, g ? din0_1 : din0_0,
                              [&](int r, int c, float v) { PT[r * ct + c0 + c] = v; }, g * 3);
     }
     lds_barrier();
@@ -1224,18 +1241,22 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
         }
         lds_barrier();
         L0B_STAMP(1);
-        l0_mma<false, false>(SL, K, DXN, D, RB, D, K, [&](int r, int j, float v) { DZ0[r * D + j] += v; });
-        l0_mma<false, true>(ZL, D, DXN, D, RB, K, D, [&](int r, int i, float v) { DS[r * K + i] = v; }, 2);
-        l0_mma<false, true>(SL, K, DAN, K, RB, K, K, [&](int r, int i, float v) { VL[r * K + i] = v; }, 4);
-        l0_mma<false, false>(TL, K, DAN, K, RB, K, K, [&](int r, int i, float v) { DS2[r * K + i] = v; }, 6);
+        // only V feeds the exchange: it goes first, and the other three products (first read behind the A V pass) run
+        // under the barrier's latency
+        l0_mma<false, true>(SL, K, DAN, K, RB, K, K, [&](int r, int i, float v) { VL[r * K + i] = v; });
         lds_barrier();
-        L0B_STAMP(2);
         l0_write_split(vs_wr(0, CTk), VL, K, CTk, a.K8, k8_0, nk8, nrows);
+        l0_arrive(a, b, sflag, ep);
+        l0_mma<false, false>(SL, K, DXN, D, RB, D, K, [&](int r, int j, float v) { DZ0[r * D + j] += v; });
+        l0_mma<false, true>(ZL, D, DXN, D, RB, K, D, [&](int r, int i, float v) { DS[r * K + i] = v; }, 3);
+        l0_mma<false, false>(TL, K, DAN, K, RB, K, K, [&](int r, int i, float v) { DS2[r * K + i] = v; }, 6);
+        lds_barrier();                                     // (the products' inputs are overwritten by the rows below)
+        L0B_STAMP(2);
         {
-            // my rows of the packed A: asked for in front of the barrier, written over the staged rows behind it
+            // my rows of the packed A: asked for under the barrier, written over the staged rows behind it
             L0RowStage<MI> q;
             l0_stage_issue<MI>(q, f.pkA + ((long)b * N + r0) * f.pk_ld, f.pk_ld, nrows, 0);
-            ok = l0_barrier(a, b, sflag, ep) && ok;
+            ok = l0_wait(a, b, sflag, ep) && ok;
             l0_stage_commit<MI>(q, Alds, a.ldp, f.pk_ld, nrows, 0);
             const int segs = (a.steps * 32 + 511) / 512;
             for (int seg = 1; seg < segs; ++seg) {
@@ -1440,6 +1461,11 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
         }
         lds_barrier();
         L0B_STAMP(8 + 8 * (L - 1 - l));
+        // dU is all the exchange needs: split and arrive now.  The bias sums (parameter gradients: nobody reads them before
+        // the final combine) and the staging of the dW operands run under the barrier's latency; the A^T dU pass
+        // overwrites dU only behind the wait.
+        l0_write_split(vs_wr(pass, CTt), DU, ct, CTt, a.K8, k8_0, nk8, nrows);
+        l0_arrive(a, b, sflag, ep);
         // bias gradients: column sums of dU over my rows
         {
             // eight row groups in parallel, added in row order
@@ -1461,7 +1487,6 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
                 SB[c] = t;
             }
         }
-        l0_write_split(vs_wr(pass, CTt), DU, ct, CTt, a.K8, k8_0, nk8, nrows);
         lds_barrier();
         if (a.cb[0][l] >= 0) l0_put_compact(gp, a.cb[0][l], EXT + RB * 4, w0);
         if (G == 2 && a.cb[1][l] >= 0) l0_put_compact(gp, a.cb[1][l], EXT + RB * 4 + w0, w1);
@@ -1470,7 +1495,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
         // (layer 0: the second stack's input rows do not fit beside the first's — they go to the adjacency block's bytes
         // once the last pass is over)
         float* XIN0 = EXT + RB * 4 + 9 * ((ct + 3) & ~3);
-        float* XIN1 = l > 0 ? XIN0 + RB * d0 : RA;
+        float* XIN1 = l > 0 ? XIN0 + RB * d0 : (f.x_shared ? XIN0 : RA);      // (one input tensor for both stacks: one copy)
         float* W0 = XIN1 + RB * d1;                        // (l > 0 only)
         float* W1 = W0 + ((d0 * w0 + 3) & ~3);
         {
@@ -1512,7 +1537,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
         if (!have_at) {
             L0RowStage<MI> q;
             l0_stage_issue<MI>(q, f.pkAt + ((long)b * N + r0) * f.pk_ld, f.pk_ld, nrows, 0);
-            ok = l0_barrier(a, b, sflag, ep) && ok;
+            ok = l0_wait(a, b, sflag, ep) && ok;
             l0_stage_commit<MI>(q, Alds, a.ldp, f.pk_ld, nrows, 0);
             const int segs = (a.steps * 32 + 511) / 512;
             for (int seg = 1; seg < segs; ++seg) {
@@ -1522,7 +1547,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
             have_at = true;
             lds_barrier();
         } else {
-            ok = l0_barrier(a, b, sflag, ep) && ok;
+            ok = l0_wait(a, b, sflag, ep) && ok;
         }
         L0B_STAMP(10 + 8 * (L - 1 - l));
         // ---- G = A^T dU (my rows), summed in place into the first reduce slot
@@ -1538,7 +1563,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
         }
         lds_barrier();
         L0B_STAMP(12 + 8 * (L - 1 - l));
-        if (l == 0 && G == 2) {
+        if (l == 0 && G == 2 && !f.x_shared) {
             const L0Copy jx[1] = {{XIN1, f.x0[1] + ((long)b * N + r0) * d1, nrows * d1, RB * d1}};
             l0_copy_many<1, 4>(jx);
             lds_barrier();

@@ -1021,6 +1021,7 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
             f.A = adj;
             f.x0[0] = x;
             f.x0[1] = assign_x;
+            f.x_shared = f.G == 2 && x == assign_x && f.st[0].dims[0] == f.st[1].dims[0];
             f.num_nodes = num_nodes;
             f.params = params;
             for (int l = 0; l < li.L; ++l) {
@@ -1291,6 +1292,7 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
             f.A = adj;
             f.x0[0] = x;
             f.x0[1] = assign_x;
+            f.x_shared = f.G == 2 && x == assign_x && f.st[0].dims[0] == f.st[1].dims[0];
             f.params = params;
             for (int l = 0; l < li.L; ++l) {
                 f.Y[l] = lv.layer[l].Y;

@@ -15,12 +15,12 @@ torch.cuda.synchronize()
 buf = (C.c_ulonglong * 192)()
 lib.dp_debug_l0b_stamps.restype = C.c_int
 assert lib.dp_debug_l0b_stamps(buf) == 0
-names = {1: "rows, dX', dA', dZe staged + sync", 2: "4 pooling products + sync", 3: "V split, graph barrier, A rows in LDS",
+names = {1: "rows, dX', dA', dZe staged + sync", 2: "V product, split, arrive, 3 products + sync", 3: "A rows asked, barrier wait, A rows in LDS",
          4: "A V aggregate + sync", 5: "reduce + softmax bwd + sync", 6: "dWp, dbp, dZa (+ stores)"}
 for i in range(3):
     o = 8 + 8 * i
-    names.update({o: f"layer {2 - i}: rownorm bwd + sync", o + 1: f"layer {2 - i}: bias sums, split, x_in / W staged",
-                  o + 2: f"layer {2 - i}: graph barrier (+ A^T rows)", o + 3: f"layer {2 - i}: A^T dU aggregate + sync",
+    names.update({o: f"layer {2 - i}: rownorm bwd + sync", o + 1: f"layer {2 - i}: split, arrive, bias sums, x_in / W staged",
+                  o + 2: f"layer {2 - i}: barrier wait (+ A^T rows)", o + 3: f"layer {2 - i}: A^T dU aggregate + sync",
                   o + 4: f"layer {2 - i}: reduce to G + sync", o + 5: f"layer {2 - i}: dW, dx_in + sync",
                   o + 6: f"layer {2 - i}: dW stored, BN partials", o + 7: f"layer {2 - i}: exchange (polled at the next phase) / sync"})
 names.update({40: "graph barrier (gradients)", 41: "combine + sync"})
