@@ -120,6 +120,7 @@ _PROTOS = {
     "dp_device_error_describe": (C.c_char_p, [_I]),
     "dp_profile_level0": (_I, [_I]),
     "dp_profile_level0_read": (_I, [_I, C.POINTER(C.c_double), C.POINTER(_I)]),
+    "dp_level0_bwd_symmetric": (_I, [C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I)]),
     "dp_sizeof_encoder_cfg": (_Z, []),
     "dp_bgemm_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _I, _I, _F, _F, _I, _P]),
     "dp_bgemm_split_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _I, _I, _F, _P]),
@@ -272,6 +273,15 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().dp_last_error_string().decode("utf-8", "replace")
         raise RuntimeError(f"{what or 'libdiffpool_hip'} failed (code {rc}): {msg}")
+
+
+def level0_bwd_symmetric():
+    """(verdicts, rows per workgroup) of the last persistent level-0 backward on the current device: per graph 1 where it
+    took the symmetric-adjacency short form (dp_level0_bwd_symmetric; synchronises the device).  ([], 0) when no such
+    launch has run."""
+    out, n, rb = (C.c_int * 64)(), C.c_int(0), C.c_int(0)
+    check(load().dp_level0_bwd_symmetric(out, 64, C.byref(n), C.byref(rb)), "dp_level0_bwd_symmetric")
+    return list(out[:n.value]), rb.value
 
 
 def ptr(t):

@@ -52,8 +52,10 @@ const Knobs& knobs() {
     return k;
 }
 
-// ---- device-side failure word: one pinned, device-mapped host int per device ordinal (diffpool_hip.h)
+// ---- device-side failure word: one pinned, device-mapped host int per device ordinal (diffpool_hip.h); the same block
+// carries, 64 ints further on, what the last persistent level-0 backward reports (level0_verdict_block)
 namespace {
+constexpr int DEV_BLOCK_INTS = 64 + 1 + 64 + 1, DEV_VERDICT_OFF = 64;
 struct DevErrSlot {
     std::once_flag once;
     int* host = nullptr;
@@ -66,8 +68,8 @@ DevErrSlot* dev_err_slot() {
     DevErrSlot& s = g_dev_err[d];
     std::call_once(s.once, [&s] {
         void* h = nullptr;
-        if (hipHostMalloc(&h, 64, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); return; }
-        memset(h, 0, 64);
+        if (hipHostMalloc(&h, DEV_BLOCK_INTS * sizeof(int), hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); return; }
+        memset(h, 0, DEV_BLOCK_INTS * sizeof(int));
         void* dv = nullptr;
         if (hipHostGetDevicePointer(&dv, h, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(h); return; }
         s.host = (int*)h;
@@ -80,10 +82,32 @@ int* device_error_word() {
     DevErrSlot* s = dev_err_slot();
     return s ? s->dev : nullptr;
 }
+int* level0_verdict_block() {
+    DevErrSlot* s = dev_err_slot();
+    return s ? s->dev + DEV_VERDICT_OFF : nullptr;
+}
 int device_error_take(bool clear) {
     DevErrSlot* s = dev_err_slot();
     if (!s) return 0;
     return clear ? __atomic_exchange_n(s->host, 0, __ATOMIC_ACQ_REL) : __atomic_load_n(s->host, __ATOMIC_ACQUIRE);
+}
+static int level0_verdicts_read(int* verdicts, int capacity, int* count, int* rows_per_block) {
+    DevErrSlot* s = dev_err_slot();
+    *count = 0;
+    if (rows_per_block) *rows_per_block = 0;
+    if (!s) return DP_OK;                      // no device: nothing ever ran
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        set_error("dp_level0_bwd_symmetric: hipDeviceSynchronize: %s", hipGetErrorString(e));
+        return (int)e;
+    }
+    const volatile int* v = s->host + DEV_VERDICT_OFF;
+    int n = v[0];
+    n = n < 0 ? 0 : (n > 64 ? 64 : n);
+    for (int b = 0; b < n && b < capacity; ++b) verdicts[b] = v[1 + b];
+    *count = n;
+    if (rows_per_block) *rows_per_block = n ? v[65] : 0;
+    return DP_OK;
 }
 static const char* device_error_text(int mask) {
     if ((mask & DP_DEVERR_BARRIER) && (mask & DP_DEVERR_NONFINITE_GRAD))
@@ -340,6 +364,11 @@ int dp_version(void) { return DP_VERSION; }
 const char* dp_last_error_string(void) { return dp::last_error(); }
 int dp_device_error(int clear) { return device_error_take(clear != 0); }
 const char* dp_device_error_describe(int mask) { return device_error_text(mask); }
+int dp_level0_bwd_symmetric(int* verdicts, int capacity, int* count, int* rows_per_block) {
+    NOTNULL(count);
+    DP_CHECK_ARG(capacity >= 0 && (capacity == 0 || verdicts != nullptr), "verdicts is NULL with capacity=%d", capacity);
+    return level0_verdicts_read(verdicts, capacity, count, rows_per_block);
+}
 #define DEVICE_GATE(name)                                     \
     do {                                                      \
         const int gate_rc_ = device_error_gate(name);         \

@@ -28,6 +28,10 @@ const char* last_error();
 // Device-visible pointer to the current device's error word (pinned, mapped host memory; nullptr when it could not be
 // set up — kernels test for null), and the host-side read.  Kernels raise a bit with dev_err_raise().
 int* device_error_word();
+// 1 + 64 + 1 ints in the same per-device block: [0] = graphs, [1 + b] = 1 when the LAST persistent level-0 backward on
+// the device took the symmetric short form for graph b, [65] = its rows per workgroup (dp_level0_bwd_symmetric reads
+// them back); null without a device
+int* level0_verdict_block();
 int device_error_take(bool clear);            // DP_DEVERR_* mask of the current device
 int device_error_gate(const char* entry);     // DP_OK, or DP_ERR_DEVICE (+ message, word cleared) when a bit is pending
 #ifdef __HIPCC__
@@ -510,6 +514,7 @@ struct Level0Fwd {
     unsigned short *pkA, *pkAt;
     int pk_ld;
     int* pk_flag;                  // 256-byte block: word 0 = "some entry is not bf16-exact", rest zero
+    int* pk_sym;                   // 64 ints, written by the launch: [b] = graph b is bf16-exact AND A == A^T bit for bit
     // exchange scratch (workspace)
     unsigned short* vs;            // level0_vs_elems(): the 3-plane split operand of every aggregation pass (write-once regions)
     float* part;                   // level0_part_floats(): [L - 1][B, N, G, 2]
@@ -547,6 +552,7 @@ struct Level0Bwd {
     const unsigned short *pkA, *pkAt;
     int pk_ld;
     const int* pk_flag;
+    const int* pk_sym;             // the forward's per-graph "symmetric" verdicts (Level0Fwd::pk_sym)
     float* slabs;                  // slab row of graph 0 (flat parameter offsets); graphs are slab_gstride floats apart
     long slab_gstride;
     unsigned short* vs;            // level0_bwd_vs_elems()

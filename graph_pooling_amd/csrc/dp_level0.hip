@@ -75,7 +75,8 @@ constexpr int L0_SPIN_LIMIT = 1 << 22;
 
 // barrier block (ints; every word that is polled or added to sits on a 64-byte line of its own)
 constexpr int BAR_GCOUNT = 0, BAR_DONE = 32, BAR_GFLAG = 48, BAR_ERR = 64, BAR_SEQ = 96, BAR_GRAPH0 = 128;
-constexpr int BAR_GSTRIDE = 48;       // per graph: +0 count, +16 generation, +32 "adjacency not bf16-exact"
+constexpr int BAR_GSTRIDE = 48;       // per graph: +0 count, +16 generation, +32 "adjacency not bf16-exact", +33 "A != A^T"
+constexpr int BAR_G_INEXACT = 32, BAR_G_ASYM = 33;      // (set once, read behind a barrier: they share a line)
 
 // ---- write-through / L1-bypassing access to what other workgroups of this launch write or read
 __device__ __forceinline__ int ag_ld(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -515,6 +516,35 @@ __device__ __forceinline__ void l0_stage_commit(const L0RowStage<MI>& s, unsigne
         if (c8 * 8 + 8 <= ldp) *reinterpret_cast<u32x4*>(Alds + row * ldp + c8 * 8) = v;
     }
 }
+// The commit of the forward's A^T rows, which land on the block's own rows of A: the 16 bytes about to be overwritten
+// are A[i][k .. k + 8), the incoming quad is A^T[i][k .. k + 8) — returns whether this thread saw any bit differ (valid
+// rows, columns inside `ld`; each thread reads exactly the bytes it then writes).  A graph none of whose blocks sees a
+// difference has A == A^T bit for bit.
+template <int MI>
+__device__ __forceinline__ bool l0_stage_commit_cmp(const L0RowStage<MI>& s, unsigned short* Alds, int ldp, int ld, int nrows,
+                                                    int seg) {
+    int tq = threadIdx.x;
+    asm volatile("" : "+v"(tq));
+    const int tr = tq >> 6;
+    tq &= 63;
+    const int c8 = seg * 64 + tq;
+    unsigned diff = 0u;
+#pragma unroll
+    for (int u = 0; u < L0RowStage<MI>::NQ; ++u) {
+        const int row = tr + 8 * u;
+        const bool in = row < nrows && c8 * 8 < ld;
+        const u32x4 v = in ? s.q[u] : (u32x4){0u, 0u, 0u, 0u};
+        if (c8 * 8 + 8 <= ldp) {
+            u32x4* p = reinterpret_cast<u32x4*>(Alds + row * ldp + c8 * 8);
+            if (in) {
+                const u32x4 o = *p;
+                diff |= (o[0] ^ v[0]) | (o[1] ^ v[1]) | (o[2] ^ v[2]) | (o[3] ^ v[3]);
+            }
+            *p = v;
+        }
+    }
+    return diff != 0u;
+}
 
 template <int MI>
 __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
@@ -647,7 +677,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
     L0_STAMP(3);
     const bool blk_bad = sflag[2] != 0;
     if (blk_bad && tid == 0) {
-        ag_st(f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE + 32, 1);
+        ag_st(f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE + BAR_G_INEXACT, 1);
         ag_st(f.bar + BAR_GFLAG, 1);
     }
     // (c) my column strip of A^T: rows k of the packed transpose get my RB rows as 8-element (16-byte) pieces
@@ -684,7 +714,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
     L0_STAMP(6);
     bool ok = l0_barrier(a, b, sflag, ep);
     L0_STAMP(7);
-    const bool exact = !f.A || ag_ld(f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE + 32) == 0;      // (packed in: bf16 IS the adjacency)
+    const bool exact = !f.A || ag_ld(f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE + BAR_G_INEXACT) == 0;      // (packed in: bf16 IS the adjacency)
     const float* Arows = f.A + ((long)b * N + r0) * N;             // fp32 fallback operands
     const float* Acols = f.A + (long)b * N * N + r0;
 
@@ -920,11 +950,15 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
             l0_stage_issue<MI>(atq, atp, f.pk_ld, nrows, 0);
             ok = l0_barrier(a, b, sflag, ep) && ok;
             L0_STAMP(44);
-            l0_stage_commit<MI>(atq, Alds, a.ldp, f.pk_ld, nrows, 0);
+            // both operands of "is this graph's adjacency symmetric" meet here: the commit compares as it overwrites.  The
+            // verdict (the last workgroup writes it to f.pk_sym) lets the backward replace A (S dA'^T) by Tt dA'^T.
+            bool asym = l0_stage_commit_cmp<MI>(atq, Alds, a.ldp, f.pk_ld, nrows, 0);
             for (int seg = 1; seg < segs; ++seg) {
                 l0_stage_issue<MI>(atq, atp, f.pk_ld, nrows, seg);
-                l0_stage_commit<MI>(atq, Alds, a.ldp, f.pk_ld, nrows, seg);
+                asym |= l0_stage_commit_cmp<MI>(atq, Alds, a.ldp, f.pk_ld, nrows, seg);
             }
+            asym |= !ok;                                 // (a wait gave up: the strips may not be the graph's)
+            if (__any(asym) && lane == 0) ag_st(f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE + BAR_G_ASYM, 1);
         }
         lds_barrier();
         L0_STAMP(45);
@@ -1075,9 +1109,19 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
     if (sflag[3]) {
         const int gflag = ag_ld(f.bar + BAR_GFLAG);
         if (tid < 64) f.pk_flag[tid] = tid == 0 ? gflag : 0;
+        // the per-graph verdict "bf16-exact and A == A^T bit for bit" (every block's stores were drained before its last
+        // arrival); graphs that never staged A^T (no pooling level) and slots >= B read 0
+        if (tid < 64) {
+            int v = 0;
+            if (tid < f.B && G == 2 && K > 0)
+                v = ag_ld(f.bar + BAR_GRAPH0 + tid * BAR_GSTRIDE + BAR_G_INEXACT) == 0 &&
+                    ag_ld(f.bar + BAR_GRAPH0 + tid * BAR_GSTRIDE + BAR_G_ASYM) == 0;
+            f.pk_sym[tid] = v;
+        }
         for (int g = tid; g < f.B; g += L0_NT) {
             ag_st(f.bar + BAR_GRAPH0 + g * BAR_GSTRIDE, 0);
-            ag_st(f.bar + BAR_GRAPH0 + g * BAR_GSTRIDE + 32, 0);
+            ag_st(f.bar + BAR_GRAPH0 + g * BAR_GSTRIDE + BAR_G_INEXACT, 0);
+            ag_st(f.bar + BAR_GRAPH0 + g * BAR_GSTRIDE + BAR_G_ASYM, 0);
         }
         if (tid == 0) {
             ag_st(f.bar + BAR_GCOUNT, 0);
@@ -1091,6 +1135,10 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
 // =========================================================================================================
 // Level-0 BACKWARD as one persistent launch (the mirror of k_level0_fwd; same decomposition, same barriers).
 //   X' = S^T Z, A' = Tt^T S   ->  dZ += S dX',  dS = Z dX'^T + Tt dA' + A (S dA'^T)      encoders.py:1278-1279
+//     the last term is the only one that is not row-local (V = S dA'^T of ALL rows, a graph barrier, my rows of A, an
+//     N x N x K aggregation).  A graph the forward found bf16-exact AND symmetric bit for bit (pk_sym[b]) has
+//     A S = A^T S = Tt, the saved rows: the term is then Tt dA'^T, one more row-local product in V's place, and the
+//     split, the barrier, the staging of A and the aggregation are skipped by all T blocks of the graph alike
 //   S = softmax(Za Wp^T + bp) * mask  ->  dlogits, dWp, dbp, dZa                          encoders.py:1273-1275
 //   every GraphConv layer, last to first: BatchNorm / ReLU / l2-normalise backward -> dU, bias sums;
 //   G = A^T dU;  dW = x_in^T G;  dx_in += G W^T (+ the BatchNorm-backward partials of the layer below)
@@ -1108,6 +1156,7 @@ struct L0BArgs {
     int seg_c[4 * DP_MAX_LAYERS + 2], seg_len[4 * DP_MAX_LAYERS + 2];
     long seg_flat[4 * DP_MAX_LAYERS + 2];
     int* dev_err;
+    int* verdict;                            // level0_verdict_block(): [0] = B, [1 + b] = graph b took the symmetric form, [65] = RB
     int spin_limit, target_bias;
 };
 
@@ -1215,6 +1264,15 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
     };
     auto vs_rd = [&](int pass, int CTt) { return f.vs + a.vs_off[pass] + (long)b * 3 * CTt * a.K8 * 128; };
     bool ok = true;
+    // uniform over the graph's T blocks: they all skip the same barrier crossing, so the epoch arithmetic stays in step
+    const bool sym = G == 2 && K > 0 && exact && f.pk_sym[b] != 0;
+    if (tid == 0 && a.verdict) {
+        if (wid == 0) {
+            a.verdict[0] = f.B;
+            a.verdict[65] = RB;
+        }
+        if (rb == 0) a.verdict[1 + b] = sym ? 1 : 0;
+    }
     lds_barrier();
 
     // my rows of dZe (the max-readout scatter of the head's backward) start the running gradient
@@ -1226,7 +1284,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
         float* TL = ZL + RB * D;                           // [RB][K]
         float* DAN = TL + RB * K;                          // [K][K]
         float* DXN = SCR;                                  // [K][D]     (reduce-slot area: free until the A V pass)
-        float* VL = DXN + ((K * D + 3) & ~3);              // [RB][K]    V = S dA'^T
+        float* VL = DXN + ((K * D + 3) & ~3);              // [RB][K]    V = S dA'^T  (symmetric graph: Tt dA'^T, the term itself)
         float* DS = EXT;                                   // [RB][K]    Z dX'^T
         float* DS2 = DS + RB * K;                          // [RB][K]    Tt dA'
         {
@@ -1243,16 +1301,19 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
         L0B_STAMP(1);
         // only V feeds the exchange: it goes first, and the other three products (first read behind the A V pass) run
         // under the barrier's latency
-        l0_mma<false, true>(SL, K, DAN, K, RB, K, K, [&](int r, int i, float v) { VL[r * K + i] = v; });
-        lds_barrier();
-        l0_write_split(vs_wr(0, CTk), VL, K, CTk, a.K8, k8_0, nk8, nrows);
-        l0_arrive(a, b, sflag, ep);
+        // (symmetric graph: the same product with my rows of Tt = A S is the whole first term — nothing is exchanged)
+        l0_mma<false, true>(sym ? TL : SL, K, DAN, K, RB, K, K, [&](int r, int i, float v) { VL[r * K + i] = v; });
+        if (!sym) {
+            lds_barrier();
+            l0_write_split(vs_wr(0, CTk), VL, K, CTk, a.K8, k8_0, nk8, nrows);
+            l0_arrive(a, b, sflag, ep);
+        }
         l0_mma<false, false>(SL, K, DXN, D, RB, D, K, [&](int r, int j, float v) { DZ0[r * D + j] += v; });
         l0_mma<false, true>(ZL, D, DXN, D, RB, K, D, [&](int r, int i, float v) { DS[r * K + i] = v; }, 3);
         l0_mma<false, false>(TL, K, DAN, K, RB, K, K, [&](int r, int i, float v) { DS2[r * K + i] = v; }, 6);
         lds_barrier();                                     // (the products' inputs are overwritten by the rows below)
         L0B_STAMP(2);
-        {
+        if (!sym) {
             // my rows of the packed A: asked for under the barrier, written over the staged rows behind it
             L0RowStage<MI> q;
             l0_stage_issue<MI>(q, f.pkA + ((long)b * N + r0) * f.pk_ld, f.pk_ld, nrows, 0);
@@ -1263,12 +1324,16 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
                 l0_stage_issue<MI>(q, f.pkA + ((long)b * N + r0) * f.pk_ld, f.pk_ld, nrows, seg);
                 l0_stage_commit<MI>(q, Alds, a.ldp, f.pk_ld, nrows, seg);
             }
+            lds_barrier();
         }
-        lds_barrier();
         L0B_STAMP(3);
         // ------------------------------------------------------------------ dS += A V;  softmax backward
-        l0_aggregate<MI>(a, Alds, exact, Arows, N, 1, nrows, vs_rd(0, CTk), CTk, SCR, ctpk, rot);
-        lds_barrier();
+        // (symmetric graph: VL already holds the term and stays where it is — nothing writes the reduce slots before
+        // the softmax backward has read it; ZAL / WP take the area only behind the barrier that follows)
+        if (!sym) {
+            l0_aggregate<MI>(a, Alds, exact, Arows, N, 1, nrows, vs_rd(0, CTk), CTk, SCR, ctpk, rot);
+            lds_barrier();
+        }
         L0B_STAMP(4);
         float* DLOG = DS;                                  // in place, row by row
         // S (and the link loss's d_assign) of all my rows first: one memory round trip, not one per row round
@@ -1299,7 +1364,8 @@ __global__ __launch_bounds__(L0_NT) void k_level0_bwd(L0BArgs a) {
             for (int k = 0; k < L0_NK; ++k) {
                 const int c = min(tl + 16 * k, K - 1);
                 const int o = r * ctpk + c;
-                const float agg = (SCR[o] + SCR[RB * ctpk + o]) + (SCR[2 * RB * ctpk + o] + SCR[3 * RB * ctpk + o]);
+                const float agg = sym ? VL[r * K + c]
+                                      : (SCR[o] + SCR[RB * ctpk + o]) + (SCR[2 * RB * ctpk + o] + SCR[3 * RB * ctpk + o]);
                 dv[k] += (agg + DS[r * K + c]) + DS2[r * K + c];
                 dot += (tl + 16 * k < K) ? sv[k] * dv[k] : 0.f;
             }
@@ -2037,6 +2103,7 @@ void level0_backward(Seq& q, const Level0Bwd& f) {
         l0b_vs_layout(f, a.vs_off, total);
     }
     a.dev_err = device_error_word();
+    a.verdict = level0_verdict_block();
     a.spin_limit = knobs().test_barrier_fail ? 64 : L0_SPIN_LIMIT;
     a.target_bias = knobs().test_barrier_fail ? 1 : 0;
     switch (g.RB / 16) {

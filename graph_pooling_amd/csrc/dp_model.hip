@@ -107,6 +107,7 @@ struct SaveLayout {
     unsigned short* pkA;     // bf16 copy of the level-0 adjacency [B, N, pk_ld] (null: not packed)
     unsigned short* pkAt;    // ... of its transpose
     int* pk_flag;
+    int* pk_sym;             // per-graph "bf16-exact and symmetric" verdicts of the persistent level-0 forward (64 ints)
     int pk_ld;
     LevelSave lv[DP_MAX_LEVELS + 1];
     float* feat;
@@ -133,6 +134,7 @@ SaveLayout layout_save(const dp_encoder_cfg& c, void* base) {
         s.pkA = b.take<unsigned short>(B * c.N * s.pk_ld);
         s.pkAt = b.take<unsigned short>(B * c.N * s.pk_ld);
         s.pk_flag = b.take<int>(64);
+        s.pk_sym = b.take<int>(64);          // (a block of its own: words 1..63 of pk_flag are dp_agg.hip's zero source)
         if (!base) s.pkA = s.pkAt = reinterpret_cast<unsigned short*>(1);   // dry run: "packing enabled" marker
     }
     for (int j = 0; j <= c.num_pooling; ++j) {
@@ -1034,7 +1036,7 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
             f.S = lv.S; f.S2 = assign_out; f.Tt = lv.T; f.Xn = lv.Xn; f.An = lv.An;
             f.feat = sv.feat;
             f.argmax = lv.argmax;
-            f.pkA = sv.pkA; f.pkAt = sv.pkAt; f.pk_flag = sv.pk_flag;
+            f.pkA = sv.pkA; f.pkAt = sv.pkAt; f.pk_flag = sv.pk_flag; f.pk_sym = sv.pk_sym;
             f.vs = sc.l0_vs; f.part = sc.l0_part; f.xpart = sc.xpart; f.mpart = sc.mpart;
             f.bar = l0_bar;
             f.zero_p = train && !q.dry ? q.ws + bz.begin : nullptr;
@@ -1306,7 +1308,7 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
             f.dAn = P >= 1 ? gr[1].dAdj : nullptr;
             f.d_assign = d_assign;
             f.dZe = gr[0].dZe;
-            f.pkA = sv.pkA; f.pkAt = sv.pkAt; f.pk_flag = sv.pk_flag;
+            f.pkA = sv.pkA; f.pkAt = sv.pkAt; f.pk_flag = sv.pk_flag; f.pk_sym = sv.pk_sym;
             f.slabs = slabs;
             f.slab_gstride = slab_stride * KS;
             f.vs = l0_vs; f.part = l0_part; f.gpart = l0_gpart;

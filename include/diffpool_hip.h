@@ -79,6 +79,15 @@ const char* dp_device_error_describe(int mask);
 int dp_profile_level0(int enable);
 int dp_profile_level0_read(int which, double* total_us, int* launches);
 
+/* Which form of dS = A (S dA'^T) + ... the LAST persistent level-0 backward on the current device took, per graph
+ * (encoders.py:1279; for tests and diagnosis, not fast: it synchronises the device).  The forward kernel decides per
+ * graph, exactly and on the device, whether the adjacency is bf16-exact and equal to its transpose bit for bit; for
+ * such a graph A S is the saved A^T S and the backward kernel multiplies that instead of aggregating over A again.
+ * verdicts[b] = 1: graph b took the short form, 0: the general one; *count = graphs of that launch (0 when no such
+ * launch has run); at most `capacity` verdicts are written.  *rows_per_block (may be NULL) = the rows of a graph one
+ * workgroup of that launch owned (16, 32, 48 or 64: the kernel instantiation; ceil(N / rows) workgroups per graph). */
+int dp_level0_bwd_symmetric(int* verdicts, int capacity, int* count, int* rows_per_block);
+
 /* ------------------------------------------------------------------ generic contraction
  * C[b] = act(alpha * op(A[b]) op(B[b]) + beta * C[b] + bias), fp32 MFMA (exact f32).
  * Replaces torch.matmul / @ at encoders.py:965,968,1278,1279,1311.  act: 0 none, 1 relu. */

@@ -15,6 +15,8 @@ torch.cuda.synchronize()
 buf = (C.c_ulonglong * 192)()
 lib.dp_debug_l0b_stamps.restype = C.c_int
 assert lib.dp_debug_l0b_stamps(buf) == 0
+print("symmetric short form per graph:", _lib.level0_bwd_symmetric()[0])
+# (a graph the forward found symmetric skips the split, the arrival and phases 3 and 4: its phase 2 is four products)
 names = {1: "rows, dX', dA', dZe staged + sync", 2: "V product, split, arrive, 3 products + sync", 3: "A rows asked, barrier wait, A rows in LDS",
          4: "A V aggregate + sync", 5: "reduce + softmax bwd + sync", 6: "dWp, dbp, dZa (+ stores)"}
 for i in range(3):
