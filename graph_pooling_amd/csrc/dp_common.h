@@ -562,7 +562,6 @@ struct Level0Bwd {
 };
 bool level0_bwd_persistent_ok(const Level0Bwd& a);
 size_t level0_bwd_vs_elems(const Level0Bwd& a);
-size_t level0_bwd_part_floats(const Level0Bwd& a);
 size_t level0_bwd_gpart_floats(const Level0Bwd& a);
 void level0_backward(Seq& q, const Level0Bwd& a);
 bool level0_persistent_ok(const Level0Fwd& a);
@@ -618,7 +617,7 @@ struct SmallHeadFold {
     HeadBwdArgs hb;          // what k_head_bwd would get; hb.lv[level].dZ is not written (that slice stays in LDS)
     int level;               // the entry of hb.lv that is this kernel's level
     int zcol;                // column of that level's readout in its concat buffer
-    float* part;             // exchange region of small_head_fold_part_floats(hb.h) floats (alloc_exchange)
+    float* part;             // exchange region of small_head_fold_part_floats(hb.h) floats (alloc_head)
 };
 size_t small_head_fold_part_floats(const HeadArgs& h);
 bool small_head_fold_fits(int B, int n, const int* dims, int L, bool dadj, const HeadArgs& h);

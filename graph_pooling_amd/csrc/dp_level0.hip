@@ -2076,7 +2076,6 @@ size_t level0_bwd_vs_elems(const Level0Bwd& f) {
     l0b_vs_layout(f, off, total);
     return total + 64;
 }
-size_t level0_bwd_part_floats(const Level0Bwd& f) { return (size_t)(f.L > 1 ? f.L - 1 : 1) * f.B * f.N * f.G * 4 + 4; }
 size_t level0_bwd_gpart_floats(const Level0Bwd& f) {
     L0BGeom g;
     if (!l0b_geometry(f, g)) return 4;

@@ -75,6 +75,30 @@ bool layer_agg_first(const LevelInfo& li, int l) {
     return ct > 128 && ct >= 2 * cin;
 }
 
+// How one call runs, decided ONCE at its top (encoder_plan): the kernels every level takes in each direction, what the
+// save buffer keeps and how the head runs.  The walks below switch on it and none of them asks a predicate again, so
+// the sizing walk, the forward and the backward cannot decide differently.  (The per-layer choices inside the generic
+// tier — layer_agg_first, plain_next, presplit, widen_fused, mv_fused — stay with the layer loops: some depend on
+// run-time pointers and none changes the workspace.)
+enum class Tier {
+    Persistent,   // level 0 as one persistent launch (dp_level0.hip)
+    WholeLevel,   // every layer of a small level in one launch (dp_small.hip: small_level_*)
+    PerLayer,     // a small level, one launch per layer and one workgroup per graph (small_gcn_*)
+    Generic,      // the per-phase sequence
+};
+struct EncoderPlan {
+    const dp_encoder_cfg* c;
+    bool sync_bn;
+    bool packed;          // the save buffer keeps bf16 copies of the level-0 A / A^T
+    bool pack_in_level;   // ... written behind the first transform GEMM of level 0's generic sequence (PackJob)
+    bool head_fused;      // pred_model (+ the last pooled level's readout) as one launch per direction
+    bool head_folded;     // ... and its backward inside the last level's whole-level backward kernel
+    LevelInfo lv[DP_MAX_LEVELS + 1];
+    Tier fwd[DP_MAX_LEVELS + 1], bwd[DP_MAX_LEVELS + 1];
+    Level0Fwd l0f;        // level 0 as the persistent kernels see it: the shape fields, pointers are the caller's
+    Level0Bwd l0b;
+};
+
 // A bump allocator over the caller's save buffer (dry when base == nullptr).
 struct Bump {
     char* base;
@@ -121,15 +145,12 @@ int readout_width(const dp_encoder_cfg& c, const LevelInfo& li) {
     return (c.flags & DP_F_LAST_ONLY) ? li.e->dims[li.L] : li.D;
 }
 
-bool level0_persistent(const dp_encoder_cfg& c);
-
-SaveLayout layout_save(const dp_encoder_cfg& c, void* base) {
+SaveLayout layout_save(const EncoderPlan& p, void* base) {
+    const dp_encoder_cfg& c = *p.c;
     SaveLayout s{};
     Bump b{(char*)base, 0};
     const size_t B = c.B;
-    // the bf16 copies of A / A^T: for the packed aggregation kernels (N >= 128) and for the persistent level-0 pair
-    // (which keeps them for its backward at any N it takes)
-    if (adj_pack_supported(c.N, 1) || level0_persistent(c)) {
+    if (p.packed) {
         s.pk_ld = adj_pack_ld(c.N);
         s.pkA = b.take<unsigned short>(B * c.N * s.pk_ld);
         s.pkAt = b.take<unsigned short>(B * c.N * s.pk_ld);
@@ -138,7 +159,7 @@ SaveLayout layout_save(const dp_encoder_cfg& c, void* base) {
         if (!base) s.pkA = s.pkAt = reinterpret_cast<unsigned short*>(1);   // dry run: "packing enabled" marker
     }
     for (int j = 0; j <= c.num_pooling; ++j) {
-        const LevelInfo li = level_info(c, j);
+        const LevelInfo& li = p.lv[j];
         LevelSave& lv = s.lv[j];
         lv.Ze = b.take<float>(B * li.n * li.D);
         lv.Za = li.a ? b.take<float>(B * li.n * li.Da) : nullptr;
@@ -160,7 +181,7 @@ SaveLayout layout_save(const dp_encoder_cfg& c, void* base) {
     s.hid[0] = s.feat;
     for (int i = 1; i < c.n_pred; ++i) s.hid[i] = b.take<float>(B * c.pred_dims[i]);
     if (c.readout == 1) {
-        const LevelInfo li = level_info(c, 0);
+        const LevelInfo& li = p.lv[0];
         s.Zm = b.take<float>(B * li.n * li.D);
         s.s2s = b.take<char>(set2set_save_bytes(c.B, li.n, li.D));
     }
@@ -244,9 +265,8 @@ int node_ksplit(const dp_encoder_cfg& c) {
 }
 
 // The backward pass's zero-initialised accumulators — level gradient buffers and the per-graph parameter-gradient
-// slabs (atomic bias sums; unused split-K rows) — are ONE block at the very start of the workspace in BOTH walks, so a
-// training forward can clear it on the side of its adjacency-pack kernel and the backward pass starts without a
-// zero-fill launch.
+// slabs (atomic bias sums; unused split-K rows) — are ONE block of the workspace head (alloc_head), so a training
+// forward can clear it on the side of its adjacency-pack kernel and the backward pass starts without a zero-fill launch.
 struct LevelGrad {
     float* dZe;    // [B, n, D]
     float* dZa;    // [B, n, Da]
@@ -259,11 +279,12 @@ struct BwdZero {
     int* bar;          // grid-barrier tickets of the whole-level backward kernels: 64 ints per level
     size_t begin, end;
 };
-BwdZero alloc_bwd_zero(Seq& q, const dp_encoder_cfg& c) {
+BwdZero alloc_bwd_zero(Seq& q, const EncoderPlan& p) {
+    const dp_encoder_cfg& c = *p.c;
     BwdZero z{};
     z.begin = q.ws_off;
     for (int j = 0; j <= c.num_pooling; ++j) {
-        const LevelInfo li = level_info(c, j);
+        const LevelInfo& li = p.lv[j];
         const size_t rows = (size_t)c.B * li.n;
         z.gr[j].dZe = q.alloc<float>(rows * li.D);
         z.gr[j].dX0 = j >= 1 ? q.alloc<float>(rows * li.e->dims[0]) : nullptr;
@@ -283,9 +304,10 @@ inline int bn_world(const dp_encoder_cfg& c) { return c.bn_world > 1 ? c.bn_worl
 // callbacks as W > 1 (what a one-GPU box can execute of the RCCL path), statistics over the local batch
 inline bool bn_sync(const dp_encoder_cfg& c) { return c.bn_world > 1 || (c.bn_world == 1 && c.exchange != nullptr); }
 // local [B, n, G, 2] block -> gathered [world * B, n, G, 2]; returns the pointer the consumer should read
-const float* bn_exchange(Seq& q, const dp_encoder_cfg& c, const float* local, float* gathered, size_t floats) {
-    if (!bn_sync(c)) return local;
+const float* bn_exchange(Seq& q, const EncoderPlan& p, const float* local, float* gathered, size_t floats) {
+    if (!p.sync_bn) return local;
     if (!q.ok()) return gathered;
+    const dp_encoder_cfg& c = *p.c;
     const int rc = c.exchange(c.exchange_user, local, gathered, floats * sizeof(float), (void*)q.stream);
     if (rc != 0) {
         set_error("sync-BN exchange callback failed (code %d)", rc);
@@ -314,11 +336,16 @@ struct PackJob {
 
 struct LevelIO {
     const PackJob* pack = nullptr;
+    const PackedAdj* pk = nullptr;   // level 0: the bf16 copies of its adjacency, or null
     const float* x0e;  // embed stack input [B, n, dims_e[0]]
     const float* x0a;  // assign stack input [B, n, dims_a[0]]
     const float* adj;  // [B, n, n]
     const float* drop = nullptr;   // dropout mask buffer (training with dropout > 0) or null
     float* xm[2] = {nullptr, nullptr};   // scratch [B, n, din] per stack: the masked layer input
+    int* bar = nullptr;              // WholeLevel tier: the kernel's grid-barrier tickets, zeroed in stream order
+    // backward only
+    const LevelGrad* gr = nullptr;
+    const SmallHeadFold* hf = nullptr;   // the head backward rides in this level's whole-level kernel
 };
 
 // mask of stack gi's layer-l input, or null (GraphConv dropout, encoders.py:962-964)
@@ -326,32 +353,14 @@ const float* drop_mask(const LevelInfo& li, const LevelIO& io, int gi, int l) {
     const dp_stack_cfg* st = gi == 0 ? li.e : li.a;
     return (io.drop && st && st->drop_off[l] >= 0) ? io.drop + st->drop_off[l] : nullptr;
 }
-bool level_has_dropout(const LevelInfo& li, const LevelIO& io) {
-    for (int gi = 0; gi < li.G; ++gi)
-        for (int l = 0; l < li.L; ++l)
-            if (drop_mask(li, io, gi, l)) return true;
+bool level_has_mask_slots(const LevelInfo& li) {
+    for (int l = 0; l < li.L; ++l)
+        if (li.e->drop_off[l] >= 0 || (li.a && li.a->drop_off[l] >= 0)) return true;
     return false;
 }
 
-// every layer of a small level in one launch per direction (dp_small.hip, whole-level kernels)
-bool level_is_fused(const dp_encoder_cfg& c, const LevelInfo& li, const LevelIO& io, bool dadj) {
-    return level_is_small(c.B, li) && !level_has_dropout(li, io) &&
-           small_level_fused_ok(c.B, li.n, li.e->dims, li.L, dadj);
-}
-// exchange scratch of the whole-level kernels over all levels that may use them
-size_t level_part_floats(const dp_encoder_cfg& c) {
-    size_t mx = 64;
-    for (int j = 0; j <= c.num_pooling; ++j) {
-        const LevelInfo li = level_info(c, j);
-        if (li.G == 1 && li.n <= 64) {
-            const size_t f = small_level_part_floats(c.B, li.n, li.L);
-            mx = f > mx ? f : mx;
-        }
-    }
-    return mx;
-}
 SmallLevelIO small_level_io(const LevelInfo& li, const LevelSave& lv, const LevelIO& io, const float* params,
-                            float* part, int* bar) {
+                            float* part) {
     SmallLevelIO s{};
     s.adj = io.adj;
     s.x0 = io.x0e;
@@ -369,15 +378,59 @@ SmallLevelIO small_level_io(const LevelInfo& li, const LevelSave& lv, const Leve
     s.Ze = lv.Ze;
     s.ldz = li.D;
     s.part = part;
-    s.bar = bar;
+    s.bar = io.bar;
     return s;
 }
 
+// The workspace of one pass behind the head (alloc_scratch): what the level loops share.
+struct Scratch {
+    float *Pj, *Uj, *part, *part_b;
+    float* part_all;         // [world * B, n, G, 2] under sync-BN
+    float* lvl_part;         // exchange region of the whole-level kernels (ExchangeRegions::lvl)
+    unsigned short* vs;      // 3-plane bf16 split of the current V operand (level 0, packed adjacency)
+    float* xm[2];            // masked layer inputs (dropout), per stack
+    // forward only
+    float* logits;
+    float *xpart, *mpart;    // persistent level-0 kernel: partial pooled products / max-readout partials,
+    unsigned short* l0_vs;   // split operands per pass (write-once exchange regions, dp_level0.hip)
+    // backward only (Uj holds dU)
+    float *Gj, *dS, *dlog, *V, *V2;
+    float* dxm[2];           // gradients of the masked layer inputs
+    float* slabs;            // per-graph parameter-gradient slabs: KS split-K rows of slab_stride floats per graph
+    long slab_stride;
+    int KS;
+};
+
+// layer l's slice of the concat buffers Ze | Za (or of their gradients), and layer l's joint Y
+template <typename GP, typename T>
+GP concat_slice(const LevelInfo& li, int l, T* ze, T* za) {
+    GP g{};
+    g.p[0] = ze + li.coff_e[l];
+    g.ld[0] = li.D;
+    g.p[1] = li.a ? za + li.coff_a[l] : nullptr;
+    g.ld[1] = li.Da;
+    return g;
+}
+template <typename GP>
+GP layer_y(const LevelInfo& li, const LevelSave& lv, int l) {
+    GP g{};
+    g.p[0] = lv.layer[l].Y;
+    g.p[1] = lv.layer[l].Y + li.e->dims[l + 1];
+    g.ld[0] = g.ld[1] = li.ctot[l];
+    return g;
+}
+GroupCPtrs layer_bias(const LevelInfo& li, const float* params, int l) {
+    GroupCPtrs b{};
+    b.p[0] = PW(params, li.e->b_off[l]);
+    b.p[1] = li.a ? PW(params, li.a->b_off[l]) : nullptr;
+    return b;
+}
+
 // P = [x_e W_e | x_a W_a]  for layer l of level li  (one grouped launch)
-void transform(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const LevelSave& lv, const LevelIO& io,
-               const float* params, int l, float* Pj, unsigned short* vs_split = nullptr) {
+void transform(Seq& q, int B, const LevelInfo& li, const LevelSave& lv, const LevelIO& io, const float* params, int l,
+               float* Pj, unsigned short* vs_split = nullptr) {
     const int ct = li.ctot[l];
-    const int B = c.B, n = li.n;
+    const int n = li.n;
     GemmDesc d[2];
     for (int g = 0; g < li.G; ++g) {
         const dp_stack_cfg* st = g == 0 ? li.e : li.a;
@@ -404,22 +457,26 @@ void transform(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const Level
     bgemm_group(q, d, li.G, B);
 }
 
-void level_forward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const LevelSave& lv, const LevelIO& io,
-                   const float* params, float* Pj, float* Uj, float* part, float* part_b, const PackedAdj* pk,
-                   unsigned short* vs, float* lvl_part, int* bar /*zeroed in stream order, or null*/,
-                   float* part_all /*[world * B, n, G, 2] under sync-BN*/) {
+// every tier but the persistent one (level 0 in one launch: encoder_forward)
+void level_forward(Seq& q, const EncoderPlan& p, int j, const LevelSave& lv, const LevelIO& io, const float* params,
+                   const Scratch& sc) {
+    const dp_encoder_cfg& c = *p.c;
+    const LevelInfo& li = p.lv[j];
     const int B = c.B, n = li.n;
     const bool bn = c.flags & DP_F_BN;
     const bool add_self = c.flags & DP_F_ADD_SELF;
     const int W = bn_world(c);
-    if (!bn_sync(c) && bar && level_is_fused(c, li, io, true)) {
-        small_level_fwd(q, small_level_io(li, lv, io, params, lvl_part, bar), B, n, li.e->dims, li.L, add_self ? 1 : 0,
+    float *const Pj = sc.Pj, *const Uj = sc.Uj, *const part = sc.part;
+    const PackedAdj* const pk = io.pk;
+    unsigned short* const vs = sc.vs;
+    if (p.fwd[j] == Tier::WholeLevel) {
+        small_level_fwd(q, small_level_io(li, lv, io, params, sc.lvl_part), B, n, li.e->dims, li.L, add_self ? 1 : 0,
                         bn ? 1 : 0);
         return;
     }
-    if (!bn_sync(c) && level_is_small(B, li) && !level_has_dropout(li, io)) {
+    if (p.fwd[j] == Tier::PerLayer) {
         // pooled level (or tiny graphs): one launch per layer, one workgroup per graph (dp_small.hip)
-        float* pbuf[2] = {part, part_b};
+        float* pbuf[2] = {part, sc.part_b};
         for (int l = 0; l < li.L; ++l) {
             const bool last = l == li.L - 1;
             const int din = li.e->dims[l], dout = li.e->dims[l + 1];
@@ -468,18 +525,11 @@ void level_forward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const L
             } else {
                 // the row-local products and the GraphConv tail in one row kernel (the last layer has no statistics)
                 const float* Wg[2] = {PW(params, li.e->w_off[l]), li.a ? PW(params, li.a->w_off[l]) : nullptr};
-                GroupCPtrs wb{};
-                wb.p[0] = PW(params, li.e->b_off[l]);
-                wb.p[1] = li.a ? PW(params, li.a->b_off[l]) : nullptr;
-                GroupPtrs wy{};
-                wy.p[0] = lv.Ze + li.coff_e[l];
-                wy.ld[0] = li.D;
-                wy.p[1] = li.a ? lv.Za + li.coff_a[l] : nullptr;
-                wy.ld[1] = li.Da;
-                widen_fwd(q, Uin, cin, c0ins, dins, Wg, wb, groups_of(li, l), wy, lv.layer[l].invn, (long)B * n, 1);
+                widen_fwd(q, Uin, cin, c0ins, dins, Wg, layer_bias(li, params, l), groups_of(li, l),
+                          concat_slice<GroupPtrs>(li, l, lv.Ze, lv.Za), lv.layer[l].invn, (long)B * n, 1);
             }
         } else if (!transformed) {
-            transform(q, c, li, lv, io, params, l, Pj, presplit ? vs : nullptr);
+            transform(q, B, li, lv, io, params, l, Pj, presplit ? vs : nullptr);
         }
         transformed = false;
         if (l == 0 && io.pack) {
@@ -490,21 +540,9 @@ void level_forward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const L
                      io.pack->zero_p, io.pack->zero_bytes);
         }
         RowGroups g = groups_of(li, l);
-        GroupCPtrs bias{};
-        bias.p[0] = PW(params, li.e->b_off[l]);
-        bias.p[1] = li.a ? PW(params, li.a->b_off[l]) : nullptr;
-        GroupPtrs yout{};
-        if (last) {
-            yout.p[0] = lv.Ze + li.coff_e[l];
-            yout.ld[0] = li.D;
-            yout.p[1] = li.a ? lv.Za + li.coff_a[l] : nullptr;
-            yout.ld[1] = li.Da;
-        } else {
-            yout.p[0] = lv.layer[l].Y;
-            yout.ld[0] = ct;
-            yout.p[1] = lv.layer[l].Y + g.c0[1];
-            yout.ld[1] = ct;
-        }
+        const GroupCPtrs bias = layer_bias(li, params, l);
+        const GroupPtrs xout = concat_slice<GroupPtrs>(li, l, lv.Ze, lv.Za);
+        const GroupPtrs yout = last ? xout : layer_y<GroupPtrs>(li, lv, l);
         const int stats_mode = (!last && bn) ? 1 : 0;
         // aggregation + GraphConv tail in one launch when the panel kernel takes the shape
         if (widen_fused) {
@@ -520,15 +558,10 @@ void level_forward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const L
                         stats_mode ? part : nullptr, (long)B * n, 1, stats_mode);
         }
         if (!last) {
-            GroupPtrs xout{};
-            xout.p[0] = lv.Ze + li.coff_e[l];
-            xout.ld[0] = li.D;
-            xout.p[1] = li.a ? lv.Za + li.coff_a[l] : nullptr;
-            xout.ld[1] = li.Da;
             // apply_bn and the NEXT layer's transform in one launch when that transform is a plain row-local product
             const RowGroups gnext = groups_of(li, l + 1);
-            const float* part_r = bn ? bn_exchange(q, c, part, part_all, (size_t)B * n * li.G * 2) : nullptr;
-            bool plain_next = !bn_sync(c) && !knobs().no_level_fusion && bn_transform_supported(g, gnext, B) &&
+            const float* part_r = bn ? bn_exchange(q, p, part, sc.part_all, (size_t)B * n * li.G * 2) : nullptr;
+            bool plain_next = !p.sync_bn && !knobs().no_level_fusion && bn_transform_supported(g, gnext, B) &&
                               !layer_agg_first(li, l + 1);
             for (int gi = 0; gi < li.G; ++gi) plain_next = plain_next && !drop_mask(li, io, gi, l + 1);
             if (plain_next) {
@@ -545,28 +578,28 @@ void level_forward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const L
     }
 }
 
-void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const LevelSave& lv, const LevelIO& io,
-                    const float* params, const LevelGrad& gr, float* slabs, long slab_stride, int KS, float* Pj,
-                    float* dUj, float* Gj, float* part, float* part_b, const PackedAdj* pk, unsigned short* vs,
-                    float* const dxm[2], float* lvl_part, int* bar, float* part_all, const SmallHeadFold* hf = nullptr) {
+void level_backward(Seq& q, const EncoderPlan& p, int j, const LevelSave& lv, const LevelIO& io, const float* params,
+                    const Scratch& sc) {
+    const dp_encoder_cfg& c = *p.c;
+    const LevelInfo& li = p.lv[j];
+    const LevelGrad& gr = *io.gr;
     const int B = c.B, n = li.n;
     const int W = bn_world(c);
-    const long gstride = slab_stride * KS;     // slab rows of one graph: KS split-K partials
-    const int ks_level = n >= 256 ? KS : 1;
+    float *const slabs = sc.slabs, *const Pj = sc.Pj, *const dUj = sc.Uj, *const Gj = sc.Gj, *const part = sc.part;
+    const long slab_stride = sc.slab_stride;
+    const long gstride = slab_stride * sc.KS;     // slab rows of one graph: KS split-K partials
+    const int ks_level = n >= 256 ? sc.KS : 1;
+    const PackedAdj* const pk = io.pk;
+    unsigned short* const vs = sc.vs;
     const bool bn = c.flags & DP_F_BN;
     const bool add_self = c.flags & DP_F_ADD_SELF;
-    if (!bn_sync(c) && lvl_part && bar && level_is_fused(c, li, io, true)) {
-        small_level_bwd(q, small_level_io(li, lv, io, params, lvl_part, bar), gr.dZe, gr.dX0, gr.dAdj, slabs, gstride,
-                        B, n, li.e->dims, li.L, add_self ? 1 : 0, bn ? 1 : 0, hf);
+    if (p.bwd[j] == Tier::WholeLevel) {
+        small_level_bwd(q, small_level_io(li, lv, io, params, sc.lvl_part), gr.dZe, gr.dX0, gr.dAdj, slabs, gstride, B,
+                        n, li.e->dims, li.L, add_self ? 1 : 0, bn ? 1 : 0, io.hf);
         return;
     }
-    if (hf) {      // (head_fold() decides with the same test: never reached)
-        set_error("level_backward: the head fold needs the whole-level backward kernel");
-        q.err = DP_ERR_UNSUPPORTED;
-        return;
-    }
-    if (!bn_sync(c) && level_is_small(B, li) && !level_has_dropout(li, io)) {
-        float* pbuf[2] = {part, part_b};
+    if (p.bwd[j] == Tier::PerLayer) {
+        float* pbuf[2] = {part, sc.part_b};
         for (int l = li.L - 1; l >= 0; --l) {
             const bool last = l == li.L - 1;
             const bool has_bn = !last && bn;
@@ -590,30 +623,14 @@ void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const 
         const int ct = li.ctot[l];
         const bool last = l == li.L - 1;
         RowGroups g = groups_of(li, l);
-        GroupCPtrs dx{}, xhat{}, y{};
-        dx.p[0] = gr.dZe + li.coff_e[l];
-        dx.ld[0] = li.D;
-        xhat.p[0] = lv.Ze + li.coff_e[l];
-        xhat.ld[0] = li.D;
-        if (li.a) {
-            dx.p[1] = gr.dZa + li.coff_a[l];
-            dx.ld[1] = li.Da;
-            xhat.p[1] = lv.Za + li.coff_a[l];
-            xhat.ld[1] = li.Da;
-        }
-        if (last) {
-            y = xhat;
-        } else {
-            y.p[0] = lv.layer[l].Y;
-            y.ld[0] = ct;
-            y.p[1] = lv.layer[l].Y + g.c0[1];
-            y.ld[1] = ct;
-        }
+        const GroupCPtrs dx = concat_slice<GroupCPtrs>(li, l, gr.dZe, gr.dZa);
+        const GroupCPtrs xhat = concat_slice<GroupCPtrs>(li, l, lv.Ze, lv.Za);
+        const GroupCPtrs y = last ? xhat : layer_y<GroupCPtrs>(li, lv, l);
         const bool has_bn = !last && bn;
         const float* part2 = part;
         if (has_bn) {
             if (!part_ready) bn_bwd_partials(q, dx, xhat, g, part, (long)B * n);
-            part2 = bn_exchange(q, c, part, part_all, (size_t)B * n * li.G * 2);
+            part2 = bn_exchange(q, p, part, sc.part_all, (size_t)B * n * li.G * 2);
         }
         part_ready = false;
         // bias gradients: column sums of dU go straight into each graph's (zeroed) slab row with float atomics
@@ -659,19 +676,8 @@ void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const 
             if (add_self) axpy(q, dxagg, Gj, 1.f, (long)B * n * cin);
             if (bn && !knobs().no_rowpart_hook && scatter_add_cols_part_supported(de, da)) {
                 // ... and the BatchNorm-backward partials of layer l - 1, whose gradient these rows complete
-                GroupPtrs dd{};
-                GroupCPtrs xh{};
-                dd.p[0] = gr.dZe + li.coff_e[l - 1];
-                dd.ld[0] = li.D;
-                xh.p[0] = lv.Ze + li.coff_e[l - 1];
-                xh.ld[0] = li.D;
-                if (li.a) {
-                    dd.p[1] = gr.dZa + li.coff_a[l - 1];
-                    dd.ld[1] = li.Da;
-                    xh.p[1] = lv.Za + li.coff_a[l - 1];
-                    xh.ld[1] = li.Da;
-                }
-                scatter_add_cols_part(q, dxagg, dd, xh, de, da, li.G, part, (long)B * n);
+                scatter_add_cols_part(q, dxagg, concat_slice<GroupPtrs>(li, l - 1, gr.dZe, gr.dZa),
+                                      concat_slice<GroupCPtrs>(li, l - 1, lv.Ze, lv.Za), de, da, li.G, part, (long)B * n);
                 part_ready = true;
             } else {
                 scatter_add_cols(q, dxagg, gr.dZe + li.coff_e[l - 1], li.D, de,
@@ -733,7 +739,7 @@ void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const 
                     masked_ld[gi] = lddx;
                     masked_m[gi] = m;
                     masked_w[gi] = din;
-                    d[nd++] = GemmDesc{Gj + g.c0[gi], PW(params, st->w_off[l]), dxm[gi], nullptr, n, din, dout, ct, dout,
+                    d[nd++] = GemmDesc{Gj + g.c0[gi], PW(params, st->w_off[l]), sc.dxm[gi], nullptr, n, din, dout, ct, dout,
                                        din, (long)n * ct, 0, (long)n * din, false, true, 1.f, 0.f, 0, 0, 0, nullptr, 0, 0,
                                        0, 1};
                 } else if (dxin && hook) {
@@ -756,7 +762,7 @@ void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const 
             part_ready = hook;
             for (int gi = 0; gi < li.G; ++gi)
                 if (masked_dst[gi])
-                    mask_axpy(q, masked_dst[gi], masked_ld[gi], dxm[gi], masked_m[gi], (long)B * n, masked_w[gi]);
+                    mask_axpy(q, masked_dst[gi], masked_ld[gi], sc.dxm[gi], masked_m[gi], (long)B * n, masked_w[gi]);
             // both stacks of a pooled level read the same input X_j: the assign stack's share is added after
             if (l == 0 && gr.dX0 && li.G == 2) {
                 const dp_stack_cfg* st = li.a;
@@ -766,7 +772,7 @@ void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const 
         }
         if (gr.dAdj) {
             // dA += dU P^T   (P = X W recomputed)
-            transform(q, c, li, lv, io, params, l, Pj);
+            transform(q, B, li, lv, io, params, l, Pj);
             bgemm(q, dUj, Pj, gr.dAdj, nullptr, B, n, n, ct, ct, ct, n, (long)n * ct, (long)n * ct, (long)n * n, false,
                   true, 1.f, 1.f, 0);
         }
@@ -774,15 +780,15 @@ void level_backward(Seq& q, const dp_encoder_cfg& c, const LevelInfo& li, const 
 }
 
 // floats of one masked-input scratch buffer (0 when no stack of the model has a dropout mask)
-size_t dropout_scratch_floats(const dp_encoder_cfg& c) {
+size_t dropout_scratch_floats(const EncoderPlan& p) {
     size_t mx = 0;
-    for (int j = 0; j <= c.num_pooling; ++j) {
-        const LevelInfo li = level_info(c, j);
+    for (int j = 0; j <= p.c->num_pooling; ++j) {
+        const LevelInfo& li = p.lv[j];
         for (int gi = 0; gi < li.G; ++gi) {
             const dp_stack_cfg* st = gi == 0 ? li.e : li.a;
             for (int l = 0; l < li.L; ++l)
                 if (st->drop_off[l] >= 0) {
-                    const size_t f = (size_t)c.B * li.n * st->dims[l];
+                    const size_t f = (size_t)p.c->B * li.n * st->dims[l];
                     mx = f > mx ? f : mx;
                 }
         }
@@ -790,17 +796,10 @@ size_t dropout_scratch_floats(const dp_encoder_cfg& c) {
     return mx;
 }
 
-struct Scratch {
-    float* xm[2];
-    float *Pj, *Uj, *part, *part_b, *logits, *lvl_part, *part_all;
-    float *xpart, *mpart;    // persistent level-0 kernel: partial pooled products / max-readout partials,
-    float* l0_part;          // BatchNorm partials per layer,
-    unsigned short* l0_vs;   // split operands per pass (write-once exchange regions, dp_level0.hip)
-    unsigned short* vs;      // 3-plane bf16 split of the current V operand (level 0, packed adjacency)
-};
-size_t vs_elems(const dp_encoder_cfg& c) {
+size_t vs_elems(const EncoderPlan& p) {
+    const dp_encoder_cfg& c = *p.c;
     if (!adj_pack_supported(c.N, 1)) return 64;
-    const LevelInfo li = level_info(c, 0);
+    const LevelInfo& li = p.lv[0];
     int cm = li.cmax > li.K ? li.cmax : li.K;
     if (cm > 320) cm = 320;     // widest operand the packed kernels take (dp_agg.hip AGGW_MAX_C)
     return split3_elems(c.B, c.N, cm) + 64;
@@ -833,8 +832,7 @@ bool head_usable(const dp_encoder_cfg& c) {
 
 // Level 0 as the persistent kernel sees it (dp_level0.hip).  Everything level0_persistent_ok() looks at comes from the
 // cfg, so the sizing walk and the call decide alike; pointers are filled in by the caller.
-Level0Fwd level0_desc(const dp_encoder_cfg& c) {
-    const LevelInfo li = level_info(c, 0);
+Level0Fwd level0_desc(const dp_encoder_cfg& c, const LevelInfo& li) {
     Level0Fwd f{};
     f.B = c.B; f.N = c.N; f.L = li.L; f.G = li.G;
     f.bn = (c.flags & DP_F_BN) ? 1 : 0;
@@ -863,8 +861,7 @@ Level0Fwd level0_desc(const dp_encoder_cfg& c) {
     f.pk_ld = adj_pack_ld(c.N);
     return f;
 }
-Level0Bwd level0_bwd_desc(const dp_encoder_cfg& c) {
-    const Level0Fwd w = level0_desc(c);
+Level0Bwd level0_bwd_desc(const Level0Fwd& w) {
     Level0Bwd f{};
     f.B = w.B; f.N = w.N; f.L = w.L; f.G = w.G; f.bn = w.bn;
     f.st[0] = w.st[0]; f.st[1] = w.st[1];
@@ -875,77 +872,167 @@ Level0Bwd level0_bwd_desc(const dp_encoder_cfg& c) {
     f.pk_ld = w.pk_ld;
     return f;
 }
-bool level0_persistent(const dp_encoder_cfg& c);
-bool level0_bwd_persistent(const dp_encoder_cfg& c) {
-    return level0_persistent(c) && !knobs().no_l0_persist_bwd && level0_bwd_persistent_ok(level0_bwd_desc(c));
-}
-bool level0_persistent(const dp_encoder_cfg& c) {
-    if (bn_sync(c) || (c.flags & DP_F_ADD_SELF)) return false;
-    const LevelInfo li = level_info(c, 0);
-    for (int l = 0; l < li.L; ++l)
-        if (li.e->drop_off[l] >= 0 || (li.a && li.a->drop_off[l] >= 0) || layer_agg_first(li, l)) return false;
-    return level0_persistent_ok(level0_desc(c));
+
+// The ONE place a plan condition lives.  What the choice depends on: the cfg, whether a dropout buffer was passed
+// (levels with mask slots then leave the small tiers), the knobs, and the device's CU count (through
+// level0_persistent_ok / level0_bwd_persistent_ok / small_level_fused_ok).  Recomputed on every call and kept nowhere:
+// the knobs are process-wide, the device is not.
+EncoderPlan encoder_plan(const dp_encoder_cfg& c, bool has_dropout) {
+    EncoderPlan p{};
+    p.c = &c;
+    const int P = c.num_pooling;
+    p.sync_bn = bn_sync(c);
+    for (int j = 0; j <= P; ++j) p.lv[j] = level_info(c, j);
+    p.l0f = level0_desc(c, p.lv[0]);
+    p.l0b = level0_bwd_desc(p.l0f);
+    p.head_fused = head_usable(c);
+    // The small tiers combine BatchNorm partials inside the launch (so: no sync-BN) and take no dropout mask.  The
+    // whole-level kernels also need a zeroed ticket block.  The backward always has one (BwdZero::bar); the forward of
+    // a level >= 1 gets one from the launch below it (the softmax launch, or the persistent level-0 launch), and level
+    // 0 allocates its own when G == 1 and n <= 64, which level_is_small implies: no small level is ever without one.
+    for (int j = 0; j <= P; ++j) {
+        const LevelInfo& li = p.lv[j];
+        Tier t = Tier::Generic;
+        if (!p.sync_bn && level_is_small(c.B, li) && !(has_dropout && level_has_mask_slots(li)))
+            t = small_level_fused_ok(c.B, li.n, li.e->dims, li.L, true) ? Tier::WholeLevel : Tier::PerLayer;
+        p.fwd[j] = p.bwd[j] = t;
+    }
+    // Level 0 as one persistent launch per direction.  Mask slots rule it out whether or not a buffer was passed (the
+    // save buffer and the workspace are sized without knowing); the backward only follows a persistent forward.
+    bool l0 = !p.sync_bn && !(c.flags & DP_F_ADD_SELF) && !level_has_mask_slots(p.lv[0]);
+    for (int l = 0; l0 && l < p.lv[0].L; ++l) l0 = !layer_agg_first(p.lv[0], l);
+    if (l0 && level0_persistent_ok(p.l0f)) {
+        p.fwd[0] = Tier::Persistent;
+        if (!knobs().no_l0_persist_bwd && level0_bwd_persistent_ok(p.l0b)) p.bwd[0] = Tier::Persistent;
+    }
+    // the bf16 copies of A / A^T: for the packed aggregation kernels (N >= 128) and for the persistent level-0 pair
+    // (which keeps them for its backward at any N it takes).  Outside the persistent plan a packed level 0 has
+    // N >= 128, so it is never a small level: the pack always has a generic sequence to run in.
+    p.packed = adj_pack_supported(c.N, 1) || p.fwd[0] == Tier::Persistent;
+    p.pack_in_level = p.packed && p.fwd[0] == Tier::Generic;
+    // The prediction-head backward runs inside the last level's whole-level backward kernel (SmallHeadFold) when that
+    // level takes the kernel and the head's operands fit its LDS; else k_head_bwd.
+    p.head_folded = !knobs().no_head_fold && P >= 1 && p.head_fused && p.bwd[P] == Tier::WholeLevel &&
+                    small_head_fold_fits(c.B, p.lv[P].n, p.lv[P].e->dims, p.lv[P].L, true,
+                                         head_args(c, SaveLayout{}, nullptr, nullptr));
+    return p;
 }
 
-// The tagged-entry exchange regions (BatchNorm partials of the persistent level-0 kernels, forward and backward, and of
-// the pooled-level kernels).  Their readers recognise an entry by its tag, so NOTHING else may ever be written there:
-// they sit right behind the barrier block, at the same offsets in the forward and the backward walk, and are never
-// handed out as scratch — they only ever hold zeros (the workspace's one-time fill) or entries of earlier launches.
+// The packed-adjacency entries (dp_encoder_forward_packed / _backward_packed) deliver level 0's adjacency as the bf16
+// pair instead of fp32: only the persistent level-0 kernels multiply straight from it (every other plan wants the
+// fp32 rows somewhere).
+bool packed_entry_ok(Seq& q, const EncoderPlan& p) {
+    if (p.fwd[0] == Tier::Persistent && p.bwd[0] == Tier::Persistent) return true;
+    set_error("the packed-adjacency entry needs the persistent level-0 plan (N >= 64, N %% 4 == 0, B * ceil(N / RB) "
+              "<= CUs, no sync-BN); pass the fp32 adjacency to dp_encoder_forward / dp_encoder_backward for this "
+              "configuration");
+    q.err = DP_ERR_UNSUPPORTED;
+    return false;
+}
+
+// The head of the workspace.  BOTH walks call alloc_head first, so its three blocks sit at the same offsets in the
+// forward and in the backward:
+//   - the persistent level-0 kernels' barrier block: zero when the workspace is first used (diffpool_hip.h),
+//     self-cleaning afterwards (dp_level0.hip); q.seq_word is one of its words;
+//   - the tagged-entry exchange regions (BatchNorm partials of the persistent level-0 kernels, forward and backward, of
+//     the whole-level kernels, and the head fold's hidden-layer gradients).  Their readers recognise an entry by its
+//     tag, so NOTHING else may ever be written there: they are never handed out as scratch and only ever hold zeros
+//     (the workspace's one-time fill) or entries of earlier launches;
+//   - the backward's zero block (BwdZero), which a training forward clears for the backward that follows.
 struct ExchangeRegions {
     float *l0_fwd, *l0_bwd, *lvl, *head;
 };
-ExchangeRegions alloc_exchange(Seq& q, const dp_encoder_cfg& c) {
-    ExchangeRegions x{};
-    x.l0_fwd = q.alloc<float>(level0_persistent(c) ? level0_part_floats(level0_desc(c)) : 4);
-    x.l0_bwd = q.alloc<float>(level0_bwd_persistent(c) ? level0_bwd_part_floats(level0_bwd_desc(c)) : 4);
-    x.lvl = q.alloc<float>(level_part_floats(c));
-    // the head fold's hidden-layer gradients (small_level_bwd with a SmallHeadFold)
-    x.head = q.alloc<float>(head_usable(c) && c.num_pooling >= 1 ? small_head_fold_part_floats(head_args(c, SaveLayout{}, nullptr,
-                                                                                                          nullptr))
-                                                                  : 4);
-    return x;
+struct WorkspaceHead {
+    int* l0_bar;
+    ExchangeRegions xr;
+    BwdZero bz;
+};
+WorkspaceHead alloc_head(Seq& q, const EncoderPlan& p) {
+    const dp_encoder_cfg& c = *p.c;
+    WorkspaceHead h{};
+    h.l0_bar = q.alloc<int>(level0_bar_ints(c.B));
+    q.seq_word = level0_seq_word(h.l0_bar);
+    h.xr.l0_fwd = q.alloc<float>(p.fwd[0] == Tier::Persistent ? level0_part_floats(p.l0f) : 4);
+    h.xr.l0_bwd = q.alloc<float>(p.bwd[0] == Tier::Persistent ? level0_part_floats(p.l0f) : 4);
+    size_t lvl = 64;     // over all levels that may take a whole-level kernel
+    for (int j = 0; j <= c.num_pooling; ++j)
+        if (p.lv[j].G == 1 && p.lv[j].n <= 64) lvl = std::max(lvl, small_level_part_floats(c.B, p.lv[j].n, p.lv[j].L));
+    h.xr.lvl = q.alloc<float>(lvl);
+    h.xr.head = q.alloc<float>(p.head_fused && c.num_pooling >= 1
+                                   ? small_head_fold_part_floats(head_args(c, SaveLayout{}, nullptr, nullptr))
+                                   : 4);
+    h.bz = alloc_bwd_zero(q, p);
+    return h;
 }
 
-// The prediction-head backward runs inside the last level's whole-level backward kernel (SmallHeadFold) when that
-// level takes the kernel (the test of level_backward) and the head's operands fit its LDS; else k_head_bwd.
-bool head_fold(const dp_encoder_cfg& c, const float* dropout) {
-    const int P = c.num_pooling;
-    if (knobs().no_head_fold || P < 1 || bn_sync(c) || !head_usable(c)) return false;
-    const LevelInfo li = level_info(c, P);
-    LevelIO io{};
-    io.drop = dropout;
-    return level_is_fused(c, li, io, true) &&
-           small_head_fold_fits(c.B, li.n, li.e->dims, li.L, true, head_args(c, SaveLayout{}, nullptr, nullptr));
-}
-
-// shared allocation walk for the forward (also used for sizing)
-Scratch fwd_scratch(Seq& q, const dp_encoder_cfg& c) {
-    size_t maxPU = 0, maxPart = 0, maxLog = 0;
+// ... and the scratch behind it that the level loops of a pass share, in each pass's own order (also used for sizing)
+Scratch alloc_scratch(Seq& q, const EncoderPlan& p, bool backward) {
+    const dp_encoder_cfg& c = *p.c;
+    size_t maxPU = 0, maxPart = 0, maxSK = 1;
     for (int j = 0; j <= c.num_pooling; ++j) {
-        const LevelInfo li = level_info(c, j);
+        const LevelInfo& li = p.lv[j];
         const size_t rows = (size_t)c.B * li.n;
-        if (rows * li.cmax > maxPU) maxPU = rows * li.cmax;
-        if (rows * li.G * 2 > maxPart) maxPart = rows * li.G * 2;
-        if (li.a && rows * li.K > maxLog) maxLog = rows * li.K;
+        maxPU = std::max(maxPU, rows * li.cmax);
+        maxPart = std::max(maxPart, rows * li.G * 2);
+        if (li.a) maxSK = std::max(maxSK, rows * li.K);
     }
     Scratch s{};
     s.Pj = q.alloc<float>(maxPU);
     s.Uj = q.alloc<float>(maxPU);
+    if (backward) s.Gj = q.alloc<float>(maxPU);
     s.part = q.alloc<float>(maxPart);
     s.part_b = q.alloc<float>(maxPart);
-    s.logits = q.alloc<float>(maxLog > 0 ? maxLog : 1);
-    s.part_all = bn_sync(c) ? q.alloc<float>(maxPart * bn_world(c)) : nullptr;
-    s.vs = q.alloc<unsigned short>(vs_elems(c));
-    if (level0_persistent(c)) {
-        const Level0Fwd f = level0_desc(c);
-        s.xpart = q.alloc<float>(level0_xpart_floats(f));
-        s.mpart = q.alloc<float>(level0_mpart_floats(f));
-        s.l0_vs = q.alloc<unsigned short>(level0_vs_elems(f));
+    if (!backward) s.logits = q.alloc<float>(maxSK);
+    s.part_all = p.sync_bn ? q.alloc<float>(maxPart * bn_world(c)) : nullptr;
+    s.vs = q.alloc<unsigned short>(vs_elems(p));
+    if (!backward && p.fwd[0] == Tier::Persistent) {
+        s.xpart = q.alloc<float>(level0_xpart_floats(p.l0f));
+        s.mpart = q.alloc<float>(level0_mpart_floats(p.l0f));
+        s.l0_vs = q.alloc<unsigned short>(level0_vs_elems(p.l0f));
     }
-    const size_t dsf = dropout_scratch_floats(c);
-    s.xm[0] = dsf ? q.alloc<float>(dsf) : nullptr;
-    s.xm[1] = dsf ? q.alloc<float>(dsf) : nullptr;
+    if (backward)
+        for (float** b : {&s.dS, &s.dlog, &s.V, &s.V2}) *b = q.alloc<float>(maxSK);
+    const size_t dsf = dropout_scratch_floats(p);
+    for (float*& m : s.xm) m = dsf ? q.alloc<float>(dsf) : nullptr;
+    if (backward)
+        for (float*& m : s.dxm) m = dsf ? q.alloc<float>(dsf) : nullptr;
     return s;
+}
+
+// what the two persistent level-0 launches read alike (F: Level0Fwd, which writes them, or Level0Bwd)
+template <typename F>
+void level0_operands(F& f, const SaveLayout& sv, const float* params, const float* x, const float* adj,
+                     const float* assign_x) {
+    const LevelSave& lv = sv.lv[0];
+    f.A = adj;
+    f.x0[0] = x;
+    f.x0[1] = assign_x;
+    f.x_shared = f.G == 2 && x == assign_x && f.st[0].dims[0] == f.st[1].dims[0];
+    f.params = params;
+    for (int l = 0; l < f.L; ++l) {
+        f.Y[l] = lv.layer[l].Y;
+        f.invn[l] = lv.layer[l].invn;
+        f.stats[l] = lv.layer[l].stats;
+    }
+    f.Z[0] = lv.Ze;
+    f.Z[1] = lv.Za;
+    f.S = lv.S;
+    f.Tt = lv.T;
+    f.pkA = sv.pkA; f.pkAt = sv.pkAt; f.pk_flag = sv.pk_flag; f.pk_sym = sv.pk_sym;
+}
+
+// level j's operands: the caller's tensors at level 0, the pooled outputs of the level below otherwise
+LevelIO level_io(int j, const SaveLayout& sv, const float* x, const float* adj, const float* assign_x,
+                 const float* dropout, const Scratch& sc, const PackedAdj* pk0) {
+    LevelIO io{};
+    io.x0e = j == 0 ? x : sv.lv[j - 1].Xn;
+    io.x0a = j == 0 ? assign_x : sv.lv[j - 1].Xn;
+    io.adj = j == 0 ? adj : sv.lv[j - 1].An;
+    io.drop = dropout;
+    io.xm[0] = sc.xm[0];
+    io.xm[1] = sc.xm[1];
+    io.pk = j == 0 ? pk0 : nullptr;
+    return io;
 }
 
 }  // namespace
@@ -953,27 +1040,17 @@ Scratch fwd_scratch(Seq& q, const dp_encoder_cfg& c) {
 int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const float* x, const float* adj,
                     const float* assign_x, const int* num_nodes, const float* dropout, float* ypred,
                     float* assign_out, void* save, int mode, long long* labels_out, const PackedAdj* given) {
-    SaveLayout sv = layout_save(c, save);
+    const EncoderPlan p = encoder_plan(c, dropout != nullptr);
+    SaveLayout sv = layout_save(p, save);
     if (given) {
-        // the level-0 adjacency arrives as the packed bf16 pair (dp_build_batch_packed) instead of fp32: only the
-        // persistent level-0 kernels multiply straight from it (every other plan wants the fp32 rows somewhere)
-        if (!level0_persistent(c) || !level0_bwd_persistent(c)) {
-            set_error("the packed-adjacency entry needs the persistent level-0 plan (N >= 64, N %% 4 == 0, B * ceil(N / RB) "
-                      "<= CUs, no sync-BN); pass the fp32 adjacency to dp_encoder_forward for this configuration");
-            return q.err = DP_ERR_UNSUPPORTED;
-        }
+        if (!packed_entry_ok(q, p)) return q.err;
         sv.pkA = const_cast<unsigned short*>(given->A);
         sv.pkAt = const_cast<unsigned short*>(given->At);
     }
-    // the persistent level-0 kernel's barrier block: first thing in the workspace in BOTH walks; zero when the workspace
-    // is first used (diffpool_hip.h), self-cleaning afterwards (dp_level0.hip)
-    int* l0_bar = q.alloc<int>(level0_bar_ints(c.B));
-    q.seq_word = level0_seq_word(l0_bar);
-    const ExchangeRegions xr = alloc_exchange(q, c);
-    const BwdZero bz = alloc_bwd_zero(q, c);      // same offsets as in encoder_backward: next block of the workspace
-    Scratch sc = fwd_scratch(q, c);
-    sc.lvl_part = xr.lvl;
-    sc.l0_part = xr.l0_fwd;
+    const WorkspaceHead wh = alloc_head(q, p);
+    const BwdZero& bz = wh.bz;
+    Scratch sc = alloc_scratch(q, p, false);
+    sc.lvl_part = wh.xr.lvl;
     if (q.err) return q.err;
     const int B = c.B, P = c.num_pooling;
     const int ldfeat = c.pred_dims[0];
@@ -985,15 +1062,10 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
     const PackedAdj* pkp = sv.pkA ? &pk0 : nullptr;
     PackJob pack{adj, sv.pkA, sv.pkAt, sv.pk_flag, sv.pk_ld, train && !q.dry ? q.ws + bz.begin : nullptr,
                  train ? bz.end - bz.begin : 0};
-    const bool l0_persist = level0_persistent(c);
-    const bool pack_in_level = pkp && !l0_persist && !(level_is_small(B, level_info(c, 0)) && !dropout);
-    if (l0_persist) {
-        // handled below (one launch for the whole level, pack included)
-    } else if (pkp && !pack_in_level) adj_pack(q, adj, sv.pkA, sv.pkAt, sv.pk_flag, B, c.N, sv.pk_ld, false, pack.zero_p,
-                                        pack.zero_bytes);
-    else if (!pkp && train && !q.dry) zero_fill(q, q.ws + bz.begin, bz.end - bz.begin);
+    // (the persistent level-0 launch packs and clears on its own)
+    if (!p.packed && train && !q.dry) zero_fill(q, q.ws + bz.begin, bz.end - bz.begin);
     int featoff = 0;
-    const bool fused_head = head_usable(c);
+    const bool fused_head = p.head_fused;
     HeadArgs head = head_args(c, sv, params, ypred);
     head.labels = labels_out;
     // grid-barrier tickets of a whole-level kernel: cleared in stream order by the softmax launch of the level below
@@ -1002,43 +1074,24 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
     const int* poison[DP_MAX_LEVELS + 1];   // error words of the whole-level kernels' barrier blocks (read by the head launch)
     int n_poison = 0;
     for (int j = 0; j <= P; ++j) {
-        const LevelInfo li = level_info(c, j);
+        const LevelInfo& li = p.lv[j];
         const LevelSave& lv = sv.lv[j];
+        const bool persistent = p.fwd[j] == Tier::Persistent;
         if (j == 0 && li.G == 1 && li.n <= 64) {
             level_bar = q.alloc<int>(64);
             if (q.ok()) zero_small(q, level_bar, 64 * sizeof(int));
         }
-        LevelIO io{};
-        io.x0e = j == 0 ? x : sv.lv[j - 1].Xn;
-        io.x0a = j == 0 ? assign_x : sv.lv[j - 1].Xn;
-        io.adj = j == 0 ? adj : sv.lv[j - 1].An;
-        io.drop = dropout;
-        io.xm[0] = sc.xm[0];
-        io.xm[1] = sc.xm[1];
-        io.pack = (j == 0 && pack_in_level) ? &pack : nullptr;
-        if (j == 0 && l0_persist) {
+        if (persistent) {
             // the whole level in ONE persistent launch: pack, GraphConv stacks, readout, assign head, pooling products
-            Level0Fwd f = level0_desc(c);
+            Level0Fwd f = p.l0f;
+            level0_operands(f, sv, params, x, adj, assign_x);
             f.train = train ? 1 : 0;
-            f.A = adj;
-            f.x0[0] = x;
-            f.x0[1] = assign_x;
-            f.x_shared = f.G == 2 && x == assign_x && f.st[0].dims[0] == f.st[1].dims[0];
             f.num_nodes = num_nodes;
-            f.params = params;
-            for (int l = 0; l < li.L; ++l) {
-                f.Y[l] = lv.layer[l].Y;
-                f.invn[l] = lv.layer[l].invn;
-                f.stats[l] = lv.layer[l].stats;
-            }
-            f.Z[0] = lv.Ze;
-            f.Z[1] = lv.Za;
-            f.S = lv.S; f.S2 = assign_out; f.Tt = lv.T; f.Xn = lv.Xn; f.An = lv.An;
+            f.S2 = assign_out; f.Xn = lv.Xn; f.An = lv.An;
             f.feat = sv.feat;
             f.argmax = lv.argmax;
-            f.pkA = sv.pkA; f.pkAt = sv.pkAt; f.pk_flag = sv.pk_flag; f.pk_sym = sv.pk_sym;
-            f.vs = sc.l0_vs; f.part = sc.l0_part; f.xpart = sc.xpart; f.mpart = sc.mpart;
-            f.bar = l0_bar;
+            f.vs = sc.l0_vs; f.part = wh.xr.l0_fwd; f.xpart = sc.xpart; f.mpart = sc.mpart;
+            f.bar = wh.l0_bar;
             f.zero_p = train && !q.dry ? q.ws + bz.begin : nullptr;
             f.zero_bytes = train ? bz.end - bz.begin : 0;
             if (j < P) {
@@ -1046,25 +1099,24 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
                 f.next_bar = level_bar;
             }
             level0_forward(q, f);
-            if (!q.dry) poison[n_poison++] = level0_error_word(l0_bar);
-            if (c.readout == 0) featoff += f.rw;
-            else {
-                mask_rows(q, lv.Ze, li.D, sv.Zm, li.D, num_nodes, B, li.n, li.D);
-                set2set_fwd(q, sv.Zm, li.D, PW(params, c.s2s_off[0]), PW(params, c.s2s_off[1]), PW(params, c.s2s_off[2]),
-                            PW(params, c.s2s_off[3]), PW(params, c.s2s_off[4]), PW(params, c.s2s_off[5]), sv.feat, B,
-                            li.n, li.D, sv.s2s);
-            }
-            continue;
+            if (!q.dry) poison[n_poison++] = level0_error_word(wh.l0_bar);
+        } else {
+            LevelIO io = level_io(j, sv, x, adj, assign_x, dropout, sc, pkp);
+            io.pack = (j == 0 && p.pack_in_level) ? &pack : nullptr;
+            io.bar = level_bar;
+            level_forward(q, p, j, lv, io, params, sc);
+            if (p.fwd[j] == Tier::WholeLevel && !q.dry) poison[n_poison++] = level_bar + 1;
+            level_bar = nullptr;
         }
-        level_forward(q, c, li, lv, io, params, sc.Pj, sc.Uj, sc.part, sc.part_b, j == 0 ? pkp : nullptr, sc.vs,
-                      sc.lvl_part, level_bar, sc.part_all);
-        if (level_bar && !q.dry && !bn_sync(c) && level_is_fused(c, li, io, true)) poison[n_poison++] = level_bar + 1;
-        level_bar = nullptr;
+        // readout (the persistent launch wrote its own max readout; pooled levels are unmasked)
+        const float* adj_j = j == 0 ? adj : sv.lv[j - 1].An;
         const int* nn_j = (j == 0) ? num_nodes : nullptr;
         if (c.readout == 0) {
             const int rw = readout_width(c, li);
             const float* zsrc = (c.flags & DP_F_LAST_ONLY) ? lv.Ze + li.coff_e[li.L - 1] : lv.Ze;
-            if (fused_head && j == P && j > 0) {          // pooled levels are unmasked: the head kernel reads it
+            if (persistent) {
+                // (written by level0_forward above)
+            } else if (fused_head && j == P && j > 0) {          // the head kernel reads it
                 head.Z = zsrc; head.ldz = li.D; head.n = li.n; head.rw = rw; head.featoff = featoff;
                 head.argmax = lv.argmax; head.lda = rw;
             } else {
@@ -1078,7 +1130,7 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
                         PW(params, c.s2s_off[3]), PW(params, c.s2s_off[4]), PW(params, c.s2s_off[5]), sv.feat, B,
                         li.n, li.D, sv.s2s);
         }
-        if (j < P) {
+        if (j < P && !persistent) {
             const int K = li.K, n = li.n;
             // S = softmax(Za Wp^T + bp) * mask
             bgemm(q, lv.Za, PW(params, c.assign_pred_w_off[j]), sc.logits, PW(params, c.assign_pred_b_off[j]), B, n, K,
@@ -1087,7 +1139,7 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
             // index (K = n): split-K with float atomics into the zeroed outputs when the level is large.  The softmax
             // launch also zero-fills those outputs and writes the bf16 split of S for the packed A^T S pass.
             const int ksn = n >= 256 ? node_ksplit(c) : 1;
-            const bool s_split = j == 0 && pkp && aggregate_packed_usable(io.adj, n, K);
+            const bool s_split = j == 0 && pkp && aggregate_packed_usable(adj_j, n, K);
             // (deterministic split-K: partial tiles + tickets, the last range sums in range order -- float atomics
             // here made X' and A' vary in the last bit from run to run, enough to flip a near-tied max-readout
             // winner downstream and route its gradient to another row; the softmax launch zero-fills the tickets)
@@ -1099,7 +1151,7 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
             softmax_mask_fwd(q, sc.logits, K, lv.S, K, nn_j, B, n, K, j == 0 ? assign_out : nullptr,
                              s_split ? sc.vs : nullptr, sync_blk, (64 + cnt_pad) * sizeof(int));
             level_bar = sync_blk;
-            aggregate(q, io.adj, lv.S, K, lv.T, K, B, n, K, true, 0.f, j == 0 ? pkp : nullptr, sc.vs, s_split);
+            aggregate(q, adj_j, lv.S, K, lv.T, K, B, n, K, true, 0.f, j == 0 ? pkp : nullptr, sc.vs, s_split);
             {
                 // both pooled outputs in ONE launch (X' does not need T, but a launch of its own costs more than
                 // waiting for the adjacency pass)
@@ -1139,71 +1191,42 @@ int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const 
 int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const float* x, const float* adj,
                      const float* assign_x, const int* num_nodes, const float* dropout, const float* d_ypred,
                      const float* d_assign, float* grads, const void* save, int prezeroed, const PackedAdj* given) {
-    SaveLayout sv = layout_save(c, (void*)save);
+    const EncoderPlan p = encoder_plan(c, dropout != nullptr);
+    SaveLayout sv = layout_save(p, (void*)save);
     if (given) {
-        if (!level0_persistent(c) || !level0_bwd_persistent(c)) {
-            set_error("the packed-adjacency entry needs the persistent level-0 plan (see dp_encoder_forward_packed)");
-            return q.err = DP_ERR_UNSUPPORTED;
-        }
+        if (!packed_entry_ok(q, p)) return q.err;
         sv.pkA = const_cast<unsigned short*>(given->A);
         sv.pkAt = const_cast<unsigned short*>(given->At);
     }
     const int B = c.B, P = c.num_pooling;
     // ---- workspace walk
-    size_t maxPU = 0, maxPart = 0, maxSK = 0, maxMeans = 0;
-    // (the forward's barrier block, then) zero-initialised gradient accumulators + slabs: ONE block (alloc_bwd_zero)
-    int* l0_bar = q.alloc<int>(level0_bar_ints(c.B));
-    q.seq_word = level0_seq_word(l0_bar);
-    const ExchangeRegions xr = alloc_exchange(q, c);
-    const BwdZero bz = alloc_bwd_zero(q, c);
-    const bool l0_persist = level0_bwd_persistent(c);
+    const WorkspaceHead wh = alloc_head(q, p);
+    const BwdZero& bz = wh.bz;
     unsigned short* l0_vs = nullptr;
-    float *l0_part = nullptr, *l0_gpart = nullptr;
-    if (l0_persist) {
-        const Level0Bwd f0 = level0_bwd_desc(c);
-        l0_vs = q.alloc<unsigned short>(level0_bwd_vs_elems(f0));
-        l0_part = xr.l0_bwd;
-        l0_gpart = q.alloc<float>(level0_bwd_gpart_floats(f0));
+    float* l0_gpart = nullptr;
+    if (p.bwd[0] == Tier::Persistent) {
+        l0_vs = q.alloc<unsigned short>(level0_bwd_vs_elems(p.l0b));
+        l0_gpart = q.alloc<float>(level0_bwd_gpart_floats(p.l0b));
     }
     LevelGrad gr[DP_MAX_LEVELS + 1]{};
-    for (int j = 0; j <= P; ++j) gr[j] = bz.gr[j];
-    const int KS = node_ksplit(c);
-    float* slabs = bz.slabs;
-    const size_t zero_begin = bz.begin, zero_end = bz.end;
     for (int j = 0; j <= P; ++j) {
-        const LevelInfo li = level_info(c, j);
-        const size_t rows = (size_t)B * li.n;
-        if (rows * li.cmax > maxPU) maxPU = rows * li.cmax;
-        if (rows * li.G * 2 > maxPart) maxPart = rows * li.G * 2;
-        if ((size_t)li.n * li.G * 2 > maxMeans) maxMeans = (size_t)li.n * li.G * 2;
-        if (li.a && rows * li.K > maxSK) maxSK = rows * li.K;
-        gr[j].dZa = li.a ? q.alloc<float>(rows * li.Da) : nullptr;
+        const LevelInfo& li = p.lv[j];
+        gr[j] = bz.gr[j];
+        gr[j].dZa = li.a ? q.alloc<float>((size_t)B * li.n * li.Da) : nullptr;
     }
-    float* Pj = q.alloc<float>(maxPU);
-    float* dUj = q.alloc<float>(maxPU);
-    float* Gj = q.alloc<float>(maxPU);
-    float* part = q.alloc<float>(maxPart);
-    float* part_b = q.alloc<float>(maxPart);
-    float* lvl_part = xr.lvl;
-    float* part_all = bn_sync(c) ? q.alloc<float>(maxPart * bn_world(c)) : nullptr;
-    unsigned short* vs = q.alloc<unsigned short>(vs_elems(c));
-    float* dS = q.alloc<float>(maxSK ? maxSK : 1);
-    float* dlog = q.alloc<float>(maxSK ? maxSK : 1);
-    float* V = q.alloc<float>(maxSK ? maxSK : 1);
-    float* V2 = q.alloc<float>(maxSK ? maxSK : 1);
-    const size_t dsf = dropout_scratch_floats(c);
-    float* xm[2] = {dsf ? q.alloc<float>(dsf) : nullptr, dsf ? q.alloc<float>(dsf) : nullptr};
-    float* dxm[2] = {dsf ? q.alloc<float>(dsf) : nullptr, dsf ? q.alloc<float>(dsf) : nullptr};
+    Scratch sc = alloc_scratch(q, p, true);
+    sc.lvl_part = wh.xr.lvl;
+    sc.slabs = bz.slabs;
+    sc.slab_stride = c.n_graph_params;
+    sc.KS = node_ksplit(c);
     float* dh[DP_MAX_PRED + 2];
     for (int i = 0; i < c.n_pred; ++i) dh[i] = q.alloc<float>((size_t)B * c.pred_dims[i]);
     dh[c.n_pred] = const_cast<float*>(d_ypred);   // read only
-    float* dZm = nullptr;
-    if (c.readout == 1) {
-        const LevelInfo li = level_info(c, 0);
-        dZm = q.alloc<float>((size_t)B * li.n * li.D);
-    }
+    float* dZm = c.readout == 1 ? q.alloc<float>((size_t)B * p.lv[0].n * p.lv[0].D) : nullptr;
     if (q.err) return q.err;
-    const long slab_stride = c.n_graph_params;
+    float* const slabs = sc.slabs;
+    const long slab_stride = sc.slab_stride;
+    const int KS = sc.KS;
     PackedAdj pk0{sv.pkA, sv.pkAt, sv.pk_ld, sv.pk_flag};
     const PackedAdj* pkp = sv.pkA ? &pk0 : nullptr;
 
@@ -1211,9 +1234,9 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
     // column sums), so no memset of it is needed
     // (one launch: level gradient accumulators + the slabs, which receive atomic adds and leave split-K rows unused)
     // (a training forward with this workspace already cleared it on the side of its adjacency pack: prezeroed)
-    if (!prezeroed) zero_fill(q, q.ws + zero_begin, zero_end - zero_begin);
-    const bool fused_head = head_usable(c);
-    const bool fold = head_fold(c, dropout);
+    if (!prezeroed) zero_fill(q, q.ws + bz.begin, bz.end - bz.begin);
+    const bool fused_head = p.head_fused;
+    const bool fold = p.head_folded;
     SmallHeadFold hf{};
     if (fused_head) {
         // pred_model backward + the max-readout scatter of every level in one launch (or folded into the last level's)
@@ -1223,7 +1246,7 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
         hb.grads = grads;
         int featoff = 0;
         for (int j = 0; j <= P; ++j) {
-            const LevelInfo li = level_info(c, j);
+            const LevelInfo& li = p.lv[j];
             const int rw = readout_width(c, li);
             HeadBwdArgs::Level& s = hb.lv[hb.n_levels++];
             s.dZ = (c.flags & DP_F_LAST_ONLY) ? gr[j].dZe + li.coff_e[li.L - 1] : gr[j].dZe;
@@ -1232,11 +1255,11 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
             featoff += rw;
         }
         if (fold) {
-            const LevelInfo li = level_info(c, P);
+            const LevelInfo& li = p.lv[P];
             hf.hb = hb;
             hf.level = P;
             hf.zcol = (c.flags & DP_F_LAST_ONLY) ? li.coff_e[li.L - 1] : 0;
-            hf.part = xr.head;
+            hf.part = wh.xr.head;
         } else {
             head_bwd(q, hb);
         }
@@ -1260,7 +1283,7 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
         // ---- readout backward -> dZe_j
         int featoff = 0;
         for (int j = 0; j <= P; ++j) {
-            const LevelInfo li = level_info(c, j);
+            const LevelInfo& li = p.lv[j];
             if (c.readout == 0) {
                 const int rw = readout_width(c, li);
                 float* dz = (c.flags & DP_F_LAST_ONLY) ? gr[j].dZe + li.coff_e[li.L - 1] : gr[j].dZe;
@@ -1277,47 +1300,30 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
     }
     // ---- levels, top down
     for (int j = P; j >= 0; --j) {
-        const LevelInfo li = level_info(c, j);
+        const LevelInfo& li = p.lv[j];
         const LevelSave& lv = sv.lv[j];
-        LevelIO io{};
-        io.x0e = j == 0 ? x : sv.lv[j - 1].Xn;
-        io.x0a = j == 0 ? assign_x : sv.lv[j - 1].Xn;
-        io.adj = j == 0 ? adj : sv.lv[j - 1].An;
-        io.drop = dropout;
-        io.xm[0] = xm[0];
-        io.xm[1] = xm[1];
         const int n = li.n;
-        if (j == 0 && l0_persist) {
+        if (p.bwd[j] == Tier::Persistent) {
             // the whole level in ONE persistent launch (dp_level0.hip): pooling products, A V, softmax / assign head
             // backward, every GraphConv layer; each graph's parameter gradients arrive as its first slab row
-            Level0Bwd f = level0_bwd_desc(c);
-            f.A = adj;
-            f.x0[0] = x;
-            f.x0[1] = assign_x;
-            f.x_shared = f.G == 2 && x == assign_x && f.st[0].dims[0] == f.st[1].dims[0];
-            f.params = params;
-            for (int l = 0; l < li.L; ++l) {
-                f.Y[l] = lv.layer[l].Y;
-                f.invn[l] = lv.layer[l].invn;
-                f.stats[l] = lv.layer[l].stats;
-            }
-            f.Z[0] = lv.Ze;
-            f.Z[1] = lv.Za;
-            f.S = lv.S; f.Tt = lv.T;
+            Level0Bwd f = p.l0b;
+            level0_operands(f, sv, params, x, adj, assign_x);
             f.dXn = P >= 1 ? gr[1].dX0 : nullptr;
             f.dAn = P >= 1 ? gr[1].dAdj : nullptr;
             f.d_assign = d_assign;
             f.dZe = gr[0].dZe;
-            f.pkA = sv.pkA; f.pkAt = sv.pkAt; f.pk_flag = sv.pk_flag; f.pk_sym = sv.pk_sym;
             f.slabs = slabs;
             f.slab_gstride = slab_stride * KS;
-            f.vs = l0_vs; f.part = l0_part; f.gpart = l0_gpart;
-            f.bar = l0_bar;
+            f.vs = l0_vs; f.part = wh.xr.l0_bwd; f.gpart = l0_gpart;
+            f.bar = wh.l0_bar;
             level0_backward(q, f);
             continue;
         }
+        LevelIO io = level_io(j, sv, x, adj, assign_x, dropout, sc, pkp);
         if (j < P) {
             const int K = li.K, D = li.D;
+            float *const dS = sc.dS, *const dlog = sc.dlog, *const V = sc.V, *const V2 = sc.V2;
+            unsigned short* const vs = sc.vs;
             bool vsplit_used = false;
             const float* dS2 = nullptr;
             const float* dXn = gr[j + 1].dX0;
@@ -1370,22 +1376,24 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
                 bgemm_group(q, d2, 2, B, ksn);
             }
         }
-        level_backward(q, c, li, lv, io, params, gr[j], slabs, slab_stride, KS, Pj, dUj, Gj, part, part_b,
-                       j == 0 ? pkp : nullptr, vs, dxm, lvl_part, bz.bar + 64 * j, part_all,
-                       fold && j == P ? &hf : nullptr);
+        io.bar = bz.bar + 64 * j;
+        io.gr = &gr[j];
+        io.hf = fold && j == P ? &hf : nullptr;
+        level_backward(q, p, j, lv, io, params, sc);
     }
     reduce_slabs(q, slabs, slab_stride, B * KS, grads, c.n_graph_params, 0);
     return q.err;
 }
 
-size_t encoder_save_bytes(const dp_encoder_cfg& c) { return layout_save(c, nullptr).total; }
+size_t encoder_save_bytes(const dp_encoder_cfg& c) { return layout_save(encoder_plan(c, false), nullptr).total; }
 
 // byte offset / float count of one saved activation of level `level` inside the save buffer (read-back for logging
 // and tests; -1 when the level has no such tensor)
 int encoder_save_locate(const dp_encoder_cfg& c, int level, int field, size_t* offset, size_t* count) {
     char* const base = reinterpret_cast<char*>(size_t(1) << 20);       // any non-null base: only differences are used
-    SaveLayout sv = layout_save(c, base);
-    const LevelInfo li = level_info(c, level);
+    const EncoderPlan plan = encoder_plan(c, false);
+    SaveLayout sv = layout_save(plan, base);
+    const LevelInfo& li = plan.lv[level];
     const LevelSave& lv = sv.lv[level];
     const size_t B = c.B;
     const void* p = nullptr;
