@@ -36,6 +36,7 @@
 // bf16 MFMA with fp32 accumulation, every product exact; a graph whose adjacency is NOT bf16-exact takes an fp32 MFMA
 // loop that reads the fp32 adjacency from global memory (correct, slow; decided per graph on the device).
 #include "dp_common.h"
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -284,6 +285,47 @@ __device__ __forceinline__ void l0_copy_in(float* dst, const float* src, int cou
     }
     if (te < count) dst[te] = tail;
     for (int e = count + (int)threadIdx.x; e < zero_to; e += L0_NT) dst[e] = 0.f;
+}
+
+// l0_copy_in in two halves, so that other loads can be asked for between them and stay in flight past the commit
+// (loads return in order: what is issued BEHIND issue() does not hold the commit up).  issue() asks for the first
+// QN quads per thread and the tail; commit() writes them; a region of more than QN * L0_NT quads needs l0_copy_rest()
+// behind its commit (one quad per thread and round trip, behind everything in flight: compact code for a rare shape).
+// issue() is branch-free (count >= 1; `safe` is any readable 16 bytes, read when the region has no whole quad): the
+// compiler's counted vmcnt in front of the commit then leaves exactly the later loads in flight — around a branch it
+// counts the shorter side.
+template <int QN>
+struct L0CopyStage {
+    f32x4_u q[QN];
+    float tail;
+};
+template <int QN>
+__device__ __forceinline__ void l0_copy_issue(L0CopyStage<QN>& s, const float* src, int count, const void* safe) {
+    const int nq = count >> 2;
+    s.tail = src[min((nq << 2) + (int)threadIdx.x, count - 1)];
+    const float* const qs = nq > 0 ? src : static_cast<const float*>(safe);
+#pragma unroll
+    for (int u = 0; u < QN; ++u)
+        s.q[u] = *reinterpret_cast<const f32x4_u*>(qs + 4 * min(u * L0_NT + (int)threadIdx.x, max(nq - 1, 0)));
+}
+template <int QN>
+__device__ __forceinline__ void l0_copy_commit(const L0CopyStage<QN>& s, float* dst, int count, int zero_to = 0) {
+    const int nq = count >> 2;
+    const int te = (nq << 2) + (int)threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < QN; ++u) {
+        const int e4 = u * L0_NT + (int)threadIdx.x;
+        if (e4 < nq) *reinterpret_cast<f32x4*>(dst + 4 * e4) = s.q[u];
+    }
+    if (te < count) dst[te] = s.tail;
+    for (int e = count + (int)threadIdx.x; e < zero_to; e += L0_NT) dst[e] = 0.f;
+}
+template <int QN>
+__device__ __forceinline__ void l0_copy_rest(float* dst, const float* src, int count) {
+    const int nq = count >> 2;
+#pragma unroll 1
+    for (int e4 = QN * L0_NT + (int)threadIdx.x; e4 < nq; e4 += L0_NT)
+        *reinterpret_cast<f32x4*>(dst + 4 * e4) = *reinterpret_cast<const f32x4_u*>(src + 4 * e4);
 }
 
 // ---- the exact 3-plane bf16 split of PT [rows][ct] (LDS) into the graph's Vs block (dp_agg.hip layout
@@ -595,76 +637,111 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
     }
     L0_STAMP(1);
     const int din0_0 = f.st[0].dims[0], din0_1 = G == 2 ? f.st[1].dims[0] : 0;
-    // (a) my rows of the fp32 adjacency -> bf16: LDS block, packed A rows, exactness.  The layer-0 inputs, weights and
-    // every bias are asked for right behind the adjacency quads, so they arrive under the same burst.
+    // Order: P_0 = [x_e W_e | x_a W_a] does not read the adjacency, so it runs UNDER the adjacency burst (a memory-system
+    // phase: every workgroup of the grid streams its rows at once).  Loads return in order, hence
+    //   ask for the layer-0 inputs and weights, THEN for segment 0 of my adjacency rows;
+    //   commit the side loads to LDS (a counted vmcnt: the adjacency quads stay in flight), lds_barrier (LDS counter only);
+    //   (d) the two products into PT, lds_barrier, the split of PT: its stores leave while the quads still arrive;
+    //   (a) the adjacency quads -> bf16: LDS block, packed A rows, exactness; block flag, barrier;
+    //   (c) the A^T strip, and the biases' one round trip under its store acknowledgements (barrier 0 drains both).
     bool bad = false;
     float* const X0s0 = SCR;
     float* const X0s1 = X0s0 + RB * din0_0;
     float* const W0s0 = X0s1 + RB * din0_1;
     float* const W0s1 = W0s0 + ((din0_0 * f.st[0].dims[1] + 3) & ~3);
     float* const PT = W0s1 + (G == 2 ? ((din0_1 * f.st[1].dims[1] + 3) & ~3) : 0);
-    const auto side_loads = [&]() {
-        l0_copy_in<4>(X0s0, f.x0[0] + ((long)b * N + r0) * din0_0, nrows * din0_0, RB * din0_0);
-        l0_copy_in<4>(W0s0, f.params + f.st[0].w_off[0], din0_0 * f.st[0].dims[1]);
-        if (G == 2) {
-            // (one tensor for both stacks — the usual call: the second product reads the first copy)
-            if (!f.x_shared) l0_copy_in<4>(X0s1, f.x0[1] + ((long)b * N + r0) * din0_1, nrows * din0_1, RB * din0_1);
-            l0_copy_in<4>(W0s1, f.params + f.st[1].w_off[0], din0_1 * f.st[1].dims[1]);
-        }
-        // biases: one 64-float slot per (layer, stack), zeros where a layer has none
-        for (int e = tid; e < (2 * L + 1) * 64; e += L0_NT) {
-            const int slot = e >> 6, c = e & 63;
-            float v0 = 0.f;
-            if (slot < 2 * L) {
-                const int l = slot >> 1, g = slot & 1;
-                if (g < G && f.st[g].b_off[l] >= 0 && c < f.st[g].dims[l + 1]) v0 = f.params[f.st[g].b_off[l] + c];
-            } else if (G == 2 && f.bp_off >= 0 && c < f.K) {
-                v0 = f.params[f.bp_off + c];
-            }
-            BIAS[(slot < 2 * L ? slot : 2 * DP_MAX_LAYERS) * 64 + c] = v0;
-        }
-    };
-    if (f.A) {
-        const float* Ab = f.A + ((long)b * N + r0) * N;
-        unsigned short* Pb = f.pkA + ((long)b * N + r0) * f.pk_ld;
-        const int tq = tid & 127, tr = tid >> 7;           // 128 column quads x 4 row lanes
-        const int segs = (a.steps * 32 + 511) / 512;
-        for (int seg = 0; seg < segs; ++seg) {
-            const int c = seg * 512 + 4 * tq;
-            f32x4_u v[4 * MI];
+    // (one x tensor for both stacks — the usual call: the second product reads the first copy)
+    const bool own_x1 = G == 2 && !f.x_shared;
+    const float* const xg0 = f.x0[0] + ((long)b * N + r0) * din0_0;
+    const float* const xg1 = own_x1 ? f.x0[1] + ((long)b * N + r0) * din0_1 : xg0;
+    const float* const wg0 = f.params + f.st[0].w_off[0];
+    const float* const wg1 = G == 2 ? f.params + f.st[1].w_off[0] : wg0;
+    const int wn0_0 = din0_0 * f.st[0].dims[1], wn0_1 = G == 2 ? din0_1 * f.st[1].dims[1] : 0;
+    const int segs = (a.steps * 32 + 511) / 512;
+    const int ct0 = f.st[0].dims[1] + (G == 2 ? f.st[1].dims[1] : 0);
+    const int CTt0 = (ct0 + 15) / 16;
+    const int k8_0 = r0 / 8;
+    const int nk8 = min(rb == a.T - 1 ? a.K8 - k8_0 : RB / 8, a.K8 - k8_0);
+    const bool big_x = RB * max(din0_0, din0_1) > 4 * 4 * L0_NT;      // input rows past the 4 quads per thread of a stage
+    // One body per adjacency form (fp32 in: f.A; packed bf16 in: dp_encoder_forward_packed), so that each has a straight
+    // line of loads and its counted waits leave ALL of its adjacency quads in flight across the products.
+    const auto phase0 = [&](auto fp32_in) {
+        constexpr bool FP32 = decltype(fp32_in)::value;
+        L0CopyStage<4> sx0, sx1, sw0, sw1;
+        l0_copy_issue<4>(sx0, xg0, nrows * din0_0, f.bar);
+        l0_copy_issue<4>(sw0, wg0, wn0_0, f.bar);
+        if (own_x1) l0_copy_issue<4>(sx1, xg1, nrows * din0_1, f.bar);
+        if (G == 2) l0_copy_issue<4>(sw1, wg1, wn0_1, f.bar);
+        // segment 0 of my adjacency rows
+        const float* const Ab = f.A + ((long)b * N + r0) * N;
+        unsigned short* const Pb = f.pkA + ((long)b * N + r0) * f.pk_ld;
+        const int tq = tid & 127, tr = tid >> 7;           // fp32: 128 column quads x 4 row lanes
+        f32x4_u v[FP32 ? 4 * MI : 1];
+        L0RowStage<MI> q;
+        if constexpr (FP32) {
 #pragma unroll
             for (int u = 0; u < 4 * MI; ++u)
-                v[u] = *reinterpret_cast<const f32x4_u*>(Ab + (long)min(tr + 4 * u, nrows - 1) * N + min(c, N - 4));
-            if (seg == 0) side_loads();
+                v[u] = *reinterpret_cast<const f32x4_u*>(Ab + (long)min(tr + 4 * u, nrows - 1) * N + min(4 * tq, N - 4));
+        } else {
+            l0_stage_issue<MI>(q, Pb, f.pk_ld, nrows, 0);
+        }
+        l0_copy_commit<4>(sx0, X0s0, nrows * din0_0, RB * din0_0);
+        l0_copy_commit<4>(sw0, W0s0, wn0_0);
+        if (own_x1) l0_copy_commit<4>(sx1, X0s1, nrows * din0_1, RB * din0_1);
+        if (G == 2) l0_copy_commit<4>(sw1, W0s1, wn0_1);
+        if (big_x) {                                       // (uniform, rare; a layer's weights never exceed the stage)
+            l0_copy_rest<4>(X0s0, xg0, nrows * din0_0);
+            if (own_x1) l0_copy_rest<4>(X0s1, xg1, nrows * din0_1);
+        }
+        lds_barrier();
+        L0_STAMP(2);
+        // (d) P_0 = [x_e W_e | x_a W_a] of my rows
+        for (int g = 0; g < G; ++g) {
+            const int dout = f.st[g].dims[1], c0 = g ? f.st[0].dims[1] : 0;
+            const float* xs = g && !f.x_shared ? X0s1 : X0s0;
+            l0_mma<false, false>(xs, g ? din0_1 : din0_0, g ? W0s1 : W0s0, dout, RB, dout, g ? din0_1 : din0_0,
+                                 [&](int r, int c, float pv) { PT[r * ct0 + c0 + c] = pv; }, g * 3);
+        }
+        lds_barrier();                                     // PT is whole (the adjacency quads are still in flight)
+        L0_STAMP(3);
+        // ... and its split: the stores leave under the burst too
+        l0_write_split(vs_wr(0, CTt0), PT, ct0, CTt0, a.K8, k8_0, nk8, nrows);
+        L0_STAMP(4);
+        // (a) the quads in flight, then (N > 512) the later segments one round trip each
+        if constexpr (FP32) {
+            for (int seg = 0; seg < segs; ++seg) {
+                const int c = seg * 512 + 4 * tq;
+                if (seg > 0) {
 #pragma unroll
-            for (int u = 0; u < 4 * MI; ++u) {
-                const int row = tr + 4 * u;
-                const bool in = row < nrows && c < N;
-                u16x4 h;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned bits = in ? __float_as_uint(v[u][j]) : 0u;
-                    bad |= (bits & 0xFFFFu) != 0;
-                    h[j] = (unsigned short)(bits >> 16);
+                    for (int u = 0; u < 4 * MI; ++u)
+                        v[u] = *reinterpret_cast<const f32x4_u*>(Ab + (long)min(tr + 4 * u, nrows - 1) * N + min(c, N - 4));
                 }
-                if (c < a.ldp) *reinterpret_cast<u16x4*>(Alds + row * a.ldp + c) = h;
-                if (row < nrows && c < f.pk_ld) *reinterpret_cast<u16x4*>(Pb + (long)row * f.pk_ld + c) = h;
+#pragma unroll
+                for (int u = 0; u < 4 * MI; ++u) {
+                    const int row = tr + 4 * u;
+                    const bool in = row < nrows && c < N;
+                    u16x4 h;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned bits = in ? __float_as_uint(v[u][j]) : 0u;
+                        bad |= (bits & 0xFFFFu) != 0;
+                        h[j] = (unsigned short)(bits >> 16);
+                    }
+                    if (c < a.ldp) *reinterpret_cast<u16x4*>(Alds + row * a.ldp + c) = h;
+                    if (row < nrows && c < f.pk_ld) *reinterpret_cast<u16x4*>(Pb + (long)row * f.pk_ld + c) = h;
+                }
+            }
+        } else {
+            // my bf16 rows go to LDS as they are
+            for (int seg = 0; seg < segs; ++seg) {
+                if (seg > 0) l0_stage_issue<MI>(q, Pb, f.pk_ld, nrows, seg);
+                l0_stage_commit<MI>(q, Alds, a.ldp, f.pk_ld, nrows, seg);
             }
         }
-    } else {
-        // the adjacency arrives packed (dp_encoder_forward_packed): my bf16 rows go to LDS as they are
-        L0RowStage<MI> q;
-        const unsigned short* rows = f.pkA + ((long)b * N + r0) * f.pk_ld;
-        l0_stage_issue<MI>(q, rows, f.pk_ld, nrows, 0);
-        side_loads();
-        l0_stage_commit<MI>(q, Alds, a.ldp, f.pk_ld, nrows, 0);
-        const int segs = (a.steps * 32 + 511) / 512;
-        for (int seg = 1; seg < segs; ++seg) {
-            l0_stage_issue<MI>(q, rows, f.pk_ld, nrows, seg);
-            l0_stage_commit<MI>(q, Alds, a.ldp, f.pk_ld, nrows, seg);
-        }
-    }
-    L0_STAMP(2);
+    };
+    if (f.A) phase0(std::true_type{});
+    else phase0(std::false_type{});
+    L0_STAMP(5);
     // side job: clear the backward accumulators (behind the adjacency burst: the stores drain under the phases below)
     if (f.zero_p) {
         uint4* zp = reinterpret_cast<uint4*>(f.zero_p);
@@ -673,8 +750,7 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
         for (long i = (long)wid * per + tid; i < end; i += L0_NT) zp[i] = make_uint4(0, 0, 0, 0);
     }
     if (__any(bad) && lane == 0) sflag[2] = 1;
-    lds_barrier();
-    L0_STAMP(3);
+    lds_barrier();                                         // Alds and the block flag are whole
     const bool blk_bad = sflag[2] != 0;
     if (blk_bad && tid == 0) {
         ag_st(f.bar + BAR_GRAPH0 + b * BAR_GSTRIDE + BAR_G_INEXACT, 1);
@@ -694,22 +770,19 @@ __global__ __launch_bounds__(L0_NT) void k_level0_fwd(L0Args a) {
             }
         }
     }
-    L0_STAMP(4);
-    // (d) P_0 = [x_e W_e | x_a W_a] of my rows, then its split
-    int ct = f.st[0].dims[1] + (G == 2 ? f.st[1].dims[1] : 0);
-    for (int g = 0; g < G; ++g) {
-        const int dout = f.st[g].dims[1], c0 = g ? f.st[0].dims[1] : 0;
-        const float* xs = g && !f.x_shared ? X0s1 : X0s0;
-        l0_mma<false, false>(xs, g ? din0_1 : din0_0, g ? W0s1 : W0s0, dout, RB, dout, g ? din0_1 : din0_0,
-                             [&](int r, int c, float v) { PT[r * ct + c0 + c] = v; }, g * 3);
-    }
-    lds_barrier();
-    L0_STAMP(5);
-    const int k8_0 = r0 / 8;
-    const int nk8 = min(rb == a.T - 1 ? a.K8 - k8_0 : RB / 8, a.K8 - k8_0);
-    {
-        const int CTt = (ct + 15) / 16;
-        l0_write_split(vs_wr(0, CTt), PT, ct, CTt, a.K8, k8_0, nk8, nrows);
+    int ct = ct0;
+    // biases: one 64-float slot per (layer, stack), zeros where a layer has none; first read in layer 0's tail.  Here their
+    // round trip falls under the store acknowledgements the arrive waits for anyway.  A wave fills a slot (scalar offsets:
+    // per-lane lookups in the argument block would be vector loads, three dependent round trips).
+    for (int slot = __builtin_amdgcn_readfirstlane(tid >> 6); slot <= 2 * L; slot += L0_NW) {
+        float v0 = 0.f;
+        if (slot < 2 * L) {
+            const int l = slot >> 1, g = slot & 1;
+            if (g < G && f.st[g].b_off[l] >= 0 && lane < f.st[g].dims[l + 1]) v0 = f.params[f.st[g].b_off[l] + lane];
+        } else if (G == 2 && f.bp_off >= 0 && lane < f.K) {
+            v0 = f.params[f.bp_off + lane];
+        }
+        BIAS[(slot < 2 * L ? slot : 2 * DP_MAX_LAYERS) * 64 + lane] = v0;
     }
     L0_STAMP(6);
     bool ok = l0_barrier(a, b, sflag, ep);

@@ -18,8 +18,9 @@ torch.cuda.synchronize()
 buf = (C.c_ulonglong * 192)()
 lib.dp_debug_l0_stamps.restype = C.c_int
 assert lib.dp_debug_l0_stamps(buf) == 0
-names = {0: "entry", 1: "side zero", 2: "A rows -> LDS + pkA", 3: "x, W0 staged + sync", 4: "A^T strip", 5: "P0 mma + sync",
-         6: "P0 split written", 7: "graph barrier 0"}
+names = {0: "entry", 1: "side zero", 2: "x, W0, A asked; x, W0 staged + sync", 3: "P0 mma + sync (A quads in flight)",
+         4: "P0 split written (A quads in flight)", 5: "A quads -> LDS + pkA", 6: "block flag + sync, A^T strip, biases",
+         7: "graph barrier 0"}
 for l in range(3):
     o = 8 + 8 * l
     names.update({o: f"L{l} aggregate", o + 1: f"L{l} sync", o + 2: f"L{l} tail", o + 3: f"L{l} (no barrier: polled below)",
