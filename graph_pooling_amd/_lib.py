@@ -167,6 +167,9 @@ _PROTOS = {
     "dp_linkpred_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_linkpred_loss_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_linkpred_loss_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_assign_entropy_workspace_bytes": (_Z, [_I, _I, _I]),
+    "dp_assign_entropy_fwd": (_I, [_P, _I, _P, _F, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "dp_assign_entropy_bwd": (_I, [_P, _I, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
     "dp_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dp_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dp_set2set_save_bytes": (_Z, [_I, _I, _I]),

@@ -936,6 +936,35 @@ int dp_linkpred_loss_bwd_packed(const float* S, const void* adj_pk, const void* 
     return q.err;
 }
 
+size_t dp_assign_entropy_workspace_bytes(int B, int n, int K) {
+    if (B < 1 || n < 1 || K < 1) return 0;
+    return sized([&](Seq& q) { assign_entropy_fwd(q, 0, K, 0, 0.f, 0, 0, B, n, K); });
+}
+int dp_assign_entropy_fwd(const float* S, int lds, const int* num_nodes, float weight, float* ent_out,
+                          float* total_inout, int B, int n, int K, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    NOTNULL(S); NOTNULL(ent_out);
+    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_CHECK_ARG(lds >= K, "dp_assign_entropy_fwd: lds=%d smaller than K=%d", lds, K);
+    NOTNULL(workspace);
+    DP_CHECK_ARG(workspace_bytes >= dp_assign_entropy_workspace_bytes(B, n, K),
+                 "dp_assign_entropy_fwd: workspace too small: need >= %zu bytes, have %zu",
+                 dp_assign_entropy_workspace_bytes(B, n, K), workspace_bytes);
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    assign_entropy_fwd(q, S, lds, num_nodes, weight, ent_out, total_inout, B, n, K);
+    return q.err;
+}
+int dp_assign_entropy_bwd(const float* S, int lds, const int* num_nodes, const float* dloss, float weight, float* dS,
+                          int ldds, int accumulate, int B, int n, int K, void* stream) {
+    NOTNULL(S); NOTNULL(dS);
+    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_CHECK_ARG(lds >= K, "dp_assign_entropy_bwd: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG(ldds >= K, "dp_assign_entropy_bwd: ldds=%d smaller than K=%d", ldds, K);
+    Seq q(STREAM(stream), nullptr, 0);
+    assign_entropy_bwd(q, S, lds, num_nodes, dloss, weight, dS, ldds, accumulate, B, n, K);
+    return q.err;
+}
+
 int dp_cross_entropy_fwd(const float* logits, const long long* label, float* loss_out, float* prob, int B, int C,
                          void* stream) {
     NOTNULL(logits); NOTNULL(label); NOTNULL(loss_out);

@@ -655,4 +655,18 @@ void linkpred_bwd_packed(Seq& q, const float* S, int lds, const unsigned short* 
                          const int* num_nodes, const float* dloss, float* dS, int ldds, int B, int n, int K,
                          int accumulate, const float* norm = nullptr);
 
+// (dp_assign_ent.hip) row entropy of the assignment: E = sum_{valid rows} -s ln(s + 1e-15) / (valid rows)
+struct AssignEntPick {
+    int lanes;       // lanes that serve one row: 4, 16 or 64
+    int quad;        // 1: 16-byte lanes
+};
+// dS == nullptr: the forward (S alone decides).  Host only; both launchers launch what it answers.
+AssignEntPick assign_ent_pick(const void* S, int lds, const void* dS, int ldds, int K);
+size_t assign_ent_part_doubles();
+// ent_out[0] = E; total_inout (or null): += weight * E, by the launch that finishes the sum
+void assign_entropy_fwd(Seq& q, const float* S, int lds, const int* num_nodes, float weight, float* ent_out,
+                        float* total_inout, int B, int n, int K);
+void assign_entropy_bwd(Seq& q, const float* S, int lds, const int* num_nodes, const float* dloss, float weight,
+                        float* dS, int ldds, int accumulate, int B, int n, int K);
+
 }  // namespace dp

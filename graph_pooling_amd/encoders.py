@@ -17,6 +17,7 @@ Reference defects and the semantics chosen here: SURVEY.md Appendix B / DESIGN.m
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -592,7 +593,7 @@ class _Loss(torch.Tensor):
 
 class _LossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, label, S, adj, num_nodes, linkpred, link_norm=None):
+    def forward(ctx, pred, label, S, adj, num_nodes, linkpred, link_norm=None, ent_w=0.0):
         lib = _lib.load()
         _lib.require_gpu_tensor(pred, "pred")
         pred = pred.contiguous().float()
@@ -627,21 +628,38 @@ class _LossFn(torch.autograd.Function):
         ctx.packed = packed
         ctx.link_norm = link_norm if linkpred else None
         ctx.dims = (B, Cc, N, K, bool(linkpred))
+        ctx.ent_w = ent_w
         total, link = out[0], out[1]
         ctx.mark_non_differentiable(link)
         ctx.set_materialize_grads(False)      # no zero-fill launch for the unused gradient of `link`
-        return total, link
+        if not ent_w > 0:
+            return total, link
+        # + ent_w * E(S): the kernel that finishes E adds the weighted term to the total itself (no torch add)
+        S = S.contiguous()
+        Be, Ne, Ke = S.shape
+        ewsb = lib.dp_assign_entropy_workspace_bytes(Be, Ne, Ke)
+        ews = torch.empty(ewsb, device=pred.device, dtype=torch.uint8)
+        ent = torch.empty((), device=pred.device, dtype=torch.float32)
+        _lib.check(lib.dp_assign_entropy_fwd(S.data_ptr(), Ke, _lib.ptr(num_nodes), ent_w, ent.data_ptr(),
+                                             out.data_ptr(), Be, Ne, Ke, ews.data_ptr(), ewsb, _lib.current_stream()),
+                   "dp_assign_entropy_fwd")
+        ctx.ent_S = S
+        ctx.mark_non_differentiable(ent)
+        return total, link, ent
 
     @staticmethod
-    def backward(ctx, dtotal, _dlink):
+    def backward(ctx, dtotal, _dlink, _dent=None):
         lib = _lib.load()
         prob, dunit, label, S, adj, num_nodes, ws = ctx.saved
         B, Cc, N, K, linkpred = ctx.dims
+        ent_w = ctx.ent_w
         if dtotal is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         unit = bool(getattr(ctx, "unit_armed", False))     # armed by _Loss.backward: the upstream gradient is exactly 1
         if unit and not linkpred:
-            return dunit, None, None, None, None, None, None     # written by the loss kernel: nothing to launch
+            if ent_w > 0:                                  # dS of the entropy term alone, for an upstream gradient of 1
+                return dunit, None, _ent_backward(lib, ctx, None, None), None, None, None, None, None
+            return dunit, None, None, None, None, None, None, None     # written by the loss kernel: nothing to launch
         dtotal = dtotal.contiguous().float()
         dpred = dunit if unit else torch.empty(B, Cc, device=prob.device, dtype=torch.float32)
         dS = torch.empty_like(S) if linkpred else None
@@ -654,11 +672,27 @@ class _LossFn(torch.autograd.Function):
         else:
             _lib.check(lib.dp_loss_backward(prob.data_ptr(), label.data_ptr(), _lib.ptr(S), _lib.ptr(adj), *tail),
                        "dp_loss_backward")
-        return dpred, None, dS, None, None, None, None
+        if ent_w > 0:                                      # after the link term's dS: added to it; alone: written
+            dS = _ent_backward(lib, ctx, None if unit else dtotal, dS)
+        return dpred, None, dS, None, None, None, None, None
 
 
-def _loss(owner, pred, label, S, adj, batch_num_nodes, linkpred):
-    nn_dev = _num_nodes_device(batch_num_nodes, pred.device) if linkpred else None
+def _ent_backward(lib, ctx, dtotal, dS):
+    """dS (+)= dtotal * ent_w * dE/dS on dp_assign_entropy_bwd: added to the link term's dS when there is one, written
+    (masked rows zero) otherwise.  dtotal None: an upstream gradient of exactly 1."""
+    S = ctx.ent_S
+    Be, Ne, Ke = S.shape
+    acc = dS is not None
+    if not acc:
+        dS = torch.empty_like(S)
+    _lib.check(lib.dp_assign_entropy_bwd(S.data_ptr(), Ke, _lib.ptr(ctx.saved[5]), _lib.ptr(dtotal), ctx.ent_w,
+                                         dS.data_ptr(), Ke, int(acc), Be, Ne, Ke, _lib.current_stream()),
+               "dp_assign_entropy_bwd")
+    return dS
+
+
+def _loss(owner, pred, label, S, adj, batch_num_nodes, linkpred, ent_w=0.0):
+    nn_dev = _num_nodes_device(batch_num_nodes, pred.device) if linkpred or ent_w > 0 else None
     link_norm = None
     sync = getattr(owner, "_sync_bn", None)
     if linkpred and sync is not None and sync.active:
@@ -667,7 +701,9 @@ def _loss(owner, pred, label, S, adj, batch_num_nodes, linkpred):
         n_eff = nn_dev.clamp(max=S.shape[1]).float() if nn_dev is not None else \
             torch.full((S.shape[0],), float(S.shape[1]), device=pred.device)
         link_norm = sync.all_reduce_sum((n_eff * n_eff).sum().reshape(1)) / float(sync.world)
-    total, link = _LossFn.apply(pred, label, S, adj, nn_dev, linkpred, link_norm)
+    total, link, *ent = _LossFn.apply(pred, label, S, adj, nn_dev, linkpred, link_norm, ent_w)
+    if ent:
+        owner.assign_ent_loss = ent[0]
     if linkpred:
         owner.link_loss = link
     _unit_seed(pred.device)                   # make sure the cached seed exists before anyone captures a graph
@@ -715,6 +751,26 @@ class GcnSet2SetEncoder(GcnEncoderGraph):
 
 
 # ----------------------------------------------------------------------------- DiffPool
+def _check_ent_weight(w):
+    """assign_ent_weight as a float; negative or non-finite values are refused."""
+    try:
+        w = float(w)
+    except (TypeError, ValueError):
+        raise ValueError(f"assign_ent_weight must be a finite number >= 0, got {w!r}") from None
+    if not math.isfinite(w) or w < 0:
+        raise ValueError(f"assign_ent_weight must be a finite number >= 0, got {w!r}")
+    return w
+
+
+def _refuse_ent_under_sync_bn(owner):
+    sync = getattr(owner, "_sync_bn", None)
+    if sync is not None and sync.active:
+        raise NotImplementedError("assign_ent_weight > 0 under sync-BN: the entropy term divides by the valid nodes of "
+                                  "the WHOLE batch, and the global normaliser (an all-reduce of sum_b n_b, as the link "
+                                  "term has for sum_b n_b^2) is not built; train with local BatchNorm statistics, where "
+                                  "each rank normalises by its own nodes")
+
+
 class SoftPoolingGcnEncoder(GcnEncoderGraph):
     """DiffPool (encoders.py:1160-1334)."""
 
@@ -723,7 +779,7 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
     def __init__(self, max_num_nodes, input_dim, hidden_dim, embedding_dim, label_dim, num_layers,
                  assign_hidden_dim, assign_ratio=0.25, assign_num_layers=-1, num_pooling=1,
                  pred_hidden_dims=[50], concat=True, bn=True, dropout=0.0, linkpred=True,
-                 assign_input_dim=-1, args=None):
+                 assign_input_dim=-1, args=None, assign_ent_weight=0.0):
         # the reference does not forward bn / dropout to the level-0 encoder (encoders.py:1172-1173)
         super().__init__(input_dim, hidden_dim, embedding_dim, label_dim, num_layers,
                          pred_hidden_dims=pred_hidden_dims, concat=concat, args=args)
@@ -733,6 +789,7 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
                              "1186) and fails with a shape error; not supported")
         if num_pooling < 1 or num_pooling > _lib.DP_MAX_LEVELS:
             raise ValueError(f"num_pooling must be in [1, {_lib.DP_MAX_LEVELS}]")
+        self.assign_ent_weight = _check_ent_weight(assign_ent_weight)
         add_self = not concat
         self.num_pooling = num_pooling
         self.linkpred = linkpred
@@ -793,6 +850,9 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
         self._init_graph_convs()
         self.assign_tensor = None
         self.link_loss = None
+        # the unweighted entropy term E of the last loss() with assign_ent_weight > 0 (a non-differentiable device
+        # scalar, as link_loss holds the link term); None until then
+        self.assign_ent_loss = None
 
     def _graph_param_groups(self):
         groups = super()._graph_param_groups()
@@ -849,9 +909,19 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
     def loss(self, pred, label, adj=None, batch_num_nodes=None, adj_hop=1):
         if adj_hop != 1:
             raise NotImplementedError("adj_hop > 1 is never used by the reference's callers (train.py:207)")
+        w = self.assign_ent_weight
+        if w > 0:
+            _refuse_ent_under_sync_bn(self)
         if self.linkpred:
             if adj is None:
                 raise ValueError("linkpred=True: loss() needs adj (train.py:207 passes it)")
             # adj: the dense fp32 batch or the PackedAdjacency the forward ran on (dp_loss_forward_packed)
-            return _loss(self, pred, label, self.assign_tensor, adj, batch_num_nodes, True)
+            return _loss(self, pred, label, self.assign_tensor, adj, batch_num_nodes, True, w)
+        if w > 0:
+            # + w * E(S_0), E = sum over the valid rows of -s ln(s + 1e-15) / (valid rows): batch_num_nodes says which
+            # rows are nodes (None: all N), the normaliser counts them, not B * N
+            if self.assign_tensor is None:
+                raise ValueError("assign_ent_weight > 0: loss() scores the assignment of the last forward, and no "
+                                 "forward pass has run yet")
+            return _loss(self, pred, label, self.assign_tensor, None, batch_num_nodes, False, w)
         return _loss(self, pred, label, None, None, None, False)

@@ -635,3 +635,52 @@ def csr_link_loss(s, graph):
     (0/1 adjacency, each edge listed once): dp_csr_linkpred_loss_* — a tile walk over s for the n^2 term that does not
     depend on the adjacency plus a gather over the edges, O(n k) memory.  Returns the device scalar."""
     return _CsrLinkLossFn.apply(s, graph)
+
+
+# ----------------------------------------------------------------------------- assignment entropy
+class _AssignEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, num_nodes):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(s, "s")
+        s = s.contiguous().float()
+        b, n, k = (1,) + tuple(s.shape) if s.dim() == 2 else tuple(s.shape)
+        ent = _f32(s, ())
+        wsb = lib.dp_assign_entropy_workspace_bytes(b, n, k)
+        ws = _workspace(wsb, s)
+        _lib.check(lib.dp_assign_entropy_fwd(s.data_ptr(), k, _lib.ptr(num_nodes), 1.0, ent.data_ptr(), None, b, n, k,
+                                             ws.data_ptr(), wsb, _lib.current_stream()), "dp_assign_entropy_fwd")
+        ctx.save_for_backward(s)
+        ctx.num_nodes, ctx.dims = num_nodes, (b, n, k)
+        return ent
+
+    @staticmethod
+    def backward(ctx, dent):
+        lib = _lib.load()
+        (s,) = ctx.saved_tensors
+        b, n, k = ctx.dims
+        dent = dent.contiguous().float()
+        ds = torch.empty_like(s)
+        _lib.check(lib.dp_assign_entropy_bwd(s.data_ptr(), k, _lib.ptr(ctx.num_nodes), dent.data_ptr(), 1.0,
+                                             ds.data_ptr(), k, 0, b, n, k, _lib.current_stream()),
+                   "dp_assign_entropy_bwd")
+        return ds, None
+
+
+def assign_entropy(s, num_nodes=None):
+    """DiffPool's assignment-entropy term E = sum over the valid rows of -s ln(s + 1e-15) / (number of valid rows) on
+    dp_assign_entropy_*: s [rows, K] (a ragged assignment: every row is a node) or [B, n, K] with `num_nodes` int32 [B]
+    on the device naming each graph's valid rows (None: all n).  The normaliser counts valid rows, not B * n.  Returns
+    the device scalar."""
+    if not isinstance(s, torch.Tensor) or s.dim() not in (2, 3):
+        got = tuple(s.shape) if isinstance(s, torch.Tensor) else type(s).__name__
+        raise ValueError(f"assign_entropy(s, num_nodes): s must be [rows, K] or [B, n, K], got {got}")
+    if num_nodes is not None:
+        if s.dim() != 3:
+            raise ValueError("assign_entropy(s, num_nodes): num_nodes goes with s [B, n, K]")
+        _lib.require_gpu_tensor(num_nodes, "num_nodes")
+        if num_nodes.dtype != torch.int32 or num_nodes.numel() != s.shape[0]:
+            raise ValueError(f"assign_entropy(s, num_nodes): num_nodes must be int32 [{s.shape[0]}], got "
+                             f"{num_nodes.dtype} {tuple(num_nodes.shape)}")
+        num_nodes = num_nodes.contiguous()
+    return _AssignEntropyFn.apply(s, num_nodes)

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .encoders import GcnEncoderGraph, SoftPoolingGcnEncoder
+from .encoders import GcnEncoderGraph, SoftPoolingGcnEncoder, _refuse_ent_under_sync_bn
 from .ops import hip_linear  # noqa: F401  (tests and tools import it from here)
 
 
@@ -365,7 +365,8 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     A linkpred=True model (the constructor default, train.py --linkpred) trains here too: `loss(pred, label, graph)`
     adds the link-prediction term on dp_csr_linkpred_loss_* (per graph of a batch: dp_csr_linkpred_batch_*) — the n^2
     part of the sum does not depend on the adjacency and is a tile walk over S, the rest a gather over the edges;
-    O(n K_0) memory, no dense adjacency.
+    O(n K_0) memory, no dense adjacency.  `assign_ent_weight=w` adds w times the assignment-entropy term of the level-0
+    assignment (ops.assign_entropy: normalised by the number of nodes), with or without the graph argument.
 
     Differences of a CsrBatch forward from the dense class's saved tensors: level-0 'assign' / 'embedding' and
     `assign_tensor` stay RAGGED, [n_total, .] (dense: [B, N, .]); level-0 'readout_argmax' rows are graph-local.
@@ -376,13 +377,14 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     def __init__(self, max_num_nodes, input_dim, hidden_dim, embedding_dim, label_dim, num_layers,
                  assign_hidden_dim, assign_ratio=0.25, assign_num_layers=-1, num_pooling=1,
                  pred_hidden_dims=[50], concat=True, bn=True, dropout=0.0, linkpred=True,
-                 assign_input_dim=-1, args=None):
+                 assign_input_dim=-1, args=None, assign_ent_weight=0.0):
         if dropout > 0.001:
             raise NotImplementedError("dropout on the CSR path")
         super().__init__(max_num_nodes, input_dim, hidden_dim, embedding_dim, label_dim, num_layers,
                          assign_hidden_dim, assign_ratio=assign_ratio, assign_num_layers=assign_num_layers,
                          num_pooling=num_pooling, pred_hidden_dims=pred_hidden_dims, concat=concat, bn=bn,
-                         dropout=dropout, linkpred=linkpred, assign_input_dim=assign_input_dim, args=args)
+                         dropout=dropout, linkpred=linkpred, assign_input_dim=assign_input_dim, args=args,
+                         assign_ent_weight=assign_ent_weight)
         if self.assign_dims[0] > 256:
             raise ValueError(f"K_0 = {self.assign_dims[0]} clusters: the CSR pooling kernel (dp_csr_pool) supports "
                              "K_0 <= 256")
@@ -466,6 +468,9 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         if adj_hop != 1:
             raise NotImplementedError("adj_hop > 1 is never used by the reference's callers (train.py:207)")
         if not self.linkpred:
+            if self.assign_ent_weight > 0:
+                ent = self._assign_ent_term(call)          # first: its refusals come before any launch
+                return ops.cross_entropy(pred, label) + ent
             return ops.cross_entropy(pred, label)
         if adj is None:
             raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the {kind.__name__} the "
@@ -482,8 +487,24 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         if adj.n != s0.shape[0]:
             raise ValueError(f"{call}: {kind.ARG} has n = {adj.n} nodes but the last forward ran on n = {s0.shape[0]}; "
                              f"pass the {kind.ARG} of that forward")
+        if self.assign_ent_weight > 0:
+            ent = self._assign_ent_term(call)
+            self.link_loss = adj.link_loss(s0)
+            return ops.cross_entropy(pred, label) + self.link_loss + ent
         self.link_loss = adj.link_loss(s0)
         return ops.cross_entropy(pred, label) + self.link_loss
+
+    def _assign_ent_term(self, call):
+        """assign_ent_weight * E of the last forward's level-0 assignment (ops.assign_entropy: every row of the ragged
+        [n_total, K_0] assignment is a node, so the normaliser is n_total — the dense class's sum_b n_b on the same
+        graphs).  The assignment is the attached one: its dS adds to the pooling's and the link term's.  The unweighted
+        E is kept in `self.assign_ent_loss`."""
+        _refuse_ent_under_sync_bn(self)
+        if self._saved is None:
+            raise ValueError(f"{call}: no forward pass has run yet, so there is no assignment to score")
+        ent = ops.assign_entropy(self._saved["assign"][0])
+        self.assign_ent_loss = ent.detach()
+        return self.assign_ent_weight * ent
 
     def saved_activation(self, level, what):
         """One activation of the LAST forward call, shaped as the dense class returns it with B = 1: 'assign' [1, n_j,

@@ -52,6 +52,7 @@ class _Slot:
         self.graph = None
         self.loss = None
         self.link = None                                  # the link-prediction term of `loss` (linkpred models)
+        self.ent = None                                   # the assignment-entropy term (assign_ent_weight > 0)
         self.errors = None
 
 
@@ -73,6 +74,7 @@ class CapturedTrainStep:
             raise ValueError("the model's link-prediction loss and CapturedTrainStep(linkpred=...) disagree: capture a "
                              "linkpred model with linkpred=True (the link term then reads the packed adjacency)")
         self.linkpred = bool(linkpred)
+        self.ent = float(getattr(model, "assign_ent_weight", 0.0)) > 0      # the model's weight: no flag of its own
         self.model, self.opt, self.builder, self.B = model, optimizer, builder, int(batch_size)
         ds = builder.ds
         ecount = np.diff(ds.edge_ptr)
@@ -114,13 +116,16 @@ class CapturedTrainStep:
         ypred = self.model(batch["feats"], batch["adj"], batch["num_nodes_device"], assign_x=batch["assign_feats"])
         if self.linkpred:
             loss = self.model.loss(ypred, label, batch["adj"], batch["num_nodes_device"])
+        elif self.ent:
+            loss = self.model.loss(ypred, label, None, batch["num_nodes_device"])     # the entropy term's valid rows
         else:
             loss = self.model.loss(ypred, label)
         loss.backward()
         self.opt.step()
-        # the link term is a non-differentiable output of the loss node: it keeps no autograd graph alive
+        # the link and entropy terms are non-differentiable outputs of the loss node: they keep no autograd graph alive
         link = self.model.link_loss if self.linkpred else None
-        return loss.detach(), link, batch["errors"]
+        ent = self.model.assign_ent_loss if self.ent else None
+        return loss.detach(), link, ent, batch["errors"]
 
     def _capture(self):
         model, opt = self.model, self.opt
@@ -145,13 +150,15 @@ class CapturedTrainStep:
         for s in self.slots:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                s.loss, s.link, s.errors = self._body(s)
+                s.loss, s.link, s.ent, s.errors = self._body(s)
             s.graph = g
             model.zero_grad(set_to_none=True)
         torch.cuda.synchronize(dev)
         # undo the warm-up
         model._flat.copy_(keep[0]); opt.exp_avg.copy_(keep[1]); opt.exp_avg_sq.copy_(keep[2]); opt.step_dev.copy_(keep[3])
         opt.step_count = keep[4]
+        if self.ent:
+            model.assign_ent_loss = None                  # no step has run yet: the captures' own output is not a term
 
     def __call__(self, indices: Sequence[int]) -> torch.Tensor:
         slot = self.slots[self.turn % len(self.slots)]
@@ -163,6 +170,8 @@ class CapturedTrainStep:
         self.opt.step_count += 1
         if slot.link is not None:
             self.model.link_loss = slot.link              # train.py:224-225 logs the link term of the step just run
+        if slot.ent is not None:
+            self.model.assign_ent_loss = slot.ent         # the entropy term of the step just run
         return slot.loss
 
     def skipped_entries(self) -> int:

@@ -407,6 +407,27 @@ int dp_linkpred_loss_bwd_packed(const float* S, const void* adj_pk, const void* 
                                 const float* dloss, float* dS, int accumulate, int B, int n, int K, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ assignment entropy (DiffPool's second auxiliary term)
+ * E = ( sum_b sum_{i < n_b} sum_k -s_bik ln(s_bik + 1e-15) ) / sum_b n_b over S [B, n, K] (rows lds apart), the epsilon
+ * added in fp32.  n_b = num_nodes[b] clamped into [0, n]; num_nodes NULL = every row valid (then B = 1, n = rows serves
+ * a ragged [rows, K] assignment, rows counted in 64 bits).  The normaliser counts VALID nodes, not B * n: padding does
+ * not shrink the term (no valid node at all: E = 0).  Rows i >= n_b are never read.  Terms are formed in fp32 and
+ * summed in fp64 in a fixed order (no atomics): E is bit-identical from run to run.  Any K >= 1, lds / ldds >= K, any
+ * 4-byte alignment (16-byte lanes are taken when pointers, leading dimensions and K allow).  NULL S / ent_out / dS /
+ * workspace, B, n or K < 1, lds or ldds < K and a short workspace are DP_ERR_INVALID_ARG before any launch.  Nothing
+ * allocates or synchronises: both entries can be captured into a hipGraph.
+ * ent_out[0] = E.  total_inout: NULL, or one float that weight * E is ADDED to (fp32: old + fl(weight * E)) by the
+ * launch that finishes the sum. */
+size_t dp_assign_entropy_workspace_bytes(int B, int n, int K);
+int dp_assign_entropy_fwd(const float* S, int lds, const int* num_nodes, float weight, float* ent_out,
+                          float* total_inout, int B, int n, int K, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* dS (+)= dloss * weight * dE/dS,  dE/ds = -(ln(s + 1e-15) + s / (s + 1e-15)) / sum_b n_b.  dloss: device scalar or
+ * NULL = 1.  Rows i >= n_b: written 0 (accumulate = 0) or left as they are (accumulate = 1); columns K..ldds-1 are
+ * never written. */
+int dp_assign_entropy_bwd(const float* S, int lds, const int* num_nodes, const float* dloss, float weight,
+                          float* dS, int ldds, int accumulate, int B, int n, int K, void* stream);
+
 /* ------------------------------------------------------------------ softmax cross entropy
  * loss = mean_b CE(logits_b, label_b) — F.cross_entropy, encoders.py:1127.  prob [B,C] is saved
  * for backward.  label: int64[B]. */

@@ -4,7 +4,9 @@ clip_grad_norm_, torch.optim.Adam: train.py:197-210) against the on-device batch
 (SURVEY.md §8(f) N1, N2).  Model math is the same HIP path in both arms.
 --linkpred: every arm trains the model with the auxiliary link-prediction loss (train.py --linkpred, train.py:207):
 the reference-style and device-builder arms pass the dense adjacency to loss(), the captured step the packed one.
-  PYTHONPATH=. python tools/e2e_train_bench.py [--graphs 200] [--steps 100] [--linkpred]"""
+--assign-ent W: every arm adds W times the assignment-entropy term (assign_ent_weight=W; loss() then gets the node counts).
+--arms captured: only the captured arm (the one a launch trace of the step is taken from).
+  PYTHONPATH=. python tools/e2e_train_bench.py [--graphs 200] [--steps 100] [--linkpred] [--assign-ent 0.3]"""
 import argparse, json, time
 import numpy as np
 import torch
@@ -30,8 +32,11 @@ def main():
     ap.add_argument("--graphs", type=int, default=200)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--linkpred", action="store_true", help="train with the link-prediction loss (train.py:207)")
+    ap.add_argument("--assign-ent", type=float, default=0.0, metavar="W",
+                    help="weight of the assignment-entropy term (assign_ent_weight), every arm")
+    ap.add_argument("--arms", choices=["all", "captured"], default="all")
     args = ap.parse_args()
-    link = args.linkpred
+    link, ent_w = args.linkpred, args.assign_ent
     B, N, F_, H, Cc = 20, 500, 89, 20, 2
     graphs = dataset(args.graphs, 30, N, F_, 0.02, seed=1)
     batches = [list(range(i, i + B)) for i in range(0, args.graphs - B + 1, B)]
@@ -39,7 +44,8 @@ def main():
 
     def run(arm):
         torch.manual_seed(0)
-        model = SoftPoolingGcnEncoder(N, F_, H, H, Cc, 3, H, assign_ratio=0.1, linkpred=link).cuda()
+        model = SoftPoolingGcnEncoder(N, F_, H, H, Cc, 3, H, assign_ratio=0.1, linkpred=link,
+                                      assign_ent_weight=ent_w).cuda()
         if arm == "reference-style":
             opt = torch.optim.Adam(model.parameters(), lr=1e-3)
         else:
@@ -58,7 +64,10 @@ def main():
                 adj, x, label, nn_ = b["adj"], b["feats"], b["label"], b["num_nodes_device"]
             model.zero_grad(set_to_none=True)
             ypred = model(x, adj, nn_, assign_x=x)
-            loss = model.loss(ypred, label, adj, nn_) if link else model.loss(ypred, label)
+            if link:
+                loss = model.loss(ypred, label, adj, nn_)
+            else:
+                loss = model.loss(ypred, label, None, nn_) if ent_w > 0 else model.loss(ypred, label)
             loss.backward()
             if arm == "reference-style":
                 torch.nn.utils.clip_grad_norm_(model.parameters(), 2.0)
@@ -77,7 +86,8 @@ def main():
         """build -> forward -> loss -> backward -> clip + Adam as ONE hipGraph launch per step (train_step.py)."""
         from graph_pooling_amd.train_step import CapturedTrainStep
         torch.manual_seed(0)
-        model = SoftPoolingGcnEncoder(N, F_, H, H, Cc, 3, H, assign_ratio=0.1, linkpred=link).cuda()
+        model = SoftPoolingGcnEncoder(N, F_, H, H, Cc, 3, H, assign_ratio=0.1, linkpred=link,
+                                      assign_ent_weight=ent_w).cuda()
         opt = FusedClipAdam(model, lr=1e-3, clip=2.0, device_step_counter=True)
         builder = DeviceBatchBuilder(EdgeListDataset.from_tu_graphs(graphs), N, F_, dev)
         step = CapturedTrainStep(model, opt, builder, B, linkpred=link)
@@ -92,10 +102,12 @@ def main():
         assert step.skipped_entries() == 0
         return dt
 
-    out = {arm: round(run(arm), 3) for arm in ("reference-style", "device-builder+fused-optimizer")}
+    arms = ("reference-style", "device-builder+fused-optimizer") if args.arms == "all" else ()
+    out = {arm: round(run(arm), 3) for arm in arms}
     out["captured: packed builder + model + fused optimizer in one hipGraph"] = round(run_captured(), 3)
     out["unit"] = "ms per training step (B=20, N_max=500, F=89), eager, host loop included"
     out["linkpred"] = link
+    out["assign_ent_weight"] = ent_w
     print(json.dumps(out))
 
 
