@@ -170,6 +170,16 @@ _PROTOS = {
     "dp_assign_entropy_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_assign_entropy_fwd": (_I, [_P, _I, _P, _F, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_assign_entropy_bwd": (_I, [_P, _I, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
+    "dp_frob_link_workspace_bytes": (_Z, [_I, _I, _I]),
+    "dp_frob_link_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "dp_frob_link_fwd_packed": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "dp_frob_link_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dp_frob_link_bwd_packed": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dp_csr_frob_link_workspace_bytes": (_Z, [_I, _I, _I]),
+    "dp_csr_frob_link_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
+    "dp_csr_frob_link_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dp_csr_frob_link_batch_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_frob_link_batch_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dp_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dp_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dp_set2set_save_bytes": (_Z, [_I, _I, _I]),

@@ -965,6 +965,150 @@ int dp_assign_entropy_bwd(const float* S, int lds, const int* num_nodes, const f
     return q.err;
 }
 
+// ------------------------------------------------------------------ Frobenius link loss
+#define FROB_K(fn)                                                                                             \
+    do {                                                                                                       \
+        if (K > 256) {                                                                                         \
+            set_error(fn ": K=%d clusters: the Frobenius link kernels support K <= 256", K);                   \
+            return DP_ERR_UNSUPPORTED;                                                                         \
+        }                                                                                                      \
+    } while (0)
+#define FROB_WS(fn, need)                                                                                      \
+    do {                                                                                                       \
+        NOTNULL(workspace);                                                                                    \
+        DP_CHECK_ARG(workspace_bytes >= (need), fn ": workspace too small: need >= %zu bytes, have %zu", (need), \
+                     workspace_bytes);                                                                         \
+    } while (0)
+
+size_t dp_frob_link_workspace_bytes(int B, int N, int K) {
+    if (B < 1 || N < 1 || K < 1 || K > 256) return 0;
+    return frob_link_ws_doubles((long long)B * N, B, K) * sizeof(double) + 3 * 256 + 256;
+}
+static int frob_link_fwd_dense(const char* fn, const float* S, int lds, const void* adj, const void* adj_t, int packed,
+                               const int* num_nodes, const float* link_norm, float* W, float* G, float* loss_out,
+                               float* total_inout, int B, int N, int K, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    const int ld = packed ? adj_pack_ld(N) : N;
+    frob_link_w_dense(q, S, lds, adj, adj_t, packed, ld, num_nodes, W, B, N, K);
+    frob_link_fwd(q, S, lds, W, adj, packed ? 3 : 1, ld, num_nodes, nullptr, nullptr, link_norm, 1.f, G, loss_out,
+                  total_inout, B, N, (long long)B * N, K);
+    return q.err;
+}
+int dp_frob_link_fwd(const float* S, int lds, const float* adj, const int* num_nodes, const float* link_norm, float* W,
+                     float* G, float* loss_out, float* total_inout, int B, int N, int K, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(adj); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
+    NONNEG(B); NONNEG(N); NONNEG(K);
+    FROB_K("dp_frob_link_fwd");
+    DP_CHECK_ARG(lds >= K, "dp_frob_link_fwd: lds=%d smaller than K=%d", lds, K);
+    FROB_WS("dp_frob_link_fwd", dp_frob_link_workspace_bytes(B, N, K));
+    return frob_link_fwd_dense("dp_frob_link_fwd", S, lds, adj, nullptr, 0, num_nodes, link_norm, W, G, loss_out,
+                               total_inout, B, N, K, workspace, workspace_bytes, stream);
+}
+int dp_frob_link_fwd_packed(const float* S, int lds, const void* adj_pk, const void* adj_pkt, const int* num_nodes,
+                            const float* link_norm, float* W, float* G, float* loss_out, float* total_inout, int B, int N,
+                            int K, void* workspace, size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(adj_pk); NOTNULL(adj_pkt); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
+    NONNEG(B); NONNEG(N); NONNEG(K);
+    FROB_K("dp_frob_link_fwd_packed");
+    DP_CHECK_ARG(lds >= K, "dp_frob_link_fwd_packed: lds=%d smaller than K=%d", lds, K);
+    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
+    FROB_WS("dp_frob_link_fwd_packed", dp_frob_link_workspace_bytes(B, N, K));
+    return frob_link_fwd_dense("dp_frob_link_fwd_packed", S, lds, adj_pk, adj_pkt, 1, num_nodes, link_norm, W, G,
+                               loss_out, total_inout, B, N, K, workspace, workspace_bytes, stream);
+}
+int dp_frob_link_bwd(const float* S, int lds, const float* W, const float* G, const int* num_nodes,
+                     const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate, int B, int N, int K,
+                     void* stream) {
+    NOTNULL(S); NOTNULL(W); NOTNULL(G); NOTNULL(dS);
+    NONNEG(B); NONNEG(N); NONNEG(K);
+    FROB_K("dp_frob_link_bwd");
+    DP_CHECK_ARG(lds >= K, "dp_frob_link_bwd: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG(ldds >= K, "dp_frob_link_bwd: ldds=%d smaller than K=%d", ldds, K);
+    Seq q(STREAM(stream), nullptr, 0);
+    frob_link_bwd(q, S, lds, W, G, num_nodes, nullptr, link_norm, dloss, 1.f, dS, ldds, accumulate, B, N,
+                  (long long)B * N, K);
+    return q.err;
+}
+int dp_frob_link_bwd_packed(const float* S, int lds, const float* W, const float* G, const int* num_nodes,
+                            const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate, int B,
+                            int N, int K, void* stream) {
+    return dp_frob_link_bwd(S, lds, W, G, num_nodes, link_norm, dloss, dS, ldds, accumulate, B, N, K, stream);
+}
+
+size_t dp_csr_frob_link_workspace_bytes(int n_total, int B, int K) {
+    if (n_total < 1 || B < 1 || K < 1 || K > 256) return 0;
+    return frob_link_ws_doubles(n_total, B, K) * sizeof(double) + 3 * 256 + 256;
+}
+static int csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                             const int* indices_t, const int* node_off, const float* link_norm, float* W, float* G,
+                             float* loss_out, float* total_inout, int B, int n, int K, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    const bool directed = indptr_t && indices_t && !(indptr_t == indptr && indices_t == indices);
+    csr_aggregate_fwd(q, S, lds, indptr, indices, W, K, n, K, 0, 0.f);                       // W = A S
+    if (directed) csr_aggregate_fwd(q, S, lds, indptr_t, indices_t, W, K, n, K, 0, 1.f);     // += A^T S
+    frob_link_fwd(q, S, lds, W, nullptr, 0, 0, nullptr, node_off, indptr + n, link_norm, directed ? 1.f : 2.f, G,
+                  loss_out, total_inout, B, n, n, K);
+    return q.err;
+}
+int dp_csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                         const int* indices_t, const float* link_norm, float* W, float* G, float* loss_out,
+                         float* total_inout, int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
+    NONNEG(n); NONNEG(K);
+    FROB_K("dp_csr_frob_link_fwd");
+    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_fwd: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
+                 "dp_csr_frob_link_fwd: indptr_t and indices_t go together (both NULL: undirected)");
+    FROB_WS("dp_csr_frob_link_fwd", dp_csr_frob_link_workspace_bytes(n, 1, K));
+    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, nullptr, link_norm, W, G, loss_out,
+                             total_inout, 1, n, K, workspace, workspace_bytes, stream);
+}
+int dp_csr_frob_link_bwd(const float* S, int lds, const float* W, const float* G, const float* link_norm,
+                         const float* dloss, float* dS, int ldds, int accumulate, int symmetric, int n, int K,
+                         void* stream) {
+    NOTNULL(S); NOTNULL(W); NOTNULL(G); NOTNULL(dS);
+    NONNEG(n); NONNEG(K);
+    FROB_K("dp_csr_frob_link_bwd");
+    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_bwd: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG(ldds >= K, "dp_csr_frob_link_bwd: ldds=%d smaller than K=%d", ldds, K);
+    Seq q(STREAM(stream), nullptr, 0);
+    frob_link_bwd(q, S, lds, W, G, nullptr, nullptr, link_norm, dloss, symmetric ? 2.f : 1.f, dS, ldds, accumulate, 1, n,
+                  n, K);
+    return q.err;
+}
+int dp_csr_frob_link_batch_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                               const int* indices_t, const int* node_off, const float* link_norm, float* W, float* G,
+                               float* loss_out, float* total_inout, int B, int n_total, int K, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(node_off); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
+    NONNEG(B); NONNEG(n_total); NONNEG(K);
+    FROB_K("dp_csr_frob_link_batch_fwd");
+    DP_CHECK_ARG(B <= n_total, "dp_csr_frob_link_batch_fwd: B=%d graphs over n_total=%d rows (every graph has >= 1 node)",
+                 B, n_total);
+    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_batch_fwd: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
+                 "dp_csr_frob_link_batch_fwd: indptr_t and indices_t go together (both NULL: undirected)");
+    FROB_WS("dp_csr_frob_link_batch_fwd", dp_csr_frob_link_workspace_bytes(n_total, B, K));
+    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, node_off, link_norm, W, G, loss_out,
+                             total_inout, B, n_total, K, workspace, workspace_bytes, stream);
+}
+int dp_csr_frob_link_batch_bwd(const float* S, int lds, const float* W, const float* G, const int* node_off,
+                               const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate,
+                               int symmetric, int B, int n_total, int K, void* stream) {
+    NOTNULL(S); NOTNULL(W); NOTNULL(G); NOTNULL(node_off); NOTNULL(dS);
+    NONNEG(B); NONNEG(n_total); NONNEG(K);
+    FROB_K("dp_csr_frob_link_batch_bwd");
+    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_batch_bwd: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG(ldds >= K, "dp_csr_frob_link_batch_bwd: ldds=%d smaller than K=%d", ldds, K);
+    Seq q(STREAM(stream), nullptr, 0);
+    frob_link_bwd(q, S, lds, W, G, nullptr, node_off, link_norm, dloss, symmetric ? 2.f : 1.f, dS, ldds, accumulate, B,
+                  n_total, n_total, K);
+    return q.err;
+}
+
 int dp_cross_entropy_fwd(const float* logits, const long long* label, float* loss_out, float* prob, int B, int C,
                          void* stream) {
     NOTNULL(logits); NOTNULL(label); NOTNULL(loss_out);

@@ -669,4 +669,17 @@ void assign_entropy_fwd(Seq& q, const float* S, int lds, const int* num_nodes, f
 void assign_entropy_bwd(Seq& q, const float* S, int lds, const int* num_nodes, const float* dloss, float weight,
                         float* dS, int ldds, int accumulate, int B, int n, int K);
 
+// (dp_frob_link.hip) Frobenius link loss F / sum_b n_b^2, F = sum (a_ij - s_i . s_j)^2 = T0 - sum_i s_i . w_i + sum_b ||G_b||^2
+// with W = (A + A^T) S (wscale 2: W holds A S of a symmetric A) and G_b = S_b^T S_b.  Row layouts: dense [B, N, .] with
+// num_nodes (or null), or ragged with node_off [B + 1]; rows = B N or n_total.
+size_t frob_link_ws_doubles(long long rows, int B, int K);
+void frob_link_w_dense(Seq& q, const float* S, int lds, const void* adj, const void* adj_t, int packed, int ld,
+                       const int* num_nodes, float* W, int B, int N, int K);
+void frob_link_fwd(Seq& q, const float* S, int lds, const float* W, const void* adj, int adj_kind, int adj_ld,
+                   const int* num_nodes, const int* node_off, const int* nnz_ptr, const float* link_norm, float wscale,
+                   float* G, float* loss_out, float* total_inout, int B, int N, long long rows, int K);
+void frob_link_bwd(Seq& q, const float* S, int lds, const float* W, const float* G, const int* num_nodes,
+                   const int* node_off, const float* link_norm, const float* dloss, float wscale, float* dS, int ldds,
+                   int accumulate, int B, int N, long long rows, int K);
+
 }  // namespace dp

@@ -593,7 +593,7 @@ class _Loss(torch.Tensor):
 
 class _LossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, label, S, adj, num_nodes, linkpred, link_norm=None, ent_w=0.0):
+    def forward(ctx, pred, label, S, adj, num_nodes, linkpred, link_norm=None, ent_w=0.0, frob=False):
         lib = _lib.load()
         _lib.require_gpu_tensor(pred, "pred")
         pred = pred.contiguous().float()
@@ -601,6 +601,7 @@ class _LossFn(torch.autograd.Function):
         B, Cc = pred.shape
         N = K = 0
         packed = linkpred and isinstance(adj, PackedAdjacency)
+        frob = bool(linkpred and frob)
         if linkpred:
             S = S.contiguous()
             N, K = S.shape[1], S.shape[2]
@@ -611,6 +612,11 @@ class _LossFn(torch.autograd.Function):
                 adj = (adj.pk, adj.pkt)
             else:
                 adj = adj.contiguous().float()
+        fr_S, fr_adj = S, adj
+        if frob:
+            # the Frobenius objective: the loss entry runs the cross entropy alone (linkpred = 0); dp_frob_link_fwd then
+            # adds the term into out[0] and writes out[1] (no torch add)
+            linkpred, packed, N, K = False, False, 0, 0
         wsb = lib.dp_loss_workspace_bytes(B, max(N, 1), max(K, 1), int(linkpred))   # covers the packed entries too
         ws = torch.empty(wsb, device=pred.device, dtype=torch.uint8)
         out = torch.empty(2, device=pred.device, dtype=torch.float32)
@@ -629,6 +635,22 @@ class _LossFn(torch.autograd.Function):
         ctx.link_norm = link_norm if linkpred else None
         ctx.dims = (B, Cc, N, K, bool(linkpred))
         ctx.ent_w = ent_w
+        ctx.frob = None
+        if frob:
+            Bf, Nf, Kf = fr_S.shape
+            fwsb = lib.dp_frob_link_workspace_bytes(Bf, Nf, Kf)
+            fws = torch.empty(max(fwsb, 1), device=pred.device, dtype=torch.uint8)
+            W = torch.empty(Bf, Nf, Kf, device=pred.device, dtype=torch.float32)
+            G = torch.empty(Bf, Kf, Kf, device=pred.device, dtype=torch.float32)
+            tail = (_lib.ptr(num_nodes), None, W.data_ptr(), G.data_ptr(), out.data_ptr() + 4, out.data_ptr(), Bf, Nf, Kf,
+                    fws.data_ptr(), fwsb, _lib.current_stream())
+            if isinstance(fr_adj, tuple):
+                _lib.check(lib.dp_frob_link_fwd_packed(fr_S.data_ptr(), Kf, fr_adj[0].data_ptr(), fr_adj[1].data_ptr(),
+                                                       *tail), "dp_frob_link_fwd_packed")
+            else:
+                _lib.check(lib.dp_frob_link_fwd(fr_S.data_ptr(), Kf, fr_adj.data_ptr(), *tail), "dp_frob_link_fwd")
+            ctx.frob = (fr_S, W, G)
+            S = fr_S                                  # the entropy term below scores the same assignment
         total, link = out[0], out[1]
         ctx.mark_non_differentiable(link)
         ctx.set_materialize_grads(False)      # no zero-fill launch for the unused gradient of `link`
@@ -644,7 +666,7 @@ class _LossFn(torch.autograd.Function):
                                              out.data_ptr(), Be, Ne, Ke, ews.data_ptr(), ewsb, _lib.current_stream()),
                    "dp_assign_entropy_fwd")
         ctx.ent_S = S
-        ctx.mark_non_differentiable(ent)
+        ctx.mark_non_differentiable(link, ent)        # one call names them all: a second call replaces the first
         return total, link, ent
 
     @staticmethod
@@ -654,12 +676,13 @@ class _LossFn(torch.autograd.Function):
         B, Cc, N, K, linkpred = ctx.dims
         ent_w = ctx.ent_w
         if dtotal is None:
-            return None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
         unit = bool(getattr(ctx, "unit_armed", False))     # armed by _Loss.backward: the upstream gradient is exactly 1
         if unit and not linkpred:
-            if ent_w > 0:                                  # dS of the entropy term alone, for an upstream gradient of 1
-                return dunit, None, _ent_backward(lib, ctx, None, None), None, None, None, None, None
-            return dunit, None, None, None, None, None, None, None     # written by the loss kernel: nothing to launch
+            dS = _frob_backward(lib, ctx, None) if ctx.frob is not None else None
+            if ent_w > 0:                                  # the entropy term's dS, for an upstream gradient of 1
+                dS = _ent_backward(lib, ctx, None, dS)
+            return dunit, None, dS, None, None, None, None, None, None   # dunit: written by the loss kernel
         dtotal = dtotal.contiguous().float()
         dpred = dunit if unit else torch.empty(B, Cc, device=prob.device, dtype=torch.float32)
         dS = torch.empty_like(S) if linkpred else None
@@ -672,9 +695,23 @@ class _LossFn(torch.autograd.Function):
         else:
             _lib.check(lib.dp_loss_backward(prob.data_ptr(), label.data_ptr(), _lib.ptr(S), _lib.ptr(adj), *tail),
                        "dp_loss_backward")
+        if ctx.frob is not None:                           # the Frobenius link term's dS, where the other form's goes
+            dS = _frob_backward(lib, ctx, dtotal)
         if ent_w > 0:                                      # after the link term's dS: added to it; alone: written
             dS = _ent_backward(lib, ctx, None if unit else dtotal, dS)
-        return dpred, None, dS, None, None, None, None, None
+        return dpred, None, dS, None, None, None, None, None, None
+
+
+def _frob_backward(lib, ctx, dtotal):
+    """dS = dtotal * d link / dS of the Frobenius link term on dp_frob_link_bwd (masked rows zero), from the W and G the
+    forward saved: no adjacency is read.  dtotal None: an upstream gradient of exactly 1."""
+    S, W, G = ctx.frob
+    Bf, Nf, Kf = S.shape
+    dS = torch.empty_like(S)
+    _lib.check(lib.dp_frob_link_bwd(S.data_ptr(), Kf, W.data_ptr(), G.data_ptr(), _lib.ptr(ctx.saved[5]), None,
+                                    _lib.ptr(dtotal), dS.data_ptr(), Kf, 0, Bf, Nf, Kf, _lib.current_stream()),
+               "dp_frob_link_bwd")
+    return dS
 
 
 def _ent_backward(lib, ctx, dtotal, dS):
@@ -692,6 +729,9 @@ def _ent_backward(lib, ctx, dtotal, dS):
 
 
 def _loss(owner, pred, label, S, adj, batch_num_nodes, linkpred, ent_w=0.0):
+    frob = bool(linkpred) and getattr(owner, "link_objective", "bce") == "frobenius"
+    if frob:
+        _refuse_frob_under_sync_bn(owner)
     nn_dev = _num_nodes_device(batch_num_nodes, pred.device) if linkpred or ent_w > 0 else None
     link_norm = None
     sync = getattr(owner, "_sync_bn", None)
@@ -701,7 +741,7 @@ def _loss(owner, pred, label, S, adj, batch_num_nodes, linkpred, ent_w=0.0):
         n_eff = nn_dev.clamp(max=S.shape[1]).float() if nn_dev is not None else \
             torch.full((S.shape[0],), float(S.shape[1]), device=pred.device)
         link_norm = sync.all_reduce_sum((n_eff * n_eff).sum().reshape(1)) / float(sync.world)
-    total, link, *ent = _LossFn.apply(pred, label, S, adj, nn_dev, linkpred, link_norm, ent_w)
+    total, link, *ent = _LossFn.apply(pred, label, S, adj, nn_dev, linkpred, link_norm, ent_w, frob)
     if ent:
         owner.assign_ent_loss = ent[0]
     if linkpred:
@@ -771,8 +811,28 @@ def _refuse_ent_under_sync_bn(owner):
                                   "each rank normalises by its own nodes")
 
 
+def _link_objective(linkpred):
+    """linkpred as the constructors take it, False | True | "bce" | "frobenius" -> (linkpred bool, link_objective).
+    True and "bce": the reference's cross-entropy link term; "frobenius": the paper's ||A - S S^T||_F^2 / sum_b n_b^2."""
+    if isinstance(linkpred, str):
+        if linkpred not in ("bce", "frobenius"):
+            raise ValueError(f'linkpred must be False, True, "bce" or "frobenius", got {linkpred!r}')
+        return True, linkpred
+    return bool(linkpred), "bce"
+
+
+def _refuse_frob_under_sync_bn(owner):
+    sync = getattr(owner, "_sync_bn", None)
+    if sync is not None and sync.active:
+        raise NotImplementedError('linkpred="frobenius" under sync-BN: the term divides by sum_b n_b^2 of the WHOLE batch, '
+                                  "and the global normaliser (the all-reduce the cross-entropy link term has) is not "
+                                  "wired to it yet; the C entries already take link_norm")
+
+
 class SoftPoolingGcnEncoder(GcnEncoderGraph):
-    """DiffPool (encoders.py:1160-1334)."""
+    """DiffPool (encoders.py:1160-1334).  `linkpred`: False, True / "bce" (the reference's cross-entropy link term) or
+    "frobenius" (the paper's ||A - S S^T||_F^2 / sum_b n_b^2 on dp_frob_link_*; unpinned by the reference, which has no
+    such term); `self.linkpred` stays a bool, `self.link_objective` names the form."""
 
     _mask_readout = 1
 
@@ -792,7 +852,7 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
         self.assign_ent_weight = _check_ent_weight(assign_ent_weight)
         add_self = not concat
         self.num_pooling = num_pooling
-        self.linkpred = linkpred
+        self.linkpred, self.link_objective = _link_objective(linkpred)
         self.assign_ent = True
         self.max_num_nodes = max_num_nodes
         if assign_num_layers == -1:

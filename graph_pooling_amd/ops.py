@@ -684,3 +684,115 @@ def assign_entropy(s, num_nodes=None):
                              f"{num_nodes.dtype} {tuple(num_nodes.shape)}")
         num_nodes = num_nodes.contiguous()
     return _AssignEntropyFn.apply(s, num_nodes)
+
+
+# ----------------------------------------------------------------------------- Frobenius link loss
+class _FrobLinkFn(torch.autograd.Function):
+    """One node for the four forms: `kind` 'dense' (fp32 adjacency), 'packed' (PackedAdjacency), 'csr' (CsrGraph),
+    'batch' (CsrBatch).  The forward saves W = (A + A^T) S (CSR of an undirected graph: A S) and the Gram matrices; the
+    backward reads no adjacency."""
+
+    @staticmethod
+    def forward(ctx, s, adj, num_nodes, kind):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(s, "s")
+        s = s.contiguous().float()
+        st = _lib.current_stream()
+        loss = _f32(s, ())
+        k = s.shape[-1]
+        if kind in ("dense", "packed"):
+            b, n, _ = s.shape
+            wsb = lib.dp_frob_link_workspace_bytes(b, n, k)
+            ws = _workspace(wsb, s)
+            w, g = torch.empty_like(s), _f32(s, (b, k, k))
+            tail = (_lib.ptr(num_nodes), None, w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, b, n, k, ws.data_ptr(),
+                    wsb, st)
+            if kind == "packed":
+                _lib.check(lib.dp_frob_link_fwd_packed(s.data_ptr(), k, adj.pk.data_ptr(), adj.pkt.data_ptr(), *tail),
+                           "dp_frob_link_fwd_packed")
+            else:
+                adj = adj.contiguous().float()
+                _lib.check(lib.dp_frob_link_fwd(s.data_ptr(), k, adj.data_ptr(), *tail), "dp_frob_link_fwd")
+            ctx.sym = 0
+        else:
+            n = s.shape[0]
+            b = adj.num_graphs if kind == "batch" else 1
+            directed = not (adj.indptr_t is adj.indptr and adj.indices_t is adj.indices)
+            wsb = lib.dp_csr_frob_link_workspace_bytes(n, b, k)
+            ws = _workspace(wsb, s)
+            w, g = torch.empty_like(s), _f32(s, (b, k, k))
+            csr = (s.data_ptr(), k, adj.indptr.data_ptr(), adj.indices.data_ptr(),
+                   adj.indptr_t.data_ptr() if directed else None, adj.indices_t.data_ptr() if directed else None)
+            if kind == "batch":
+                _lib.check(lib.dp_csr_frob_link_batch_fwd(*csr, adj.node_off.data_ptr(), None, w.data_ptr(), g.data_ptr(),
+                                                          loss.data_ptr(), None, b, n, k, ws.data_ptr(), wsb, st),
+                           "dp_csr_frob_link_batch_fwd")
+            else:
+                _lib.check(lib.dp_csr_frob_link_fwd(*csr, None, w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, n, k,
+                                                    ws.data_ptr(), wsb, st), "dp_csr_frob_link_fwd")
+            ctx.sym = 0 if directed else 1
+        ctx.save_for_backward(s, w, g)
+        ctx.kind, ctx.num_nodes, ctx.adj, ctx.b = kind, num_nodes, adj if kind == "batch" else None, b
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        s, w, g = ctx.saved_tensors
+        k = s.shape[-1]
+        dloss = dloss.contiguous().float()
+        ds = torch.empty_like(s)
+        st = _lib.current_stream()
+        head = (s.data_ptr(), k, w.data_ptr(), g.data_ptr())
+        if ctx.kind in ("dense", "packed"):
+            fn = lib.dp_frob_link_bwd_packed if ctx.kind == "packed" else lib.dp_frob_link_bwd
+            _lib.check(fn(*head, _lib.ptr(ctx.num_nodes), None, dloss.data_ptr(), ds.data_ptr(), k, 0, s.shape[0],
+                          s.shape[1], k, st), "dp_frob_link_bwd")
+        elif ctx.kind == "batch":
+            _lib.check(lib.dp_csr_frob_link_batch_bwd(*head, ctx.adj.node_off.data_ptr(), None, dloss.data_ptr(),
+                                                      ds.data_ptr(), k, 0, ctx.sym, ctx.b, s.shape[0], k, st),
+                       "dp_csr_frob_link_batch_bwd")
+        else:
+            _lib.check(lib.dp_csr_frob_link_bwd(*head, None, dloss.data_ptr(), ds.data_ptr(), k, 0, ctx.sym, s.shape[0], k,
+                                                st), "dp_csr_frob_link_bwd")
+        return ds, None, None, None
+
+
+def frob_link_loss(s, adj, num_nodes=None):
+    """The Frobenius link loss sum_b sum_{i,j < n_b} (a_bij - s_bi . s_bj)^2 / sum_b n_b^2 — the DiffPool paper's
+    ||A - S S^T||_F^2 over the normaliser of the cross-entropy link term; all pairs, the diagonal included, no clamp;
+    unpinned by the reference, which has no such term — on dp_frob_link_* / dp_csr_frob_link_*, without any n x n
+    temporary.  Dense: s [B, N, K] with adj an fp32 [B, N, N] tensor (any values) or a `PackedAdjacency`, `num_nodes`
+    int32 [B] on the device (None: all N).  Ragged: s [n, K] with a `CsrGraph`, or s [n_total, K] with a `CsrBatch`
+    (0/1 adjacency, each entry stored once).  Returns the device scalar."""
+    if not isinstance(s, torch.Tensor) or s.dim() not in (2, 3):
+        got = tuple(s.shape) if isinstance(s, torch.Tensor) else type(s).__name__
+        raise ValueError(f"frob_link_loss(s, adj, num_nodes): s must be [n, K] or [B, N, K], got {got}")
+    if s.dim() == 3:
+        if isinstance(adj, torch.Tensor):
+            if tuple(adj.shape) != (s.shape[0], s.shape[1], s.shape[1]):
+                raise ValueError(f"frob_link_loss: adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
+            _lib.require_gpu_tensor(adj, "adj")
+            kind = "dense"
+        elif hasattr(adj, "pk") and hasattr(adj, "pkt"):
+            if adj.B != s.shape[0] or adj.N != s.shape[1]:
+                raise ValueError(f"frob_link_loss: packed adjacency [B={adj.B}, N={adj.N}] does not match s "
+                                 f"{tuple(s.shape)}")
+            kind = "packed"
+        else:
+            raise TypeError("frob_link_loss: s [B, N, K] goes with an fp32 [B, N, N] tensor or a PackedAdjacency, got "
+                            f"{type(adj).__name__}")
+        if num_nodes is not None:
+            _lib.require_gpu_tensor(num_nodes, "num_nodes")
+            if num_nodes.dtype != torch.int32 or num_nodes.numel() != s.shape[0]:
+                raise ValueError(f"frob_link_loss: num_nodes must be int32 [{s.shape[0]}], got {num_nodes.dtype} "
+                                 f"{tuple(num_nodes.shape)}")
+            num_nodes = num_nodes.contiguous()
+        return _FrobLinkFn.apply(s, adj, num_nodes, kind)
+    if num_nodes is not None:
+        raise ValueError("frob_link_loss: num_nodes goes with s [B, N, K]")
+    if not (hasattr(adj, "indptr") and hasattr(adj, "indices")):
+        raise TypeError(f"frob_link_loss: s [n, K] goes with a CsrGraph or a CsrBatch, got {type(adj).__name__}")
+    if adj.n != s.shape[0]:
+        raise ValueError(f"frob_link_loss: the {adj.ARG} has n = {adj.n} rows but s has {s.shape[0]}")
+    return _FrobLinkFn.apply(s, adj, None, "batch" if hasattr(adj, "node_off") else "csr")

@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .encoders import GcnEncoderGraph, SoftPoolingGcnEncoder, _refuse_ent_under_sync_bn
+from .encoders import (GcnEncoderGraph, SoftPoolingGcnEncoder, _refuse_ent_under_sync_bn,
+                       _refuse_frob_under_sync_bn)
 from .ops import hip_linear  # noqa: F401  (tests and tools import it from here)
 
 
@@ -65,8 +66,9 @@ class CsrGraph:
         xp, ap = ops.csr_pool(s, z, self)
         return xp.unsqueeze(0), ap.unsqueeze(0)
 
-    def link_loss(self, s):
-        return ops.csr_link_loss(s, self)
+    def link_loss(self, s, objective="bce"):
+        """The link term of the assignment s [n, K]: the reference's cross-entropy form, or 'frobenius'."""
+        return ops.frob_link_loss(s, self) if objective == "frobenius" else ops.csr_link_loss(s, self)
 
     @staticmethod
     def from_edges(n, src, dst, device, symmetric=True):
@@ -237,8 +239,10 @@ class CsrBatch:
         """Per graph S^T Z [B, K, D] and S^T A S [B, K, K]: dp_csr_pool_batch_*."""
         return ops.csr_pool_batch(s, z, self)
 
-    def link_loss(self, s):
-        return ops.csr_link_loss_batch(s, self)
+    def link_loss(self, s, objective="bce"):
+        """The link term of the ragged assignment s [n_total, K]: the reference's cross-entropy form (per-graph
+        launches), or 'frobenius' (one set of launches for the batch)."""
+        return ops.frob_link_loss(s, self) if objective == "frobenius" else ops.csr_link_loss_batch(s, self)
 
     @staticmethod
     def from_graphs(graphs, pad_to=None):
@@ -487,11 +491,13 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         if adj.n != s0.shape[0]:
             raise ValueError(f"{call}: {kind.ARG} has n = {adj.n} nodes but the last forward ran on n = {s0.shape[0]}; "
                              f"pass the {kind.ARG} of that forward")
+        if self.link_objective == "frobenius":
+            _refuse_frob_under_sync_bn(self)
         if self.assign_ent_weight > 0:
             ent = self._assign_ent_term(call)
-            self.link_loss = adj.link_loss(s0)
+            self.link_loss = adj.link_loss(s0, self.link_objective)
             return ops.cross_entropy(pred, label) + self.link_loss + ent
-        self.link_loss = adj.link_loss(s0)
+        self.link_loss = adj.link_loss(s0, self.link_objective)
         return ops.cross_entropy(pred, label) + self.link_loss
 
     def _assign_ent_term(self, call):

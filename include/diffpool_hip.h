@@ -428,6 +428,66 @@ int dp_assign_entropy_fwd(const float* S, int lds, const int* num_nodes, float w
 int dp_assign_entropy_bwd(const float* S, int lds, const int* num_nodes, const float* dloss, float weight,
                           float* dS, int ldds, int accumulate, int B, int n, int K, void* stream);
 
+/* ------------------------------------------------------------------ Frobenius link loss (the DiffPool paper's L_LP, squared)
+ *     link = sum_b sum_{i,j < n_b} (a_bij - s_bi . s_bj)^2 / sum_b n_b^2
+ * on the level-0 assignment: all pairs count, the diagonal included, no clamp; link * sum_b n_b^2 is the paper's
+ * ||A - S S^T||_F^2 summed over the graphs.  The reference has no such term (its link term is the cross-entropy form of
+ * A8): the definition is unpinned by the reference.  Evaluated without any n x n temporary as T0 - sum_i s_i . w_i +
+ * sum_b ||G_b||_F^2 with T0 = sum a^2, W = (A + A^T) S and G_b = S_b^T S_b [K, K]; the backward is row-local,
+ * dS_i (+)= dloss (4 G_b s_i - 2 w_i) / norm.  F is a difference of three non-negative sums: its absolute error scales
+ * with T0 + sum s.w + T2, so near a perfect fit the RELATIVE error of the term is unbounded — inherent, not a defect.
+ * G is summed in fp64 over row slabs of DP_FROB_LINK_SLAB global rows in a fixed order, the row term and T0 from fp32
+ * products in fp64 in a fixed order, the quotient taken in fp64 and rounded once: no atomics, bit-identical repeats.
+ *
+ * S [B, N, K] (rows lds >= K apart), 1 <= K <= 256 (DP_ERR_UNSUPPORTED above, before any launch).  n_b = num_nodes[b]
+ * clamped into [0, N], NULL = N.  Rows i >= n_b of S (and of W) are never read; adjacency entries outside the leading
+ * n_b x n_b block are never read either.  link_norm (device scalar or NULL) replaces sum_b n_b^2, as in dp_loss_forward.
+ * The forward writes W [B, N, K] (contiguous; rows i >= n_b are left as they are) and G [B, K, K], both caller-owned, for
+ * the backward, which reads no adjacency.  loss_out[0] = link; total_inout: NULL, or one float the term is ADDED to
+ * (fp32) by the launch that finishes the sum.  The fp32 entry takes any adjacency values (weighted, asymmetric); the
+ * packed entry takes the bf16 rows of dp_adj_pack / dp_build_batch_packed (16-byte aligned, rows of dp_adj_pack_ld(N);
+ * adj_pkt == adj_pk: one read and a factor 2) and equals the fp32 entry BIT FOR BIT on an adjacency bf16 holds exactly.
+ * NULL pointers, B, N, K < 1, lds / ldds < K, a short workspace: DP_ERR_INVALID_ARG before any launch.  Nothing
+ * allocates or synchronises, no memset / memcpy nodes: every entry can be captured into a hipGraph. */
+#define DP_FROB_LINK_SLAB 512
+size_t dp_frob_link_workspace_bytes(int B, int N, int K);
+int dp_frob_link_fwd(const float* S, int lds, const float* adj, const int* num_nodes, const float* link_norm, float* W,
+                     float* G, float* loss_out, float* total_inout, int B, int N, int K, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int dp_frob_link_fwd_packed(const float* S, int lds, const void* adj_pk, const void* adj_pkt, const int* num_nodes,
+                            const float* link_norm, float* W, float* G, float* loss_out, float* total_inout, int B, int N,
+                            int K, void* workspace, size_t workspace_bytes, void* stream);
+/* dloss: device scalar or NULL = 1.  accumulate = 0: rows i >= n_b are written 0; accumulate = 1: dS += and those rows
+ * are left alone.  Columns K..ldds-1 are never written.  W / G: the forward's.  _bwd_packed is the same function under
+ * the name of the forward it pairs with (the backward reads no adjacency). */
+int dp_frob_link_bwd(const float* S, int lds, const float* W, const float* G, const int* num_nodes,
+                     const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate, int B, int N, int K,
+                     void* stream);
+int dp_frob_link_bwd_packed(const float* S, int lds, const float* W, const float* G, const int* num_nodes,
+                            const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate, int B,
+                            int N, int K, void* stream);
+/* The same term on CSR: one graph (n rows), or a ragged batch (block-diagonal CSR with GLOBAL column indices, node_off
+ * int32 [B + 1] ON THE DEVICE, every graph >= 1 node) with one set of launches for the whole batch, none per graph.
+ * CSR contract: 0/1 adjacency, each (i, j) stored at most once, so T0 is the number of stored entries (read from
+ * indptr on the device).  W [n, K] = A S by the dp_csr_aggregate gather; indptr_t / indices_t: CSR of A^T, NULL or the
+ * forward arrays themselves for an undirected graph (one gather, counted twice) — the backward is told with
+ * symmetric != 0.  G [B, K, K].  Work O(n K^2 + nnz K), workspace O(n K + B K^2); a batch of one graph equals the
+ * single-graph entry bit for bit. */
+size_t dp_csr_frob_link_workspace_bytes(int n_total, int B, int K);
+int dp_csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                         const int* indices_t, const float* link_norm, float* W, float* G, float* loss_out,
+                         float* total_inout, int n, int K, void* workspace, size_t workspace_bytes, void* stream);
+int dp_csr_frob_link_bwd(const float* S, int lds, const float* W, const float* G, const float* link_norm,
+                         const float* dloss, float* dS, int ldds, int accumulate, int symmetric, int n, int K,
+                         void* stream);
+int dp_csr_frob_link_batch_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                               const int* indices_t, const int* node_off, const float* link_norm, float* W, float* G,
+                               float* loss_out, float* total_inout, int B, int n_total, int K, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int dp_csr_frob_link_batch_bwd(const float* S, int lds, const float* W, const float* G, const int* node_off,
+                               const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate,
+                               int symmetric, int B, int n_total, int K, void* stream);
+
 /* ------------------------------------------------------------------ softmax cross entropy
  * loss = mean_b CE(logits_b, label_b) — F.cross_entropy, encoders.py:1127.  prob [B,C] is saved
  * for backward.  label: int64[B]. */
