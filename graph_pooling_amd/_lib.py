@@ -210,6 +210,16 @@ _PROTOS = {
     "dp_segment_max_workspace_bytes": (_Z, [_I, _I]),
     "dp_segment_max_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _Z, _P]),
     "dp_segment_max_bwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    # the base encoder's unmasked max readout on a ragged batch
+    "dp_ragged_padval_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dp_ragged_suffix_max_workspace_bytes": (_Z, [_I, _I, _I]),
+    "dp_ragged_suffix_max": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_segment_max_floor_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _I, _P, _Z, _P]),
+    "dp_segment_max_floor_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dp_bn_ragged_g_bwd": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z,
+                                _P]),
+    "dp_gcn_row_const_fwd": (_I, [_P, _P, _I, _I, _P]),
+    "dp_gcn_row_const_bwd": (_I, [_P, _P, _P, _I, _I, _P]),
     "dp_csr_pool_batch_plan": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "dp_csr_pool_batch_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "dp_csr_pool_batch_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),

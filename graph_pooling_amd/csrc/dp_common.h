@@ -643,6 +643,10 @@ void csr_aggregate_fwd(Seq& q, const float* table, int ldt, const int* indptr, c
 void csr_aggregate_bwd_scatter(Seq& q, const float* dout, int ldo, const int* indptr, const int* indices, float* dtable,
                                int ldt, int n_rows, int feat, int mean);
 
+// (dp_csr_batch.hip) stage 1 of the segmented max, which dp_ragged_readout.hip launches as well: per chunk of the chunk
+// table {graph, first row, end row, 0} the column maxima pv [n_chunks, F] and their global rows pi, ties to the lowest row
+void segment_max_part(Seq& q, const float* Z, int ldz, const int* chunk_tab, int n_chunks, int F, float* pv, int* pi);
+
 // (dp_linkpred.hip)
 void linkpred_fwd(Seq& q, const float* S, int lds, const float* adj, const int* num_nodes, float* loss_out,
                   int B, int n, int K, const float* norm = nullptr /*device scalar replacing sum n_b^2*/);

@@ -7,6 +7,7 @@
 //                         sits inside the statistics of its node index; here index i takes its statistics over the rows
 //                         node_off[b] + i of the cnt[i] graphs that own it plus (B - cnt[i]) copies of `pad`.
 //   dp_gcn_pad_const_*    that constant from the layer's bias, and the way back from its gradient to the bias gradient.
+//   dp_gcn_row_const_*    the same without the ReLU: a padded row behind the last GraphConv layer (dp_ragged_readout.hip).
 //   dp_segment_max_*      max readout per graph (encoders.py:1257) with the zero floor of a graph that has padded rows.
 //
 // Ownership.  `order` lists the graphs by size, largest first (ties by graph number), so the owners of index i are
@@ -179,20 +180,25 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return r;
 }
 
-// pad = relu(u), u = bias / max(||bias||, 1e-12) (the GraphConv output of a row with a zero adjacency row); one workgroup
-__global__ __launch_bounds__(256) void k_pad_const_fwd(const float* bias, float* pad, int F, int normalize) {
+// pad = relu(u), u = bias / max(||bias||, 1e-12) (the GraphConv output of a row with a zero adjacency row); one workgroup.
+// relu = 0: u itself (the last GraphConv layer has no ReLU behind it)
+__global__ __launch_bounds__(256) void k_pad_const_fwd(const float* bias, float* pad, int F, int normalize, int relu) {
     __shared__ float red[256];
     float ss = 0.f;
     if (bias)
         for (int f = threadIdx.x; f < F; f += 256) ss += bias[f] * bias[f];
     ss = block_sum(ss, red);
     const float inv = normalize ? 1.f / fmaxf(sqrtf(ss), RB_L2_EPS) : 1.f;
-    for (int f = threadIdx.x; f < F; f += 256) pad[f] = bias ? fmaxf(bias[f] * inv, 0.f) : 0.f;
+    for (int f = threadIdx.x; f < F; f += 256) {
+        const float u = bias ? bias[f] * inv : 0.f;
+        pad[f] = relu ? fmaxf(u, 0.f) : u;
+    }
 }
 // dbias = J^T (dpad * [u > 0]): J of u = b / max(||b||, eps) is inv (I - u u^T) above eps and inv I below
 // (dp_rowops.hip `project`).  A zero bias gives u = 0, every ReLU gate closed and dbias = 0, as torch's relu'(0) = 0.
+// relu = 0: no gate
 __global__ __launch_bounds__(256) void k_pad_const_bwd(const float* bias, const float* dpad, float* dbias, int F,
-                                                       int normalize) {
+                                                       int normalize, int relu) {
     __shared__ float red[256];
     float ss = 0.f;
     for (int f = threadIdx.x; f < F; f += 256) ss += bias[f] * bias[f];
@@ -202,12 +208,12 @@ __global__ __launch_bounds__(256) void k_pad_const_bwd(const float* bias, const 
     float dot = 0.f;
     for (int f = threadIdx.x; f < F; f += 256) {
         const float u = bias[f] * inv;
-        dot += (u > 0.f ? dpad[f] : 0.f) * u;
+        dot += ((!relu || u > 0.f) ? dpad[f] : 0.f) * u;
     }
     dot = block_sum(dot, red);
     for (int f = threadIdx.x; f < F; f += 256) {
         const float u = bias[f] * inv;
-        const float du = u > 0.f ? dpad[f] : 0.f;
+        const float du = (!relu || u > 0.f) ? dpad[f] : 0.f;
         dbias[f] = inv * (du - (project ? u * dot : 0.f));
     }
 }
@@ -289,6 +295,14 @@ __global__ __launch_bounds__(256) void k_segment_max_bwd(const float* dout, int 
 }
 
 }  // namespace
+
+void segment_max_part(Seq& q, const float* Z, int ldz, const int* chunk_tab, int n_chunks, int F, float* pv, int* pi) {
+    if (!q.ok()) return;
+    hipLaunchKernelGGL(k_segment_max_part, dim3(cdiv(F, 64), n_chunks), dim3(256), 0, q.stream, Z, ldz, chunk_tab, F, pv,
+                       pi);
+    q.check_launch("segment_max_part");
+}
+
 }  // namespace dp
 
 using namespace dp;
@@ -369,7 +383,8 @@ int dp_gcn_pad_const_fwd(const float* bias, float* pad, int F, int flags, void* 
     RB_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
              "dp_gcn_pad_const_fwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
     Seq q((hipStream_t)stream, nullptr, 0);
-    hipLaunchKernelGGL(k_pad_const_fwd, dim3(1), dim3(256), 0, q.stream, bias, pad, F, (flags & DP_F_NORMALIZE) ? 1 : 0);
+    hipLaunchKernelGGL(k_pad_const_fwd, dim3(1), dim3(256), 0, q.stream, bias, pad, F, (flags & DP_F_NORMALIZE) ? 1 : 0,
+                       1);
     q.check_launch("gcn_pad_const_fwd");
     return q.err;
 }
@@ -381,8 +396,31 @@ int dp_gcn_pad_const_bwd(const float* bias, const float* dpad, float* dbias, int
              "dp_gcn_pad_const_bwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
     Seq q((hipStream_t)stream, nullptr, 0);
     hipLaunchKernelGGL(k_pad_const_bwd, dim3(1), dim3(256), 0, q.stream, bias, dpad, dbias, F,
-                       (flags & DP_F_NORMALIZE) ? 1 : 0);
+                       (flags & DP_F_NORMALIZE) ? 1 : 0, 1);
     q.check_launch("gcn_pad_const_bwd");
+    return q.err;
+}
+
+int dp_gcn_row_const_fwd(const float* bias, float* c, int F, int flags, void* stream) {
+    RB_PTR(c);
+    RB_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_row_const_fwd: F=%d must be positive", F);
+    RB_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
+             "dp_gcn_row_const_fwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
+    Seq q((hipStream_t)stream, nullptr, 0);
+    hipLaunchKernelGGL(k_pad_const_fwd, dim3(1), dim3(256), 0, q.stream, bias, c, F, (flags & DP_F_NORMALIZE) ? 1 : 0, 0);
+    q.check_launch("gcn_row_const_fwd");
+    return q.err;
+}
+
+int dp_gcn_row_const_bwd(const float* bias, const float* dc, float* dbias, int F, int flags, void* stream) {
+    RB_PTR(bias); RB_PTR(dc); RB_PTR(dbias);
+    RB_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_row_const_bwd: F=%d must be positive", F);
+    RB_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
+             "dp_gcn_row_const_bwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
+    Seq q((hipStream_t)stream, nullptr, 0);
+    hipLaunchKernelGGL(k_pad_const_bwd, dim3(1), dim3(256), 0, q.stream, bias, dc, dbias, F,
+                       (flags & DP_F_NORMALIZE) ? 1 : 0, 0);
+    q.check_launch("gcn_row_const_bwd");
     return q.err;
 }
 

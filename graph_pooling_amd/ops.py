@@ -482,6 +482,153 @@ def segment_max(z, batch):
     return _SegmentMaxFn.apply(z, batch)
 
 
+# -- the base encoder's UNMASKED max readout on a ragged batch: the padded rows enter the maximum
+class _RowConstFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bias, flags):
+        lib = _lib.load()
+        bias = bias.contiguous()
+        f = bias.numel()
+        c = _f32(bias, f)
+        _lib.check(lib.dp_gcn_row_const_fwd(bias.data_ptr(), c.data_ptr(), f, flags, _lib.current_stream()),
+                   "dp_gcn_row_const_fwd")
+        ctx.save_for_backward(bias)
+        ctx.flags = flags
+        return c
+
+    @staticmethod
+    def backward(ctx, dc):
+        lib = _lib.load()
+        (bias,) = ctx.saved_tensors
+        f = bias.numel()
+        dc = dc.contiguous()
+        dbias = torch.empty_like(bias)
+        _lib.check(lib.dp_gcn_row_const_bwd(bias.data_ptr(), dc.data_ptr(), dbias.data_ptr(), f, ctx.flags,
+                                            _lib.current_stream()), "dp_gcn_row_const_bwd")
+        return dbias, None
+
+
+def gcn_row_const(bias, flags):
+    """l2norm(bias) [F], `gcn_pad_const` without the ReLU: what a padded row of the dense batch holds behind the LAST
+    GraphConv layer (no ReLU, no BatchNorm behind it) — dp_gcn_row_const_*; the backward returns the bias gradient."""
+    return _RowConstFn.apply(bias, flags)
+
+
+class _BnReluRaggedPadvalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pad, batch):
+        lib = _lib.load()
+        x = x.contiguous()
+        n, f = x.shape
+        pad = None if pad is None else pad.contiguous()
+        y = torch.empty_like(x)
+        stats = _f32(x, batch.n_idx, 2)
+        padval = _f32(x, batch.n_idx, f)
+        st = _lib.current_stream()
+        _lib.check(lib.dp_bn_ragged_fwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), batch.node_off.data_ptr(),
+                                        batch.order.data_ptr(), batch.cnt.data_ptr(), _lib.ptr(pad), batch.num_graphs,
+                                        batch.max_n, f, 1, st), "dp_bn_ragged_fwd")
+        _lib.check(lib.dp_ragged_padval_fwd(stats.data_ptr(), _lib.ptr(pad), padval.data_ptr(), f, batch.min_n,
+                                            batch.max_n, batch.n_idx, f, st), "dp_ragged_padval_fwd")
+        ctx.save_for_backward(x, y, stats, pad)
+        ctx.batch = batch
+        ctx.set_materialize_grads(False)      # G = None: no padded row won anything, no zero table is made up
+        return y, padval
+
+    @staticmethod
+    def backward(ctx, dy, g):
+        lib = _lib.load()
+        x, y, stats, pad = ctx.saved_tensors
+        batch = ctx.batch
+        n, f = x.shape
+        dy = torch.zeros_like(x) if dy is None else dy.contiguous()
+        g = None if g is None else g.contiguous()
+        dx = torch.empty_like(x)
+        dpad = torch.empty_like(pad) if pad is not None and ctx.needs_input_grad[1] else None
+        wsb = lib.dp_bn_ragged_workspace_bytes(batch.n_idx, f)
+        ws = _workspace(wsb, x)
+        _lib.check(lib.dp_bn_ragged_g_bwd(x.data_ptr(), f, y.data_ptr(), f, stats.data_ptr(), dy.data_ptr(), f,
+                                          dx.data_ptr(), f, _lib.ptr(dpad), _lib.ptr(g), f, batch.node_off.data_ptr(),
+                                          batch.order.data_ptr(), batch.cnt.data_ptr(), _lib.ptr(pad), batch.num_graphs,
+                                          batch.max_n, batch.n_idx, f, 1, ws.data_ptr(), wsb, _lib.current_stream()),
+                   "dp_bn_ragged_g_bwd")
+        return dx, dpad, None
+
+
+def bn_relu_ragged_padval(x, pad, batch):
+    """`bn_relu_ragged` that also returns what the PADDED rows of the dense batch hold behind the BatchNorm: (y [n_total,
+    f], padval [batch.n_idx, f]) with padval[i] = (pad - mean_i) rstd_i for the node indices i >= batch.min_n that have
+    a padded row (lower rows are not written; row max_n, there when pad_to > max_n, stands for every index from max_n
+    up) — dp_bn_ragged_fwd + dp_ragged_padval_fwd.  The backward takes (dy, G), G the gradient of padval (the padded
+    rows' output gradients summed per node index): dp_bn_ragged_g_bwd."""
+    return _BnReluRaggedPadvalFn.apply(x, pad, batch)
+
+
+class _SegmentMaxFloorFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, floor, batch):
+        lib = _lib.load()
+        z = z.contiguous()
+        n, f = z.shape
+        b = batch.num_graphs
+        st = _lib.current_stream()
+        out = _f32(z, b, f)
+        arg = torch.empty(b, f, device=z.device, dtype=torch.int32)
+        sufv = sufi = row = None
+        if floor is not None and floor.dim() == 2:
+            floor = floor.contiguous()
+            sufv = torch.empty_like(floor)
+            sufi = torch.empty(floor.shape, device=z.device, dtype=torch.int32)
+            wsb = lib.dp_ragged_suffix_max_workspace_bytes(batch.min_n, batch.n_idx, f)
+            ws = _workspace(wsb, z)
+            _lib.check(lib.dp_ragged_suffix_max(floor.data_ptr(), f, sufv.data_ptr(), sufi.data_ptr(), f, batch.min_n,
+                                                batch.n_idx, f, ws.data_ptr(), wsb, st), "dp_ragged_suffix_max")
+        elif floor is not None:
+            row = floor.contiguous()
+        nch = batch.seg_chunks
+        wsb = lib.dp_segment_max_workspace_bytes(nch, f)
+        ws = _workspace(wsb, z)
+        _lib.check(lib.dp_segment_max_floor_fwd(z.data_ptr(), f, batch.node_off.data_ptr(), batch.seg_tab.data_ptr(),
+                                                batch.seg_off.data_ptr(), nch, batch.floor_flag.data_ptr(),
+                                                _lib.ptr(sufv), _lib.ptr(sufi), f, batch.min_n, batch.n_idx,
+                                                _lib.ptr(row), out.data_ptr(), f, arg.data_ptr(), b, f, ws.data_ptr(),
+                                                wsb, st), "dp_segment_max_floor_fwd")
+        ctx.save_for_backward(arg)
+        ctx.batch, ctx.shape = batch, (n, f)
+        ctx.floor_shape = None if floor is None else tuple(floor.shape)
+        ctx.mark_non_differentiable(arg)
+        ctx.set_materialize_grads(False)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        lib = _lib.load()
+        (arg,) = ctx.saved_tensors
+        n, f = ctx.shape
+        batch = ctx.batch
+        dz = torch.zeros(n, f, device=dout.device, dtype=torch.float32)
+        dout = dout.contiguous()
+        g = None
+        if ctx.floor_shape is not None and ctx.needs_input_grad[1]:
+            g = torch.empty(ctx.floor_shape, device=dout.device, dtype=torch.float32)
+        table = 1 if ctx.floor_shape is not None and len(ctx.floor_shape) == 2 else 0
+        _lib.check(lib.dp_segment_max_floor_bwd(dout.data_ptr(), f, arg.data_ptr(), batch.node_off.data_ptr(),
+                                                dz.data_ptr(), f, _lib.ptr(g), f, batch.min_n, batch.n_idx, table,
+                                                batch.num_graphs, f, _lib.current_stream()),
+                   "dp_segment_max_floor_bwd")
+        return dz, g, None
+
+
+def segment_max_floor(z, floor, batch):
+    """The UNMASKED max readout per graph of a ragged batch (torch.max over all pad_to rows of the dense batch,
+    encoders.py:1093), z [n_total, f] -> (out [B, f], arg-max rows of the DENSE batch int32 [B, f]: < n_b a real row,
+    graph-local; in [n_b, pad_to) a padded one).  `floor` is what the padded rows hold: the table [batch.n_idx, f] of
+    `bn_relu_ragged_padval` (graph b takes the suffix maximum from node index n_b up, lowest index on equal values:
+    dp_ragged_suffix_max), one constant row [f] (winner n_b), or None (no graph has a padded row).  A real row wins an
+    exact tie.  The backward returns (dz, G) with G shaped like `floor` — dp_segment_max_floor_*."""
+    return _SegmentMaxFloorFn.apply(z, floor, batch)
+
+
 class _CsrPoolBatchFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s, z, batch):

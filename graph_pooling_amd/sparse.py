@@ -11,7 +11,15 @@ The neighbour sum  A x  is the CSR gather of dp_csr_aggregate (the MeanAggregato
 aggregators.py:50-62), the transform, bias, l2-normalisation and their backward the kernels of the dense path
 (dp_sparse_gcn_layer_fwd / bwd); apply_bn on a single graph is dp_bn_node_* with B = 1; the Linear layers of the
 prediction head run on dp_bgemm_f32 (`hip_linear`).  No torch arithmetic on the path.  The autograd wrappers of these
-entries live in `ops.py`; this module holds the CSR container and the two model classes.
+entries live in `ops.py`; this module holds the CSR containers and the model classes.
+
+`SparseBatchGcnEncoderGraph` is the same base model on a ragged `CsrBatch`.  The base class's max readout is unmasked,
+so in the dense batch the padded rows compete: behind apply_bn a padded row holds the layer's constant pushed through
+the statistics of its node index, and a small graph's readout is often such a value.  The subclass keeps a table of
+those values per node index (dp_ragged_padval_fwd), takes its suffix maximum (dp_ragged_suffix_max) as the floor of
+the segmented max (dp_segment_max_floor_*), and sends a padded winner's gradient back through its node index's
+statistics (dp_bn_ragged_g_bwd) and into the bias (dp_gcn_pad_const_* / dp_gcn_row_const_*).  The parent class keeps
+refusing a batch, and says so.
 
 `SparseSoftPoolingGcnEncoder` does the same for DiffPool (`SoftPoolingGcnEncoder`) on one `CsrGraph` or on a ragged
 `CsrBatch`, in ONE forward and one loss.  The two containers differ in four steps, each a method of the container:
@@ -127,7 +135,7 @@ class CsrBatch:
     to `pad_to` nodes (default: max_b n_b).
 
     Fields: `num_graphs`, `num_nodes` (host int array [B]), `node_off` (int32 [B+1] on the device) / `node_off_host`,
-    `n_total`, `max_n`, `pad_to`.  The adjacency is one block-diagonal CSR: `indptr` [n_total+1] with `indices` holding
+    `n_total`, `max_n`, `min_n`, `pad_to`, `n_idx`.  The adjacency is one block-diagonal CSR: `indptr` [n_total+1] with `indices` holding
     GLOBAL columns (rows of the concatenated tensors: GraphConv, pooling) and `indices_local` graph-local ones (link
     loss); `indptr_t` / `indices_t` / `indices_t_local` the CSR of A^T — the same tensors unless a graph is directed.
 
@@ -196,6 +204,10 @@ class CsrBatch:
         self.order = torch.from_numpy(order.astype(np.int32)).to(self.device)
         self.cnt = torch.from_numpy(cnt.astype(np.int32)).to(self.device)
         self.has_padding = bool((sizes < self.max_n).any())
+        # the unmasked readout's table of padded-row values: node indices min_n .. n_idx - 1 have a padded row in the
+        # dense batch; row max_n (there when pad_to > max_n) stands for every index from max_n up
+        self.min_n = int(sizes.min())
+        self.n_idx = self.max_n + int(self.pad_to > self.max_n)
         self.floor_flag = torch.from_numpy((sizes < self.pad_to).astype(np.int32)).to(self.device)
         # segmented max: row chunks that never cross a graph boundary
         tab, seg_off = [], [0]
@@ -330,7 +342,8 @@ class SparseGcnEncoderGraph(GcnEncoderGraph):
         if isinstance(graph, CsrBatch):
             raise TypeError("SparseGcnEncoderGraph takes one CsrGraph per call: its max readout is unmasked, so on a "
                             "batch the padded rows' post-BatchNorm values enter the maximum (a suffix-max over node "
-                            "indices), which is not built; SparseSoftPoolingGcnEncoder accepts a CsrBatch")
+                            "indices), which its subclass SparseBatchGcnEncoderGraph computes; "
+                            "SparseSoftPoolingGcnEncoder accepts a CsrBatch too")
         if not isinstance(graph, CsrGraph):
             raise TypeError("SparseGcnEncoderGraph.forward(x [n, F], graph: CsrGraph): the dense (x [B, N, F], adj, "
                             "batch_num_nodes) form is GcnEncoderGraph's")
@@ -343,6 +356,92 @@ class SparseGcnEncoderGraph(GcnEncoderGraph):
     @torch.no_grad()
     def predict(self, x, graph):
         return self.forward(x, graph).argmax(dim=1)
+
+
+class SparseBatchGcnEncoderGraph(SparseGcnEncoderGraph):
+    """`GcnEncoderGraph` on a ragged `CsrBatch`: forward(x [n_total, F], batch) -> ypred [B, label_dim], computing what
+    the dense class computes on the same graphs padded to `batch.pad_to` rows, without storing a padded row.  Same
+    constructor and `state_dict` keys as the dense class; a `CsrGraph` goes to the parent's forward.
+
+    The base class's readout is UNMASKED (encoders.py:1093: torch.max over all rows, the mask of :1087 is never used),
+    so the padded rows of the dense batch compete.  Behind GraphConv -> ReLU -> apply_bn a padded row of node index i
+    holds (p - mean_i) rstd_i, p = relu(l2norm(bias)): a different value per node index, and a graph with n_b rows
+    sees the maximum over the indices n_b .. pad_to - 1 (`ops.bn_relu_ragged_padval` makes the table, indices from
+    max_n up share one row; `ops.segment_max_floor` takes its suffix maximum).  Without BatchNorm every padded row
+    holds p, behind the last layer l2norm(bias): one constant row as the floor.  The gradient of a padded winner flows
+    through its node index's statistics into every graph that owns the index, and into the layer's bias.
+
+    `saved_activation(layer, 'readout_argmax')` gives the winners of the last batch forward as rows of the DENSE batch.
+
+    Not on this path: concat=False (add_self: a padded row is then not a constant of the layer), dropout."""
+
+    def forward(self, x, graph):
+        if not isinstance(graph, CsrBatch):
+            self._saved_argmax = None
+            return super().forward(x, graph)
+        batch = graph
+        if not self.concat:
+            raise NotImplementedError("add_self GraphConv layers (concat=False) on a CsrBatch: a padded row of the dense "
+                                      "batch is then not a constant of the layer")
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != batch.n:
+            got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"expected x {batch.rows()}, got {got}")
+        if x.shape[1] != self.input_dim:
+            raise ValueError(f"x has {x.shape[1]} features, the encoder was built for {self.input_dim}")
+        _lib.require_gpu_tensor(x, "x")
+        h = x.contiguous().float()
+        mods = self._stack_modules(self.conv_first, self.conv_block, self.conv_last)
+        floored = batch.n_idx > batch.min_n          # some graph has a padded row in the dense batch
+        outs, argmax = [], []
+        for i, m in enumerate(mods):
+            flags = m._flags()
+            h = ops.csr_graph_conv(h, m.weight, m.bias, batch, flags)
+            if not floored:
+                floor = None
+                if i < len(mods) - 1:
+                    h = ops.bn_relu_ragged(h, None, batch) if self.bn else torch.relu(h)
+            elif i == len(mods) - 1:                 # no ReLU, no BatchNorm: every padded row holds l2norm(bias)
+                floor = self._row_const(ops.gcn_row_const, m, flags, h)
+            elif self.bn:
+                pad = None if m.bias is None else ops.gcn_pad_const(m.bias, flags)
+                h, floor = ops.bn_relu_ragged_padval(h, pad, batch)
+            else:                                    # every padded row holds relu(l2norm(bias))
+                h = torch.relu(h)
+                floor = self._row_const(ops.gcn_pad_const, m, flags, h)
+            out, arg = ops.segment_max_floor(h, floor, batch)                                    # :1093, :1100, :1107
+            outs.append(out)
+            argmax.append(arg)
+        self._saved_argmax = argmax
+        return ops.mlp_head(torch.cat(outs, dim=1), self._pred_linears())
+
+    @staticmethod
+    def _row_const(fn, layer, flags, like):
+        if layer.bias is None:
+            return torch.zeros(layer.weight.shape[1], device=like.device, dtype=torch.float32)
+        return fn(layer.bias, flags)
+
+    def loss(self, pred, label, type='softmax'):
+        """Cross entropy of the prediction (encoders.py:1124-1127) on dp_cross_entropy_*; label [B] for a batch."""
+        if type != 'softmax':
+            return super().loss(pred, label, type=type)
+        if pred.dim() != 2 or not isinstance(label, torch.Tensor) or label.numel() != pred.shape[0]:
+            got = label.numel() if isinstance(label, torch.Tensor) else label.__class__.__name__
+            raise ValueError(f"SparseBatchGcnEncoderGraph.loss(pred, label): label must hold one class per row of pred "
+                             f"{tuple(pred.shape)}, got {got}")
+        return ops.cross_entropy(pred, label.reshape(-1))
+
+    def saved_activation(self, level, what):
+        """'readout_argmax' of GraphConv layer `level` of the LAST batch forward: int32 [B, F_layer] rows of the dense
+        batch — a value < n_b is a real row (graph-local), a value in [n_b, pad_to) a padded row (the lowest node index
+        that holds the maximum; max_n stands for every index from max_n up).  Detached: clone to keep it."""
+        if what != "readout_argmax":
+            raise ValueError(f"saved_activation(): unknown activation {what!r} on the CSR path")
+        saved = getattr(self, "_saved_argmax", None)
+        if saved is None:
+            raise RuntimeError("saved_activation(): no batch forward pass has run yet")
+        if not 0 <= level < len(saved):
+            raise IndexError(f"saved_activation(): layer {level} out of range ({len(saved)} layers)")
+        return saved[level].detach()
 
 
 # ----------------------------------------------------------------------------- DiffPool on a CSR graph

@@ -636,6 +636,53 @@ int dp_segment_max_fwd(const float* Z, int ldz, const int* node_off, const int* 
 int dp_segment_max_bwd(const float* dout, int ldo, const int* argmax, const int* node_off, float* dZ, int lddz, int B,
                        int F, void* stream);
 
+/* The UNMASKED max readout of the base encoder (A11: torch.max over all P = pad_to rows of the dense batch) on a ragged
+ * batch.  Behind apply_bn every padded row of node index i holds v[i,f] = (pad[f] - mean_i) rstd_i, so the padded rows of
+ * a graph with n_b < P contribute max_{i >= n_b} v[i,f]: a suffix maximum over node indices.  n_min = min_b n_b (lower
+ * indices have no padded row), n_idx = max_n + (P > max_n): the TAIL ROW max_n stands for every index >= max_n, whose B
+ * rows all hold pad (statistics of pad alone: mean over f, biased variance, eps 1e-5).  Every table below is [n_idx, .];
+ * rows below n_min are never read or written.  The argmax of these entries is the row of the DENSE batch: < n_b a real
+ * row (graph-local), in n_b .. P-1 a padded one (the lowest index that attains the maximum; the tail reports max_n).
+ *
+ * dp_ragged_padval_fwd: padval rows n_min .. n_idx-1 from stats [n_idx,2] (rows < max_n as dp_bn_ragged_fwd wrote them;
+ * row max_n is WRITTEN here when n_idx > max_n) and pad [F] (NULL = zeros).  One launch.
+ * dp_ragged_suffix_max: sufv[i,f] = max_{j >= i} padval[j,f], sufi the lowest such j, for i = n_min .. n_idx-1.  Two
+ * launches: maxima of 64-row blocks, then each block scans its rows downwards from the combined maxima of the blocks
+ * above it; equal values keep the lowest index at both levels. */
+int dp_ragged_padval_fwd(float* stats, const float* pad, float* padval, int ldp, int n_min, int max_n, int n_idx, int F,
+                         void* stream);
+size_t dp_ragged_suffix_max_workspace_bytes(int n_min, int n_idx, int F);
+int dp_ragged_suffix_max(const float* padval, int ldp, float* sufv, int* sufi, int lds, int n_min, int n_idx, int F,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* dp_segment_max_floor_*: dp_segment_max_* (same chunk tables, same first launch, workspace of
+ * dp_segment_max_workspace_bytes) whose floor for the graphs with floor_flag != 0 is row n_b of the suffix table (sufv,
+ * sufi: winner sufi[n_b,f]) or the constant row floor_row [F] (winner n_b) — one of the two, or neither (no floor).  A
+ * real row wins an exact tie with the floor.  The backward ACCUMULATES INTO dZ for real winners and builds the floor's
+ * gradient G in a fixed order (one thread per column walks b = 0 .. B-1): table != 0: G [n_idx, F] (ldg), rows
+ * n_min .. n_idx-1 zero-filled here, G[i,f] = sum of dout[b,f] over the graphs whose winner is padded index i; table == 0:
+ * G [F] (OVERWRITTEN) = sum over the graphs whose floor won.  G NULL: only dZ.  Launch counts do not depend on B. */
+int dp_segment_max_floor_fwd(const float* Z, int ldz, const int* node_off, const int* chunk_tab, const int* chunk_off,
+                             int n_chunks, const int* floor_flag, const float* sufv, const int* sufi, int lds,
+                             int n_min, int n_idx, const float* floor_row, float* out, int ldo, int* argmax, int B,
+                             int F, void* workspace, size_t workspace_bytes, void* stream);
+int dp_segment_max_floor_bwd(const float* dout, int ldo, const int* argmax, const int* node_off, float* dZ, int lddz,
+                             float* G, int ldg, int n_min, int n_idx, int table, int B, int F, void* stream);
+/* dp_bn_ragged_bwd when the padded rows received output gradients: G [n_idx, F] (ldg) holds, per node index and feature,
+ * the sum of dy over that index's padded rows (rows of indices without a padded row are not read).  With xhat_pad = v[i,f]:
+ * mean(dy) and mean(dy xhat) of index i gain sum_f G and sum_f G v, dx of the real rows keeps its formula, and
+ * dpad[f] = sum_i rstd_i (G[i,f] - (B - cnt[i]) (m1_i + v[i,f] m2_i)); the tail row counts as one index with cnt = 0.
+ * (the per-workgroup partial rows of dpad are summed in double in a fixed order and rounded once: with G the running
+ * sums reach hundreds of times an entry).  stats [n_idx,2]; workspace: dp_bn_ragged_workspace_bytes(n_idx, F).
+ * G == NULL is dp_bn_ragged_bwd itself. */
+int dp_bn_ragged_g_bwd(const float* x, int ldx, const float* y, int ldy, const float* stats, const float* dy, int lddy,
+                       float* dx, int lddx, float* dpad, const float* G, int ldg, const int* node_off, const int* order,
+                       const int* cnt, const float* pad, int B, int max_n, int n_idx, int F, int relu, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* dp_gcn_pad_const_* without the ReLU: c [F] = bias / max(||bias||, 1e-12) (without DP_F_NORMALIZE: bias; NULL: zeros),
+ * what a padded row holds behind the LAST GraphConv layer, and dbias [F] (OVERWRITTEN) through the l2norm Jacobian. */
+int dp_gcn_row_const_fwd(const float* bias, float* c, int F, int flags, void* stream);
+int dp_gcn_row_const_bwd(const float* bias, const float* dc, float* dbias, int F, int flags, void* stream);
+
 /* dp_csr_pool_batch_*: the level-0 pooling of dp_csr_pool_* for every graph of the batch, Xp [B,K,D], Ap [B,K,K], from
  * the ragged S [n_total,K], Z [n_total,D] and the block-diagonal CSR (GLOBAL column indices).  The kernels are those of
  * dp_csr_pool_*, driven by tables: dp_csr_pool_batch_plan (host only, no GPU call) writes for the sizes node_off_host
