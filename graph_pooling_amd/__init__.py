@@ -2,8 +2,19 @@
 
     from graph_pooling_amd.encoders import SoftPoolingGcnEncoder, GcnEncoderGraph, GcnSet2SetEncoder
     from graph_pooling_amd.set2set import Set2Set
+    from graph_pooling_amd import SparseGcnSet2SetEncoder      # GCN + Set2Set on CSR graphs and ragged batches (sparse.py)
 
 The arithmetic lives in libdiffpool_hip.so (graph_pooling_amd/csrc, C ABI in include/diffpool_hip.h).
 Importing this package does not load the library; the first forward does, and raises if it is missing.
 """
 __version__ = "0.1.0"
+
+__all__ = ["SparseGcnSet2SetEncoder"]
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package (or graph_pooling_amd.ops alone) pulls in no model module
+    if name == "SparseGcnSet2SetEncoder":
+        from .sparse import SparseGcnSet2SetEncoder
+        return SparseGcnSet2SetEncoder
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

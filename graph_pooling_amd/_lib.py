@@ -188,6 +188,13 @@ _PROTOS = {
     "dp_set2set_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_set2set_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P,
                             _I, _I, _I, _P, _Z, _P, _Z, _P]),
+    # Set2Set on a ragged batch (node_off_host is a host pointer, passed as an address)
+    "dp_set2set_ragged_plan": (_I, [_I, _I]),
+    "dp_set2set_ragged_save_bytes": (_Z, [_P, _I, _I, _I]),
+    "dp_set2set_ragged_bwd_workspace_bytes": (_Z, [_P, _I, _I, _I]),
+    "dp_set2set_ragged_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "dp_set2set_ragged_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
+                                   _P, _P, _P, _Z, _P, _Z, _P]),
     "dp_mean_aggregate_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "dp_mean_aggregate_bwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "dp_csr_aggregate": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),

@@ -647,6 +647,10 @@ void csr_aggregate_bwd_scatter(Seq& q, const float* dout, int ldo, const int* in
 // table {graph, first row, end row, 0} the column maxima pv [n_chunks, F] and their global rows pi, ties to the lowest row
 void segment_max_part(Seq& q, const float* Z, int ldz, const int* chunk_tab, int n_chunks, int F, float* pv, int* pi);
 
+// (dp_set2set.hip) wt [2d][4d + 1], row k: W_ih[:, k] (+ W_hh[:, k] for k < d) — the LSTM weights as the persistent
+// Set2Set kernels read them
+void set2set_prep_weights(Seq& q, const float* w_ih, const float* w_hh, float* wt, int d);
+
 // (dp_linkpred.hip)
 void linkpred_fwd(Seq& q, const float* S, int lds, const float* adj, const int* num_nodes, float* loss_out,
                   int B, int n, int K, const float* norm = nullptr /*device scalar replacing sum n_b^2*/);

@@ -509,6 +509,14 @@ constexpr int S2S_WL = 1, S2S_EL = 2, S2S_WF = 4;      // bits of set2set_plan (
 
 size_t set2set_save_bytes(int B, int n, int d) { return s2s_layout(B, n, d).total * sizeof(float) + 256; }
 
+// wt [2d][4d + 1] = the combined, transposed LSTM weights (k_s2s_prep) for a caller with its own buffer: the ragged
+// backward (dp_set2set_ragged.hip)
+void set2set_prep_weights(Seq& q, const float* w_ih, const float* w_hh, float* wt, int d) {
+    if (!q.ok()) return;
+    hipLaunchKernelGGL(k_s2s_prep, dim3((8 * d * d + 255) / 256), dim3(256), 0, q.stream, w_ih, w_hh, wt, d, 4 * d + 1);
+    q.check_launch("s2s_prep");
+}
+
 // The ONE place that picks the k_set2set_* variant, for the forward and the backward alike (host only, no GPU call).
 // The embedding is staged in LDS only beside weights that sit in registers or in LDS: no instance of the kernels
 // combines it with weights read from global memory, so d >= 70 never asks for that LDS.

@@ -713,6 +713,73 @@ def csr_link_loss_batch(s, batch):
     return _CsrLinkLossBatchFn.apply(s, batch)
 
 
+# ----------------------------------------------------------------------------- Set2Set on ragged rows
+def _s2s_offsets(graph):
+    """(node_off on the device, address of node_off_host, B, T) of a CsrBatch, or of a CsrGraph as the batch of one
+    without padding (its two-entry offset table is made once and kept on the graph)."""
+    if hasattr(graph, "node_off_host"):
+        return graph.node_off, graph.node_off_host.ctypes.data, graph.num_graphs, graph.pad_to
+    cached = getattr(graph, "_s2s_off", None)
+    if cached is None:
+        host = torch.tensor([0, graph.n], dtype=torch.int32)
+        cached = graph._s2s_off = (host.to(graph.indptr.device), host)
+    return cached[0], cached[1].data_ptr(), 1, graph.n
+
+
+class _Set2SetRaggedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, graph, keep, w_ih, w_hh, b_ih, b_hh, wp, bp):
+        lib = _lib.load()
+        _lib.require_gpu_tensor(emb, "embedding")
+        emb = emb.contiguous().float()
+        n_total, d = emb.shape
+        off, off_host, nb, t = _s2s_offsets(graph)
+        ts = [p.contiguous() for p in (w_ih, w_hh, b_ih, b_hh, wp, bp)]
+        out = _f32(emb, nb, d)
+        sb = lib.dp_set2set_ragged_save_bytes(off_host, nb, t, d) if keep else 0
+        save = _workspace(sb, emb) if keep else None
+        _lib.check(lib.dp_set2set_ragged_fwd(emb.data_ptr(), d, off.data_ptr(), off_host, nb, t, d,
+                                             *[p.data_ptr() for p in ts], out.data_ptr(), _lib.ptr(save), sb,
+                                             _lib.current_stream()), "dp_set2set_ragged_fwd")
+        ctx.save_for_backward(emb, *ts, out)
+        ctx.s2s = (graph, save)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        emb, w_ih, w_hh, b_ih, b_hh, wp, bp, out = ctx.saved_tensors
+        graph, save = ctx.s2s
+        if save is None:
+            raise RuntimeError("set2set_ragged: the forward ran without a save buffer (torch.no_grad()), there is "
+                               "nothing to differentiate")
+        n_total, d = emb.shape
+        off, off_host, nb, t = _s2s_offsets(graph)
+        dout = dout.contiguous().float()
+        demb = torch.empty_like(emb)
+        grads = [torch.empty_like(p) for p in (w_ih, w_hh, b_ih, b_hh, wp, bp)]
+        wsb = lib.dp_set2set_ragged_bwd_workspace_bytes(off_host, nb, t, d)
+        ws = _workspace(wsb, emb)
+        _lib.check(lib.dp_set2set_ragged_bwd(emb.data_ptr(), d, off.data_ptr(), off_host, nb, t, d,
+                                             w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(),
+                                             wp.data_ptr(), bp.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                                             demb.data_ptr(), d, *[g.data_ptr() for g in grads], save.data_ptr(),
+                                             save.numel(), ws.data_ptr(), wsb, _lib.current_stream()),
+                   "dp_set2set_ragged_bwd")
+        return (demb, None, None, *grads)
+
+
+def set2set_ragged(emb, graph, w_ih, w_hh, b_ih, b_hh, wp, bp):
+    """Set2Set.forward (set2set.py:32-57) of the ragged rows emb [n_total, d] of a CsrBatch -> [B, d]: what the dense
+    kernels give on the batch zero-padded to `pad_to` rows (that many steps, the padded rows' zero logits in every
+    softmax), on dp_set2set_ragged_*; a CsrGraph is the batch of one without padding -> [1, d].  Parameters in nn.LSTM /
+    nn.Linear layout.  Under torch.no_grad() no per-step state is kept (the entry gets no save buffer)."""
+    if emb.dim() != 2 or emb.shape[0] != graph.n:
+        raise ValueError(f"set2set_ragged: expected embedding [n, d] with n = {graph.n}, got {tuple(emb.shape)}")
+    keep = torch.is_grad_enabled() and any(t.requires_grad for t in (emb, w_ih, w_hh, b_ih, b_hh, wp, bp))
+    return _Set2SetRaggedFn.apply(emb, graph, keep, w_ih, w_hh, b_ih, b_hh, wp, bp)
+
+
 # ----------------------------------------------------------------------------- loss
 class _CrossEntropyFn(torch.autograd.Function):
     @staticmethod

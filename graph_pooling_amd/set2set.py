@@ -4,13 +4,17 @@
 The parameters live in the same ``nn.LSTM`` / ``nn.Linear`` containers as the reference (state_dict
 keys ``lstm.weight_ih_l0`` ... ``pred.bias``); the n sequential steps run inside one persistent HIP
 kernel per pass (libdiffpool_hip.so: dp_set2set_fwd / dp_set2set_bwd), not as n x 6 torch ops.
+
+``forward(embedding, graph)`` takes the RAGGED rows ``[n_total, d]`` of a ``sparse.CsrBatch`` (or the ``[n, d]`` of a
+``sparse.CsrGraph``) and gives ``[B, d]``: what the one-argument call gives on the batch zero-padded to ``pad_to``
+rows, on dp_set2set_ragged_* — without the dense kernels' limit of 1024 rows.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, ops
 
 
 class _Set2SetFn(torch.autograd.Function):
@@ -73,7 +77,10 @@ class Set2Set(nn.Module):
             raise NotImplementedError("the HIP Set2Set supports num_layers=1, hidden_dim == 2*input_dim, ReLU "
                                       "(the only configuration the reference instantiates)")
 
-    def forward(self, embedding):
+    def forward(self, embedding, graph=None):
         l = self.lstm
+        if graph is not None:
+            return ops.set2set_ragged(embedding, graph, l.weight_ih_l0, l.weight_hh_l0, l.bias_ih_l0, l.bias_hh_l0,
+                                      self.pred.weight, self.pred.bias)
         return _Set2SetFn.apply(embedding, l.weight_ih_l0, l.weight_hh_l0, l.bias_ih_l0, l.bias_hh_l0,
                                 self.pred.weight, self.pred.bias)

@@ -21,6 +21,10 @@ the segmented max (dp_segment_max_floor_*), and sends a padded winner's gradient
 statistics (dp_bn_ragged_g_bwd) and into the bias (dp_gcn_pad_const_* / dp_gcn_row_const_*).  The parent class keeps
 refusing a batch, and says so.
 
+`SparseGcnSet2SetEncoder` is `GcnSet2SetEncoder` on either container: the GCN stack as above, the embedding mask for
+free (a ragged batch stores no padded row, and the dense batch's are zero behind the mask), and the Set2Set readout
+on dp_set2set_ragged_*, where the zero rows of the dense batch are one closed-form term of every step's softmax.
+
 `SparseSoftPoolingGcnEncoder` does the same for DiffPool (`SoftPoolingGcnEncoder`) on one `CsrGraph` or on a ragged
 `CsrBatch`, in ONE forward and one loss.  The two containers differ in four steps, each a method of the container:
 `bn_relu` (dp_bn_node_* / dp_bn_ragged_*), `readout` (dp_masked_max_* / dp_segment_max_*), `pool` — S^T Z, S^T A S,
@@ -35,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .encoders import (GcnEncoderGraph, SoftPoolingGcnEncoder, _refuse_ent_under_sync_bn,
+from .encoders import (GcnEncoderGraph, GcnSet2SetEncoder, SoftPoolingGcnEncoder, _refuse_ent_under_sync_bn,
                        _refuse_frob_under_sync_bn)
 from .ops import hip_linear  # noqa: F401  (tests and tools import it from here)
 
@@ -442,6 +446,66 @@ class SparseBatchGcnEncoderGraph(SparseGcnEncoderGraph):
         if not 0 <= level < len(saved):
             raise IndexError(f"saved_activation(): layer {level} out of range ({len(saved)} layers)")
         return saved[level].detach()
+
+
+# ----------------------------------------------------------------------------- GCN + Set2Set on CSR graphs
+class SparseGcnSet2SetEncoder(GcnSet2SetEncoder):
+    """`GcnSet2SetEncoder` (encoders.py:1137-1157) on one `CsrGraph` — forward(x [n, F], graph) -> ypred [1, label_dim]
+    — or on a ragged `CsrBatch` — forward(x [n_total, F], batch) -> ypred [B, label_dim], computing what the dense
+    class computes on the same graphs padded to `batch.pad_to` rows.  Same constructor and `state_dict` keys as the
+    dense class (it IS the dense class's module tree), so `load_state_dict(dense.state_dict())` works.
+
+    The embedding is the concatenation of every GraphConv layer's output (gcn_forward, encoders.py:1078) times the
+    embedding mask (:1079-1080), so the padded rows of the dense batch are exactly zero: a ragged batch stores none of
+    them.  They still take part in the readout: Set2Set runs `pad_to` steps and its softmax runs over all `pad_to`
+    rows, where a zero row has logit 0 (`ops.set2set_ragged`: one term P_b exp(-m) in the denominator).  In front of
+    the mask `CsrBatch.bn_relu` puts the padded rows' constants into the BatchNorm statistics and carries their
+    gradient into the bias; no readout gradient reaches a padded row.  No row limit of 1024: a graph may have up to
+    16 384 nodes (dp_set2set_ragged_*); the per-step attention kept for the backward costs 2 * pad_to * n_total floats.
+
+    Not on this path: dropout; concat=False (gcn_forward concatenates every layer whatever the flag, while `s2s` is
+    built for `pred_input_dim`, and on a batch add_self breaks the padded rows' constant)."""
+
+    def __init__(self, input_dim, hidden_dim, embedding_dim, label_dim, num_layers, pred_hidden_dims=[], concat=True,
+                 bn=True, dropout=0.0, args=None):
+        if dropout > 0.001:
+            raise NotImplementedError("dropout on the CSR path")
+        if not concat:
+            raise NotImplementedError("concat=False on the CSR Set2Set path: gcn_forward concatenates every layer "
+                                      "whatever the flag while s2s is built for pred_input_dim, and on a CsrBatch an "
+                                      "add_self layer's padded row is not a constant of the layer")
+        super().__init__(input_dim, hidden_dim, embedding_dim, label_dim, num_layers, pred_hidden_dims=pred_hidden_dims,
+                         concat=concat, bn=bn, dropout=dropout, args=args)
+
+    def forward(self, x, graph):
+        """x [n, F] and a CsrGraph -> ypred [1, label_dim]; x [n_total, F] and a CsrBatch -> ypred [B, label_dim]."""
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError("SparseGcnSet2SetEncoder.forward(x [n, F], graph: CsrGraph or CsrBatch): the dense "
+                            "(x [B, N, F], adj, batch_num_nodes) form is GcnSet2SetEncoder's")
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != graph.n:
+            got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"expected x {graph.rows()}, got {got}")
+        if x.shape[1] != self.input_dim:
+            raise ValueError(f"x has {x.shape[1]} features, the encoder was built for {self.input_dim}")
+        _lib.require_gpu_tensor(x, "x")
+        mods = self._stack_modules(self.conv_first, self.conv_block, self.conv_last)
+        z = torch.cat(list(_gcn_stack(mods, x.contiguous().float(), graph, self.bn)), dim=1)      # :1078
+        return ops.mlp_head(self.s2s(z, graph), self._pred_linears())                             # :1152-1156
+
+    @torch.no_grad()
+    def predict(self, x, graph):
+        """Arg-max class per graph: int64 [B] on the device ([1] for a CsrGraph)."""
+        return self.forward(x, graph).argmax(dim=1)
+
+    def loss(self, pred, label, type='softmax'):
+        """Cross entropy of the prediction (encoders.py:1124-1127) on dp_cross_entropy_*; label [B] for a batch."""
+        if type != 'softmax':
+            return super().loss(pred, label, type=type)
+        if pred.dim() != 2 or not isinstance(label, torch.Tensor) or label.numel() != pred.shape[0]:
+            got = label.numel() if isinstance(label, torch.Tensor) else label.__class__.__name__
+            raise ValueError(f"SparseGcnSet2SetEncoder.loss(pred, label): label must hold one class per row of pred "
+                             f"{tuple(pred.shape)}, got {got}")
+        return ops.cross_entropy(pred, label.reshape(-1))
 
 
 # ----------------------------------------------------------------------------- DiffPool on a CSR graph

@@ -522,6 +522,39 @@ int dp_set2set_bwd(const float* emb, int lde, const float* w_ih, const float* w_
                    float* dbp, int B, int n, int d, const void* save, size_t save_bytes, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* A10 on a RAGGED batch (N4 conventions: graph b owns rows node_off[b] .. node_off[b+1]-1 of emb [n_total, .];
+ * node_off int32 [B+1] on the device, node_off_host the same values on the host, read only by the host).  The batch
+ * stands for the dense batch padded to T rows whose padded rows are exactly zero (the embedding mask,
+ * encoders.py:1079-1080): the recurrence runs T steps, and with P_b = T - n_b zero rows, each with logit 0,
+ *     m = max(max_i e_i, 0) if P_b > 0 else max_i e_i;  Z = sum_i exp(e_i - m) + P_b exp(-m);  a_i = exp(e_i - m) / Z
+ * over the n_b real rows.  out [B,d] and the gradients are those of dp_set2set_fwd / _bwd on the padded batch (demb
+ * [n_total, .]: real rows only).  A single graph is B = 1, T = n.  No row limit of 1024:
+ * Limits: 1 <= d <= 256, 1 <= n_b <= DP_SET2SET_RAGGED_MAX_ROWS at every d, T >= max_b n_b, B <= 65535, B * T < 2^31.  d = 0, T = 0,
+ * an empty graph, T < max_b n_b or a buffer too small: DP_ERR_INVALID_ARG; d > 256 or n_b above the bound:
+ * DP_ERR_UNSUPPORTED; always before any launch, no buffer touched.  B = 0 as dp_set2set_*.
+ * One persistent workgroup per graph; dp_set2set_ragged_plan(n_b, d) is the variant a graph of n_b rows runs, in the
+ * bits of dp_set2set_plan: bit 1 the graph's embedding is staged in LDS (else read from global memory every step),
+ * bit 2 the LSTM weights sit in registers (d <= 64; else read from global memory); bit 0 is never set.  A pass launches
+ * one grid per bit-1 value present in the batch, so launch counts do not depend on B.  Host only.
+ * Memory: the backward keeps a_t and de_t of every step, [T, n_b] per graph: `save` holds T * n_total floats of a_t
+ * plus 8 * B * T * d of LSTM state, the backward workspace T * n_total floats of de_t plus 5 * B * T * d; the size
+ * queries (host only, computed in size_t) return 0 for arguments the entries refuse.  save == NULL in the forward is
+ * inference: nothing is saved and no T x n_b array is touched; `out` is bit for bit that of a saving run.
+ * lde / ldde >= d are row strides as in A10; columns beyond d are never touched.  No atomics: fixed summation order,
+ * two runs agree bit for bit. */
+#define DP_SET2SET_RAGGED_MAX_ROWS 16384
+int dp_set2set_ragged_plan(int n_b, int d);
+size_t dp_set2set_ragged_save_bytes(const int* node_off_host, int B, int T, int d);
+size_t dp_set2set_ragged_bwd_workspace_bytes(const int* node_off_host, int B, int T, int d);
+int dp_set2set_ragged_fwd(const float* emb, int lde, const int* node_off, const int* node_off_host, int B, int T, int d,
+                          const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* Wp,
+                          const float* bp, float* out, void* save, size_t save_bytes, void* stream);
+int dp_set2set_ragged_bwd(const float* emb, int lde, const int* node_off, const int* node_off_host, int B, int T, int d,
+                          const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* Wp,
+                          const float* bp, const float* out, const float* dout, float* demb, int ldde, float* dw_ih,
+                          float* dw_hh, float* db_ih, float* db_hh, float* dWp, float* dbp, const void* save,
+                          size_t save_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ A9  mean aggregator
  * out[i,:] = mean_{j in indices[indptr[i]:indptr[i+1]]} table[j,:] — MeanAggregator.forward with
  * num_sample=None, aggregators.py:50-62 (the row-normalised mask times the embedding matrix, as a
