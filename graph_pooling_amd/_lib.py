@@ -235,6 +235,22 @@ _PROTOS = {
     "dp_csr_linkpred_batch_workspace_bytes": (_Z, [_P, _I, _I]),
     "dp_csr_linkpred_batch_loss_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _Z, _P]),
     "dp_csr_linkpred_batch_loss_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    # weighted CSR: `values` behind each index array (`values_t` behind a transposed one)
+    "dp_csr_aggregate_w": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "dp_sparse_gcn_layer_fwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_sparse_gcn_layer_bwd_w": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I,
+                                       _P, _Z, _P]),
+    "dp_csr_pool_fwd_w": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_pool_bwd_w": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_pool_batch_fwd_w": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_pool_batch_bwd_w": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I,
+                                     _I, _P, _Z, _P]),
+    "dp_csr_linkpred_loss_fwd_w": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
+    "dp_csr_linkpred_loss_bwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_linkpred_batch_loss_fwd_w": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _Z, _P]),
+    "dp_csr_linkpred_batch_loss_bwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_frob_link_fwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
+    "dp_csr_frob_link_batch_fwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -1044,13 +1044,18 @@ size_t dp_csr_frob_link_workspace_bytes(int n_total, int B, int K) {
 static int csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                              const int* indices_t, const int* node_off, const float* link_norm, float* W, float* G,
                              float* loss_out, float* total_inout, int B, int n, int K, void* workspace,
-                             size_t workspace_bytes, void* stream) {
+                             size_t workspace_bytes, void* stream, const float* values = nullptr,
+                             const float* values_t = nullptr) {
     Seq q(STREAM(stream), workspace, workspace_bytes);
     const bool directed = indptr_t && indices_t && !(indptr_t == indptr && indices_t == indices);
-    csr_aggregate_fwd(q, S, lds, indptr, indices, W, K, n, K, 0, 0.f);                       // W = A S
-    if (directed) csr_aggregate_fwd(q, S, lds, indptr_t, indices_t, W, K, n, K, 0, 1.f);     // += A^T S
-    frob_link_fwd(q, S, lds, W, nullptr, 0, 0, nullptr, node_off, indptr + n, link_norm, directed ? 1.f : 2.f, G,
-                  loss_out, total_inout, B, n, n, K);
+    csr_aggregate_fwd(q, S, lds, indptr, indices, W, K, n, K, 0, 0.f, values);                       // W = A S
+    if (directed) csr_aggregate_fwd(q, S, lds, indptr_t, indices_t, W, K, n, K, 0, 1.f, values_t);   // += A^T S
+    if (values)      // T0 = sum of the stored values' squares, by the row kernel (fp64, fixed order)
+        frob_link_fwd(q, S, lds, W, values, 4, 0, nullptr, node_off, nullptr, link_norm, directed ? 1.f : 2.f, G,
+                      loss_out, total_inout, B, n, n, K, indptr);
+    else
+        frob_link_fwd(q, S, lds, W, nullptr, 0, 0, nullptr, node_off, indptr + n, link_norm, directed ? 1.f : 2.f, G,
+                      loss_out, total_inout, B, n, n, K);
     return q.err;
 }
 int dp_csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
@@ -1065,6 +1070,23 @@ int dp_csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* 
     FROB_WS("dp_csr_frob_link_fwd", dp_csr_frob_link_workspace_bytes(n, 1, K));
     return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, nullptr, link_norm, W, G, loss_out,
                              total_inout, 1, n, K, workspace, workspace_bytes, stream);
+}
+int dp_csr_frob_link_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                           const int* indptr_t, const int* indices_t, const float* values_t, const float* link_norm,
+                           float* W, float* G, float* loss_out, float* total_inout, int n, int K, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
+    NONNEG(n); NONNEG(K);
+    FROB_K("dp_csr_frob_link_fwd_w");
+    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_fwd_w: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
+                 "dp_csr_frob_link_fwd_w: indptr_t and indices_t go together (both NULL: undirected)");
+    DP_CHECK_ARG(!indices_t || indices_t == indices || values_t,
+                 "dp_csr_frob_link_fwd_w: values_t is NULL but indices_t is a CSR of its own");
+    FROB_WS("dp_csr_frob_link_fwd_w", dp_csr_frob_link_workspace_bytes(n, 1, K));
+    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, nullptr, link_norm, W, G, loss_out,
+                             total_inout, 1, n, K, workspace, workspace_bytes, stream, values,
+                             indices_t && indices_t != indices ? values_t : values);
 }
 int dp_csr_frob_link_bwd(const float* S, int lds, const float* W, const float* G, const float* link_norm,
                          const float* dloss, float* dS, int ldds, int accumulate, int symmetric, int n, int K,
@@ -1094,6 +1116,26 @@ int dp_csr_frob_link_batch_fwd(const float* S, int lds, const int* indptr, const
     FROB_WS("dp_csr_frob_link_batch_fwd", dp_csr_frob_link_workspace_bytes(n_total, B, K));
     return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, node_off, link_norm, W, G, loss_out,
                              total_inout, B, n_total, K, workspace, workspace_bytes, stream);
+}
+int dp_csr_frob_link_batch_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                                 const int* indptr_t, const int* indices_t, const float* values_t, const int* node_off,
+                                 const float* link_norm, float* W, float* G, float* loss_out, float* total_inout, int B,
+                                 int n_total, int K, void* workspace, size_t workspace_bytes, void* stream) {
+    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(node_off); NOTNULL(W); NOTNULL(G);
+    NOTNULL(loss_out);
+    NONNEG(B); NONNEG(n_total); NONNEG(K);
+    FROB_K("dp_csr_frob_link_batch_fwd_w");
+    DP_CHECK_ARG(B <= n_total, "dp_csr_frob_link_batch_fwd_w: B=%d graphs over n_total=%d rows (every graph has >= 1 node)",
+                 B, n_total);
+    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_batch_fwd_w: lds=%d smaller than K=%d", lds, K);
+    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
+                 "dp_csr_frob_link_batch_fwd_w: indptr_t and indices_t go together (both NULL: undirected)");
+    DP_CHECK_ARG(!indices_t || indices_t == indices || values_t,
+                 "dp_csr_frob_link_batch_fwd_w: values_t is NULL but indices_t is a CSR of its own");
+    FROB_WS("dp_csr_frob_link_batch_fwd_w", dp_csr_frob_link_workspace_bytes(n_total, B, K));
+    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, node_off, link_norm, W, G, loss_out,
+                             total_inout, B, n_total, K, workspace, workspace_bytes, stream, values,
+                             indices_t && indices_t != indices ? values_t : values);
 }
 int dp_csr_frob_link_batch_bwd(const float* S, int lds, const float* W, const float* G, const int* node_off,
                                const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate,
@@ -1203,13 +1245,21 @@ int dp_csr_aggregate(const float* table, int ldt, const int* indptr, const int* 
     csr_aggregate_fwd(q, table, ldt, indptr, indices, out, ldo, n_rows, feat, mean, beta);
     return q.err;
 }
+int dp_csr_aggregate_w(const float* table, int ldt, const int* indptr, const int* indices, const float* values,
+                       float* out, int ldo, int n_rows, int feat, float beta, void* stream) {
+    NOTNULL(table); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(out);
+    NONNEG(n_rows); NONNEG(feat);
+    Seq q(STREAM(stream), nullptr, 0);
+    csr_aggregate_fwd(q, table, ldt, indptr, indices, out, ldo, n_rows, feat, 0, beta, values);
+    return q.err;
+}
 namespace {
 void sparse_gcn_fwd_seq(Seq& q, const float* x, int ldx, const int* indptr, const int* indices, const float* W,
                         const float* bias, float* y, int ldy, float* ax, float* invn, int n, int Fin, int Fout,
-                        int flags) {
+                        int flags, const float* values = nullptr) {
     float* U = q.alloc<float>((size_t)n * Fout);
     if (q.err) return;
-    csr_aggregate_fwd(q, x, ldx, indptr, indices, ax, Fin, n, Fin, 0, 0.f);
+    csr_aggregate_fwd(q, x, ldx, indptr, indices, ax, Fin, n, Fin, 0, 0.f, values);
     if (flags & DP_F_ADD_SELF) axpy(q, ax, x, 1.f, (long)n * Fin);          // (x is contiguous: checked at the ABI)
     bgemm(q, ax, W, U, nullptr, 1, n, Fout, Fin, Fin, Fout, Fout, 0, 0, 0, false, false, 1.f, 0.f, 0);
     rownorm_fwd(q, U, Fout, nullptr, gcp(bias, 0), one_group(Fout), gp(y, ldy), invn, nullptr, n,
@@ -1218,7 +1268,7 @@ void sparse_gcn_fwd_seq(Seq& q, const float* x, int ldx, const int* indptr, cons
 void sparse_gcn_bwd_seq(Seq& q, const float* ax, const int* indptr, const int* indices, const int* indptr_t,
                         const int* indices_t, const float* W, const float* y, int ldy, const float* invn,
                         const float* dy, int lddy, float* dx, int lddx, float* dW, float* db, int n, int Fin, int Fout,
-                        int flags) {
+                        int flags, const float* values = nullptr, const float* values_t = nullptr) {
     float* dU = q.alloc<float>((size_t)n * Fout);
     float* dax = dx ? q.alloc<float>((size_t)n * Fin) : nullptr;
     if (q.err) return;
@@ -1229,10 +1279,10 @@ void sparse_gcn_bwd_seq(Seq& q, const float* ax, const int* indptr, const int* i
     if (!dx) return;
     bgemm(q, dU, W, dax, nullptr, 1, n, Fin, Fout, Fout, Fout, Fin, 0, 0, 0, false, true, 1.f, 0.f, 0);
     if (indptr_t && indices_t) {
-        csr_aggregate_fwd(q, dax, Fin, indptr_t, indices_t, dx, lddx, n, Fin, 0, 0.f);      // dx = A^T dax, a gather
+        csr_aggregate_fwd(q, dax, Fin, indptr_t, indices_t, dx, lddx, n, Fin, 0, 0.f, values_t);      // dx = A^T dax, a gather
     } else {
         zero_fill(q, dx, (size_t)n * Fin * sizeof(float));
-        csr_aggregate_bwd_scatter(q, dax, Fin, indptr, indices, dx, lddx, n, Fin, 0);
+        csr_aggregate_bwd_scatter(q, dax, Fin, indptr, indices, dx, lddx, n, Fin, 0, values);
     }
     if (flags & DP_F_ADD_SELF) axpy(q, dx, dax, 1.f, (long)n * Fin);
 }
@@ -1265,6 +1315,35 @@ int dp_sparse_gcn_layer_bwd(const float* ax, const int* indptr, const int* indic
     Seq q(STREAM(stream), workspace, workspace_bytes);
     sparse_gcn_bwd_seq(q, ax, indptr, indices, indptr_t, indices_t, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n,
                        Fin, Fout, flags);
+    return q.err;
+}
+
+int dp_sparse_gcn_layer_fwd_w(const float* x, int ldx, const int* indptr, const int* indices, const float* values,
+                              const float* W, const float* bias, float* y, int ldy, float* ax, float* invnorm, int n,
+                              int Fin, int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    NOTNULL(x); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(W); NOTNULL(y); NOTNULL(ax);
+    NOTNULL(invnorm);
+    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
+    DP_CHECK_ARG(!(flags & DP_F_ADD_SELF) || ldx == Fin, "add_self needs a contiguous x (ldx == Fin)");
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    sparse_gcn_fwd_seq(q, x, ldx, indptr, indices, W, bias, y, ldy, ax, invnorm, n, Fin, Fout, flags, values);
+    return q.err;
+}
+int dp_sparse_gcn_layer_bwd_w(const float* ax, const int* indptr, const int* indices, const float* values,
+                              const int* indptr_t, const int* indices_t, const float* values_t, const float* W,
+                              const float* y, int ldy, const float* invnorm, const float* dy, int lddy, float* dx,
+                              int lddx, float* dW, float* db, int n, int Fin, int Fout, int flags, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    NOTNULL(ax); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(W); NOTNULL(y); NOTNULL(invnorm);
+    NOTNULL(dy); NOTNULL(dW);
+    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
+    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr), "indptr_t and indices_t come together");
+    DP_CHECK_ARG(!indices_t || indices_t == indices || values_t,
+                 "dp_sparse_gcn_layer_bwd_w: values_t is NULL but indices_t is a CSR of its own");
+    DP_CHECK_ARG(!dx || lddx == Fin, "dx must be contiguous (lddx == Fin)");
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    sparse_gcn_bwd_seq(q, ax, indptr, indices, indptr_t, indices_t, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n,
+                       Fin, Fout, flags, values, indices_t && indices_t != indices ? values_t : values);
     return q.err;
 }
 

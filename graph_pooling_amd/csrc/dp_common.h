@@ -638,10 +638,12 @@ void clip_adam_step(Seq& q, float* params, float* grads, float* exp_avg, float* 
                     int* step_counter = nullptr, float lr = 0.f);
 
 // (dp_meanagg.hip) CSR neighbour aggregation: out[i] = (mean | sum) of table[indices[indptr[i]:indptr[i+1]]] (+ beta out)
+// values (or null: every stored entry is 1): fp32 [nnz] in the order of indices — out[i] = sum_e values[e] table[indices[e]]
+// (the weighted form has no mean: mean must be 0 with values)
 void csr_aggregate_fwd(Seq& q, const float* table, int ldt, const int* indptr, const int* indices, float* out, int ldo,
-                       int n_rows, int feat, int mean, float beta);
+                       int n_rows, int feat, int mean, float beta, const float* values = nullptr);
 void csr_aggregate_bwd_scatter(Seq& q, const float* dout, int ldo, const int* indptr, const int* indices, float* dtable,
-                               int ldt, int n_rows, int feat, int mean);
+                               int ldt, int n_rows, int feat, int mean, const float* values = nullptr);
 
 // (dp_csr_batch.hip) stage 1 of the segmented max, which dp_ragged_readout.hip launches as well: per chunk of the chunk
 // table {graph, first row, end row, 0} the column maxima pv [n_chunks, F] and their global rows pi, ties to the lowest row
@@ -685,7 +687,8 @@ void frob_link_w_dense(Seq& q, const float* S, int lds, const void* adj, const v
                        const int* num_nodes, float* W, int B, int N, int K);
 void frob_link_fwd(Seq& q, const float* S, int lds, const float* W, const void* adj, int adj_kind, int adj_ld,
                    const int* num_nodes, const int* node_off, const int* nnz_ptr, const float* link_norm, float wscale,
-                   float* G, float* loss_out, float* total_inout, int B, int N, long long rows, int K);
+                   float* G, float* loss_out, float* total_inout, int B, int N, long long rows, int K,
+                   const int* csr_indptr = nullptr /*adj_kind 4: adj holds the CSR values, T0 = sum of their squares*/);
 void frob_link_bwd(Seq& q, const float* S, int lds, const float* W, const float* G, const int* num_nodes,
                    const int* node_off, const float* link_norm, const float* dloss, float wscale, float* dS, int ldds,
                    int accumulate, int B, int N, long long rows, int K);

@@ -6,7 +6,11 @@
 // so no n x n adjacency is ever read or built; memory is O(n K).  loss = sum / n^2 and the backward scale dloss / n^2
 // are formed in double, as k_link_final does (dp_linkpred.hip).
 //
-// CSR contract: 0/1 adjacency, every (i, j) listed at most once.  Self loops are allowed (their term comes from the edge
+// Weighted entries (_w): the loss is linear in a_ij, so the dense term is unchanged and the edge term becomes
+// a_ij [ -log(p_ij + eps) + log(1 - p_ij + eps) ] with values[e .. e+3] loaded next to indices[e .. e+3]; its backward
+// coefficient scales likewise.  Weights of exactly 1.0 give the unweighted bits.
+//
+// CSR contract: 0/1 adjacency (or the stored values of the _w entries), every (i, j) listed at most once.  Self loops are allowed (their term comes from the edge
 // kernels like any other edge); so are isolated nodes and empty rows.
 //
 // Dense forward : the P-tile walk of dp_linkpred.hip without an adjacency, over the upper triangle only (tiles with
@@ -280,9 +284,10 @@ __device__ __forceinline__ float edge_coef(float raw) {
     return lk_min_gate(raw) * (-1.f / (pv + LINK_EPS) - 1.f / (1.f - pv + LINK_EPS));
 }
 
-template <int VEC, int NCH>
-__global__ __launch_bounds__(256) void k_csr_link_edge_fwd(const float* S, int lds_ld, const int* indptr,
-                                                           const int* indices, int n, int K, double* partial) {
+template <int VEC, int NCH, bool WT>
+__device__ __forceinline__ void csr_link_edge_fwd_body(const float* S, int lds_ld, const int* indptr,
+                                                       const int* indices, int n, int K, double* partial,
+                                                       const float* values) {
     __shared__ double red[256];
     const int l15 = threadIdx.x & 15;
     const int row = blockIdx.x * LK_TEAM_ROWS + (threadIdx.x >> 4);
@@ -301,14 +306,19 @@ __global__ __launch_bounds__(256) void k_csr_link_edge_fwd(const float* S, int l
             a1.load(S, lds, j1, l15, K);
             a2.load(S, lds, j2, l15, K);
             a3.load(S, lds, j3, l15, K);
-            const float t0 = edge_term(si.dot(a0)), t1 = edge_term(si.dot(a1));
-            const float t2 = edge_term(si.dot(a2)), t3 = edge_term(si.dot(a3));
+            float t0 = edge_term(si.dot(a0)), t1 = edge_term(si.dot(a1));
+            float t2 = edge_term(si.dot(a2)), t3 = edge_term(si.dot(a3));
+            if constexpr (WT) {
+                t0 *= values[e]; t1 *= values[e + 1]; t2 *= values[e + 2]; t3 *= values[e + 3];
+            }
             tot += (double)((t0 + t1) + (t2 + t3));
         }
         for (; e < end; ++e) {
             TeamRow<VEC, NCH> a0;
             a0.load(S, lds, indices[e], l15, K);
-            tot += (double)edge_term(si.dot(a0));
+            float t0 = edge_term(si.dot(a0));
+            if constexpr (WT) t0 *= values[e];
+            tot += (double)t0;
         }
         if (l15 != 0) tot = 0.0;                  // every lane of the team holds the row's sum: count it once
     }
@@ -316,11 +326,24 @@ __global__ __launch_bounds__(256) void k_csr_link_edge_fwd(const float* S, int l
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
+// the 0/1 kernel and the weighted one: one body, two names
 template <int VEC, int NCH>
-__global__ __launch_bounds__(256) void k_csr_link_edge_bwd(const float* S, int lds_ld, const int* indptr,
-                                                           const int* indices, const int* indptr_t,
-                                                           const int* indices_t, const float* scale_ptr, float* dS,
-                                                           int ldds, int n, int K, int directed) {
+__global__ __launch_bounds__(256) void k_csr_link_edge_fwd(const float* S, int lds_ld, const int* indptr,
+                                                           const int* indices, int n, int K, double* partial) {
+    csr_link_edge_fwd_body<VEC, NCH, false>(S, lds_ld, indptr, indices, n, K, partial, nullptr);
+}
+template <int VEC, int NCH>
+__global__ __launch_bounds__(256) void k_csr_link_edge_fwd_w(const float* S, int lds_ld, const int* indptr,
+                                                             const int* indices, const float* values, int n, int K,
+                                                             double* partial) {
+    csr_link_edge_fwd_body<VEC, NCH, true>(S, lds_ld, indptr, indices, n, K, partial, values);
+}
+
+template <int VEC, int NCH, bool WT>
+__device__ __forceinline__ void csr_link_edge_bwd_body(const float* S, int lds_ld, const int* indptr,
+                                                       const int* indices, const int* indptr_t, const int* indices_t,
+                                                       const float* scale_ptr, float* dS, int ldds, int n, int K,
+                                                       int directed, const float* values, const float* values_t) {
     const int l15 = threadIdx.x & 15;
     const int row = blockIdx.x * LK_TEAM_ROWS + (threadIdx.x >> 4);
     if (row >= n) return;
@@ -333,7 +356,7 @@ __global__ __launch_bounds__(256) void k_csr_link_edge_bwd(const float* S, int l
 #pragma unroll
     for (int m = 0; m < NCH; ++m) acc[m] = RowVec<VEC>::zero();
     // p_ij = p_ji bit for bit (the same products in the same order), so both lists take c(<S_i, S_j>)
-    auto walk = [&](const int* ip, const int* ix) {
+    auto walk = [&](const int* ip, const int* ix, const float* val) {
         const int beg = ip[row], end = ip[row + 1];
         int e = beg;
         for (; e + 4 <= end; e += 4) {
@@ -343,21 +366,25 @@ __global__ __launch_bounds__(256) void k_csr_link_edge_bwd(const float* S, int l
             a1.load(S, lds, j1, l15, K);
             a2.load(S, lds, j2, l15, K);
             a3.load(S, lds, j3, l15, K);
-            const float c0 = edge_coef(si.dot(a0)), c1 = edge_coef(si.dot(a1));
-            const float c2 = edge_coef(si.dot(a2)), c3 = edge_coef(si.dot(a3));
+            float c0 = edge_coef(si.dot(a0)), c1 = edge_coef(si.dot(a1));
+            float c2 = edge_coef(si.dot(a2)), c3 = edge_coef(si.dot(a3));
+            if constexpr (WT) {
+                c0 *= val[e]; c1 *= val[e + 1]; c2 *= val[e + 2]; c3 *= val[e + 3];
+            }
 #pragma unroll
             for (int m = 0; m < NCH; ++m) acc[m] += (c0 * a0.v[m] + c1 * a1.v[m]) + (c2 * a2.v[m] + c3 * a3.v[m]);
         }
         for (; e < end; ++e) {
             TeamRow<VEC, NCH> a0;
             a0.load(S, lds, ix[e], l15, K);
-            const float c0 = edge_coef(si.dot(a0));
+            float c0 = edge_coef(si.dot(a0));
+            if constexpr (WT) c0 *= val[e];
 #pragma unroll
             for (int m = 0; m < NCH; ++m) acc[m] += c0 * a0.v[m];
         }
     };
-    walk(indptr, indices);
-    if (directed) walk(indptr_t, indices_t);
+    walk(indptr, indices, values);
+    if (directed) walk(indptr_t, indices_t, values_t);
     const float f = directed ? scale_ptr[0] : 2.f * scale_ptr[0];
 #pragma unroll
     for (int m = 0; m < NCH; ++m) {
@@ -367,6 +394,24 @@ __global__ __launch_bounds__(256) void k_csr_link_edge_bwd(const float* S, int l
             *q = *q + f * acc[m];
         }
     }
+}
+
+template <int VEC, int NCH>
+__global__ __launch_bounds__(256) void k_csr_link_edge_bwd(const float* S, int lds_ld, const int* indptr,
+                                                           const int* indices, const int* indptr_t,
+                                                           const int* indices_t, const float* scale_ptr, float* dS,
+                                                           int ldds, int n, int K, int directed) {
+    csr_link_edge_bwd_body<VEC, NCH, false>(S, lds_ld, indptr, indices, indptr_t, indices_t, scale_ptr, dS, ldds, n, K,
+                                            directed, nullptr, nullptr);
+}
+template <int VEC, int NCH>
+__global__ __launch_bounds__(256) void k_csr_link_edge_bwd_w(const float* S, int lds_ld, const int* indptr,
+                                                             const int* indices, const float* values,
+                                                             const int* indptr_t, const int* indices_t,
+                                                             const float* values_t, const float* scale_ptr, float* dS,
+                                                             int ldds, int n, int K, int directed) {
+    csr_link_edge_bwd_body<VEC, NCH, true>(S, lds_ld, indptr, indices, indptr_t, indices_t, scale_ptr, dS, ldds, n, K,
+                                           directed, values, values_t);
 }
 
 // ------------------------------------------------------------------ launch sequences
@@ -409,7 +454,7 @@ int fwd_partials(int n) {
 }
 // the dense and the edge partials of one graph -> partial[0 .. fwd_partials(n) - 1]
 void csr_link_fwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, int n, int K,
-                        double* partial) {
+                        double* partial, const float* values) {
     const int T = cdiv(n, 64), Z = fwd_splits(T);
     const int n_dense = ((T + 1) / 2) * Z;
     if (!q.ok()) return;
@@ -420,15 +465,16 @@ void csr_link_fwd_graph(Seq& q, const float* S, int lds, const int* indptr, cons
     q.check_launch("csr_link_dense_fwd");
     if (!q.ok()) return;
     const bool v4 = K % 4 == 0 && lds % 4 == 0 && aligned16(S);
-    LK_EDGE_DISPATCH(k_csr_link_edge_fwd, v4, K, S, lds, indptr, indices, n, K, partial + n_dense);
+    if (values) LK_EDGE_DISPATCH(k_csr_link_edge_fwd_w, v4, K, S, lds, indptr, indices, values, n, K, partial + n_dense);
+    else LK_EDGE_DISPATCH(k_csr_link_edge_fwd, v4, K, S, lds, indptr, indices, n, K, partial + n_dense);
     q.check_launch("csr_link_edge_fwd");
 }
 void csr_link_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
-                      int K) {
+                      int K, const float* values = nullptr) {
     const int count = fwd_partials(n);
     double* partial = q.alloc<double>((size_t)count);
     if (!q.ok()) return;
-    csr_link_fwd_graph(q, S, lds, indptr, indices, n, K, partial);
+    csr_link_fwd_graph(q, S, lds, indptr, indices, n, K, partial, values);
     if (!q.ok()) return;
     hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)partial, count,
                        (double)n * (double)n, loss_out, (float*)nullptr, (const float*)nullptr);
@@ -463,9 +509,10 @@ size_t bwd_part_floats(int n, int K, int* splits_out, int* split_tiles_out) {
 }
 void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                         const int* indices_t, const float* scale, float* part, float* dS, int ldds, int accumulate,
-                        int n, int K, int directed);
+                        int n, int K, int directed, const float* values, const float* values_t);
 void csr_link_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
-                      const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n, int K) {
+                      const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n, int K,
+                      const float* values = nullptr, const float* values_t = nullptr) {
     float* scale = q.alloc<float>(64);
     float* part = nullptr;
     if (const size_t pf = bwd_part_floats(n, K, nullptr, nullptr)) part = q.alloc<float>(pf);
@@ -475,12 +522,12 @@ void csr_link_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const 
     q.check_launch("csr_link_scale");
     const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
     csr_link_bwd_graph(q, S, lds, indptr, indices, indptr_t, indices_t, scale, part, dS, ldds, accumulate, n, K,
-                       directed);
+                       directed, values, values_t);
 }
 // one graph's dS from the ready scale; `part`: bwd_part_floats(n, K) floats (null when that is 0)
 void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                         const int* indices_t, const float* scale, float* part, float* dS, int ldds, int accumulate,
-                        int n, int K, int directed) {
+                        int n, int K, int directed, const float* values, const float* values_t) {
     const int kt = lk_kt(K);
     int splits, split_tiles;
     if (!bwd_part_floats(n, K, &splits, &split_tiles)) part = nullptr;
@@ -502,8 +549,12 @@ void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, cons
         q.check_launch("csr_link_reduce");
     }
     const bool v4 = K % 4 == 0 && lds % 4 == 0 && ldds % 4 == 0 && aligned16(S) && aligned16(dS);
-    LK_EDGE_DISPATCH(k_csr_link_edge_bwd, v4, K, S, lds, indptr, indices, indptr_t, indices_t, (const float*)scale, dS,
-                     ldds, n, K, directed);
+    if (values)
+        LK_EDGE_DISPATCH(k_csr_link_edge_bwd_w, v4, K, S, lds, indptr, indices, values, indptr_t, indices_t, values_t,
+                         (const float*)scale, dS, ldds, n, K, directed);
+    else
+        LK_EDGE_DISPATCH(k_csr_link_edge_bwd, v4, K, S, lds, indptr, indices, indptr_t, indices_t, (const float*)scale, dS,
+                         ldds, n, K, directed);
     q.check_launch("csr_link_edge_bwd");
 }
 
@@ -525,7 +576,7 @@ double batch_norm(const int* off, int B) {
     return nn;
 }
 void csr_link_batch_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* off,
-                            int B, float* loss_out, int K) {
+                            int B, float* loss_out, int K, const float* values = nullptr) {
     size_t count = 0;
     for (int b = 0; b < B; ++b) count += fwd_partials(off[b + 1] - off[b]);
     double* partial = q.alloc<double>(count);
@@ -533,7 +584,7 @@ void csr_link_batch_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, 
     size_t at = 0;
     for (int b = 0; b < B && q.ok(); ++b) {
         const int n = off[b + 1] - off[b];
-        csr_link_fwd_graph(q, S + (long)off[b] * lds, lds, indptr + off[b], indices, n, K, partial + at);
+        csr_link_fwd_graph(q, S + (long)off[b] * lds, lds, indptr + off[b], indices, n, K, partial + at, values);
         at += fwd_partials(n);
     }
     if (!q.ok()) return;
@@ -543,7 +594,7 @@ void csr_link_batch_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, 
 }
 void csr_link_batch_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                             const int* indices_t, const int* off, int B, const float* dloss, float* dS, int ldds,
-                            int accumulate, int K) {
+                            int accumulate, int K, const float* values = nullptr, const float* values_t = nullptr) {
     float* scale = q.alloc<float>(64);
     size_t pf = 0;
     for (int b = 0; b < B; ++b) pf = std::max(pf, bwd_part_floats(off[b + 1] - off[b], K, nullptr, nullptr));
@@ -555,7 +606,8 @@ void csr_link_batch_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, 
     const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
     for (int b = 0; b < B && q.ok(); ++b)
         csr_link_bwd_graph(q, S + (long)off[b] * lds, lds, indptr + off[b], indices, indptr_t + off[b], indices_t, scale,
-                           part, dS + (long)off[b] * ldds, ldds, accumulate, off[b + 1] - off[b], K, directed);
+                           part, dS + (long)off[b] * ldds, ldds, accumulate, off[b + 1] - off[b], K, directed, values,
+                           values_t);
 }
 size_t batch_sized_bytes(const int* off, int B, int K) {
     Seq f = Seq::sizing();
@@ -605,25 +657,72 @@ size_t dp_csr_linkpred_workspace_bytes(int n, int K) {
     return sized_bytes(n, K);
 }
 
+// a _w entry (weighted): values must be there; values_t next to a transposed CSR of its own
+#define CL_VALUES(entry)                                                                    \
+    do {                                                                                    \
+        if (weighted) {                                                                     \
+            CL_CHECK(values != nullptr, DP_ERR_INVALID_ARG, "%s: values is NULL", entry);   \
+            CL_CHECK(((uintptr_t)values & 3) == 0, DP_ERR_INVALID_ARG, "%s: values is not 4-byte aligned", entry); \
+        }                                                                                   \
+    } while (0)
+#define CL_VALUES_T(entry, ixt, ix)                                                         \
+    do {                                                                                    \
+        if (weighted && (ixt) != (ix)) {                                                    \
+            CL_CHECK(values_t != nullptr, DP_ERR_INVALID_ARG,                               \
+                     "%s: values_t is NULL but the transposed CSR is one of its own", entry); \
+            CL_CHECK(((uintptr_t)values_t & 3) == 0, DP_ERR_INVALID_ARG, "%s: values_t is not 4-byte aligned", entry); \
+        }                                                                                   \
+    } while (0)
+
+static int link_fwd_entry(const char* entry, const float* S, int lds, const int* indptr, const int* indices,
+                          const float* values, bool weighted, float* loss_out, int n, int K, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(loss_out);
+    CL_VALUES(entry);
+    if (int rc = check_call(entry, n, K, lds, workspace, workspace_bytes)) return rc;
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_fwd_seq(q, S, lds, indptr, indices, loss_out, n, K, weighted ? values : nullptr);
+    return q.err;
+}
+static int link_bwd_entry(const char* entry, const float* S, int lds, const int* indptr, const int* indices,
+                          const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
+                          bool weighted, const float* dloss, float* dS, int ldds, int accumulate, int n, int K,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(indptr_t); CL_PTR(indices_t); CL_PTR(dS);
+    CL_VALUES(entry);
+    CL_VALUES_T(entry, indices_t, indices);
+    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
+    if (int rc = check_call(entry, n, K, lds, workspace, workspace_bytes)) return rc;
+    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", entry, ldds, K);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_bwd_seq(q, S, lds, indptr, indices, indptr_t, indices_t, dloss, dS, ldds, accumulate, n, K,
+                     weighted ? values : nullptr, weighted ? (indices_t != indices ? values_t : values) : nullptr);
+    return q.err;
+}
+
 int dp_csr_linkpred_loss_fwd(const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
                              int K, void* workspace, size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(loss_out);
-    if (int rc = check_call("dp_csr_linkpred_loss_fwd", n, K, lds, workspace, workspace_bytes)) return rc;
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_fwd_seq(q, S, lds, indptr, indices, loss_out, n, K);
-    return q.err;
+    return link_fwd_entry("dp_csr_linkpred_loss_fwd", S, lds, indptr, indices, nullptr, false, loss_out, n, K, workspace,
+                          workspace_bytes, stream);
+}
+int dp_csr_linkpred_loss_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                               float* loss_out, int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
+    return link_fwd_entry("dp_csr_linkpred_loss_fwd_w", S, lds, indptr, indices, values, true, loss_out, n, K, workspace,
+                          workspace_bytes, stream);
 }
 
 int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                              const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n,
                              int K, void* workspace, size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(indptr_t); CL_PTR(indices_t); CL_PTR(dS);
-    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
-    if (int rc = check_call("dp_csr_linkpred_loss_bwd", n, K, lds, workspace, workspace_bytes)) return rc;
-    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "dp_csr_linkpred_loss_bwd: ldds=%d smaller than K=%d", ldds, K);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_bwd_seq(q, S, lds, indptr, indices, indptr_t, indices_t, dloss, dS, ldds, accumulate, n, K);
-    return q.err;
+    return link_bwd_entry("dp_csr_linkpred_loss_bwd", S, lds, indptr, indices, nullptr, indptr_t, indices_t, nullptr,
+                          false, dloss, dS, ldds, accumulate, n, K, workspace, workspace_bytes, stream);
+}
+int dp_csr_linkpred_loss_bwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                               const int* indptr_t, const int* indices_t, const float* values_t, const float* dloss,
+                               float* dS, int ldds, int accumulate, int n, int K, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return link_bwd_entry("dp_csr_linkpred_loss_bwd_w", S, lds, indptr, indices, values, indptr_t, indices_t, values_t,
+                          true, dloss, dS, ldds, accumulate, n, K, workspace, workspace_bytes, stream);
 }
 
 // ---- the same loss on a ragged batch (node_off_host: int32 [B + 1] on the HOST)
@@ -652,30 +751,64 @@ size_t dp_csr_linkpred_batch_workspace_bytes(const int* node_off_host, int B, in
     return batch_sized_bytes(node_off_host, B, K);
 }
 
+static int link_batch_fwd_entry(const char* entry, const float* S, int lds, const int* indptr,
+                                const int* indices_local, const float* values, bool weighted,
+                                const int* node_off_host, int B, float* loss_out, int K, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(loss_out);
+    CL_VALUES(entry);
+    if (int rc = check_batch(entry, node_off_host, B, K, lds, workspace, workspace_bytes)) return rc;
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_batch_fwd_seq(q, S, lds, indptr, indices_local, node_off_host, B, loss_out, K, weighted ? values : nullptr);
+    return q.err;
+}
+static int link_batch_bwd_entry(const char* entry, const float* S, int lds, const int* indptr,
+                                const int* indices_local, const float* values, const int* indptr_t,
+                                const int* indices_t_local, const float* values_t, bool weighted,
+                                const int* node_off_host, int B, const float* dloss, float* dS, int ldds,
+                                int accumulate, int K, void* workspace, size_t workspace_bytes, void* stream) {
+    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(indptr_t); CL_PTR(indices_t_local); CL_PTR(dS);
+    CL_VALUES(entry);
+    CL_VALUES_T(entry, indices_t_local, indices_local);
+    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
+    if (int rc = check_batch(entry, node_off_host, B, K, lds, workspace, workspace_bytes)) return rc;
+    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", entry, ldds, K);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_batch_bwd_seq(q, S, lds, indptr, indices_local, indptr_t, indices_t_local, node_off_host, B, dloss, dS, ldds,
+                           accumulate, K, weighted ? values : nullptr,
+                           weighted ? (indices_t_local != indices_local ? values_t : values) : nullptr);
+    return q.err;
+}
+
 int dp_csr_linkpred_batch_loss_fwd(const float* S, int lds, const int* indptr, const int* indices_local,
                                    const int* node_off_host, int B, float* loss_out, int K, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(loss_out);
-    if (int rc = check_batch("dp_csr_linkpred_batch_loss_fwd", node_off_host, B, K, lds, workspace, workspace_bytes))
-        return rc;
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_batch_fwd_seq(q, S, lds, indptr, indices_local, node_off_host, B, loss_out, K);
-    return q.err;
+    return link_batch_fwd_entry("dp_csr_linkpred_batch_loss_fwd", S, lds, indptr, indices_local, nullptr, false,
+                                node_off_host, B, loss_out, K, workspace, workspace_bytes, stream);
+}
+int dp_csr_linkpred_batch_loss_fwd_w(const float* S, int lds, const int* indptr, const int* indices_local,
+                                     const float* values, const int* node_off_host, int B, float* loss_out, int K,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    return link_batch_fwd_entry("dp_csr_linkpred_batch_loss_fwd_w", S, lds, indptr, indices_local, values, true,
+                                node_off_host, B, loss_out, K, workspace, workspace_bytes, stream);
 }
 
 int dp_csr_linkpred_batch_loss_bwd(const float* S, int lds, const int* indptr, const int* indices_local,
                                    const int* indptr_t, const int* indices_t_local, const int* node_off_host, int B,
                                    const float* dloss, float* dS, int ldds, int accumulate, int K, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(indptr_t); CL_PTR(indices_t_local); CL_PTR(dS);
-    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
-    if (int rc = check_batch("dp_csr_linkpred_batch_loss_bwd", node_off_host, B, K, lds, workspace, workspace_bytes))
-        return rc;
-    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "dp_csr_linkpred_batch_loss_bwd: ldds=%d smaller than K=%d", ldds, K);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_batch_bwd_seq(q, S, lds, indptr, indices_local, indptr_t, indices_t_local, node_off_host, B, dloss, dS, ldds,
-                           accumulate, K);
-    return q.err;
+    return link_batch_bwd_entry("dp_csr_linkpred_batch_loss_bwd", S, lds, indptr, indices_local, nullptr, indptr_t,
+                                indices_t_local, nullptr, false, node_off_host, B, dloss, dS, ldds, accumulate, K,
+                                workspace, workspace_bytes, stream);
+}
+int dp_csr_linkpred_batch_loss_bwd_w(const float* S, int lds, const int* indptr, const int* indices_local,
+                                     const float* values, const int* indptr_t, const int* indices_t_local,
+                                     const float* values_t, const int* node_off_host, int B, const float* dloss,
+                                     float* dS, int ldds, int accumulate, int K, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return link_batch_bwd_entry("dp_csr_linkpred_batch_loss_bwd_w", S, lds, indptr, indices_local, values, indptr_t,
+                                indices_t_local, values_t, true, node_off_host, B, dloss, dS, ldds, accumulate, K,
+                                workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

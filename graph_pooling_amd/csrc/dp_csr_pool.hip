@@ -50,21 +50,33 @@ __device__ __forceinline__ typename Vec<VEC>::T vload(const float* p) {
     return *reinterpret_cast<const typename Vec<VEC>::T*>(p);
 }
 
-// (A S)_row, columns c .. c+VEC-1: four neighbour rows in flight per lane before the first add
-template <int VEC>
+// (A S)_row, columns c .. c+VEC-1: four neighbour rows in flight per lane before the first add.  WT: values[e .. e+3]
+// are loaded next to indices[e .. e+3] and each row is multiplied before it is added, in the same order (weights of
+// exactly 1.0 give the unweighted bits).
+template <int VEC, bool WT>
 __device__ __forceinline__ typename Vec<VEC>::T gather_row(const float* S, long lds, const int* indptr,
-                                                           const int* indices, int row, int c) {
+                                                           const int* indices, const float* values, int row, int c) {
     typedef typename Vec<VEC>::T T;
     const int beg = indptr[row], end = indptr[row + 1];
     T s0 = Vec<VEC>::zero(), s1 = s0, s2 = s0, s3 = s0;
     int e = beg;
     for (; e + 4 <= end; e += 4) {
         const long j0 = indices[e], j1 = indices[e + 1], j2 = indices[e + 2], j3 = indices[e + 3];
-        const T v0 = vload<VEC>(S + j0 * lds + c), v1 = vload<VEC>(S + j1 * lds + c);
-        const T v2 = vload<VEC>(S + j2 * lds + c), v3 = vload<VEC>(S + j3 * lds + c);
-        s0 += v0; s1 += v1; s2 += v2; s3 += v3;
+        if constexpr (WT) {
+            const float w0 = values[e], w1 = values[e + 1], w2 = values[e + 2], w3 = values[e + 3];
+            const T v0 = vload<VEC>(S + j0 * lds + c), v1 = vload<VEC>(S + j1 * lds + c);
+            const T v2 = vload<VEC>(S + j2 * lds + c), v3 = vload<VEC>(S + j3 * lds + c);
+            s0 += w0 * v0; s1 += w1 * v1; s2 += w2 * v2; s3 += w3 * v3;
+        } else {
+            const T v0 = vload<VEC>(S + j0 * lds + c), v1 = vload<VEC>(S + j1 * lds + c);
+            const T v2 = vload<VEC>(S + j2 * lds + c), v3 = vload<VEC>(S + j3 * lds + c);
+            s0 += v0; s1 += v1; s2 += v2; s3 += v3;
+        }
     }
-    for (; e < end; ++e) s0 += vload<VEC>(S + (long)indices[e] * lds + c);
+    for (; e < end; ++e) {
+        if constexpr (WT) s0 += values[e] * vload<VEC>(S + (long)indices[e] * lds + c);
+        else s0 += vload<VEC>(S + (long)indices[e] * lds + c);
+    }
     return (s0 + s1) + (s2 + s3);
 }
 
@@ -76,12 +88,13 @@ struct PoolFwdArgs {
     float* part;            // [nslab][K][K+D]
     int lds, ldz, n, K, D, rows_per_slab;
     const int* tab;         // batch: slab table {first row, end row, graph, 0} per slab (rows global); null: one graph
+    const float* values;    // weighted kernels: fp32 [nnz] in the order of indices (behind the unweighted fields)
 };
 
 // MI / NI: 16x16 MFMA tiles per wave along the K result rows / the 64 output columns; WM waves along the rows
 // (4 / WM along the columns).  TM = WM * MI * 16 >= K covers every result row, so A S is gathered once per column.
-template <int MI, int NI, int WM, int VEC>
-__global__ __launch_bounds__(256) void k_csr_pool_fwd(PoolFwdArgs a) {
+template <int MI, int NI, int WM, int VEC, bool WT>
+__device__ __forceinline__ void csr_pool_fwd_body(const PoolFwdArgs& a) {
     constexpr int WN = 4 / WM;
     constexpr int TM = WM * MI * 16;
     static_assert(WN * NI * 16 == FWD_TN, "the column tile is 64 wide");
@@ -129,7 +142,7 @@ __global__ __launch_bounds__(256) void k_csr_pool_fwd(PoolFwdArgs a) {
             const int row = r0 + r;
             typename Vec<VEC>::T v = Vec<VEC>::zero();
             if (row < rend) {
-                if (gcol < a.K) v = gather_row<VEC>(a.S, lds, a.indptr, a.indices, row, gcol);
+                if (gcol < a.K) v = gather_row<VEC, WT>(a.S, lds, a.indptr, a.indices, a.values, row, gcol);
                 else if (gcol < KD) v = vload<VEC>(a.Z + (long)row * ldz + (gcol - a.K));
             }
             Vec<VEC>::put(&Bimg[r * BP + (lane % LPR) * VEC], v);
@@ -162,6 +175,16 @@ __global__ __launch_bounds__(256) void k_csr_pool_fwd(PoolFwdArgs a) {
                 if (m < a.K && col < KD) P[(long)m * KD + col] = acc[i][j][r];
             }
         }
+}
+
+// the 0/1 kernel and the weighted one (values[e] multiplies neighbour row e): one body, two names
+template <int MI, int NI, int WM, int VEC>
+__global__ __launch_bounds__(256) void k_csr_pool_fwd(PoolFwdArgs a) {
+    csr_pool_fwd_body<MI, NI, WM, VEC, false>(a);
+}
+template <int MI, int NI, int WM, int VEC>
+__global__ __launch_bounds__(256) void k_csr_pool_fwd_w(PoolFwdArgs a) {
+    csr_pool_fwd_body<MI, NI, WM, VEC, true>(a);
 }
 
 // [Ap | Xp] = sum over slabs of the partials, in slab order.  A workgroup sums 64 entries: wave w takes the slabs
@@ -239,12 +262,14 @@ struct PoolBwdArgs {
     float* dZ;
     int lds, ldz, ldds, lddz, n, K, D, KX, KXp, Kp, Dp, directed;
     const int* tab;         // batch: row-block table {first row, end row, graph, 0} (rows global); null: one graph
+    const float* values;    // weighted kernels: fp32 [nnz] in the order of indices / of indices_t (behind the
+    const float* values_t;  //   unweighted fields)
 };
 
 // NI: 16-column MFMA tiles per wave (NI * 16 >= K; also the dZ column block).  Wave w owns rows 16w .. 16w + 15 of the
 // workgroup's 64 and every output column of the block.
-template <int NI, int VEC>
-__global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
+template <int NI, int VEC, bool WT>
+__device__ __forceinline__ void csr_pool_bwd_body(const PoolBwdArgs& a) {
     constexpr int TN = NI * 16;
     constexpr int XP = BWD_KC + 4;     // A image [64 rows][XP]: 16-byte rows for the gather's vector stores
     constexpr int WP = TN + 16;        // B image [32 k][WP]: = 16 mod 32
@@ -300,8 +325,8 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
             const int row = row0 + r;
             typename Vec<VEC>::T v = Vec<VEC>::zero();
             if (row < rend) {
-                if (c < a.K) v = gather_row<VEC>(a.S, lds, a.indptr, a.indices, row, c);
-                else if (c < koff) v = gather_row<VEC>(a.S, lds, a.indptr_t, a.indices_t, row, c - a.K);
+                if (c < a.K) v = gather_row<VEC, WT>(a.S, lds, a.indptr, a.indices, a.values, row, c);
+                else if (c < koff) v = gather_row<VEC, WT>(a.S, lds, a.indptr_t, a.indices_t, a.values_t, row, c - a.K);
                 else if (c < a.KX) v = vload<VEC>(a.Z + (long)row * ldz + (c - koff));
             }
             Vec<VEC>::put(&Ximg[r * XP + ac], v);
@@ -352,6 +377,15 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
     }
 }
 
+template <int NI, int VEC>
+__global__ __launch_bounds__(256) void k_csr_pool_bwd(PoolBwdArgs a) {
+    csr_pool_bwd_body<NI, VEC, false>(a);
+}
+template <int NI, int VEC>
+__global__ __launch_bounds__(256) void k_csr_pool_bwd_w(PoolBwdArgs a) {
+    csr_pool_bwd_body<NI, VEC, true>(a);
+}
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // slab partition of the forward: >= FWD_TARGET_WGS workgroups when the rows allow, slabs a multiple of the stage
@@ -370,24 +404,30 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // tab / slab_off / nslab_batch / B: the slab table of a batch (dp_csr_pool_batch_plan); null / 0: one graph of n rows
 void csr_pool_fwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                       float* Xp, float* Ap, int n, int K, int D, const int* tab = nullptr,
-                      const int* slab_off = nullptr, int nslab_batch = 0, int B = 1) {
+                      const int* slab_off = nullptr, int nslab_batch = 0, int B = 1, const float* values = nullptr) {
     int nslab, rows;
     fwd_slabs(n, K, D, &nslab, &rows);
     if (nslab_batch) nslab = nslab_batch;
     float* part = q.alloc<float>((size_t)nslab * K * (K + D));
     if (!q.ok()) return;
     const bool v4 = K % 4 == 0 && D % 4 == 0 && lds % 4 == 0 && ldz % 4 == 0 && aligned16(S) && aligned16(Z);
-    PoolFwdArgs a{S, Z, indptr, indices, part, lds, ldz, n, K, D, rows, tab};
+    PoolFwdArgs a{S, Z, indptr, indices, part, lds, ldz, n, K, D, rows, tab, values};
     const dim3 grid(cdiv(K + D, FWD_TN), nslab);
-#define DP_POOL_FWD(MI, NI, WM)                                                                        \
-    do {                                                                                               \
-        if (v4) hipLaunchKernelGGL((k_csr_pool_fwd<MI, NI, WM, 4>), grid, dim3(256), 0, q.stream, a); \
-        else hipLaunchKernelGGL((k_csr_pool_fwd<MI, NI, WM, 1>), grid, dim3(256), 0, q.stream, a);    \
+#define DP_POOL_FWD_(KERNEL, MI, NI, WM)                                                       \
+    do {                                                                                       \
+        if (v4) hipLaunchKernelGGL((KERNEL<MI, NI, WM, 4>), grid, dim3(256), 0, q.stream, a); \
+        else hipLaunchKernelGGL((KERNEL<MI, NI, WM, 1>), grid, dim3(256), 0, q.stream, a);    \
+    } while (0)
+#define DP_POOL_FWD(MI, NI, WM)                                  \
+    do {                                                         \
+        if (values) DP_POOL_FWD_(k_csr_pool_fwd_w, MI, NI, WM);  \
+        else DP_POOL_FWD_(k_csr_pool_fwd, MI, NI, WM);           \
     } while (0)
     if (K <= 64) DP_POOL_FWD(2, 2, 2);
     else if (K <= 128) DP_POOL_FWD(4, 2, 2);
     else DP_POOL_FWD(4, 4, 4);
 #undef DP_POOL_FWD
+#undef DP_POOL_FWD_
     q.check_launch("csr_pool_fwd");
     hipLaunchKernelGGL(k_csr_pool_reduce, dim3(cdiv((long)K * (K + D), 64), B), dim3(256), 0, q.stream, part, nslab, K,
                        D, Xp, Ap, slab_off);
@@ -397,7 +437,7 @@ void csr_pool_fwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, 
 void csr_pool_bwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                       const int* indptr_t, const int* indices_t, const float* dXp, const float* dAp, float* dS,
                       int ldds, float* dZ, int lddz, int n, int K, int D, const int* tab = nullptr, int nblk_batch = 0,
-                      int B = 1) {
+                      int B = 1, const float* values = nullptr, const float* values_t = nullptr) {
     const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
     const int NI = bwd_ni(K), TN = NI * 16;
     const int KX = (directed ? 2 * K : K) + D;
@@ -411,17 +451,23 @@ void csr_pool_bwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, 
     q.check_launch("csr_pool_bwd_prep");
     const bool v4 = K % 4 == 0 && D % 4 == 0 && lds % 4 == 0 && ldz % 4 == 0 && aligned16(S) && aligned16(Z);
     PoolBwdArgs a{S, Z, indptr, indices, indptr_t, indices_t, W, dXpP, dS, dZ, lds, ldz, ldds, lddz, n, K, D, KX, KXp,
-                  Kp, Dp, directed, tab};
+                  Kp, Dp, directed, tab, values, values_t};
     const dim3 grid(nblk_batch ? nblk_batch : cdiv(n, BWD_ROWS));
-#define DP_POOL_BWD(NI_)                                                                           \
-    do {                                                                                           \
-        if (v4) hipLaunchKernelGGL((k_csr_pool_bwd<NI_, 4>), grid, dim3(256), 0, q.stream, a);    \
-        else hipLaunchKernelGGL((k_csr_pool_bwd<NI_, 1>), grid, dim3(256), 0, q.stream, a);       \
+#define DP_POOL_BWD_(KERNEL, NI_)                                                      \
+    do {                                                                               \
+        if (v4) hipLaunchKernelGGL((KERNEL<NI_, 4>), grid, dim3(256), 0, q.stream, a); \
+        else hipLaunchKernelGGL((KERNEL<NI_, 1>), grid, dim3(256), 0, q.stream, a);    \
+    } while (0)
+#define DP_POOL_BWD(NI_)                                   \
+    do {                                                   \
+        if (values) DP_POOL_BWD_(k_csr_pool_bwd_w, NI_);   \
+        else DP_POOL_BWD_(k_csr_pool_bwd, NI_);            \
     } while (0)
     if (NI == 4) DP_POOL_BWD(4);
     else if (NI == 8) DP_POOL_BWD(8);
     else DP_POOL_BWD(16);
 #undef DP_POOL_BWD
+#undef DP_POOL_BWD_
     q.check_launch("csr_pool_bwd");
 }
 
@@ -505,31 +551,84 @@ size_t dp_csr_pool_workspace_bytes(int n, int K, int D) {
     return sized_bytes(n, K, D);
 }
 
+// values == NULL with weighted set (a _w entry) is an argument error; values_t matters only next to a transposed CSR of
+// its own (indices_t != indices)
+#define CP_VALUES(entry)                                                                                      \
+    do {                                                                                                      \
+        if (weighted) {                                                                                       \
+            CP_CHECK(values != nullptr, DP_ERR_INVALID_ARG, "%s: values is NULL", entry);                     \
+            CP_ALIGNED(values);                                                                               \
+        }                                                                                                     \
+    } while (0)
+#define CP_VALUES_T(entry)                                                                                    \
+    do {                                                                                                      \
+        if (weighted && indices_t != indices) {                                                               \
+            CP_CHECK(values_t != nullptr, DP_ERR_INVALID_ARG,                                                 \
+                     "%s: values_t is NULL but indices_t is a CSR of its own", entry);                        \
+            CP_ALIGNED(values_t);                                                                             \
+        }                                                                                                     \
+    } while (0)
+
+static int pool_fwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
+                          const int* indices, const float* values, bool weighted, float* Xp, float* Ap, int n, int K,
+                          int D, void* workspace, size_t workspace_bytes, void* stream) {
+    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(Xp); CP_NOTNULL(Ap);
+    CP_VALUES(entry);
+    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(Xp); CP_ALIGNED(Ap);
+    if (int rc = check_shape(entry, n, K, D, lds, ldz)) return rc;
+    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n, K, D, nullptr, nullptr, 0, 1,
+                     weighted ? values : nullptr);
+    return q.err;
+}
+
+static int pool_bwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
+                          const int* indices, const float* values, const int* indptr_t, const int* indices_t,
+                          const float* values_t, bool weighted, const float* dXp, const float* dAp, float* dS, int ldds,
+                          float* dZ, int lddz, int n, int K, int D, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(indptr_t); CP_NOTNULL(indices_t);
+    CP_NOTNULL(dXp); CP_NOTNULL(dAp); CP_NOTNULL(dS); CP_NOTNULL(dZ);
+    CP_VALUES(entry);
+    CP_VALUES_T(entry);
+    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(indptr_t); CP_ALIGNED(indices_t);
+    CP_ALIGNED(dXp); CP_ALIGNED(dAp); CP_ALIGNED(dS); CP_ALIGNED(dZ);
+    if (int rc = check_shape(entry, n, K, D, lds, ldz)) return rc;
+    CP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG, "%s: ldds=%d / lddz=%d smaller than K=%d / D=%d", entry, ldds,
+             lddz, K, D);
+    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n, K, D,
+                     nullptr, 0, 1, weighted ? values : nullptr,
+                     weighted ? (indices_t != indices ? values_t : values) : nullptr);
+    return q.err;
+}
+
 int dp_csr_pool_fwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices, float* Xp,
                     float* Ap, int n, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(Xp); CP_NOTNULL(Ap);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(Xp); CP_ALIGNED(Ap);
-    if (int rc = check_shape("dp_csr_pool_fwd", n, K, D, lds, ldz)) return rc;
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_fwd: workspace is not 16-byte aligned");
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n, K, D);
-    return q.err;
+    return pool_fwd_entry("dp_csr_pool_fwd", S, lds, Z, ldz, indptr, indices, nullptr, false, Xp, Ap, n, K, D,
+                          workspace, workspace_bytes, stream);
+}
+int dp_csr_pool_fwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                      const float* values, float* Xp, float* Ap, int n, int K, int D, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return pool_fwd_entry("dp_csr_pool_fwd_w", S, lds, Z, ldz, indptr, indices, values, true, Xp, Ap, n, K, D,
+                          workspace, workspace_bytes, stream);
 }
 
 int dp_csr_pool_bwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                     const int* indptr_t, const int* indices_t, const float* dXp, const float* dAp, float* dS, int ldds,
                     float* dZ, int lddz, int n, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(indptr_t); CP_NOTNULL(indices_t);
-    CP_NOTNULL(dXp); CP_NOTNULL(dAp); CP_NOTNULL(dS); CP_NOTNULL(dZ);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(indptr_t); CP_ALIGNED(indices_t);
-    CP_ALIGNED(dXp); CP_ALIGNED(dAp); CP_ALIGNED(dS); CP_ALIGNED(dZ);
-    if (int rc = check_shape("dp_csr_pool_bwd", n, K, D, lds, ldz)) return rc;
-    CP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG, "dp_csr_pool_bwd: ldds=%d / lddz=%d smaller than K=%d / D=%d",
-             ldds, lddz, K, D);
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_bwd: workspace is not 16-byte aligned");
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n, K, D);
-    return q.err;
+    return pool_bwd_entry("dp_csr_pool_bwd", S, lds, Z, ldz, indptr, indices, nullptr, indptr_t, indices_t, nullptr,
+                          false, dXp, dAp, dS, ldds, dZ, lddz, n, K, D, workspace, workspace_bytes, stream);
+}
+int dp_csr_pool_bwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                      const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
+                      const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int n, int K, int D,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    return pool_bwd_entry("dp_csr_pool_bwd_w", S, lds, Z, ldz, indptr, indices, values, indptr_t, indices_t, values_t,
+                          true, dXp, dAp, dS, ldds, dZ, lddz, n, K, D, workspace, workspace_bytes, stream);
 }
 
 // ---- the same on a ragged batch of B graphs (rows concatenated, block-diagonal CSR with GLOBAL column indices)
@@ -552,40 +651,79 @@ size_t dp_csr_pool_batch_workspace_bytes(int n_slabs, int B, int K, int D) {
     return batch_sized_bytes(n_slabs, B, K, D);
 }
 
+static int pool_batch_fwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
+                                const int* indices, const float* values, bool weighted, const int* fwd_tab,
+                                const int* slab_off, int n_slabs, float* Xp, float* Ap, int B, int n_total, int K, int D,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(fwd_tab); CP_NOTNULL(slab_off);
+    CP_NOTNULL(Xp); CP_NOTNULL(Ap);
+    CP_VALUES(entry);
+    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(fwd_tab); CP_ALIGNED(slab_off);
+    CP_ALIGNED(Xp); CP_ALIGNED(Ap);
+    if (int rc = check_shape(entry, n_total, K, D, lds, ldz)) return rc;
+    CP_CHECK(B >= 1 && B <= 65535 && n_slabs >= B && n_slabs <= 65535, DP_ERR_INVALID_ARG,
+             "%s: B=%d / n_slabs=%d outside 1..65535 (every graph has a slab)", entry, B, n_slabs);
+    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n_total, K, D, fwd_tab, slab_off, n_slabs, B,
+                     weighted ? values : nullptr);
+    return q.err;
+}
+
+static int pool_batch_bwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
+                                const int* indices, const float* values, const int* indptr_t, const int* indices_t,
+                                const float* values_t, bool weighted, const int* bwd_tab, int n_blocks,
+                                const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int B,
+                                int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
+    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(indptr_t); CP_NOTNULL(indices_t);
+    CP_NOTNULL(bwd_tab); CP_NOTNULL(dXp); CP_NOTNULL(dAp); CP_NOTNULL(dS); CP_NOTNULL(dZ);
+    CP_VALUES(entry);
+    CP_VALUES_T(entry);
+    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(indptr_t); CP_ALIGNED(indices_t);
+    CP_ALIGNED(bwd_tab); CP_ALIGNED(dXp); CP_ALIGNED(dAp); CP_ALIGNED(dS); CP_ALIGNED(dZ);
+    if (int rc = check_shape(entry, n_total, K, D, lds, ldz)) return rc;
+    CP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG, "%s: ldds=%d / lddz=%d smaller than K=%d / D=%d", entry, ldds,
+             lddz, K, D);
+    CP_CHECK(B >= 1 && B <= 65535 && n_blocks >= B, DP_ERR_INVALID_ARG,
+             "%s: B=%d / n_blocks=%d (every graph has a row block)", entry, B, n_blocks);
+    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n_total, K,
+                     D, bwd_tab, n_blocks, B, weighted ? values : nullptr,
+                     weighted ? (indices_t != indices ? values_t : values) : nullptr);
+    return q.err;
+}
+
 int dp_csr_pool_batch_fwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                           const int* fwd_tab, const int* slab_off, int n_slabs, float* Xp, float* Ap, int B,
                           int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(fwd_tab); CP_NOTNULL(slab_off);
-    CP_NOTNULL(Xp); CP_NOTNULL(Ap);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(fwd_tab); CP_ALIGNED(slab_off);
-    CP_ALIGNED(Xp); CP_ALIGNED(Ap);
-    if (int rc = check_shape("dp_csr_pool_batch_fwd", n_total, K, D, lds, ldz)) return rc;
-    CP_CHECK(B >= 1 && B <= 65535 && n_slabs >= B && n_slabs <= 65535, DP_ERR_INVALID_ARG,
-             "dp_csr_pool_batch_fwd: B=%d / n_slabs=%d outside 1..65535 (every graph has a slab)", B, n_slabs);
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_fwd: workspace is not 16-byte aligned");
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n_total, K, D, fwd_tab, slab_off, n_slabs, B);
-    return q.err;
+    return pool_batch_fwd_entry("dp_csr_pool_batch_fwd", S, lds, Z, ldz, indptr, indices, nullptr, false, fwd_tab,
+                                slab_off, n_slabs, Xp, Ap, B, n_total, K, D, workspace, workspace_bytes, stream);
+}
+int dp_csr_pool_batch_fwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                            const float* values, const int* fwd_tab, const int* slab_off, int n_slabs, float* Xp,
+                            float* Ap, int B, int n_total, int K, int D, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    return pool_batch_fwd_entry("dp_csr_pool_batch_fwd_w", S, lds, Z, ldz, indptr, indices, values, true, fwd_tab,
+                                slab_off, n_slabs, Xp, Ap, B, n_total, K, D, workspace, workspace_bytes, stream);
 }
 
 int dp_csr_pool_batch_bwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                           const int* indptr_t, const int* indices_t, const int* bwd_tab, int n_blocks,
                           const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int B,
                           int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(indptr_t); CP_NOTNULL(indices_t);
-    CP_NOTNULL(bwd_tab); CP_NOTNULL(dXp); CP_NOTNULL(dAp); CP_NOTNULL(dS); CP_NOTNULL(dZ);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(indptr_t); CP_ALIGNED(indices_t);
-    CP_ALIGNED(bwd_tab); CP_ALIGNED(dXp); CP_ALIGNED(dAp); CP_ALIGNED(dS); CP_ALIGNED(dZ);
-    if (int rc = check_shape("dp_csr_pool_batch_bwd", n_total, K, D, lds, ldz)) return rc;
-    CP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG,
-             "dp_csr_pool_batch_bwd: ldds=%d / lddz=%d smaller than K=%d / D=%d", ldds, lddz, K, D);
-    CP_CHECK(B >= 1 && B <= 65535 && n_blocks >= B, DP_ERR_INVALID_ARG,
-             "dp_csr_pool_batch_bwd: B=%d / n_blocks=%d (every graph has a row block)", B, n_blocks);
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_bwd: workspace is not 16-byte aligned");
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n_total, K,
-                     D, bwd_tab, n_blocks, B);
-    return q.err;
+    return pool_batch_bwd_entry("dp_csr_pool_batch_bwd", S, lds, Z, ldz, indptr, indices, nullptr, indptr_t, indices_t,
+                                nullptr, false, bwd_tab, n_blocks, dXp, dAp, dS, ldds, dZ, lddz, B, n_total, K, D,
+                                workspace, workspace_bytes, stream);
+}
+int dp_csr_pool_batch_bwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                            const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
+                            const int* bwd_tab, int n_blocks, const float* dXp, const float* dAp, float* dS, int ldds,
+                            float* dZ, int lddz, int B, int n_total, int K, int D, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    return pool_batch_bwd_entry("dp_csr_pool_batch_bwd_w", S, lds, Z, ldz, indptr, indices, values, indptr_t,
+                                indices_t, values_t, true, bwd_tab, n_blocks, dXp, dAp, dS, ldds, dZ, lddz, B, n_total,
+                                K, D, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

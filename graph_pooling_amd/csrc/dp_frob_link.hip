@@ -1,7 +1,7 @@
 // Frobenius link loss of the soft assignment S (the DiffPool paper's L_LP, squared):
 //
 //     F      = sum_b sum_{i,j < n_b} (a_bij - s_bi . s_bj)^2  =  T0 - 2 T1 + T2
-//     T0     = sum a^2                      (0/1 CSR: the number of stored entries)
+//     T0     = sum a^2                      (0/1 CSR: the number of stored entries; weighted CSR: sum of values^2)
 //     2 T1   = sum_i s_i . w_i,   W = (A + A^T) S
 //     T2     = sum_b ||G_b||_F^2,  G_b = S_b^T S_b  [K, K]
 //     link   = F / sum_b n_b^2
@@ -245,17 +245,19 @@ __global__ __launch_bounds__(FL_THREADS) void k_fl_w_dense(const float* __restri
 
 // ----------------------------------------------------------------------------------------------- row term (+ dense T0)
 // part[2 blk] = sum over the workgroup's valid rows of s_i . w_i, part[2 blk + 1] = of sum_{j < n_b} a_ij^2
-// ADJ 0: no adjacency (CSR: T0 is the entry count); 1: fp32, 4-byte loads; 2: fp32, 16-byte loads; 3: bf16, 16-byte loads
+// ADJ 0: no adjacency (CSR: T0 is the entry count); 1: fp32, 4-byte loads; 2: fp32, 16-byte loads; 3: bf16, 16-byte loads;
+// 4: weighted CSR — adj holds the stored values, row r's are indptr[r] .. indptr[r + 1] - 1, squared and summed in fp64
 template <int ADJ>
-__global__ __launch_bounds__(FL_THREADS) void k_fl_rows(const float* __restrict__ S, int lds, const float* __restrict__ W,
-                                                        const void* __restrict__ adj, int ld, FlLayout L,
-                                                        double* __restrict__ part, long long rows, int K) {
+__device__ __forceinline__ void fl_rows_body(const float* __restrict__ S, int lds, const float* __restrict__ W,
+                                             const void* __restrict__ adj, int ld, const FlLayout& L,
+                                             double* __restrict__ part, long long rows, int K,
+                                             const int* __restrict__ indptr) {
     __shared__ double sh[FL_THREADS];
     const int grp = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double t1 = 0.0, t0 = 0.0;
     for (long long r = (long long)blockIdx.x * 4 + grp; r < rows; r += (long long)gridDim.x * 4) {
         int nb = 0;
-        if (L.node_off == nullptr && (L.num_nodes != nullptr || ADJ != 0)) {
+        if (L.node_off == nullptr && (L.num_nodes != nullptr || (ADJ != 0 && ADJ != 4))) {
             const int b = (int)(r / L.N);
             nb = fl_nb(L, b);
             if ((int)(r - (long long)b * L.N) >= nb) continue;
@@ -289,6 +291,13 @@ __global__ __launch_bounds__(FL_THREADS) void k_fl_rows(const float* __restrict_
                     if (j + e < nb) t0 += (double)(a * a);
                 }
             }
+        } else if constexpr (ADJ == 4) {
+            const float* val = static_cast<const float*>(adj);
+            const int e1 = indptr[r + 1];
+            for (int e = indptr[r] + lane; e < e1; e += 64) {
+                const double a = (double)val[e];
+                t0 += a * a;
+            }
         }
     }
     const double s1 = fl_block_sum(t1, sh);
@@ -297,6 +306,20 @@ __global__ __launch_bounds__(FL_THREADS) void k_fl_rows(const float* __restrict_
         part[2 * blockIdx.x] = s1;
         part[2 * blockIdx.x + 1] = s0;
     }
+}
+
+template <int ADJ>
+__global__ __launch_bounds__(FL_THREADS) void k_fl_rows(const float* __restrict__ S, int lds, const float* __restrict__ W,
+                                                        const void* __restrict__ adj, int ld, FlLayout L,
+                                                        double* __restrict__ part, long long rows, int K) {
+    fl_rows_body<ADJ>(S, lds, W, adj, ld, L, part, rows, K, nullptr);
+}
+// the weighted CSR form (ADJ 4): values and the CSR's indptr
+__global__ __launch_bounds__(FL_THREADS) void k_fl_rows_w(const float* __restrict__ S, int lds,
+                                                          const float* __restrict__ W, const float* __restrict__ values,
+                                                          const int* __restrict__ indptr, FlLayout L,
+                                                          double* __restrict__ part, long long rows, int K) {
+    fl_rows_body<4>(S, lds, W, values, 0, L, part, rows, K, indptr);
 }
 
 // ----------------------------------------------------------------------------------------------- finish
@@ -385,10 +408,11 @@ size_t frob_link_ws_doubles(long long rows, int B, int K) {
 }
 
 // W is already in place ([rows, K], every valid row written).  adj_kind: 0 none (nnz_ptr gives T0), 1 fp32 [B, N, N],
-// 3 bf16 rows (ld = adj_pack_ld(N)).
+// 3 bf16 rows (ld = adj_pack_ld(N)), 4 the stored values of a weighted CSR (adj) with its indptr (csr_indptr; nnz_ptr null).
 void frob_link_fwd(Seq& q, const float* S, int lds, const float* W, const void* adj, int adj_kind, int adj_ld,
                    const int* num_nodes, const int* node_off, const int* nnz_ptr, const float* link_norm, float wscale,
-                   float* G, float* loss_out, float* total_inout, int B, int N, long long rows, int K) {
+                   float* G, float* loss_out, float* total_inout, int B, int N, long long rows, int K,
+                   const int* csr_indptr) {
     const size_t slabs = (size_t)((rows + FL_SLAB - 1) / FL_SLAB);
     const int tiles = (K + FL_TILE - 1) / FL_TILE;
     const int g2blocks = (K * K + FL_THREADS - 1) / FL_THREADS;
@@ -407,7 +431,9 @@ void frob_link_fwd(Seq& q, const float* S, int lds, const float* W, const void* 
     if (kind == 1 && ((uintptr_t)adj & 15) == 0 && (adj_ld & 3) == 0) kind = 2;
 #define FL_ROWS(A) \
     hipLaunchKernelGGL((k_fl_rows<A>), dim3(grid), dim3(FL_THREADS), 0, q.stream, S, lds, W, adj, adj_ld, L, rpart, rows, K)
-    if (kind == 0) FL_ROWS(0); else if (kind == 1) FL_ROWS(1); else if (kind == 2) FL_ROWS(2); else FL_ROWS(3);
+    if (kind == 0) FL_ROWS(0); else if (kind == 1) FL_ROWS(1); else if (kind == 2) FL_ROWS(2); else if (kind == 3) FL_ROWS(3);
+    else hipLaunchKernelGGL(k_fl_rows_w, dim3(grid), dim3(FL_THREADS), 0, q.stream, S, lds, W, static_cast<const float*>(adj),
+                            csr_indptr, L, rpart, rows, K);
 #undef FL_ROWS
     q.check_launch("k_fl_rows");
     if (!q.ok()) return;

@@ -127,6 +127,11 @@ def graph_conv(x, adj, weight, bias, flags):
     return _GraphConvFn.apply(x, adj, weight, bias, flags)
 
 
+def _weighted(graph):
+    """A CsrGraph / CsrBatch that stores values: its ops take the `_w` entries (same launches; the values are data)."""
+    return bool(getattr(graph, "weighted", False))
+
+
 class _CsrGraphConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, g, flags):
@@ -139,10 +144,14 @@ class _CsrGraphConvFn(torch.autograd.Function):
         y, ax, invn = _f32(x, n, fout), _f32(x, n, fin), _f32(x, n)
         wsb = lib.dp_sparse_gcn_layer_workspace_bytes(n, fin, fout)
         ws = _workspace(wsb, x)
-        _lib.check(lib.dp_sparse_gcn_layer_fwd(x.data_ptr(), fin, g.indptr.data_ptr(), g.indices.data_ptr(), w.data_ptr(),
-                                               _lib.ptr(bias), y.data_ptr(), fout, ax.data_ptr(), invn.data_ptr(), n,
-                                               fin, fout, flags, ws.data_ptr(), wsb, _lib.current_stream()),
-                   "dp_sparse_gcn_layer_fwd")
+        tail = (w.data_ptr(), _lib.ptr(bias), y.data_ptr(), fout, ax.data_ptr(), invn.data_ptr(), n, fin, fout, flags,
+                ws.data_ptr(), wsb, _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_sparse_gcn_layer_fwd_w(x.data_ptr(), fin, g.indptr.data_ptr(), g.indices.data_ptr(),
+                                                     g.values.data_ptr(), *tail), "dp_sparse_gcn_layer_fwd_w")
+        else:
+            _lib.check(lib.dp_sparse_gcn_layer_fwd(x.data_ptr(), fin, g.indptr.data_ptr(), g.indices.data_ptr(), *tail),
+                       "dp_sparse_gcn_layer_fwd")
         ctx.save_for_backward(ax, w, y, invn)
         ctx.g, ctx.flags, ctx.ws, ctx.has_bias = g, flags, ws, bias is not None
         return y
@@ -158,18 +167,23 @@ class _CsrGraphConvFn(torch.autograd.Function):
         dx = torch.empty_like(ax) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w)
         db = _f32(ax, fout) if ctx.has_bias else None
-        _lib.check(lib.dp_sparse_gcn_layer_bwd(ax.data_ptr(), g.indptr.data_ptr(), g.indices.data_ptr(),
-                                               g.indptr_t.data_ptr(), g.indices_t.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                               fout, invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin,
-                                               dw.data_ptr(), _lib.ptr(db), n, fin, fout, ctx.flags, ctx.ws.data_ptr(),
-                                               ctx.ws.numel(), _lib.current_stream()), "dp_sparse_gcn_layer_bwd")
+        tail = (w.data_ptr(), y.data_ptr(), fout, invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin, dw.data_ptr(),
+                _lib.ptr(db), n, fin, fout, ctx.flags, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_sparse_gcn_layer_bwd_w(ax.data_ptr(), g.indptr.data_ptr(), g.indices.data_ptr(),
+                                                     g.values.data_ptr(), g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
+                                                     g.values_t.data_ptr(), *tail), "dp_sparse_gcn_layer_bwd_w")
+        else:
+            _lib.check(lib.dp_sparse_gcn_layer_bwd(ax.data_ptr(), g.indptr.data_ptr(), g.indices.data_ptr(),
+                                                   g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
+                       "dp_sparse_gcn_layer_bwd")
         return dx, dw, db, None, None
 
 
 def csr_graph_conv(x, weight, bias, graph, flags):
     """`graph_conv` on node rows x [n, F] with the adjacency as CSR: `graph` (a CsrGraph, or a CsrBatch with its
     block-diagonal CSR and n = n_total) carries int32 indptr / indices of A and of A^T (the neighbour sum A x is the
-    gather of dp_csr_aggregate, the backward gathers over A^T)."""
+    gather of dp_csr_aggregate, the backward gathers over A^T) and, when it is `weighted`, their fp32 values."""
     return _CsrGraphConvFn.apply(x, weight, bias, graph, flags)
 
 
@@ -300,9 +314,12 @@ class _CsrPoolFn(torch.autograd.Function):
         xp, ap = _f32(s, k, d), _f32(s, k, k)
         wsb = lib.dp_csr_pool_workspace_bytes(n, k, d)
         ws = _workspace(wsb, s)
-        _lib.check(lib.dp_csr_pool_fwd(s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr(),
-                                       xp.data_ptr(), ap.data_ptr(), n, k, d, ws.data_ptr(), wsb,
-                                       _lib.current_stream()), "dp_csr_pool_fwd")
+        head = (s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr())
+        tail = (xp.data_ptr(), ap.data_ptr(), n, k, d, ws.data_ptr(), wsb, _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_csr_pool_fwd_w(*head, g.values.data_ptr(), *tail), "dp_csr_pool_fwd_w")
+        else:
+            _lib.check(lib.dp_csr_pool_fwd(*head, *tail), "dp_csr_pool_fwd")
         ctx.save_for_backward(s, z)
         ctx.g, ctx.ws = g, ws
         return xp, ap
@@ -317,10 +334,15 @@ class _CsrPoolFn(torch.autograd.Function):
         dxp, dap = dxp.contiguous(), dap.contiguous()
         ds = torch.empty_like(s)
         dz = torch.zeros_like(z)
-        _lib.check(lib.dp_csr_pool_bwd(s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr(),
-                                       g.indptr_t.data_ptr(), g.indices_t.data_ptr(), dxp.data_ptr(), dap.data_ptr(),
-                                       ds.data_ptr(), k, dz.data_ptr(), d, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                       _lib.current_stream()), "dp_csr_pool_bwd")
+        head = (s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr())
+        tail = (dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d, n, k, d, ctx.ws.data_ptr(),
+                ctx.ws.numel(), _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_csr_pool_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
+                                             g.values_t.data_ptr(), *tail), "dp_csr_pool_bwd_w")
+        else:
+            _lib.check(lib.dp_csr_pool_bwd(*head, g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
+                       "dp_csr_pool_bwd")
         return ds, dz, None
 
 
@@ -641,10 +663,13 @@ class _CsrPoolBatchFn(torch.autograd.Function):
         xp, ap = _f32(s, b, k, d), _f32(s, b, k, k)
         wsb = lib.dp_csr_pool_batch_workspace_bytes(plan.n_slabs, b, k, d)
         ws = _workspace(wsb, s)
-        _lib.check(lib.dp_csr_pool_batch_fwd(s.data_ptr(), k, z.data_ptr(), d, batch.indptr.data_ptr(),
-                                             batch.indices.data_ptr(), plan.fwd_tab.data_ptr(),
-                                             plan.slab_off.data_ptr(), plan.n_slabs, xp.data_ptr(), ap.data_ptr(), b, n,
-                                             k, d, ws.data_ptr(), wsb, _lib.current_stream()), "dp_csr_pool_batch_fwd")
+        head = (s.data_ptr(), k, z.data_ptr(), d, batch.indptr.data_ptr(), batch.indices.data_ptr())
+        tail = (plan.fwd_tab.data_ptr(), plan.slab_off.data_ptr(), plan.n_slabs, xp.data_ptr(), ap.data_ptr(), b, n, k, d,
+                ws.data_ptr(), wsb, _lib.current_stream())
+        if _weighted(batch):
+            _lib.check(lib.dp_csr_pool_batch_fwd_w(*head, batch.values.data_ptr(), *tail), "dp_csr_pool_batch_fwd_w")
+        else:
+            _lib.check(lib.dp_csr_pool_batch_fwd(*head, *tail), "dp_csr_pool_batch_fwd")
         ctx.save_for_backward(s, z)
         ctx.batch, ctx.plan, ctx.ws = batch, plan, ws
         return xp, ap
@@ -659,11 +684,16 @@ class _CsrPoolBatchFn(torch.autograd.Function):
         dxp, dap = dxp.contiguous(), dap.contiguous()
         ds = torch.empty_like(s)
         dz = torch.zeros_like(z)
-        _lib.check(lib.dp_csr_pool_batch_bwd(s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr(),
-                                             g.indptr_t.data_ptr(), g.indices_t.data_ptr(), plan.bwd_tab.data_ptr(),
-                                             plan.n_blocks, dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k,
-                                             dz.data_ptr(), d, g.num_graphs, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                             _lib.current_stream()), "dp_csr_pool_batch_bwd")
+        head = (s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr())
+        tail = (plan.bwd_tab.data_ptr(), plan.n_blocks, dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d,
+                g.num_graphs, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_csr_pool_batch_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(),
+                                                   g.indices_t.data_ptr(), g.values_t.data_ptr(), *tail),
+                       "dp_csr_pool_batch_bwd_w")
+        else:
+            _lib.check(lib.dp_csr_pool_batch_bwd(*head, g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
+                       "dp_csr_pool_batch_bwd")
         return ds, dz, None
 
 
@@ -684,9 +714,13 @@ class _CsrLinkLossBatchFn(torch.autograd.Function):
         loss = _f32(s, ())
         wsb = lib.dp_csr_linkpred_batch_workspace_bytes(off, g.num_graphs, k)
         ws = _workspace(wsb, s)
-        _lib.check(lib.dp_csr_linkpred_batch_loss_fwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr(),
-                                                      off, g.num_graphs, loss.data_ptr(), k, ws.data_ptr(), wsb,
-                                                      _lib.current_stream()), "dp_csr_linkpred_batch_loss_fwd")
+        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr())
+        tail = (off, g.num_graphs, loss.data_ptr(), k, ws.data_ptr(), wsb, _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_csr_linkpred_batch_loss_fwd_w(*head, g.values.data_ptr(), *tail),
+                       "dp_csr_linkpred_batch_loss_fwd_w")
+        else:
+            _lib.check(lib.dp_csr_linkpred_batch_loss_fwd(*head, *tail), "dp_csr_linkpred_batch_loss_fwd")
         ctx.save_for_backward(s)
         ctx.g, ctx.ws = g, ws
         return loss
@@ -699,11 +733,16 @@ class _CsrLinkLossBatchFn(torch.autograd.Function):
         n, k = s.shape
         dloss = dloss.contiguous().float()
         ds = torch.empty_like(s)
-        _lib.check(lib.dp_csr_linkpred_batch_loss_bwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr(),
-                                                      g.indptr_t.data_ptr(), g.indices_t_local.data_ptr(),
-                                                      g.node_off_host.ctypes.data, g.num_graphs, dloss.data_ptr(),
-                                                      ds.data_ptr(), k, 0, k, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                                      _lib.current_stream()), "dp_csr_linkpred_batch_loss_bwd")
+        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr())
+        tail = (g.node_off_host.ctypes.data, g.num_graphs, dloss.data_ptr(), ds.data_ptr(), k, 0, k, ctx.ws.data_ptr(),
+                ctx.ws.numel(), _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_csr_linkpred_batch_loss_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(),
+                                                            g.indices_t_local.data_ptr(), g.values_t.data_ptr(), *tail),
+                       "dp_csr_linkpred_batch_loss_bwd_w")
+        else:
+            _lib.check(lib.dp_csr_linkpred_batch_loss_bwd(*head, g.indptr_t.data_ptr(), g.indices_t_local.data_ptr(),
+                                                          *tail), "dp_csr_linkpred_batch_loss_bwd")
         return ds, None
 
 
@@ -822,9 +861,12 @@ class _CsrLinkLossFn(torch.autograd.Function):
         loss = _f32(s, ())
         wsb = lib.dp_csr_linkpred_workspace_bytes(n, k)
         ws = _workspace(wsb, s)
-        _lib.check(lib.dp_csr_linkpred_loss_fwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(),
-                                                loss.data_ptr(), n, k, ws.data_ptr(), wsb, _lib.current_stream()),
-                   "dp_csr_linkpred_loss_fwd")
+        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr())
+        tail = (loss.data_ptr(), n, k, ws.data_ptr(), wsb, _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_csr_linkpred_loss_fwd_w(*head, g.values.data_ptr(), *tail), "dp_csr_linkpred_loss_fwd_w")
+        else:
+            _lib.check(lib.dp_csr_linkpred_loss_fwd(*head, *tail), "dp_csr_linkpred_loss_fwd")
         ctx.save_for_backward(s)
         ctx.g, ctx.ws = g, ws
         return loss
@@ -837,17 +879,23 @@ class _CsrLinkLossFn(torch.autograd.Function):
         n, k = s.shape
         dloss = dloss.contiguous().float()
         ds = torch.empty_like(s)
-        _lib.check(lib.dp_csr_linkpred_loss_bwd(s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(),
-                                                g.indptr_t.data_ptr(), g.indices_t.data_ptr(), dloss.data_ptr(),
-                                                ds.data_ptr(), k, 0, n, k, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                                _lib.current_stream()), "dp_csr_linkpred_loss_bwd")
+        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr())
+        tail = (dloss.data_ptr(), ds.data_ptr(), k, 0, n, k, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+        if _weighted(g):
+            _lib.check(lib.dp_csr_linkpred_loss_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(),
+                                                      g.indices_t.data_ptr(), g.values_t.data_ptr(), *tail),
+                       "dp_csr_linkpred_loss_bwd_w")
+        else:
+            _lib.check(lib.dp_csr_linkpred_loss_bwd(*head, g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
+                       "dp_csr_linkpred_loss_bwd")
         return ds, None
 
 
 def csr_link_loss(s, graph):
     """DiffPool's link-prediction loss (encoders.py:1309-1331) of the assignment s [n, k] on ONE graph given as CSR
-    (0/1 adjacency, each edge listed once): dp_csr_linkpred_loss_* — a tile walk over s for the n^2 term that does not
-    depend on the adjacency plus a gather over the edges, O(n k) memory.  Returns the device scalar."""
+    (0/1 adjacency, or the stored values of a weighted graph; each edge listed once): dp_csr_linkpred_loss_* — a tile
+    walk over s for the n^2 term that does not depend on the adjacency plus a gather over the edges, O(n k) memory.
+    Returns the device scalar."""
     return _CsrLinkLossFn.apply(s, graph)
 
 
@@ -935,15 +983,19 @@ class _FrobLinkFn(torch.autograd.Function):
             wsb = lib.dp_csr_frob_link_workspace_bytes(n, b, k)
             ws = _workspace(wsb, s)
             w, g = torch.empty_like(s), _f32(s, (b, k, k))
-            csr = (s.data_ptr(), k, adj.indptr.data_ptr(), adj.indices.data_ptr(),
-                   adj.indptr_t.data_ptr() if directed else None, adj.indices_t.data_ptr() if directed else None)
+            wt = _weighted(adj)
+            csr = (s.data_ptr(), k, adj.indptr.data_ptr(), adj.indices.data_ptr()) + \
+                ((adj.values.data_ptr(),) if wt else ()) + \
+                (adj.indptr_t.data_ptr() if directed else None, adj.indices_t.data_ptr() if directed else None) + \
+                ((adj.values_t.data_ptr() if directed else None,) if wt else ())
             if kind == "batch":
-                _lib.check(lib.dp_csr_frob_link_batch_fwd(*csr, adj.node_off.data_ptr(), None, w.data_ptr(), g.data_ptr(),
-                                                          loss.data_ptr(), None, b, n, k, ws.data_ptr(), wsb, st),
-                           "dp_csr_frob_link_batch_fwd")
+                fn = lib.dp_csr_frob_link_batch_fwd_w if wt else lib.dp_csr_frob_link_batch_fwd
+                _lib.check(fn(*csr, adj.node_off.data_ptr(), None, w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, b,
+                              n, k, ws.data_ptr(), wsb, st), "dp_csr_frob_link_batch_fwd" + "_w" * wt)
             else:
-                _lib.check(lib.dp_csr_frob_link_fwd(*csr, None, w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, n, k,
-                                                    ws.data_ptr(), wsb, st), "dp_csr_frob_link_fwd")
+                fn = lib.dp_csr_frob_link_fwd_w if wt else lib.dp_csr_frob_link_fwd
+                _lib.check(fn(*csr, None, w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, n, k, ws.data_ptr(), wsb,
+                              st), "dp_csr_frob_link_fwd" + "_w" * wt)
             ctx.sym = 0 if directed else 1
         ctx.save_for_backward(s, w, g)
         ctx.kind, ctx.num_nodes, ctx.adj, ctx.b = kind, num_nodes, adj if kind == "batch" else None, b
@@ -978,7 +1030,7 @@ def frob_link_loss(s, adj, num_nodes=None):
     unpinned by the reference, which has no such term — on dp_frob_link_* / dp_csr_frob_link_*, without any n x n
     temporary.  Dense: s [B, N, K] with adj an fp32 [B, N, N] tensor (any values) or a `PackedAdjacency`, `num_nodes`
     int32 [B] on the device (None: all N).  Ragged: s [n, K] with a `CsrGraph`, or s [n_total, K] with a `CsrBatch`
-    (0/1 adjacency, each entry stored once).  Returns the device scalar."""
+    (0/1 adjacency, or a weighted container's stored values; each entry stored once).  Returns the device scalar."""
     if not isinstance(s, torch.Tensor) or s.dim() not in (2, 3):
         got = tuple(s.shape) if isinstance(s, torch.Tensor) else type(s).__name__
         raise ValueError(f"frob_link_loss(s, adj, num_nodes): s must be [n, K] or [B, N, K], got {got}")

@@ -45,21 +45,69 @@ from .ops import hip_linear  # noqa: F401  (tests and tools import it from here)
 
 
 # ----------------------------------------------------------------------------- CSR helpers
+def _check_values(values, indices, what):
+    """A container's `values`: an fp32 tensor with one entry per stored index, on the indices' device."""
+    if not isinstance(values, torch.Tensor):
+        raise TypeError(f"{what} must be a tensor, got {type(values).__name__}")
+    if values.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32, got {values.dtype}")
+    if values.dim() != 1 or values.numel() != indices.numel():
+        raise ValueError(f"{what} must hold one value per stored entry [{indices.numel()}], got {tuple(values.shape)}")
+    if values.device != indices.device:
+        raise ValueError(f"{what} is on {values.device} but the index arrays are on {indices.device}")
+    return values.contiguous()
+
+
+def _inv_sqrt_degree(n, cols, vals, what):
+    """1 / sqrt(column sum of the stored values), in float64 (graph_sampler.py:27: np.sum(adj, axis=0)); a node of
+    degree 0 raises — the reference's inf * 0 = NaN row has no place in a CSR."""
+    deg = np.zeros(n, dtype=np.float64)
+    np.add.at(deg, cols, vals.astype(np.float64))
+    bad = np.nonzero(~(deg > 0))[0]
+    if bad.size:
+        raise ValueError(f"{what}.normalized(): node {int(bad[0])} has degree {deg[bad[0]]:g} (column sum of the stored "
+                         f"values; {bad.size} such node(s)): D^-1/2 A D^-1/2 is not defined there")
+    return 1.0 / np.sqrt(deg)
+
+
+def _csr_rows(indptr, nnz):
+    """Row of every stored entry of a host CSR."""
+    return np.repeat(np.arange(indptr.size - 1, dtype=np.int64), np.diff(indptr.astype(np.int64)))[:nnz]
+
+
 class CsrGraph:
     """CSR of one graph's adjacency on the device: int32 indptr [n + 1], indices [nnz] — row i lists the j with
     A[i, j] != 0 (0/1 adjacency, graph_sampler.py:26) — plus the CSR of A^T for the backward gather (the same arrays
-    for an undirected graph).
+    for an undirected graph).  `values` (fp32 [nnz] on the device, in the order of `indices`; `values_t` in the order
+    of `indices_t`, the same tensor for an undirected graph) makes it a weighted adjacency: A[i, indices[e]] =
+    values[e], stored zeros allowed.  `weighted` tells which.
 
     `bn_relu`, `readout`, `pool` and `link_loss` are the four steps of the DiffPool model that differ between one graph
     and a `CsrBatch`; `ARG` and `rows()` are how the model's messages name the container and its node rows."""
 
     ARG = "graph"
 
-    def __init__(self, indptr, indices, indptr_t=None, indices_t=None):
+    def __init__(self, indptr, indices, indptr_t=None, indices_t=None, values=None, values_t=None):
         self.indptr, self.indices = indptr, indices
         self.indptr_t = indptr if indptr_t is None else indptr_t
         self.indices_t = indices if indices_t is None else indices_t
         self.n = indptr.numel() - 1
+        self.weighted = values is not None
+        self.values = self.values_t = None
+        if values is None:
+            if values_t is not None:
+                raise ValueError("CsrGraph: values_t without values")
+            return
+        self.values = _check_values(values, indices, "CsrGraph: values")
+        if self.indices_t is self.indices:
+            if values_t is not None and values_t is not values:
+                raise ValueError("CsrGraph: an undirected graph (no transposed CSR of its own) stores a_ij = a_ji: "
+                                 "values_t must be values or None")
+            self.values_t = self.values
+        elif values_t is None:
+            raise ValueError("CsrGraph: a weighted graph with a transposed CSR of its own needs values_t")
+        else:
+            self.values_t = _check_values(values_t, self.indices_t, "CsrGraph: values_t")
 
     def rows(self):
         return f"[n, F] with n = {self.n}"
@@ -83,12 +131,35 @@ class CsrGraph:
         return ops.frob_link_loss(s, self) if objective == "frobenius" else ops.csr_link_loss(s, self)
 
     @staticmethod
-    def from_edges(n, src, dst, device, symmetric=True):
-        """Edge list -> CSR (both directions when symmetric, duplicates removed, no self loops added)."""
-        src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    def from_edges(n, src, dst, device, symmetric=True, weight=None):
+        """Edge list -> CSR (both directions when symmetric, duplicates removed, no self loops added).  `weight`: one
+        value per edge (mirrored when symmetric; zeros are stored) -> a weighted graph; an (i, j) given twice with two
+        different weights — also as (i, j) and (j, i) under symmetric=True — raises, with the same weight it is
+        merged."""
+        src, dst = np.asarray(src, dtype=np.int64).reshape(-1), np.asarray(dst, dtype=np.int64).reshape(-1)
+        w = None
+        if weight is not None:
+            w = np.asarray(weight, dtype=np.float32).reshape(-1)
+            if w.size != src.size:
+                raise ValueError(f"CsrGraph.from_edges: {w.size} weights for {src.size} edges")
         if symmetric:
             src, dst = np.concatenate([src, dst]), np.concatenate([dst, src])
-        key = np.unique(src * n + dst)
+            if w is not None:
+                w = np.concatenate([w, w])
+        if w is None:
+            key = np.unique(src * n + dst)
+        else:
+            order = np.argsort(src * n + dst, kind="stable")
+            key, w = (src * n + dst)[order], w[order]
+            first = np.ones(key.size, dtype=bool)
+            first[1:] = key[1:] != key[:-1]
+            head = np.maximum.accumulate(np.where(first, np.arange(key.size), 0))     # first entry of each run
+            clash = np.nonzero(w != w[head])[0]
+            if clash.size:
+                e = int(clash[0])
+                raise ValueError(f"CsrGraph.from_edges: entry ({int(key[e] // n)}, {int(key[e] % n)}) is given with two "
+                                 f"weights ({w[head[e]]:g} and {w[e]:g})")
+            key, w = key[first], w[first]
         rows, cols = key // n, key % n
 
         def csr(r, c):
@@ -96,20 +167,41 @@ class CsrGraph:
             r, c = r[order], c[order]
             indptr = np.zeros(n + 1, dtype=np.int32)
             np.add.at(indptr, r + 1, 1)
+            val = None if w is None else torch.from_numpy(np.ascontiguousarray(w[order])).to(device)
             return (torch.from_numpy(np.cumsum(indptr, dtype=np.int64).astype(np.int32)).to(device),
-                    torch.from_numpy(c.astype(np.int32)).to(device))
-        ip, ix = csr(rows, cols)
+                    torch.from_numpy(c.astype(np.int32)).to(device), val)
+        ip, ix, val = csr(rows, cols)
         if symmetric:
-            return CsrGraph(ip, ix)
-        ipt, ixt = csr(cols, rows)
-        return CsrGraph(ip, ix, ipt, ixt)
+            return CsrGraph(ip, ix, values=val)
+        ipt, ixt, valt = csr(cols, rows)
+        return CsrGraph(ip, ix, ipt, ixt, val, valt)
 
     @staticmethod
-    def from_dense(adj):
-        """[n, n] tensor (any device) -> CSR on adj's device (testing aid)."""
-        a = adj.detach().cpu().numpy() != 0
-        r, c = np.nonzero(a)
-        return CsrGraph.from_edges(a.shape[0], r, c, adj.device, symmetric=False)
+    def from_dense(adj, weighted=False):
+        """[n, n] tensor (any device) -> CSR on adj's device (testing aid); weighted=True keeps the nonzero values."""
+        a = adj.detach().cpu().numpy()
+        r, c = np.nonzero(a != 0)
+        return CsrGraph.from_edges(a.shape[0], r, c, adj.device, symmetric=False,
+                                   weight=a[r, c].astype(np.float32) if weighted else None)
+
+    def normalized(self):
+        """A new weighted graph holding D^-1/2 A D^-1/2 — what GraphSampler(normalize=True) feeds the dense model
+        (graph_sampler.py:27-29; `tu_dataset.normalized_adjacency`): the degree is the column sum of the stored values
+        (ones for a 0/1 graph), as the reference takes it (axis=0).  Computed once on the host in float64 and rounded
+        to fp32; the index arrays are shared.  A node of degree 0 raises ValueError."""
+        ip, ix = self.indptr.cpu().numpy(), self.indices.cpu().numpy().astype(np.int64)
+        nnz = int(ip[-1])
+        val = self.values.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
+        rows, cols = _csr_rows(ip, nnz), ix[:nnz]
+        inv = _inv_sqrt_degree(self.n, cols, val, "CsrGraph")
+        dev = lambda a: torch.from_numpy(a.astype(np.float32)).to(self.indices.device)
+        new = dev((val * inv[rows]) * inv[cols])
+        if self.indices_t is self.indices:
+            return CsrGraph(self.indptr, self.indices, values=new)
+        ipt, ixt = self.indptr_t.cpu().numpy(), self.indices_t.cpu().numpy().astype(np.int64)
+        valt = self.values_t.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
+        rt, ct = _csr_rows(ipt, nnz), ixt[:nnz]              # entry (rt, ct) of A^T is a_{ct, rt}
+        return CsrGraph(self.indptr, self.indices, self.indptr_t, self.indices_t, new, dev((valt * inv[ct]) * inv[rt]))
 
 
 class _PoolPlan:
@@ -142,6 +234,8 @@ class CsrBatch:
     `n_total`, `max_n`, `min_n`, `pad_to`, `n_idx`.  The adjacency is one block-diagonal CSR: `indptr` [n_total+1] with `indices` holding
     GLOBAL columns (rows of the concatenated tensors: GraphConv, pooling) and `indices_local` graph-local ones (link
     loss); `indptr_t` / `indices_t` / `indices_t_local` the CSR of A^T — the same tensors unless a graph is directed.
+    A batch is `weighted` if any of its graphs is (the others get ones): `values` / `values_t`, fp32 in the order of
+    `indices` / `indices_t`, serve the global and the graph-local index arrays alike.
 
     `pad_to` only decides which graphs get the max readout's zero floor (n_b < pad_to: the dense batch has a masked
     zero row for them); host code that knows `max_num_nodes` reproduces a dense run at that padding with it.  Everything
@@ -152,8 +246,9 @@ class CsrBatch:
     ARG = "batch"
 
     def __init__(self, sizes, parts, device, pad_to=None):
-        """`parts`: per graph (indptr, indices, indptr_t, indices_t) as host int arrays with graph-local columns, the
-        transposed pair None for an undirected graph.  Use the from_* constructors."""
+        """`parts`: per graph (indptr, indices, indptr_t, indices_t[, values, values_t]) as host arrays with graph-local
+        columns, the transposed pair None for an undirected graph; values (float, one per stored entry; values_t next
+        to a transposed pair) or None / absent for a 0/1 graph.  Use the from_* constructors."""
         sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
         if sizes.size == 0:
             raise ValueError("CsrBatch: no graph")
@@ -173,9 +268,11 @@ class CsrBatch:
         self.n_total = self.n = int(self.node_off_host[-1])
         self.device = torch.device(device)
         directed = any(p[2] is not None for p in parts)
+        parts = [tuple(p) + (None,) * (6 - len(p)) for p in parts]
+        self.weighted = any(p[4] is not None for p in parts)
 
         def stack(which):
-            ips, loc, glob, e0 = [], [], [], 0
+            ips, loc, glob, vals, e0 = [], [], [], [], 0
             for b, p in enumerate(parts):
                 ip = np.asarray(p[which] if p[which] is not None else p[0], dtype=np.int64)
                 ix = np.asarray(p[which + 1] if p[which] is not None else p[1], dtype=np.int64)
@@ -184,6 +281,18 @@ class CsrBatch:
                     raise ValueError(f"CsrBatch: graph {b}: indptr does not describe {n} rows over {ix.size} entries")
                 if ix.size and (ix.min() < 0 or ix.max() >= n):
                     raise ValueError(f"CsrBatch: graph {b}: column index outside 0..{n - 1}")
+                if self.weighted:
+                    v = p[4 + which // 2] if p[which] is not None else p[4]
+                    if v is None:
+                        if p[4] is not None:
+                            raise ValueError(f"CsrBatch: graph {b}: a weighted graph with a transposed CSR needs values_t")
+                        v = np.ones(ix.size, dtype=np.float32)
+                    v = np.asarray(v)
+                    if v.ndim != 1 or v.size != ix.size:
+                        raise ValueError(f"CsrBatch: graph {b}: {v.size} values for {ix.size} stored entries")
+                    if not np.issubdtype(v.dtype, np.floating):
+                        raise ValueError(f"CsrBatch: graph {b}: values must be floating point, got {v.dtype}")
+                    vals.append(v.astype(np.float32))
                 ips.append(ip[:-1] + e0)
                 loc.append(ix)
                 glob.append(ix + int(self.node_off_host[b]))
@@ -193,13 +302,18 @@ class CsrBatch:
             ips.append(np.array([e0]))
             pad = [np.zeros(1, dtype=np.int64)] if e0 == 0 else []      # the kernels want non-NULL index arrays
             dev = lambda a: torch.from_numpy(np.concatenate(a).astype(np.int32)).to(self.device)
-            return dev(ips), dev(glob + pad), dev(loc + pad)
+            val = None
+            if self.weighted:
+                fpad = [np.zeros(1, dtype=np.float32)] if e0 == 0 else []
+                val = torch.from_numpy(np.concatenate(vals + fpad).astype(np.float32)).to(self.device)
+            return dev(ips), dev(glob + pad), dev(loc + pad), val
 
-        self.indptr, self.indices, self.indices_local = stack(0)
+        self.indptr, self.indices, self.indices_local, self.values = stack(0)
         if directed:
-            self.indptr_t, self.indices_t, self.indices_t_local = stack(2)
+            self.indptr_t, self.indices_t, self.indices_t_local, self.values_t = stack(2)
         else:
             self.indptr_t, self.indices_t, self.indices_t_local = self.indptr, self.indices, self.indices_local
+            self.values_t = self.values
         self.node_off = torch.from_numpy(self.node_off_host).to(self.device)
         # node-index BatchNorm: graphs by size, largest first; cnt[i] = graphs with n_b > i
         order = np.argsort(-sizes, kind="stable")
@@ -271,41 +385,77 @@ class CsrBatch:
             if not isinstance(g, CsrGraph):
                 raise TypeError(f"CsrBatch.from_graphs: expected CsrGraph, got {type(g).__name__}")
             ip, ix = g.indptr.cpu().numpy(), g.indices.cpu().numpy()
+            val = g.values.cpu().numpy()[:ip[-1]] if g.weighted else None
             if g.indptr_t is g.indptr and g.indices_t is g.indices:
-                parts.append((ip, ix[:ip[-1]], None, None))
+                parts.append((ip, ix[:ip[-1]], None, None, val, None))
             else:
                 ipt, ixt = g.indptr_t.cpu().numpy(), g.indices_t.cpu().numpy()
-                parts.append((ip, ix[:ip[-1]], ipt, ixt[:ipt[-1]]))
+                valt = g.values_t.cpu().numpy()[:ipt[-1]] if g.weighted else None
+                parts.append((ip, ix[:ip[-1]], ipt, ixt[:ipt[-1]], val, valt))
         return CsrBatch([g.n for g in graphs], parts, graphs[0].indptr.device, pad_to=pad_to)
 
     @staticmethod
-    def from_edge_lists(sizes, srcs, dsts, device, symmetric=True, pad_to=None):
-        """Per graph an edge list (graph-local node ids) -> the batch; `symmetric` as in `CsrGraph.from_edges`."""
-        if not (len(sizes) == len(srcs) == len(dsts)):
-            raise ValueError("CsrBatch.from_edge_lists: sizes, srcs and dsts must have one entry per graph")
+    def from_edge_lists(sizes, srcs, dsts, device, symmetric=True, pad_to=None, weights=None):
+        """Per graph an edge list (graph-local node ids) -> the batch; `symmetric` as in `CsrGraph.from_edges`.
+        `weights`: per graph the edges' weights (`CsrGraph.from_edges`' `weight`), or None for a 0/1 graph."""
+        if weights is None:
+            weights = [None] * len(sizes)
+        if not (len(sizes) == len(srcs) == len(dsts) == len(weights)):
+            raise ValueError("CsrBatch.from_edge_lists: sizes, srcs, dsts (and weights) must have one entry per graph")
         parts = []
-        for n, src, dst in zip(sizes, srcs, dsts):
-            g = CsrGraph.from_edges(int(n), src, dst, "cpu", symmetric=symmetric)
+        for n, src, dst, w in zip(sizes, srcs, dsts, weights):
+            g = CsrGraph.from_edges(int(n), src, dst, "cpu", symmetric=symmetric, weight=w)
             ip, ix = g.indptr.numpy(), g.indices.numpy()
-            parts.append((ip, ix, None, None) if symmetric else (ip, ix, g.indptr_t.numpy(), g.indices_t.numpy()))
+            val = g.values.numpy() if g.weighted else None
+            if symmetric:
+                parts.append((ip, ix, None, None, val, None))
+            else:
+                parts.append((ip, ix, g.indptr_t.numpy(), g.indices_t.numpy(), val,
+                              g.values_t.numpy() if g.weighted else None))
         return CsrBatch(sizes, parts, device, pad_to=pad_to)
 
+    def normalized(self):
+        """A new weighted batch holding D^-1/2 A D^-1/2 of every graph (`CsrGraph.normalized`: column sums of the stored
+        values, host float64, a node of degree 0 raises).  Everything but `values` / `values_t` is shared with this
+        batch."""
+        import copy
+        ip, ix = self.indptr.cpu().numpy(), self.indices.cpu().numpy().astype(np.int64)
+        nnz = int(ip[-1])
+        val = self.values.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
+        rows, cols = _csr_rows(ip, nnz), ix[:nnz]
+        inv = _inv_sqrt_degree(self.n_total, cols, val, "CsrBatch")
+        pad = np.zeros(int(nnz == 0))
+        dev = lambda a: torch.from_numpy(np.concatenate([a, pad]).astype(np.float32)).to(self.device)
+        new = copy.copy(self)
+        new.weighted = True
+        new.values = dev((val * inv[rows]) * inv[cols])
+        if self.indices_t is self.indices:
+            new.values_t = new.values
+        else:
+            ipt, ixt = self.indptr_t.cpu().numpy(), self.indices_t.cpu().numpy().astype(np.int64)
+            valt = self.values_t.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
+            rt, ct = _csr_rows(ipt, nnz), ixt[:nnz]
+            new.values_t = dev((valt * inv[ct]) * inv[rt])
+        return new
+
     @staticmethod
-    def from_dense(adj, num_nodes, pad_to=None):
+    def from_dense(adj, num_nodes, pad_to=None, weighted=False):
         """[B, N, N] tensor (any device) + node counts -> the batch on adj's device, reading only the leading
-        n_b x n_b block of each graph (testing aid, like `CsrGraph.from_dense`)."""
-        a = adj.detach().cpu().numpy() != 0
+        n_b x n_b block of each graph (testing aid, like `CsrGraph.from_dense`); weighted=True keeps the nonzero
+        values."""
+        a = adj.detach().cpu().numpy()
         nn_ = np.asarray(num_nodes, dtype=np.int64).reshape(-1)
         if a.ndim != 3 or a.shape[0] != nn_.size or a.shape[1] != a.shape[2]:
             raise ValueError(f"CsrBatch.from_dense: adj {tuple(a.shape)} does not match {nn_.size} node counts")
         if (nn_ > a.shape[1]).any():
             raise ValueError("CsrBatch.from_dense: a node count exceeds the padded size")
-        srcs, dsts = [], []
+        srcs, dsts, ws = [], [], []
         for b, n in enumerate(nn_):
-            r, c = np.nonzero(a[b, :n, :n])
+            r, c = np.nonzero(a[b, :n, :n] != 0)
             srcs.append(r)
             dsts.append(c)
-        return CsrBatch.from_edge_lists(nn_, srcs, dsts, adj.device, symmetric=False, pad_to=pad_to)
+            ws.append(a[b, :n, :n][r, c].astype(np.float32) if weighted else None)
+        return CsrBatch.from_edge_lists(nn_, srcs, dsts, adj.device, symmetric=False, pad_to=pad_to, weights=ws)
 
 
 def _gcn_stack(mods, h, graph, bn=True):
@@ -529,6 +679,11 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     on the dense per-op entries (dp_gcn_layer_*, dp_bn_node_*, dp_assign_softmax_mask_*, dp_pool_*, dp_masked_max_*);
     pred_model on `hip_linear`, the loss on dp_cross_entropy_*.
 
+Both containers may carry one fp32 value per stored entry (`values`, and `values_t` for the CSR of A^T): the weighted
+adjacency of the dense path, e.g. the reference sampler's default D^-1/2 A D^-1/2 (graph_sampler.py:27-29), which
+`normalized()` builds.  Every op then takes its `_w` entry (`graph.weighted`), with the launches of the 0/1 call; the
+values are data, no gradient flows to them.
+
     A linkpred=True model (the constructor default, train.py --linkpred) trains here too: `loss(pred, label, graph)`
     adds the link-prediction term on dp_csr_linkpred_loss_* (per graph of a batch: dp_csr_linkpred_batch_*) — the n^2
     part of the sum does not depend on the adjacency and is a tile walk over S, the rest a gather over the edges;
@@ -538,7 +693,7 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     Differences of a CsrBatch forward from the dense class's saved tensors: level-0 'assign' / 'embedding' and
     `assign_tensor` stay RAGGED, [n_total, .] (dense: [B, N, .]); level-0 'readout_argmax' rows are graph-local.
 
-    Not on this path: dropout, adj_hop > 1, weighted adjacencies, K_0 > 256 or a concatenated embedding wider than 512
+    Not on this path: dropout, adj_hop > 1, K_0 > 256 or a concatenated embedding wider than 512
     (dp_csr_pool's limits); on a CsrBatch also concat=False."""
 
     def __init__(self, max_num_nodes, input_dim, hidden_dim, embedding_dim, label_dim, num_layers,

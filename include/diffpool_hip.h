@@ -487,6 +487,19 @@ int dp_csr_frob_link_batch_fwd(const float* S, int lds, const int* indptr, const
 int dp_csr_frob_link_batch_bwd(const float* S, int lds, const float* W, const float* G, const int* node_off,
                                const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate,
                                int symmetric, int B, int n_total, int K, void* stream);
+/* The weighted forms (a CSR that stores values, e.g. D^-1/2 A D^-1/2 of graph_sampler.py:27-29): values fp32 [nnz] in the
+ * order of indices, values_t in the order of indices_t (needed only next to a transposed CSR of its own; NULL values, or
+ * NULL values_t there, is DP_ERR_INVALID_ARG).  T0 = sum of the stored values' squares, summed in fp64 in a fixed order
+ * by the row kernel; W = (A + A^T) S by dp_csr_aggregate_w.  Same launches and workspace as the unweighted entries; the
+ * backward reads no adjacency: dp_csr_frob_link_bwd / _batch_bwd serve both.  Weights of 1.0 give the unweighted bits. */
+int dp_csr_frob_link_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                           const int* indptr_t, const int* indices_t, const float* values_t, const float* link_norm,
+                           float* W, float* G, float* loss_out, float* total_inout, int n, int K, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int dp_csr_frob_link_batch_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                                 const int* indptr_t, const int* indices_t, const float* values_t, const int* node_off,
+                                 const float* link_norm, float* W, float* G, float* loss_out, float* total_inout, int B,
+                                 int n_total, int K, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ softmax cross entropy
  * loss = mean_b CE(logits_b, label_b) — F.cross_entropy, encoders.py:1127.  prob [B,C] is saved
@@ -584,6 +597,25 @@ int dp_sparse_gcn_layer_bwd(const float* ax, const int* indptr, const int* indic
                             const int* indices_t, const float* W, const float* y, int ldy, const float* invnorm,
                             const float* dy, int lddy, float* dx, int lddx, float* dW, float* db, int n, int Fin,
                             int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream);
+/* Weighted CSR (_w): the entries above read a stored entry as 1; these take its value — values fp32 [nnz] in the order
+ * of indices, values_t in the order of indices_t — so GraphConv runs on the reference's default adjacency
+ * D^-1/2 A D^-1/2 (graph_sampler.py:27-29, the `adj` of encoders.py:965) or on any weighted graph:
+ *     (A x)_i = sum_e values[e] x[indices[e]].
+ * dp_csr_aggregate_w has no `mean` (the reference defines no weighted mean).  The backward covers both forms of dx: the
+ * gather over A^T with values_t, and with indptr_t == NULL the atomic scatter dx[indices[e]] += values[e] dax_i.  NULL
+ * values, or NULL values_t next to an indices_t that is not `indices`, is DP_ERR_INVALID_ARG before any launch; all
+ * other checks, the workspace (dp_sparse_gcn_layer_workspace_bytes) and the launch count are the unweighted entries'.
+ * The summation order is theirs too: weights of exactly 1.0 give the same bits. */
+int dp_csr_aggregate_w(const float* table, int ldt, const int* indptr, const int* indices, const float* values,
+                       float* out, int ldo, int n_rows, int feat, float beta, void* stream);
+int dp_sparse_gcn_layer_fwd_w(const float* x, int ldx, const int* indptr, const int* indices, const float* values,
+                              const float* W, const float* bias, float* y, int ldy, float* ax, float* invnorm, int n,
+                              int Fin, int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream);
+int dp_sparse_gcn_layer_bwd_w(const float* ax, const int* indptr, const int* indices, const float* values,
+                              const int* indptr_t, const int* indices_t, const float* values_t, const float* W,
+                              const float* y, int ldy, const float* invnorm, const float* dy, int lddy, float* dx,
+                              int lddx, float* dW, float* db, int n, int Fin, int Fout, int flags, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ N4  level-0 pooling on a CSR graph
  * Xp = S^T Z [K,D], Ap = S^T A S [K,K] — encoders.py:1278-1279 on ONE graph whose 0/1 adjacency A is given as CSR
@@ -601,6 +633,17 @@ int dp_csr_pool_bwd(const float* S, int lds, const float* Z, int ldz, const int*
                     const int* indptr_t, const int* indices_t, const float* dXp, const float* dAp,
                     float* dS, int ldds, float* dZ, int lddz, int n, int K, int D,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* Weighted CSR (_w): Ap = S^T A S and dS = (A S) dAp^T + (A^T S) dAp + Z dXp^T (encoders.py:1278-1279 and its
+ * transpose) with A's stored values — values / values_t as in dp_sparse_gcn_layer_*_w, loaded next to the column indices
+ * by the same gathers.  Same launches, limits, checks and workspace (dp_csr_pool_workspace_bytes); NULL values, or NULL
+ * values_t next to an indices_t that is not `indices`, is DP_ERR_INVALID_ARG.  Weights of 1.0 give the unweighted bits. */
+int dp_csr_pool_fwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                      const float* values, float* Xp, float* Ap, int n, int K, int D, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int dp_csr_pool_bwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                      const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
+                      const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int n, int K, int D,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ N4  link-prediction loss on a CSR graph
  * The loss of A8 — loss = sum_ij [-A log(P+1e-7) - (1-A) log(1-P+1e-7)] / n^2, P = min(S S^T, 1), encoders.py:1309-1331
@@ -623,6 +666,18 @@ int dp_csr_linkpred_loss_fwd(const float* S, int lds, const int* indptr, const i
 int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                              const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate,
                              int n, int K, void* workspace, size_t workspace_bytes, void* stream);
+/* Weighted CSR (_w): the loss of encoders.py:1309-1331 is linear in a_ij, so the dense term (the tile walk over all
+ * pairs) is unchanged and the edge term becomes sum_{(i,j) stored} a_ij [ -log(p_ij + eps) + log(1 - p_ij + eps) ]; the
+ * backward's edge coefficient scales likewise.  values / values_t as in dp_sparse_gcn_layer_*_w (an undirected graph —
+ * indices_t == indices — must store a_ij = a_ji).  Same launches, checks and workspace (dp_csr_linkpred_workspace_bytes);
+ * NULL values, or NULL values_t next to an indices_t that is not `indices`, is DP_ERR_INVALID_ARG.  Weights of 1.0 give
+ * the unweighted bits. */
+int dp_csr_linkpred_loss_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                               float* loss_out, int n, int K, void* workspace, size_t workspace_bytes, void* stream);
+int dp_csr_linkpred_loss_bwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                               const int* indptr_t, const int* indices_t, const float* values_t, const float* dloss,
+                               float* dS, int ldds, int accumulate, int n, int K, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ N4  ragged batches of CSR graphs
  * B graphs with their node rows CONCATENATED, no padding: graph b owns rows node_off[b] .. node_off[b+1]-1 of every
@@ -735,6 +790,17 @@ int dp_csr_pool_batch_bwd(const float* S, int lds, const float* Z, int ldz, cons
                           const int* indptr_t, const int* indices_t, const int* bwd_tab, int n_blocks,
                           const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int B,
                           int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream);
+/* The weighted forms (encoders.py:1278-1279 with stored values): values / values_t fp32 [nnz of the batch] in the order of
+ * indices / indices_t — one array serves the GLOBAL and the graph-LOCAL index arrays.  Contract of dp_csr_pool_*_w. */
+int dp_csr_pool_batch_fwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                            const float* values, const int* fwd_tab, const int* slab_off, int n_slabs, float* Xp,
+                            float* Ap, int B, int n_total, int K, int D, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int dp_csr_pool_batch_bwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
+                            const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
+                            const int* bwd_tab, int n_blocks, const float* dXp, const float* dAp, float* dS, int ldds,
+                            float* dZ, int lddz, int B, int n_total, int K, int D, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* dp_csr_linkpred_batch_*: the link loss of a batch, sum_b (graph b's sum) / sum_b n_b^2 (encoders.py:1326-1331), with
  * O(n_total K) memory and no dense adjacency.  Built from PER-GRAPH launches of the dp_csr_linkpred_* kernels (the
@@ -749,6 +815,16 @@ int dp_csr_linkpred_batch_loss_bwd(const float* S, int lds, const int* indptr, c
                                    const int* indptr_t, const int* indices_t_local, const int* node_off_host, int B,
                                    const float* dloss, float* dS, int ldds, int accumulate, int K, void* workspace,
                                    size_t workspace_bytes, void* stream);
+/* The weighted forms (encoders.py:1309-1331 with stored values): contract of dp_csr_linkpred_loss_*_w, values / values_t
+ * the batch's arrays (GLOBAL edge offsets, as indptr gives them). */
+int dp_csr_linkpred_batch_loss_fwd_w(const float* S, int lds, const int* indptr, const int* indices_local,
+                                     const float* values, const int* node_off_host, int B, float* loss_out, int K,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int dp_csr_linkpred_batch_loss_bwd_w(const float* S, int lds, const int* indptr, const int* indices_local,
+                                     const float* values, const int* indptr_t, const int* indices_t_local,
+                                     const float* values_t, const int* node_off_host, int B, const float* dloss,
+                                     float* dS, int ldds, int accumulate, int K, void* workspace,
+                                     size_t workspace_bytes, void* stream);
 
 /* ================================================================== model-level entry points
  * One call enqueues the whole forward (or backward) of an encoder, so the Python host pays one

@@ -1,0 +1,280 @@
+"""Inputs, fp64 references and derived error bounds of the weighted CSR entries (dp_*_w), shared by
+tests/test_csr_weights_cpu.py (which shows that these inputs tell a bug from rounding) and tests/test_gpu_csr_weights.py.
+
+Every reference is computed in float64 from the DENSE weighted matrix A (A[i, indices[e]] = values[e]) on the fp32 inputs.
+Bounds are a rounding count times the sum of absolute terms, u = 2^-24, counted from the kernels' arithmetic, first order:
+
+  aggregation   out_i = sum_e a_e x_e (+ beta old): a product and an add per stored entry of the row, kept in four
+                partial sums that three adds combine, one more for beta: the longest chain an entry sees is
+                deg / 4 + 2 adds and its product.  Budgeted as (deg + 2) u sum |a||x| (+ |old|).
+  pooling fwd   Ap = S^T (A S): the gather as above, then a contraction over the n rows on the fp32 matrix cores
+                (exact products), slab partials added in slab order: (n + deg + 8) u |S|^T |A| |S|; Xp: (n + 8) u.
+  pooling bwd   dS = [A S | A^T S | Z] Wcat: gather, then a contraction over 2K + D columns (Wcat of an undirected
+                graph adds dAp^T + dAp first): (deg + 2K + D + 8) u of the absolute terms; dZ = old + S dXp: (K + 4) u.
+  link loss     p = <s_i, s_j> carries (K + 1) u p (S >= 0); 1 - p + eps and p + eps round once each; logf is good to
+                2 u of its value.  d(-log(1 - p + eps)) <= ((K + 4) u p + 2 u) / (1 - p + eps) + 4 u |log|, likewise
+                for log(p + eps); the weight multiplies once and the four-term fp32 sum adds three roundings; every
+                further sum is fp64.  The coefficient of the backward, c = -1/(p + eps) - 1/(1 - p + eps), moves by
+                (K + 4) u [p / (p + eps)^2 + (p + 1) / (1 - p + eps)^2] + 4 u |c|, and the row sums over n terms
+                (dense part, matrix cores) or deg terms (edge part) add (n + 8) u / (deg + 8) u of their absolute terms.
+  Frobenius     the bounds of tests/frob_link_cases.py with two roundings per stored entry in W (a product and an add):
+                C_FWD = 2 D + 4, C_BWD = max(K, 2 D) + 4.
+  GCN layer     z = ax W + b over Fin terms, y = z / |z| (a sum of Fout squares, rsqrt to 2 u), and the backward
+                dU = inv (dy - y <y, dy>), dW = ax^T dU, db = 1^T dU, dax = dU W^T, dx = A^T dax (+ dax): each stage's
+                rounding count times its absolute terms plus the incoming error pushed through the absolute operator.
+"""
+import numpy as np
+import torch
+
+from graph_pooling_amd.sparse import CsrBatch, CsrGraph
+
+U = 2.0 ** -24
+EPS = 1e-7
+AGG_DEGREES = (0, 1, 3, 4, 5, 63, 64, 65, 129)
+AGG_FEATS = (1, 63, 64, 65, 130)
+BATCH_SIZES = [1, 37, 64, 130]
+LINK_K = (1, 7, 50, 64, 128, 256)
+GRID_WEIGHTS = np.array([0.25, 0.5, 1.0, 2.0], dtype=np.float32)
+
+
+# ------------------------------------------------------------------ graphs
+def _weights(rng, m, grid):
+    if grid:
+        return GRID_WEIGHTS[rng.integers(0, 4, m)]
+    w = rng.uniform(0.1, 2.0, m).astype(np.float32)
+    if m > 4:
+        w[rng.integers(0, m)] = 0.0                      # a stored zero
+    return w
+
+
+def edges(n, deg, seed, directed, grid=False):
+    """Random weighted edge list without self loops or repeats (n > 1); node 0 keeps no edge when n > 2.  Undirected:
+    one weight per unordered pair."""
+    if n == 1:
+        return np.array([0]), np.array([0]), np.array([0.5 if grid else 0.7], dtype=np.float32)
+    rng = np.random.default_rng(seed)
+    lo = 1 if n > 2 else 0
+    src, dst = rng.integers(lo, n, n * deg), rng.integers(lo, n, n * deg)
+    keep = src != dst
+    src, dst = src[keep], dst[keep]
+    if not directed:
+        src, dst = np.minimum(src, dst), np.maximum(src, dst)
+    _, first = np.unique(src * n + dst, return_index=True)
+    src, dst = src[first], dst[first]
+    return src, dst, _weights(rng, src.size, grid)
+
+
+def graph(n, deg, seed, directed, grid=False, device="cpu"):
+    src, dst, w = edges(n, deg, seed, directed, grid)
+    return CsrGraph.from_edges(n, src, dst, device, symmetric=not directed, weight=w)
+
+
+def agg_graph(grid=False, device="cpu"):
+    """Directed graph of 160 nodes whose rows 0 .. 8 have AGG_DEGREES stored entries (the 64-id chunk and the 4-way
+    unroll of k_csr_agg_fwd); the other rows 0 .. 6."""
+    n = 160
+    rng = np.random.default_rng(7)
+    src, dst = [], []
+    for r in range(n):
+        d = AGG_DEGREES[r] if r < len(AGG_DEGREES) else int(rng.integers(0, 7))
+        src.append(np.full(d, r))
+        dst.append(rng.choice(n, d, replace=False))
+    src, dst = np.concatenate(src), np.concatenate(dst)
+    return CsrGraph.from_edges(n, src, dst, device, symmetric=False, weight=_weights(rng, src.size, grid))
+
+
+def batch(sizes, deg, seed, directed, grid=False, device="cpu", pad_to=None):
+    srcs, dsts, ws = zip(*[edges(n, deg, seed + 31 * b, directed, grid) if n > 1 else
+                           (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32))
+                           for b, n in enumerate(sizes)])
+    return CsrBatch.from_edge_lists(sizes, srcs, dsts, device, symmetric=not directed, pad_to=pad_to, weights=ws)
+
+
+def to_device(g, device):
+    """The same container on another device (index identity of an undirected graph kept)."""
+    import copy
+    new = copy.copy(g)
+    moved = {}
+    for name in ("indptr", "indices", "indices_local", "values", "indptr_t", "indices_t", "indices_t_local", "values_t",
+                 "node_off", "order", "cnt", "floor_flag", "seg_tab", "seg_off"):
+        t = getattr(g, name, None)
+        if isinstance(t, torch.Tensor):
+            if id(t) not in moved:
+                moved[id(t)] = t.to(device)
+            setattr(new, name, moved[id(t)])
+    if hasattr(new, "device"):
+        new.device = torch.device(device)
+        new._pool_plans = {}
+    return new
+
+
+def rows_of(g):
+    ip = g.indptr.cpu().numpy().astype(np.int64)
+    return np.repeat(np.arange(ip.size - 1), np.diff(ip))
+
+
+def dense(g, values=None, transposed=False):
+    """float64 [n, n] of the stored entries (a CsrBatch: the block-diagonal matrix).  `values`: other values in the order
+    of the container's; transposed: read the CSR of A^T back into A's orientation."""
+    ip = (g.indptr_t if transposed else g.indptr).cpu().numpy().astype(np.int64)
+    ix = (g.indices_t if transposed else g.indices).cpu().numpy().astype(np.int64)[:ip[-1]]
+    if values is None:
+        values = (g.values_t if transposed else g.values).cpu().numpy()
+    r = np.repeat(np.arange(ip.size - 1), np.diff(ip))
+    a = np.zeros((g.n, g.n), dtype=np.float64)
+    a[r, ix] = np.asarray(values, dtype=np.float64)[:ip[-1]]
+    return a.T if transposed else a
+
+
+def faulty(g):
+    """Dense matrices a buggy kernel would compute with: weights ignored, one weight dropped, and — where the graph has a
+    transposed CSR of its own — `values` read in the order of the transposed CSR."""
+    nnz = int(g.indptr.cpu()[-1])
+    v = g.values.cpu().numpy()[:nnz]
+    out = {"weights ignored": dense(g, np.ones(nnz))}
+    e = int(np.argmax(np.abs(v)))
+    drop = v.copy()
+    drop[e] = 1.0 if v[e] != 1.0 else 0.0                # the entry read as a 0/1 entry
+    out["one weight dropped"] = dense(g, drop)
+    if g.indices_t is not g.indices:
+        out["values in transposed order"] = dense(g, g.values_t.cpu().numpy()[:nnz])
+    return out
+
+
+def degrees(a_or_g):
+    """Stored entries per row of a container."""
+    return np.diff(a_or_g.indptr.cpu().numpy().astype(np.int64))
+
+
+# ------------------------------------------------------------------ aggregation
+def agg_ref(a, x, old=None, beta=0.0, deg=None):
+    x = np.asarray(x, dtype=np.float64)
+    ref = a @ x
+    mag = np.abs(a) @ np.abs(x)
+    if beta:
+        ref = ref + beta * old
+        mag = mag + np.abs(beta * old)
+    return ref, (deg[:, None] + 2 + (1 if beta else 0)) * U * mag
+
+
+# ------------------------------------------------------------------ pooling
+def pool_ref(a, S, Z, dXp, dAp, dz_old, deg, deg_t):
+    S, Z, dXp, dAp = (np.asarray(t, dtype=np.float64) for t in (S, Z, dXp, dAp))
+    n, K = S.shape
+    D = Z.shape[1]
+    aS, atS = a @ S, a.T @ S
+    aa, sa = np.abs(a), np.abs(S)
+    dmax = int(max(deg.max(), deg_t.max())) if n else 0
+    ref = dict(Xp=S.T @ Z, Ap=S.T @ aS, dS=aS @ dAp.T + atS @ dAp + Z @ dXp.T, dZ=dz_old + S @ dXp)
+    bound = dict(Xp=(n + 8) * U * (sa.T @ np.abs(Z)), Ap=(n + dmax + 8) * U * (sa.T @ (aa @ sa)),
+                 dS=(dmax + 2 * K + D + 8) * U * ((aa @ sa) @ np.abs(dAp).T + (aa.T @ sa) @ np.abs(dAp)
+                                                 + np.abs(Z) @ np.abs(dXp).T),
+                 dZ=(K + 4) * U * (np.abs(dz_old) + sa @ np.abs(dXp)))
+    return ref, bound
+
+
+# ------------------------------------------------------------------ link loss (one graph; a batch sums the graphs)
+def link_terms(a, S, deg, deg_t):
+    """(sum of the n^2 terms, bound of that sum, d sum / dS, its bound) in float64 for one graph."""
+    S = np.asarray(S, dtype=np.float64)
+    n, K = S.shape
+    p = np.minimum(S @ S.T, 1.0)
+    gate = (S @ S.T <= 1.0).astype(np.float64)
+    lp, lq = np.log(p + EPS), np.log(1.0 - p + EPS)
+    tot = float((-a * lp - (1.0 - a) * lq).sum())
+    dq = ((K + 4) * U * p + 2 * U) / (1.0 - p + EPS) + 4 * U * np.abs(lq)
+    dp_ = ((K + 4) * U * p + 2 * U) / (p + EPS) + 4 * U * np.abs(lp)
+    aa = np.abs(a)
+    bt = float((dq + aa * (dq + dp_ + 4 * U * (np.abs(lp) + np.abs(lq)))).sum())
+    # gradient: d/dp of the dense term g' = 1 / (1 - p + eps), of the edge term c = -1/(p + eps) - 1/(1 - p + eps)
+    g1 = gate / (1.0 - p + EPS)
+    c = gate * (-1.0 / (p + EPS) - 1.0 / (1.0 - p + EPS))
+    coef = g1 + a * c
+    dS = (coef + coef.T) @ S
+    dg = (K + 4) * U * (p + 1.0) / (1.0 - p + EPS) ** 2 + 4 * U * g1
+    dc = (K + 4) * U * (p / (p + EPS) ** 2 + (p + 1.0) / (1.0 - p + EPS) ** 2) + 4 * U * np.abs(c)
+    dmax = int(max(deg.max(), deg_t.max())) if n else 0
+    bS = 2.0 * (dg + (n + K + 8) * U * g1) @ S
+    edge = aa * (dc + (dmax + 8) * U * np.abs(c))
+    bS = bS + (edge + edge.T) @ S
+    return tot, bt, dS, bS
+
+
+def link_ref(graphs, dloss=1.0):
+    """graphs: [(a, S, deg, deg_t)] -> dict(loss, loss_bound, dS [n_total, K], dS_bound)."""
+    terms = [link_terms(*g) for g in graphs]
+    nn = float(sum(g[1].shape[0] ** 2 for g in graphs))
+    loss = sum(t[0] for t in terms) / nn
+    dS = np.concatenate([t[2] for t in terms]) * dloss / nn
+    bS = np.concatenate([t[3] for t in terms]) * abs(dloss) / nn
+    return dict(loss=loss, loss_bound=sum(t[1] for t in terms) / nn + U * abs(loss), dS=dS,
+                dS_bound=bS + 3 * U * np.abs(dS))
+
+
+# ------------------------------------------------------------------ Frobenius link loss
+def frob_ref(graphs):
+    """graphs: [(a float64 [n_b, n_b], S)] -> tests/frob_link_cases.batch_ref with this file's rounding counts."""
+    from tests import frob_link_cases as FC
+    ref = FC.batch_ref([(a, np.asarray(s)) for a, s in graphs])
+    K = graphs[0][1].shape[1]
+    ref["loss_bound"] = (2 * ref["D"] + 4.0) * U * ref["mag"]
+    ref["dS_bound"] = np.concatenate([(max(K, 2 * ref["D"]) + 4.0) * U * m for m in ref["dmag"]])
+    ref["dS_all"] = np.concatenate(ref["dS"])
+    return ref
+
+
+# ------------------------------------------------------------------ sparse GCN layer
+def gcn_ref(a, x, W, b, dy, add_self, normalize, deg, deg_t, scatter):
+    """Forward y, ax and backward dx, dW, db of y = l2norm((A x [+ x]) W + b) in float64 with bounds (see the module
+    docstring): dict name -> (reference, bound)."""
+    x, W, b, dy = (np.asarray(t, dtype=np.float64) for t in (x, W, b, dy))
+    n, Fin = x.shape
+    Fout = W.shape[1]
+    aa = np.abs(a)
+    dcol = (deg[:, None] + 3) * U
+    ax = a @ x + (x if add_self else 0.0)
+    m_ax = aa @ np.abs(x) + (np.abs(x) if add_self else 0.0)
+    e_ax = dcol * m_ax
+    z = ax @ W + b
+    e_z = (Fin + 3) * U * (np.abs(ax) @ np.abs(W) + np.abs(b)) + e_ax @ np.abs(W)
+    if normalize:
+        nrm = np.maximum(np.sqrt((z * z).sum(axis=1, keepdims=True)), 1e-12)
+        inv = 1.0 / nrm
+        y = z * inv
+        rel = (Fout + 6) * U + np.sqrt((e_z * e_z).sum(axis=1, keepdims=True)) * inv      # of inv
+        e_y = e_z * inv + np.abs(y) * rel + 2 * U * np.abs(y)
+        ydy = (y * dy).sum(axis=1, keepdims=True)
+        dU = inv * (dy - y * ydy)
+        m_dU = inv * (np.abs(dy) + np.abs(y) * (np.abs(y) * np.abs(dy)).sum(axis=1, keepdims=True))
+        e_ydy = (Fout + 2) * U * (np.abs(y) * np.abs(dy)).sum(axis=1, keepdims=True) \
+            + (e_y * np.abs(dy)).sum(axis=1, keepdims=True)
+        e_dU = (6 * U + rel) * m_dU + inv * (e_y * np.abs(ydy) + np.abs(y) * e_ydy)
+    else:
+        y, e_y, dU = z, e_z, dy
+        e_dU = np.zeros_like(dy)
+    dW = ax.T @ dU
+    e_dW = (n + 4) * U * (np.abs(ax).T @ np.abs(dU)) + e_ax.T @ np.abs(dU) + np.abs(ax).T @ e_dU
+    db = dU.sum(axis=0)
+    e_db = (n + 4) * U * np.abs(dU).sum(axis=0) + e_dU.sum(axis=0)
+    dax = dU @ W.T
+    e_dax = (Fout + 3) * U * (np.abs(dU) @ np.abs(W).T) + e_dU @ np.abs(W).T
+    dx = a.T @ dax + (dax if add_self else 0.0)
+    # the gather over A^T sums deg_t terms per row; the scatter adds them by float atomics in any order: the same count
+    cnt = (deg_t[:, None] + 4) * U
+    e_dx = cnt * (aa.T @ np.abs(dax) + (np.abs(dax) if add_self else 0.0)) + aa.T @ e_dax + (e_dax if add_self else 0.0)
+    return dict(ax=(ax, e_ax), y=(y, e_y), dW=(dW, e_dW), db=(db, e_db), dx=(dx, e_dx))
+
+
+def assign_rows(rng, rows, K):
+    """Assignment rows for the link losses: a softmax of N(0, 1) logits; K = 1 (where a softmax is the constant 1, p = 1
+    and 1 / (1 - p + eps) = 1e7 makes any fp32 evaluation meaningless) takes rows uniform in (0.2, 0.8)."""
+    if K == 1:
+        return rng.uniform(0.2, 0.8, (rows, 1)).astype(np.float32)
+    return softmax_rows(rng, rows, K, 1.0)
+
+
+def softmax_rows(rng, rows, K, scale=2.0):
+    z = rng.standard_normal((rows, K)) * scale
+    z -= z.max(axis=1, keepdims=True)
+    e = np.exp(z)
+    return (e / e.sum(axis=1, keepdims=True)).astype(np.float32)
