@@ -132,6 +132,24 @@ def _weighted(graph):
     return bool(getattr(graph, "weighted", False))
 
 
+def _csr_args(g, local=False, null_t=False):
+    """How every CSR entry takes the adjacency of a CsrGraph / CsrBatch `g`: (entry-name suffix, (indptr, indices
+    [, values]), (indptr_t, indices_t [, values_t])) as device pointers — the values and the suffix of the weighted
+    entry when `g` stores values.  `local`: the graph-local index arrays of a CsrBatch (link loss).  `null_t`: NULL for
+    the transposed group of an undirected container (the Frobenius entries then skip the A^T S gather)."""
+    ix, ix_t = (g.indices_local, g.indices_t_local) if local else (g.indices, g.indices_t)
+    null = null_t and g.indptr_t is g.indptr and g.indices_t is g.indices
+    if _weighted(g):
+        return ("_w", (g.indptr.data_ptr(), ix.data_ptr(), g.values.data_ptr()),
+                (None, None, None) if null else (g.indptr_t.data_ptr(), ix_t.data_ptr(), g.values_t.data_ptr()))
+    return "", (g.indptr.data_ptr(), ix.data_ptr()), (None, None) if null else (g.indptr_t.data_ptr(), ix_t.data_ptr())
+
+
+def _call(lib, name, *args):
+    """Call the C entry `name` and raise on a non-zero return code."""
+    _lib.check(getattr(lib, name)(*args), name)
+
+
 class _CsrGraphConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, g, flags):
@@ -144,14 +162,9 @@ class _CsrGraphConvFn(torch.autograd.Function):
         y, ax, invn = _f32(x, n, fout), _f32(x, n, fin), _f32(x, n)
         wsb = lib.dp_sparse_gcn_layer_workspace_bytes(n, fin, fout)
         ws = _workspace(wsb, x)
-        tail = (w.data_ptr(), _lib.ptr(bias), y.data_ptr(), fout, ax.data_ptr(), invn.data_ptr(), n, fin, fout, flags,
-                ws.data_ptr(), wsb, _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_sparse_gcn_layer_fwd_w(x.data_ptr(), fin, g.indptr.data_ptr(), g.indices.data_ptr(),
-                                                     g.values.data_ptr(), *tail), "dp_sparse_gcn_layer_fwd_w")
-        else:
-            _lib.check(lib.dp_sparse_gcn_layer_fwd(x.data_ptr(), fin, g.indptr.data_ptr(), g.indices.data_ptr(), *tail),
-                       "dp_sparse_gcn_layer_fwd")
+        sfx, a, _ = _csr_args(g)
+        _call(lib, "dp_sparse_gcn_layer_fwd" + sfx, x.data_ptr(), fin, *a, w.data_ptr(), _lib.ptr(bias), y.data_ptr(),
+              fout, ax.data_ptr(), invn.data_ptr(), n, fin, fout, flags, ws.data_ptr(), wsb, _lib.current_stream())
         ctx.save_for_backward(ax, w, y, invn)
         ctx.g, ctx.flags, ctx.ws, ctx.has_bias = g, flags, ws, bias is not None
         return y
@@ -167,16 +180,10 @@ class _CsrGraphConvFn(torch.autograd.Function):
         dx = torch.empty_like(ax) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w)
         db = _f32(ax, fout) if ctx.has_bias else None
-        tail = (w.data_ptr(), y.data_ptr(), fout, invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin, dw.data_ptr(),
-                _lib.ptr(db), n, fin, fout, ctx.flags, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_sparse_gcn_layer_bwd_w(ax.data_ptr(), g.indptr.data_ptr(), g.indices.data_ptr(),
-                                                     g.values.data_ptr(), g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
-                                                     g.values_t.data_ptr(), *tail), "dp_sparse_gcn_layer_bwd_w")
-        else:
-            _lib.check(lib.dp_sparse_gcn_layer_bwd(ax.data_ptr(), g.indptr.data_ptr(), g.indices.data_ptr(),
-                                                   g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
-                       "dp_sparse_gcn_layer_bwd")
+        sfx, a, at = _csr_args(g)
+        _call(lib, "dp_sparse_gcn_layer_bwd" + sfx, ax.data_ptr(), *a, *at, w.data_ptr(), y.data_ptr(), fout,
+              invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin, dw.data_ptr(), _lib.ptr(db), n, fin, fout,
+              ctx.flags, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
         return dx, dw, db, None, None
 
 
@@ -314,12 +321,9 @@ class _CsrPoolFn(torch.autograd.Function):
         xp, ap = _f32(s, k, d), _f32(s, k, k)
         wsb = lib.dp_csr_pool_workspace_bytes(n, k, d)
         ws = _workspace(wsb, s)
-        head = (s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr())
-        tail = (xp.data_ptr(), ap.data_ptr(), n, k, d, ws.data_ptr(), wsb, _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_csr_pool_fwd_w(*head, g.values.data_ptr(), *tail), "dp_csr_pool_fwd_w")
-        else:
-            _lib.check(lib.dp_csr_pool_fwd(*head, *tail), "dp_csr_pool_fwd")
+        sfx, a, _ = _csr_args(g)
+        _call(lib, "dp_csr_pool_fwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, xp.data_ptr(), ap.data_ptr(), n, k, d,
+              ws.data_ptr(), wsb, _lib.current_stream())
         ctx.save_for_backward(s, z)
         ctx.g, ctx.ws = g, ws
         return xp, ap
@@ -334,15 +338,9 @@ class _CsrPoolFn(torch.autograd.Function):
         dxp, dap = dxp.contiguous(), dap.contiguous()
         ds = torch.empty_like(s)
         dz = torch.zeros_like(z)
-        head = (s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr())
-        tail = (dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d, n, k, d, ctx.ws.data_ptr(),
-                ctx.ws.numel(), _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_csr_pool_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
-                                             g.values_t.data_ptr(), *tail), "dp_csr_pool_bwd_w")
-        else:
-            _lib.check(lib.dp_csr_pool_bwd(*head, g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
-                       "dp_csr_pool_bwd")
+        sfx, a, at = _csr_args(g)
+        _call(lib, "dp_csr_pool_bwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, *at, dxp.data_ptr(), dap.data_ptr(),
+              ds.data_ptr(), k, dz.data_ptr(), d, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
         return ds, dz, None
 
 
@@ -663,13 +661,10 @@ class _CsrPoolBatchFn(torch.autograd.Function):
         xp, ap = _f32(s, b, k, d), _f32(s, b, k, k)
         wsb = lib.dp_csr_pool_batch_workspace_bytes(plan.n_slabs, b, k, d)
         ws = _workspace(wsb, s)
-        head = (s.data_ptr(), k, z.data_ptr(), d, batch.indptr.data_ptr(), batch.indices.data_ptr())
-        tail = (plan.fwd_tab.data_ptr(), plan.slab_off.data_ptr(), plan.n_slabs, xp.data_ptr(), ap.data_ptr(), b, n, k, d,
-                ws.data_ptr(), wsb, _lib.current_stream())
-        if _weighted(batch):
-            _lib.check(lib.dp_csr_pool_batch_fwd_w(*head, batch.values.data_ptr(), *tail), "dp_csr_pool_batch_fwd_w")
-        else:
-            _lib.check(lib.dp_csr_pool_batch_fwd(*head, *tail), "dp_csr_pool_batch_fwd")
+        sfx, a, _ = _csr_args(batch)
+        _call(lib, "dp_csr_pool_batch_fwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, plan.fwd_tab.data_ptr(),
+              plan.slab_off.data_ptr(), plan.n_slabs, xp.data_ptr(), ap.data_ptr(), b, n, k, d, ws.data_ptr(), wsb,
+              _lib.current_stream())
         ctx.save_for_backward(s, z)
         ctx.batch, ctx.plan, ctx.ws = batch, plan, ws
         return xp, ap
@@ -684,16 +679,10 @@ class _CsrPoolBatchFn(torch.autograd.Function):
         dxp, dap = dxp.contiguous(), dap.contiguous()
         ds = torch.empty_like(s)
         dz = torch.zeros_like(z)
-        head = (s.data_ptr(), k, z.data_ptr(), d, g.indptr.data_ptr(), g.indices.data_ptr())
-        tail = (plan.bwd_tab.data_ptr(), plan.n_blocks, dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d,
-                g.num_graphs, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_csr_pool_batch_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(),
-                                                   g.indices_t.data_ptr(), g.values_t.data_ptr(), *tail),
-                       "dp_csr_pool_batch_bwd_w")
-        else:
-            _lib.check(lib.dp_csr_pool_batch_bwd(*head, g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
-                       "dp_csr_pool_batch_bwd")
+        sfx, a, at = _csr_args(g)
+        _call(lib, "dp_csr_pool_batch_bwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, *at, plan.bwd_tab.data_ptr(),
+              plan.n_blocks, dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d, g.num_graphs, n, k, d,
+              ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
         return ds, dz, None
 
 
@@ -714,13 +703,9 @@ class _CsrLinkLossBatchFn(torch.autograd.Function):
         loss = _f32(s, ())
         wsb = lib.dp_csr_linkpred_batch_workspace_bytes(off, g.num_graphs, k)
         ws = _workspace(wsb, s)
-        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr())
-        tail = (off, g.num_graphs, loss.data_ptr(), k, ws.data_ptr(), wsb, _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_csr_linkpred_batch_loss_fwd_w(*head, g.values.data_ptr(), *tail),
-                       "dp_csr_linkpred_batch_loss_fwd_w")
-        else:
-            _lib.check(lib.dp_csr_linkpred_batch_loss_fwd(*head, *tail), "dp_csr_linkpred_batch_loss_fwd")
+        sfx, a, _ = _csr_args(g, local=True)
+        _call(lib, "dp_csr_linkpred_batch_loss_fwd" + sfx, s.data_ptr(), k, *a, off, g.num_graphs, loss.data_ptr(), k,
+              ws.data_ptr(), wsb, _lib.current_stream())
         ctx.save_for_backward(s)
         ctx.g, ctx.ws = g, ws
         return loss
@@ -733,16 +718,10 @@ class _CsrLinkLossBatchFn(torch.autograd.Function):
         n, k = s.shape
         dloss = dloss.contiguous().float()
         ds = torch.empty_like(s)
-        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices_local.data_ptr())
-        tail = (g.node_off_host.ctypes.data, g.num_graphs, dloss.data_ptr(), ds.data_ptr(), k, 0, k, ctx.ws.data_ptr(),
-                ctx.ws.numel(), _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_csr_linkpred_batch_loss_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(),
-                                                            g.indices_t_local.data_ptr(), g.values_t.data_ptr(), *tail),
-                       "dp_csr_linkpred_batch_loss_bwd_w")
-        else:
-            _lib.check(lib.dp_csr_linkpred_batch_loss_bwd(*head, g.indptr_t.data_ptr(), g.indices_t_local.data_ptr(),
-                                                          *tail), "dp_csr_linkpred_batch_loss_bwd")
+        sfx, a, at = _csr_args(g, local=True)
+        _call(lib, "dp_csr_linkpred_batch_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, g.node_off_host.ctypes.data,
+              g.num_graphs, dloss.data_ptr(), ds.data_ptr(), k, 0, k, ctx.ws.data_ptr(), ctx.ws.numel(),
+              _lib.current_stream())
         return ds, None
 
 
@@ -753,18 +732,6 @@ def csr_link_loss_batch(s, batch):
 
 
 # ----------------------------------------------------------------------------- Set2Set on ragged rows
-def _s2s_offsets(graph):
-    """(node_off on the device, address of node_off_host, B, T) of a CsrBatch, or of a CsrGraph as the batch of one
-    without padding (its two-entry offset table is made once and kept on the graph)."""
-    if hasattr(graph, "node_off_host"):
-        return graph.node_off, graph.node_off_host.ctypes.data, graph.num_graphs, graph.pad_to
-    cached = getattr(graph, "_s2s_off", None)
-    if cached is None:
-        host = torch.tensor([0, graph.n], dtype=torch.int32)
-        cached = graph._s2s_off = (host.to(graph.indptr.device), host)
-    return cached[0], cached[1].data_ptr(), 1, graph.n
-
-
 class _Set2SetRaggedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, emb, graph, keep, w_ih, w_hh, b_ih, b_hh, wp, bp):
@@ -772,7 +739,7 @@ class _Set2SetRaggedFn(torch.autograd.Function):
         _lib.require_gpu_tensor(emb, "embedding")
         emb = emb.contiguous().float()
         n_total, d = emb.shape
-        off, off_host, nb, t = _s2s_offsets(graph)
+        off, off_host, nb, t = graph.node_off, graph.node_off_host.ctypes.data, graph.num_graphs, graph.pad_to
         ts = [p.contiguous() for p in (w_ih, w_hh, b_ih, b_hh, wp, bp)]
         out = _f32(emb, nb, d)
         sb = lib.dp_set2set_ragged_save_bytes(off_host, nb, t, d) if keep else 0
@@ -793,7 +760,7 @@ class _Set2SetRaggedFn(torch.autograd.Function):
             raise RuntimeError("set2set_ragged: the forward ran without a save buffer (torch.no_grad()), there is "
                                "nothing to differentiate")
         n_total, d = emb.shape
-        off, off_host, nb, t = _s2s_offsets(graph)
+        off, off_host, nb, t = graph.node_off, graph.node_off_host.ctypes.data, graph.num_graphs, graph.pad_to
         dout = dout.contiguous().float()
         demb = torch.empty_like(emb)
         grads = [torch.empty_like(p) for p in (w_ih, w_hh, b_ih, b_hh, wp, bp)]
@@ -861,12 +828,9 @@ class _CsrLinkLossFn(torch.autograd.Function):
         loss = _f32(s, ())
         wsb = lib.dp_csr_linkpred_workspace_bytes(n, k)
         ws = _workspace(wsb, s)
-        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr())
-        tail = (loss.data_ptr(), n, k, ws.data_ptr(), wsb, _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_csr_linkpred_loss_fwd_w(*head, g.values.data_ptr(), *tail), "dp_csr_linkpred_loss_fwd_w")
-        else:
-            _lib.check(lib.dp_csr_linkpred_loss_fwd(*head, *tail), "dp_csr_linkpred_loss_fwd")
+        sfx, a, _ = _csr_args(g)
+        _call(lib, "dp_csr_linkpred_loss_fwd" + sfx, s.data_ptr(), k, *a, loss.data_ptr(), n, k, ws.data_ptr(), wsb,
+              _lib.current_stream())
         ctx.save_for_backward(s)
         ctx.g, ctx.ws = g, ws
         return loss
@@ -879,15 +843,9 @@ class _CsrLinkLossFn(torch.autograd.Function):
         n, k = s.shape
         dloss = dloss.contiguous().float()
         ds = torch.empty_like(s)
-        head = (s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr())
-        tail = (dloss.data_ptr(), ds.data_ptr(), k, 0, n, k, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        if _weighted(g):
-            _lib.check(lib.dp_csr_linkpred_loss_bwd_w(*head, g.values.data_ptr(), g.indptr_t.data_ptr(),
-                                                      g.indices_t.data_ptr(), g.values_t.data_ptr(), *tail),
-                       "dp_csr_linkpred_loss_bwd_w")
-        else:
-            _lib.check(lib.dp_csr_linkpred_loss_bwd(*head, g.indptr_t.data_ptr(), g.indices_t.data_ptr(), *tail),
-                       "dp_csr_linkpred_loss_bwd")
+        sfx, a, at = _csr_args(g)
+        _call(lib, "dp_csr_linkpred_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, dloss.data_ptr(), ds.data_ptr(), k, 0, n,
+              k, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
         return ds, None
 
 
@@ -979,24 +937,17 @@ class _FrobLinkFn(torch.autograd.Function):
         else:
             n = s.shape[0]
             b = adj.num_graphs if kind == "batch" else 1
-            directed = not (adj.indptr_t is adj.indptr and adj.indices_t is adj.indices)
             wsb = lib.dp_csr_frob_link_workspace_bytes(n, b, k)
             ws = _workspace(wsb, s)
             w, g = torch.empty_like(s), _f32(s, (b, k, k))
-            wt = _weighted(adj)
-            csr = (s.data_ptr(), k, adj.indptr.data_ptr(), adj.indices.data_ptr()) + \
-                ((adj.values.data_ptr(),) if wt else ()) + \
-                (adj.indptr_t.data_ptr() if directed else None, adj.indices_t.data_ptr() if directed else None) + \
-                ((adj.values_t.data_ptr() if directed else None,) if wt else ())
+            sfx, a, at = _csr_args(adj, null_t=True)
             if kind == "batch":
-                fn = lib.dp_csr_frob_link_batch_fwd_w if wt else lib.dp_csr_frob_link_batch_fwd
-                _lib.check(fn(*csr, adj.node_off.data_ptr(), None, w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, b,
-                              n, k, ws.data_ptr(), wsb, st), "dp_csr_frob_link_batch_fwd" + "_w" * wt)
+                _call(lib, "dp_csr_frob_link_batch_fwd" + sfx, s.data_ptr(), k, *a, *at, adj.node_off.data_ptr(), None,
+                      w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, b, n, k, ws.data_ptr(), wsb, st)
             else:
-                fn = lib.dp_csr_frob_link_fwd_w if wt else lib.dp_csr_frob_link_fwd
-                _lib.check(fn(*csr, None, w.data_ptr(), g.data_ptr(), loss.data_ptr(), None, n, k, ws.data_ptr(), wsb,
-                              st), "dp_csr_frob_link_fwd" + "_w" * wt)
-            ctx.sym = 0 if directed else 1
+                _call(lib, "dp_csr_frob_link_fwd" + sfx, s.data_ptr(), k, *a, *at, None, w.data_ptr(), g.data_ptr(),
+                      loss.data_ptr(), None, n, k, ws.data_ptr(), wsb, st)
+            ctx.sym = int(at[0] is None)          # an undirected container: W = A S
         ctx.save_for_backward(s, w, g)
         ctx.kind, ctx.num_nodes, ctx.adj, ctx.b = kind, num_nodes, adj if kind == "batch" else None, b
         return loss
@@ -1061,4 +1012,4 @@ def frob_link_loss(s, adj, num_nodes=None):
         raise TypeError(f"frob_link_loss: s [n, K] goes with a CsrGraph or a CsrBatch, got {type(adj).__name__}")
     if adj.n != s.shape[0]:
         raise ValueError(f"frob_link_loss: the {adj.ARG} has n = {adj.n} rows but s has {s.shape[0]}")
-    return _FrobLinkFn.apply(s, adj, None, "batch" if hasattr(adj, "node_off") else "csr")
+    return _FrobLinkFn.apply(s, adj, None, "batch" if hasattr(adj, "indices_local") else "csr")

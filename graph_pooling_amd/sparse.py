@@ -35,6 +35,10 @@ behind a CsrGraph.
 """
 from __future__ import annotations
 
+import copy
+from functools import cached_property
+from typing import Any, NamedTuple
+
 import numpy as np
 import torch
 
@@ -58,21 +62,90 @@ def _check_values(values, indices, what):
     return values.contiguous()
 
 
-def _inv_sqrt_degree(n, cols, vals, what):
-    """1 / sqrt(column sum of the stored values), in float64 (graph_sampler.py:27: np.sum(adj, axis=0)); a node of
-    degree 0 raises — the reference's inf * 0 = NaN row has no place in a CSR."""
+class HostCsr(NamedTuple):
+    """One graph's CSR as host arrays with graph-local columns — the per-graph record of `CsrBatch.__init__`, and what
+    the containers' host code passes around.  The transposed trio is None for an undirected graph, `values` /
+    `values_t` (one per stored entry, next to `indices` / `indices_t`) None for a 0/1 graph."""
+    indptr: Any
+    indices: Any
+    indptr_t: Any = None
+    indices_t: Any = None
+    values: Any = None
+    values_t: Any = None
+
+
+def _host_csr(n, src, dst, symmetric=True, weight=None):
+    """The host part of `CsrGraph.from_edges`: edge list -> HostCsr (int32 indices sorted by row then column, duplicates
+    merged, fp32 values), raising on an entry given with two weights."""
+    src, dst = np.asarray(src, dtype=np.int64).reshape(-1), np.asarray(dst, dtype=np.int64).reshape(-1)
+    w = None
+    if weight is not None:
+        w = np.asarray(weight, dtype=np.float32).reshape(-1)
+        if w.size != src.size:
+            raise ValueError(f"CsrGraph.from_edges: {w.size} weights for {src.size} edges")
+    if symmetric:
+        src, dst = np.concatenate([src, dst]), np.concatenate([dst, src])
+        if w is not None:
+            w = np.concatenate([w, w])
+    if w is None:
+        key = np.unique(src * n + dst)
+    else:
+        order = np.argsort(src * n + dst, kind="stable")
+        key, w = (src * n + dst)[order], w[order]
+        first = np.ones(key.size, dtype=bool)
+        first[1:] = key[1:] != key[:-1]
+        head = np.maximum.accumulate(np.where(first, np.arange(key.size), 0))     # first entry of each run
+        clash = np.nonzero(w != w[head])[0]
+        if clash.size:
+            e = int(clash[0])
+            raise ValueError(f"CsrGraph.from_edges: entry ({int(key[e] // n)}, {int(key[e] % n)}) is given with two "
+                             f"weights ({w[head[e]]:g} and {w[e]:g})")
+        key, w = key[first], w[first]
+    rows, cols = key // n, key % n
+
+    def csr(r, c):
+        order = np.lexsort((c, r))
+        r, c = r[order], c[order]
+        indptr = np.zeros(n + 1, dtype=np.int32)
+        np.add.at(indptr, r + 1, 1)
+        return (np.cumsum(indptr, dtype=np.int64).astype(np.int32), c.astype(np.int32),
+                None if w is None else np.ascontiguousarray(w[order]))
+    (ip, ix, val), (ipt, ixt, valt) = csr(rows, cols), (None, None, None) if symmetric else csr(cols, rows)
+    return HostCsr(ip, ix, ipt, ixt, val, valt)
+
+
+def _read_back(g):
+    """A container's CSR read back to the host once -> HostCsr, trimmed to the indptr[-1] stored entries (an edgeless
+    batch pads its arrays)."""
+    def trio(indptr, indices, values):
+        ip = indptr.cpu().numpy()
+        return ip, indices.cpu().numpy()[:ip[-1]], None if values is None else values.cpu().numpy()[:ip[-1]]
+    ip, ix, val = trio(g.indptr, g.indices, g.values)
+    undirected = g.indptr_t is g.indptr and g.indices_t is g.indices
+    ipt, ixt, valt = (None, None, None) if undirected else trio(g.indptr_t, g.indices_t, g.values_t)
+    return HostCsr(ip, ix, ipt, ixt, val, valt)
+
+
+def _normalized_values(n, h, what):
+    """(values, values_t | None), fp32, of D^-1/2 A D^-1/2 for the HostCsr `h` of n nodes.  The degree is the column sum
+    of the stored values (ones for a 0/1 graph) as the reference takes it (graph_sampler.py:27: np.sum(adj, axis=0)), in
+    float64 on the host, rounded once.  A node of degree 0 raises, naming the container `what`: the reference's
+    inf * 0 = NaN row has no place in a CSR."""
+    def rows(indptr):          # the row of every stored entry
+        return np.repeat(np.arange(indptr.size - 1), np.diff(indptr.astype(np.int64)))
+    val = np.ones(h.indices.size) if h.values is None else h.values.astype(np.float64)
     deg = np.zeros(n, dtype=np.float64)
-    np.add.at(deg, cols, vals.astype(np.float64))
+    np.add.at(deg, h.indices, val)
     bad = np.nonzero(~(deg > 0))[0]
     if bad.size:
         raise ValueError(f"{what}.normalized(): node {int(bad[0])} has degree {deg[bad[0]]:g} (column sum of the stored "
                          f"values; {bad.size} such node(s)): D^-1/2 A D^-1/2 is not defined there")
-    return 1.0 / np.sqrt(deg)
-
-
-def _csr_rows(indptr, nnz):
-    """Row of every stored entry of a host CSR."""
-    return np.repeat(np.arange(indptr.size - 1, dtype=np.int64), np.diff(indptr.astype(np.int64)))[:nnz]
+    inv = 1.0 / np.sqrt(deg)
+    new = ((val * inv[rows(h.indptr)]) * inv[h.indices]).astype(np.float32)
+    if h.indptr_t is None:
+        return new, None
+    valt = np.ones(val.size) if h.values_t is None else h.values_t.astype(np.float64)
+    return new, ((valt * inv[h.indices_t]) * inv[rows(h.indptr_t)]).astype(np.float32)      # (r, c) of A^T is a_cr
 
 
 class CsrGraph:
@@ -109,6 +182,12 @@ class CsrGraph:
         else:
             self.values_t = _check_values(values_t, self.indices_t, "CsrGraph: values_t")
 
+    # the batch-of-one view (no padding) for the ops that take either container; the offsets are made on first use
+    num_graphs = 1
+    pad_to = property(lambda self: self.n)
+    node_off_host = cached_property(lambda self: np.array([0, self.n], dtype=np.int32))
+    node_off = cached_property(lambda self: torch.from_numpy(self.node_off_host).to(self.indptr.device))
+
     def rows(self):
         return f"[n, F] with n = {self.n}"
 
@@ -136,45 +215,8 @@ class CsrGraph:
         value per edge (mirrored when symmetric; zeros are stored) -> a weighted graph; an (i, j) given twice with two
         different weights — also as (i, j) and (j, i) under symmetric=True — raises, with the same weight it is
         merged."""
-        src, dst = np.asarray(src, dtype=np.int64).reshape(-1), np.asarray(dst, dtype=np.int64).reshape(-1)
-        w = None
-        if weight is not None:
-            w = np.asarray(weight, dtype=np.float32).reshape(-1)
-            if w.size != src.size:
-                raise ValueError(f"CsrGraph.from_edges: {w.size} weights for {src.size} edges")
-        if symmetric:
-            src, dst = np.concatenate([src, dst]), np.concatenate([dst, src])
-            if w is not None:
-                w = np.concatenate([w, w])
-        if w is None:
-            key = np.unique(src * n + dst)
-        else:
-            order = np.argsort(src * n + dst, kind="stable")
-            key, w = (src * n + dst)[order], w[order]
-            first = np.ones(key.size, dtype=bool)
-            first[1:] = key[1:] != key[:-1]
-            head = np.maximum.accumulate(np.where(first, np.arange(key.size), 0))     # first entry of each run
-            clash = np.nonzero(w != w[head])[0]
-            if clash.size:
-                e = int(clash[0])
-                raise ValueError(f"CsrGraph.from_edges: entry ({int(key[e] // n)}, {int(key[e] % n)}) is given with two "
-                                 f"weights ({w[head[e]]:g} and {w[e]:g})")
-            key, w = key[first], w[first]
-        rows, cols = key // n, key % n
-
-        def csr(r, c):
-            order = np.lexsort((c, r))
-            r, c = r[order], c[order]
-            indptr = np.zeros(n + 1, dtype=np.int32)
-            np.add.at(indptr, r + 1, 1)
-            val = None if w is None else torch.from_numpy(np.ascontiguousarray(w[order])).to(device)
-            return (torch.from_numpy(np.cumsum(indptr, dtype=np.int64).astype(np.int32)).to(device),
-                    torch.from_numpy(c.astype(np.int32)).to(device), val)
-        ip, ix, val = csr(rows, cols)
-        if symmetric:
-            return CsrGraph(ip, ix, values=val)
-        ipt, ixt, valt = csr(cols, rows)
-        return CsrGraph(ip, ix, ipt, ixt, val, valt)
+        h = _host_csr(n, src, dst, symmetric, weight)
+        return CsrGraph(*(None if a is None else torch.from_numpy(a).to(device) for a in h))
 
     @staticmethod
     def from_dense(adj, weighted=False):
@@ -189,19 +231,11 @@ class CsrGraph:
         (graph_sampler.py:27-29; `tu_dataset.normalized_adjacency`): the degree is the column sum of the stored values
         (ones for a 0/1 graph), as the reference takes it (axis=0).  Computed once on the host in float64 and rounded
         to fp32; the index arrays are shared.  A node of degree 0 raises ValueError."""
-        ip, ix = self.indptr.cpu().numpy(), self.indices.cpu().numpy().astype(np.int64)
-        nnz = int(ip[-1])
-        val = self.values.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
-        rows, cols = _csr_rows(ip, nnz), ix[:nnz]
-        inv = _inv_sqrt_degree(self.n, cols, val, "CsrGraph")
-        dev = lambda a: torch.from_numpy(a.astype(np.float32)).to(self.indices.device)
-        new = dev((val * inv[rows]) * inv[cols])
+        val, val_t = (torch.from_numpy(v).to(self.indices.device) if v is not None else None
+                      for v in _normalized_values(self.n, _read_back(self), "CsrGraph"))
         if self.indices_t is self.indices:
-            return CsrGraph(self.indptr, self.indices, values=new)
-        ipt, ixt = self.indptr_t.cpu().numpy(), self.indices_t.cpu().numpy().astype(np.int64)
-        valt = self.values_t.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
-        rt, ct = _csr_rows(ipt, nnz), ixt[:nnz]              # entry (rt, ct) of A^T is a_{ct, rt}
-        return CsrGraph(self.indptr, self.indices, self.indptr_t, self.indices_t, new, dev((valt * inv[ct]) * inv[rt]))
+            return CsrGraph(self.indptr, self.indices, values=val)
+        return CsrGraph(self.indptr, self.indices, self.indptr_t, self.indices_t, val, val_t)
 
 
 class _PoolPlan:
@@ -246,9 +280,9 @@ class CsrBatch:
     ARG = "batch"
 
     def __init__(self, sizes, parts, device, pad_to=None):
-        """`parts`: per graph (indptr, indices, indptr_t, indices_t[, values, values_t]) as host arrays with graph-local
-        columns, the transposed pair None for an undirected graph; values (float, one per stored entry; values_t next
-        to a transposed pair) or None / absent for a 0/1 graph.  Use the from_* constructors."""
+        """`parts`: per graph a `HostCsr`, or a plain (indptr, indices, indptr_t, indices_t[, values, values_t]): host
+        arrays with graph-local columns, the transposed pair None for an undirected graph; values (float, one per stored
+        entry; values_t next to a transposed pair) or None / absent for a 0/1 graph.  Use the from_* constructors."""
         sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
         if sizes.size == 0:
             raise ValueError("CsrBatch: no graph")
@@ -267,24 +301,24 @@ class CsrBatch:
         self.node_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
         self.n_total = self.n = int(self.node_off_host[-1])
         self.device = torch.device(device)
-        directed = any(p[2] is not None for p in parts)
-        parts = [tuple(p) + (None,) * (6 - len(p)) for p in parts]
-        self.weighted = any(p[4] is not None for p in parts)
+        parts = [p if isinstance(p, HostCsr) else HostCsr(*p) for p in parts]
+        directed = any(p.indptr_t is not None for p in parts)
+        self.weighted = any(p.values is not None for p in parts)
 
-        def stack(which):
+        def stack(transposed):
             ips, loc, glob, vals, e0 = [], [], [], [], 0
             for b, p in enumerate(parts):
-                ip = np.asarray(p[which] if p[which] is not None else p[0], dtype=np.int64)
-                ix = np.asarray(p[which + 1] if p[which] is not None else p[1], dtype=np.int64)
+                own = transposed and p.indptr_t is not None          # an undirected graph's A^T is its A
+                ip, ix, v = (p.indptr_t, p.indices_t, p.values_t) if own else (p.indptr, p.indices, p.values)
+                ip, ix = np.asarray(ip, dtype=np.int64), np.asarray(ix, dtype=np.int64)
                 n = int(sizes[b])
                 if ip.size != n + 1 or ip[0] != 0 or ip[-1] != ix.size or (np.diff(ip) < 0).any():
                     raise ValueError(f"CsrBatch: graph {b}: indptr does not describe {n} rows over {ix.size} entries")
                 if ix.size and (ix.min() < 0 or ix.max() >= n):
                     raise ValueError(f"CsrBatch: graph {b}: column index outside 0..{n - 1}")
                 if self.weighted:
-                    v = p[4 + which // 2] if p[which] is not None else p[4]
                     if v is None:
-                        if p[4] is not None:
+                        if p.values is not None:
                             raise ValueError(f"CsrBatch: graph {b}: a weighted graph with a transposed CSR needs values_t")
                         v = np.ones(ix.size, dtype=np.float32)
                     v = np.asarray(v)
@@ -308,9 +342,9 @@ class CsrBatch:
                 val = torch.from_numpy(np.concatenate(vals + fpad).astype(np.float32)).to(self.device)
             return dev(ips), dev(glob + pad), dev(loc + pad), val
 
-        self.indptr, self.indices, self.indices_local, self.values = stack(0)
+        self.indptr, self.indices, self.indices_local, self.values = stack(False)
         if directed:
-            self.indptr_t, self.indices_t, self.indices_t_local, self.values_t = stack(2)
+            self.indptr_t, self.indices_t, self.indices_t_local, self.values_t = stack(True)
         else:
             self.indptr_t, self.indices_t, self.indices_t_local = self.indptr, self.indices, self.indices_local
             self.values_t = self.values
@@ -380,19 +414,10 @@ class CsrBatch:
         graphs = list(graphs)
         if not graphs:
             raise ValueError("CsrBatch: no graph")
-        parts = []
         for g in graphs:
             if not isinstance(g, CsrGraph):
                 raise TypeError(f"CsrBatch.from_graphs: expected CsrGraph, got {type(g).__name__}")
-            ip, ix = g.indptr.cpu().numpy(), g.indices.cpu().numpy()
-            val = g.values.cpu().numpy()[:ip[-1]] if g.weighted else None
-            if g.indptr_t is g.indptr and g.indices_t is g.indices:
-                parts.append((ip, ix[:ip[-1]], None, None, val, None))
-            else:
-                ipt, ixt = g.indptr_t.cpu().numpy(), g.indices_t.cpu().numpy()
-                valt = g.values_t.cpu().numpy()[:ipt[-1]] if g.weighted else None
-                parts.append((ip, ix[:ip[-1]], ipt, ixt[:ipt[-1]], val, valt))
-        return CsrBatch([g.n for g in graphs], parts, graphs[0].indptr.device, pad_to=pad_to)
+        return CsrBatch([g.n for g in graphs], [_read_back(g) for g in graphs], graphs[0].indptr.device, pad_to=pad_to)
 
     @staticmethod
     def from_edge_lists(sizes, srcs, dsts, device, symmetric=True, pad_to=None, weights=None):
@@ -402,40 +427,19 @@ class CsrBatch:
             weights = [None] * len(sizes)
         if not (len(sizes) == len(srcs) == len(dsts) == len(weights)):
             raise ValueError("CsrBatch.from_edge_lists: sizes, srcs, dsts (and weights) must have one entry per graph")
-        parts = []
-        for n, src, dst, w in zip(sizes, srcs, dsts, weights):
-            g = CsrGraph.from_edges(int(n), src, dst, "cpu", symmetric=symmetric, weight=w)
-            ip, ix = g.indptr.numpy(), g.indices.numpy()
-            val = g.values.numpy() if g.weighted else None
-            if symmetric:
-                parts.append((ip, ix, None, None, val, None))
-            else:
-                parts.append((ip, ix, g.indptr_t.numpy(), g.indices_t.numpy(), val,
-                              g.values_t.numpy() if g.weighted else None))
+        parts = [_host_csr(int(n), src, dst, symmetric, w) for n, src, dst, w in zip(sizes, srcs, dsts, weights)]
         return CsrBatch(sizes, parts, device, pad_to=pad_to)
 
     def normalized(self):
         """A new weighted batch holding D^-1/2 A D^-1/2 of every graph (`CsrGraph.normalized`: column sums of the stored
         values, host float64, a node of degree 0 raises).  Everything but `values` / `values_t` is shared with this
         batch."""
-        import copy
-        ip, ix = self.indptr.cpu().numpy(), self.indices.cpu().numpy().astype(np.int64)
-        nnz = int(ip[-1])
-        val = self.values.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
-        rows, cols = _csr_rows(ip, nnz), ix[:nnz]
-        inv = _inv_sqrt_degree(self.n_total, cols, val, "CsrBatch")
-        pad = np.zeros(int(nnz == 0))
-        dev = lambda a: torch.from_numpy(np.concatenate([a, pad]).astype(np.float32)).to(self.device)
+        val, val_t = _normalized_values(self.n_total, _read_back(self), "CsrBatch")
+        pad = np.zeros(int(val.size == 0), dtype=np.float32)          # the one-element pad of an edgeless batch
         new = copy.copy(self)
         new.weighted = True
-        new.values = dev((val * inv[rows]) * inv[cols])
-        if self.indices_t is self.indices:
-            new.values_t = new.values
-        else:
-            ipt, ixt = self.indptr_t.cpu().numpy(), self.indices_t.cpu().numpy().astype(np.int64)
-            valt = self.values_t.cpu().numpy()[:nnz].astype(np.float64) if self.weighted else np.ones(nnz)
-            rt, ct = _csr_rows(ipt, nnz), ixt[:nnz]
-            new.values_t = dev((valt * inv[ct]) * inv[rt])
+        new.values = torch.from_numpy(np.concatenate([val, pad])).to(self.device)
+        new.values_t = new.values if val_t is None else torch.from_numpy(np.concatenate([val_t, pad])).to(self.device)
         return new
 
     @staticmethod
@@ -456,6 +460,33 @@ class CsrBatch:
             dsts.append(c)
             ws.append(a[b, :n, :n][r, c].astype(np.float32) if weighted else None)
         return CsrBatch.from_edge_lists(nn_, srcs, dsts, adj.device, symmetric=False, pad_to=pad_to, weights=ws)
+
+
+def _check_node_rows(graph, x, input_dim, assign_x=None, assign_input_dim=None):
+    """The forwards' input check: x is a GPU tensor `graph.rows()` of width `input_dim` — and, in the DiffPool forward,
+    assign_x one of width `assign_input_dim`."""
+    named = (("x", x),) if assign_input_dim is None else (("x", x), ("assign_x", assign_x))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"expected {name} {graph.rows()}, got {got}")
+    if assign_input_dim is None:
+        if x.shape[1] != input_dim:
+            raise ValueError(f"x has {x.shape[1]} features, the encoder was built for {input_dim}")
+    elif x.shape[1] != input_dim or assign_x.shape[1] != assign_input_dim:
+        raise ValueError(f"feature widths {x.shape[1]}/{assign_x.shape[1]} do not match the model "
+                         f"({input_dim}/{assign_input_dim})")
+    for name, t in named:
+        _lib.require_gpu_tensor(t, name)
+
+
+def _cross_entropy_loss(model, pred, label):
+    """Cross entropy of the prediction (encoders.py:1124-1127) on dp_cross_entropy_*; label [B] for a batch."""
+    if pred.dim() != 2 or not isinstance(label, torch.Tensor) or label.numel() != pred.shape[0]:
+        got = label.numel() if isinstance(label, torch.Tensor) else label.__class__.__name__
+        raise ValueError(f"{type(model).__name__}.loss(pred, label): label must hold one class per row of pred "
+                         f"{tuple(pred.shape)}, got {got}")
+    return ops.cross_entropy(pred, label.reshape(-1))
 
 
 def _gcn_stack(mods, h, graph, bn=True):
@@ -537,12 +568,7 @@ class SparseBatchGcnEncoderGraph(SparseGcnEncoderGraph):
         if not self.concat:
             raise NotImplementedError("add_self GraphConv layers (concat=False) on a CsrBatch: a padded row of the dense "
                                       "batch is then not a constant of the layer")
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != batch.n:
-            got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
-            raise ValueError(f"expected x {batch.rows()}, got {got}")
-        if x.shape[1] != self.input_dim:
-            raise ValueError(f"x has {x.shape[1]} features, the encoder was built for {self.input_dim}")
-        _lib.require_gpu_tensor(x, "x")
+        _check_node_rows(batch, x, self.input_dim)
         h = x.contiguous().float()
         mods = self._stack_modules(self.conv_first, self.conv_block, self.conv_last)
         floored = batch.n_idx > batch.min_n          # some graph has a padded row in the dense batch
@@ -576,13 +602,7 @@ class SparseBatchGcnEncoderGraph(SparseGcnEncoderGraph):
 
     def loss(self, pred, label, type='softmax'):
         """Cross entropy of the prediction (encoders.py:1124-1127) on dp_cross_entropy_*; label [B] for a batch."""
-        if type != 'softmax':
-            return super().loss(pred, label, type=type)
-        if pred.dim() != 2 or not isinstance(label, torch.Tensor) or label.numel() != pred.shape[0]:
-            got = label.numel() if isinstance(label, torch.Tensor) else label.__class__.__name__
-            raise ValueError(f"SparseBatchGcnEncoderGraph.loss(pred, label): label must hold one class per row of pred "
-                             f"{tuple(pred.shape)}, got {got}")
-        return ops.cross_entropy(pred, label.reshape(-1))
+        return _cross_entropy_loss(self, pred, label) if type == 'softmax' else super().loss(pred, label, type=type)
 
     def saved_activation(self, level, what):
         """'readout_argmax' of GraphConv layer `level` of the LAST batch forward: int32 [B, F_layer] rows of the dense
@@ -632,12 +652,7 @@ class SparseGcnSet2SetEncoder(GcnSet2SetEncoder):
         if not isinstance(graph, (CsrGraph, CsrBatch)):
             raise TypeError("SparseGcnSet2SetEncoder.forward(x [n, F], graph: CsrGraph or CsrBatch): the dense "
                             "(x [B, N, F], adj, batch_num_nodes) form is GcnSet2SetEncoder's")
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != graph.n:
-            got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
-            raise ValueError(f"expected x {graph.rows()}, got {got}")
-        if x.shape[1] != self.input_dim:
-            raise ValueError(f"x has {x.shape[1]} features, the encoder was built for {self.input_dim}")
-        _lib.require_gpu_tensor(x, "x")
+        _check_node_rows(graph, x, self.input_dim)
         mods = self._stack_modules(self.conv_first, self.conv_block, self.conv_last)
         z = torch.cat(list(_gcn_stack(mods, x.contiguous().float(), graph, self.bn)), dim=1)      # :1078
         return ops.mlp_head(self.s2s(z, graph), self._pred_linears())                             # :1152-1156
@@ -649,13 +664,7 @@ class SparseGcnSet2SetEncoder(GcnSet2SetEncoder):
 
     def loss(self, pred, label, type='softmax'):
         """Cross entropy of the prediction (encoders.py:1124-1127) on dp_cross_entropy_*; label [B] for a batch."""
-        if type != 'softmax':
-            return super().loss(pred, label, type=type)
-        if pred.dim() != 2 or not isinstance(label, torch.Tensor) or label.numel() != pred.shape[0]:
-            got = label.numel() if isinstance(label, torch.Tensor) else label.__class__.__name__
-            raise ValueError(f"SparseGcnSet2SetEncoder.loss(pred, label): label must hold one class per row of pred "
-                             f"{tuple(pred.shape)}, got {got}")
-        return ops.cross_entropy(pred, label.reshape(-1))
+        return _cross_entropy_loss(self, pred, label) if type == 'softmax' else super().loss(pred, label, type=type)
 
 
 # ----------------------------------------------------------------------------- DiffPool on a CSR graph
@@ -679,10 +688,10 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     on the dense per-op entries (dp_gcn_layer_*, dp_bn_node_*, dp_assign_softmax_mask_*, dp_pool_*, dp_masked_max_*);
     pred_model on `hip_linear`, the loss on dp_cross_entropy_*.
 
-Both containers may carry one fp32 value per stored entry (`values`, and `values_t` for the CSR of A^T): the weighted
-adjacency of the dense path, e.g. the reference sampler's default D^-1/2 A D^-1/2 (graph_sampler.py:27-29), which
-`normalized()` builds.  Every op then takes its `_w` entry (`graph.weighted`), with the launches of the 0/1 call; the
-values are data, no gradient flows to them.
+    Both containers may carry one fp32 value per stored entry (`values`, and `values_t` for the CSR of A^T): the
+    weighted adjacency of the dense path, e.g. the reference sampler's default D^-1/2 A D^-1/2 (graph_sampler.py:27-29),
+    which `normalized()` builds.  Every op then takes its `_w` entry (`graph.weighted`), with the launches of the 0/1
+    call; the values are data, no gradient flows to them.
 
     A linkpred=True model (the constructor default, train.py --linkpred) trains here too: `loss(pred, label, graph)`
     adds the link-prediction term on dp_csr_linkpred_loss_* (per graph of a batch: dp_csr_linkpred_batch_*) — the n^2
@@ -721,15 +730,7 @@ values are data, no gradient flows to them.
             raise TypeError("SparseSoftPoolingGcnEncoder.forward(x [n, F], graph: CsrGraph[, assign_x]): the dense "
                             "(x [B, N, F], adj, batch_num_nodes) form is SoftPoolingGcnEncoder's")
         x_a = x if assign_x is None else assign_x
-        for t, name in ((x, "x"), (x_a, "assign_x")):
-            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
-                got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"expected {name} {graph.rows()}, got {got}")
-        if x.shape[1] != self.input_dim or x_a.shape[1] != self.assign_input_dim:
-            raise ValueError(f"feature widths {x.shape[1]}/{x_a.shape[1]} do not match the model "
-                             f"({self.input_dim}/{self.assign_input_dim})")
-        _lib.require_gpu_tensor(x, "x")
-        _lib.require_gpu_tensor(x_a, "assign_x")
+        _check_node_rows(graph, x, self.input_dim, x_a, self.assign_input_dim)
         x, x_a = x.contiguous().float(), x_a.contiguous().float()
 
         def embed(stack, first, block, last, h, adj):
@@ -789,34 +790,30 @@ values are data, no gradient flows to them.
             label = label.reshape(-1)
         if adj_hop != 1:
             raise NotImplementedError("adj_hop > 1 is never used by the reference's callers (train.py:207)")
-        if not self.linkpred:
-            if self.assign_ent_weight > 0:
-                ent = self._assign_ent_term(call)          # first: its refusals come before any launch
-                return ops.cross_entropy(pred, label) + ent
-            return ops.cross_entropy(pred, label)
-        if adj is None:
-            raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the {kind.__name__} the "
-                                      "forward ran on; it cannot be formed from the prediction alone")
-        if not isinstance(adj, kind):
-            raise TypeError(f"{call}: {kind.ARG} must be the {kind.__name__} of the last forward, got "
-                            f"{type(adj).__name__} (the dense (pred, label, adj, batch_num_nodes) form is "
-                            "SoftPoolingGcnEncoder's)")
-        if self._saved is None:
-            raise ValueError(f"{call}: no forward pass has run yet, so there is no assignment to score")
-        s0 = self._saved["assign"][0]                # attached: dS of the link term and of the pooling add up
-        if kind is CsrBatch and last is not adj:
-            raise ValueError(f"{call}: this is not the batch the last forward ran on; pass the batch of that forward")
-        if adj.n != s0.shape[0]:
-            raise ValueError(f"{call}: {kind.ARG} has n = {adj.n} nodes but the last forward ran on n = {s0.shape[0]}; "
-                             f"pass the {kind.ARG} of that forward")
-        if self.link_objective == "frobenius":
-            _refuse_frob_under_sync_bn(self)
-        if self.assign_ent_weight > 0:
-            ent = self._assign_ent_term(call)
+        if self.linkpred:                            # every refusal of the link term comes before the first launch
+            if adj is None:
+                raise NotImplementedError(f"{call}: the link-prediction loss (linkpred=True) needs the {kind.__name__} "
+                                          "the forward ran on; it cannot be formed from the prediction alone")
+            if not isinstance(adj, kind):
+                raise TypeError(f"{call}: {kind.ARG} must be the {kind.__name__} of the last forward, got "
+                                f"{type(adj).__name__} (the dense (pred, label, adj, batch_num_nodes) form is "
+                                "SoftPoolingGcnEncoder's)")
+            if self._saved is None:
+                raise ValueError(f"{call}: no forward pass has run yet, so there is no assignment to score")
+            s0 = self._saved["assign"][0]            # attached: dS of the link term and of the pooling add up
+            if kind is CsrBatch and last is not adj:
+                raise ValueError(f"{call}: this is not the batch the last forward ran on; pass the batch of that forward")
+            if adj.n != s0.shape[0]:
+                raise ValueError(f"{call}: {kind.ARG} has n = {adj.n} nodes but the last forward ran on n = "
+                                 f"{s0.shape[0]}; pass the {kind.ARG} of that forward")
+            if self.link_objective == "frobenius":
+                _refuse_frob_under_sync_bn(self)
+        # enqueued in this order: entropy (its own refusals first), link, cross entropy; summed as ce + link + ent
+        terms = [self._assign_ent_term(call)] if self.assign_ent_weight > 0 else []
+        if self.linkpred:
             self.link_loss = adj.link_loss(s0, self.link_objective)
-            return ops.cross_entropy(pred, label) + self.link_loss + ent
-        self.link_loss = adj.link_loss(s0, self.link_objective)
-        return ops.cross_entropy(pred, label) + self.link_loss
+            terms.insert(0, self.link_loss)
+        return sum(terms, ops.cross_entropy(pred, label))
 
     def _assign_ent_term(self, call):
         """assign_ent_weight * E of the last forward's level-0 assignment (ops.assign_entropy: every row of the ragged
