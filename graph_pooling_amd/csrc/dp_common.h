@@ -611,15 +611,22 @@ size_t small_level_part_floats(int B, int n, int L);
 void small_level_fwd(Seq& q, const SmallLevelIO& io, int B, int n, const int* dims, int L, int add_self, int bn);
 // The prediction-head backward folded into the LAST level's whole-level backward (dp_small.hip): each workgroup runs
 // its graph's pred_model backward and max-readout scatter in a prologue (this level's slice straight into its LDS
-// gradient totals, the other levels' slices into their dZe), publishes the graph's hidden-layer gradients as tagged
-// entries, and at the end sums a fixed slice of the head's weight / bias gradients over the batch into `grads`.
+// gradient totals, the other levels' slices into their dZe) and stores the graph's hidden-layer gradients as its row
+// of `part`.  The head's weight / bias gradients, sums over the batch that nothing in the backward reads, are left to
+// the step's final launch (reduce_slabs_head).
 struct SmallHeadFold {
     HeadBwdArgs hb;          // what k_head_bwd would get; hb.lv[level].dZ is not written (that slice stays in LDS)
     int level;               // the entry of hb.lv that is this kernel's level
     int zcol;                // column of that level's readout in its concat buffer
-    float* part;             // exchange region of small_head_fold_part_floats(hb.h) floats (alloc_head)
+    float* part;             // [B][hup] hidden-layer gradients, small_head_fold_part_floats(hb.h) floats (alloc_head)
 };
 size_t small_head_fold_part_floats(const HeadArgs& h);
+long head_grad_entries(const HeadArgs& h);      // weight + bias gradient entries of pred_model
+// (dp_rowops.hip) reduce_slabs plus, in the SAME launch, pred_model's dW / db from d_ypred, the saved hid[] and the
+// [B][hup] hidden-layer gradients `hf.part` (workgroups past the slab tiles; each entry the b-ascending chain of
+// k_head_bwd, bit-identical to it)
+void reduce_slabs_head(Seq& q, const float* slabs, long stride, int B, float* out, long count,
+                       const SmallHeadFold& hf);
 bool small_head_fold_fits(int B, int n, const int* dims, int L, bool dadj, const HeadArgs& h);
 void small_level_bwd(Seq& q, const SmallLevelIO& io, const float* dZe, float* dX0, float* dadj, float* slabs,
                      long slab_stride, int B, int n, const int* dims, int L, int add_self, int bn,

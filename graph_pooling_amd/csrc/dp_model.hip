@@ -934,10 +934,12 @@ bool packed_entry_ok(Seq& q, const EncoderPlan& p) {
 // forward and in the backward:
 //   - the persistent level-0 kernels' barrier block: zero when the workspace is first used (diffpool_hip.h),
 //     self-cleaning afterwards (dp_level0.hip); q.seq_word is one of its words;
-//   - the tagged-entry exchange regions (BatchNorm partials of the persistent level-0 kernels, forward and backward, of
-//     the whole-level kernels, and the head fold's hidden-layer gradients).  Their readers recognise an entry by its
-//     tag, so NOTHING else may ever be written there: they are never handed out as scratch and only ever hold zeros
-//     (the workspace's one-time fill) or entries of earlier launches;
+//   - the tagged-entry exchange regions (BatchNorm partials of the persistent level-0 kernels, forward and backward,
+//     and of the whole-level kernels).  Their readers recognise an entry by its tag, so NOTHING else may ever be
+//     written there: they are never handed out as scratch and only ever hold zeros (the workspace's one-time fill) or
+//     entries of earlier launches;
+//   - the head fold's [B][hup] hidden-layer gradients (xr.head): an ordinary buffer, written by the last level's
+//     backward kernel and read by the step's final launch, kept here so that no level's scratch overlaps it;
 //   - the backward's zero block (BwdZero), which a training forward clears for the backward that follows.
 struct ExchangeRegions {
     float *l0_fwd, *l0_bwd, *lvl, *head;
@@ -1381,7 +1383,10 @@ int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const
         io.hf = fold && j == P ? &hf : nullptr;
         level_backward(q, p, j, lv, io, params, sc);
     }
-    reduce_slabs(q, slabs, slab_stride, B * KS, grads, c.n_graph_params, 0);
+    // the step's last launch: the slabs, and with a folded head also pred_model's dW / db (they wait for nothing but
+    // the hidden-layer gradients of every graph, which the last level's kernel stored long before)
+    if (fold) reduce_slabs_head(q, slabs, slab_stride, B * KS, grads, c.n_graph_params, hf);
+    else reduce_slabs(q, slabs, slab_stride, B * KS, grads, c.n_graph_params, 0);
     return q.err;
 }
 

@@ -2038,9 +2038,99 @@ void argmax_rows(Seq& q, const float* X, int ldx, long long* out, int rows, int 
 
 // ------------------------------------------------------------------ slab reduce
 // out[p] (+)= sum_b slabs[b, p]   — per-graph parameter-gradient slabs -> the flat gradient buffer
-__global__ __launch_bounds__(1024) void k_reduce_slabs(const float* slabs, long stride, int B, float* out,
-                                                       long count, int accumulate) {
-    __shared__ float red[16][64];
+//
+// The step's final launch also finishes the prediction head when its backward rode in the last level's kernel
+// (SmallHeadFold; k_reduce_slabs_head below): workgroups past the `tiles` slab tiles take entries of pred_model's
+// dW / db, one per thread, each the b-ascending chain of k_head_bwd ( s += go[b][j] * hin[b][k], s += go[b][j] for a
+// bias ), operands straight from global memory -- d_ypred, the saved hid[i] and the [B][hup] hidden-layer gradients
+// k_small_level_bwd stored, all complete since that launch ended.  Every load of a chunk of HG_CHUNK graphs is issued
+// before the chunk's adds, so a batch of up to HG_CHUNK graphs costs these workgroups ONE memory round trip, as a slab
+// tile costs its own; and only HG_THREADS threads of a workgroup take an entry (the other waves leave at once),
+// because a thread issues 2 B loads where a slab-tile thread issues B / 16: spread thin over the idle CUs, the entries
+// end inside the slab tiles' time.
+// Limit: the 2 x HG_CHUNK operand registers put k_reduce_slabs_head at ~100 VGPRs, so ONE of its 1024-thread workgroups
+// fits a CU where the 12-VGPR k_reduce_slabs fits two.  While tiles + head workgroups <= CUs (DD: 196 + 49 on 256)
+// that costs nothing; a folded plan with more of them than CUs runs its slab tiles in more rounds than k_reduce_slabs
+// would.  No such shape has been measured.
+struct HeadGradArgs {
+    int tiles;                              // slab tiles in front (blockIdx.x < tiles)
+    int n_pred, B, hup;
+    int htot;                               // entries (< 2^30)
+    int dims[DP_MAX_PRED + 2];
+    long w_off[DP_MAX_PRED + 1], b_off[DP_MAX_PRED + 1];
+    const float* hid[DP_MAX_PRED + 1];      // hid[0] = features [B, dims[0]], hid[i] = post-ReLU activations
+    const float* d_ypred;                   // [B, dims[n_pred]]
+    const float* hgrad;                     // [B][hup]: row b = [grad hid[1] | grad hid[2] | ..] of graph b
+    float* grads;
+};
+constexpr int HG_CHUNK = 32;                // graphs per round of loads (2 x 32 VGPRs)
+constexpr int HG_THREADS = 128;             // entries per head workgroup
+
+__device__ inline void head_grad_entry(const HeadGradArgs& a, int e) {
+    // the entry's layer i, found with constant indices into the argument block (a lane-dependent index would fetch
+    // dims / offsets / hid with vector loads: one more memory round trip in front of the chain's own)
+    int i = 0, r = e, rem = e, goff = 0, gcol = 0;      // goff: column of grad hid[i + 1] in a hgrad row
+    int din = a.dims[0], dout = a.dims[1];
+    long woff = a.w_off[0], boff = a.b_off[0];
+    const float* hin = a.hid[0];
+    bool found = false;
+#pragma unroll
+    for (int t = 0; t < DP_MAX_PRED + 1; ++t) {
+        if (t < a.n_pred) {
+            const int seg = a.dims[t + 1] * (a.dims[t] + (a.b_off[t] >= 0 ? 1 : 0));
+            if (!found && (rem < seg || t == a.n_pred - 1)) {
+                i = t; r = rem; goff = gcol;
+                din = a.dims[t]; dout = a.dims[t + 1];
+                woff = a.w_off[t]; boff = a.b_off[t];
+                hin = a.hid[t];
+                found = true;
+            }
+            rem -= seg;
+            gcol += a.dims[t + 1];
+        }
+    }
+    const int B = a.B;
+    const bool weight = r < dout * din;
+    const int j = weight ? r / din : r - dout * din;
+    const int k = weight ? r - j * din : 0;
+    // go[b][j]: d_ypred for the last Linear, else the gradient w.r.t. hid[i + 1];  hin[b][k]: hid[i]
+    const bool top = i == a.n_pred - 1;
+    const float* gp = (top ? a.d_ypred : a.hgrad + goff) + j;
+    const int gs = top ? dout : a.hup;
+    const float* xp = hin + (weight ? k : 0);
+    const int xs = weight ? din : 0;        // (a bias entry loads hin[0][0] for nothing: no branch around the loads)
+    float s = 0.f;
+    for (int b0 = 0; b0 < B; b0 += HG_CHUNK) {
+        float g[HG_CHUNK], x[HG_CHUNK];
+        // groups of eight graphs behind a uniform test, rows clamped inside the last group: every load of the chunk
+        // is in flight before the first add, and at most seven of them are repeats
+#pragma unroll
+        for (int u0 = 0; u0 < HG_CHUNK; u0 += 8) {
+            if (b0 + u0 < B) {
+#pragma unroll
+                for (int u = u0; u < u0 + 8; ++u) {
+                    const long row = min(b0 + u, B - 1);
+                    g[u] = gp[row * gs];
+                    x[u] = xp[row * xs];
+                }
+            }
+        }
+        if (weight) {
+#pragma unroll
+            for (int u = 0; u < HG_CHUNK; ++u)
+                if (b0 + u < B) s += g[u] * x[u];
+        } else {
+#pragma unroll
+            for (int u = 0; u < HG_CHUNK; ++u)
+                if (b0 + u < B) s += g[u];
+        }
+    }
+    if (weight) a.grads[woff + r] = s;
+    else a.grads[boff + j] = s;
+}
+
+__device__ inline void reduce_slab_tile(const float* slabs, long stride, int B, float* out, long count, int accumulate,
+                                        float (&red)[16][64]) {
     const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
     const long i = (long)blockIdx.x * 64 + cl;
     float s = 0.f;
@@ -2055,11 +2145,52 @@ __global__ __launch_bounds__(1024) void k_reduce_slabs(const float* slabs, long 
         out[i] = accumulate ? out[i] + t : t;
     }
 }
+__global__ __launch_bounds__(1024) void k_reduce_slabs(const float* slabs, long stride, int B, float* out,
+                                                       long count, int accumulate) {
+    __shared__ float red[16][64];
+    reduce_slab_tile(slabs, stride, B, out, count, accumulate, red);
+}
+// ... and the sibling the folded-head plan launches in its place: the same slab tiles, then the head's entries (its
+// 2 x HG_CHUNK operand registers stay out of the slab-only kernel, which every other plan keeps launching)
+__global__ __launch_bounds__(1024) void k_reduce_slabs_head(const float* slabs, long stride, int B, float* out,
+                                                            long count, HeadGradArgs hg) {
+    __shared__ float red[16][64];
+    if ((int)blockIdx.x >= hg.tiles) {      // (uniform per workgroup: these never reach the tile's barrier)
+        const int e = ((int)blockIdx.x - hg.tiles) * HG_THREADS + threadIdx.x;
+        if (threadIdx.x < HG_THREADS && e < hg.htot) head_grad_entry(hg, e);
+        return;
+    }
+    reduce_slab_tile(slabs, stride, B, out, count, 0, red);
+}
 void reduce_slabs(Seq& q, const float* slabs, long stride, int B, float* out, long count, int accumulate) {
     if (!q.ok() || count <= 0) return;
     hipLaunchKernelGGL(k_reduce_slabs, dim3((count + 63) / 64), dim3(1024), 0, q.stream, slabs, stride, B, out, count,
                        accumulate);
     q.check_launch("reduce_slabs");
+}
+void reduce_slabs_head(Seq& q, const float* slabs, long stride, int B, float* out, long count,
+                       const SmallHeadFold& hf) {
+    if (!q.ok()) return;
+    const HeadArgs& h = hf.hb.h;
+    HeadGradArgs hg{};
+    hg.tiles = count > 0 ? (int)((count + 63) / 64) : 0;
+    hg.n_pred = h.n_pred;
+    hg.B = h.B;
+    hg.htot = (int)head_grad_entries(h);      // (< 2^30: small_head_fold_fits)
+    for (int i = 0; i <= h.n_pred; ++i) hg.dims[i] = h.dims[i];
+    for (int i = 0; i < h.n_pred; ++i) {
+        hg.w_off[i] = h.w_off[i];
+        hg.b_off[i] = h.b_off[i];
+        hg.hid[i] = h.hid[i];
+        if (i >= 1) hg.hup += h.dims[i];
+    }
+    hg.d_ypred = hf.hb.d_ypred;
+    hg.hgrad = hf.part;
+    hg.grads = hf.hb.grads;
+    const int head_wgs = (hg.htot + HG_THREADS - 1) / HG_THREADS;
+    hipLaunchKernelGGL(k_reduce_slabs_head, dim3(hg.tiles + head_wgs), dim3(1024), 0, q.stream, slabs, stride, B, out,
+                       count, hg);
+    q.check_launch("reduce_slabs_head");
 }
 
 }  // namespace dp

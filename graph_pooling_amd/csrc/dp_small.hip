@@ -740,30 +740,26 @@ struct SmallLevelBwdArgs {
     SmDiv qd0, qD;
     SmDiv qdout[DP_MAX_LAYERS];
     // the prediction-head backward folded in (fold != 0; see SmallHeadFold): hb as k_head_bwd gets it, hlevel / zcol
-    // this level's entry of hb.lv and its readout column, hpart the exchange of the hidden-layer gradients
-    int fold, hlevel, zcol, htot;      // htot: head weight + bias gradient entries (B * htot < 2^31)
+    // this level's entry of hb.lv and its readout column, hgrad the [B][hup] hidden-layer gradients for the final launch
+    int fold, hlevel, zcol;
     HeadBwdArgs hb;
-    float* hpart;
+    float* hgrad;
 };
 
 // Head-fold sizes: widths of pred_model, its hidden-layer widths hup = dims[1] + .. + dims[n_pred - 1] (the per-graph
-// gradients that are exchanged, two floats per tagged entry) and the LDS it stages
+// gradients handed to the final launch) and the LDS the kernel stages: one graph's operands, whatever the batch
 struct SmHead {
-    int nP, d0, d1, C, wup, hup, E;
+    int nP, d0, d1, C, wup, hup;
     __host__ __device__ SmHead(const HeadArgs& h) : nP(h.n_pred), d0(h.dims[0]), d1(h.dims[1]), C(h.dims[h.n_pred]) {
         wup = hup = 0;
         for (int i = 1; i < nP; ++i) {
             wup += h.dims[i] * h.dims[i + 1];
             hup += h.dims[i];
         }
-        E = (hup + 1) / 2;
     }
-    // W0 [d1][d0], upper weights, hid[1..nP-1] and their gradients [B][dims[i]] each, features [B][d0], d_ypred [B][C]
-    __host__ __device__ size_t lds_floats(int B) const {
-        return (size_t)d1 * d0 + wup + 2 * (size_t)B * hup + (size_t)B * d0 + (size_t)B * C;
-    }
+    // W0 [d1][d0], upper weights, this graph's hid[1..nP-1] and their gradients [hup] each, its d_ypred [C]
+    __host__ __device__ size_t lds_floats() const { return (size_t)d1 * d0 + wup + 2 * (size_t)hup + (size_t)C; }
 };
-constexpr unsigned SM_HEAD_TAG = 15u;     // tag low bits of the head-gradient entries (BN entries use 1..L)
 
 __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -788,15 +784,13 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     float* DBW = DB + a.omax;              // [16 waves][omax] per-wave partials of the bias sums
     const int tl = tid & 15, team = tid >> 4;
     const int NT = blockDim.x, NTEAMS = blockDim.x >> 4;
-    // head fold (a.fold): its operands behind the level's
+    // head fold (a.fold): this graph's operands behind the level's
     const SmHead hz(a.hb.h);
-    const int B = a.B;
     float* HW0 = DBW + 16 * a.omax;        // [d1][d0] first Linear's weight
     float* HWU = HW0 + hz.d1 * hz.d0;      // the upper Linears' weights, layer 1 first
-    float* HH = HWU + hz.wup;              // hid[i] of every graph, i = 1..nP-1: [B][dims[i]] blocks
-    float* HG = HH + B * hz.hup;           // gradients w.r.t. hid[i], same layout (this graph's, then every graph's)
-    float* HF = HG + B * hz.hup;           // features hid[0] of every graph [B][d0]
-    float* HY = HF + B * hz.d0;            // d_ypred [B][C]
+    float* HH = HWU + hz.wup;              // this graph's hid[i], i = 1..nP-1: [hid[1] | hid[2] | ..]
+    float* HG = HH + hz.hup;               // gradients w.r.t. them, same layout
+    float* HY = HG + hz.hup;               // this graph's d_ypred [C]
     SM_STAMP(1, 16);
     int win = -1;                          // max-readout winner row of feature tid (first pass of the scatter)
     if (a.fold) {
@@ -807,17 +801,16 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
             }
         }
         const HeadArgs& h = a.hb.h;
-        sm_dma(HY, B * hz.C, [&](int e) { return a.hb.d_ypred + e; });
+        sm_dma(HY, hz.C, [&](int e) { return a.hb.d_ypred + (long)b * hz.C + e; });
         sm_dma(HW0, hz.d1 * hz.d0, [&](int e) { return h.params + h.w_off[0] + e; });
         int wo = 0, ho = 0;
         for (int i = 1; i < hz.nP; ++i) {
             const int cnt = h.dims[i] * h.dims[i + 1];
             sm_dma(HWU + wo, cnt, [&](int e) { return h.params + h.w_off[i] + e; });
-            sm_dma(HH + ho, B * h.dims[i], [&](int e) { return h.hid[i] + e; });
+            sm_dma(HH + ho, h.dims[i], [&](int e) { return h.hid[i] + (long)b * h.dims[i] + e; });
             wo += cnt;
-            ho += B * h.dims[i];
+            ho += h.dims[i];
         }
-        sm_dma(HF, B * hz.d0, [&](int e) { return h.hid[0] + e; });
     }
 
     // ---- one burst
@@ -855,38 +848,27 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     if (a.fold) {
         // ---- head prologue: this graph's pred_model backward, in k_head_bwd's expression order (bit-identical)
         const HeadArgs& h = a.hb.h;
-        int ho = B * hz.hup, wo = hz.wup;
+        int ho = hz.hup, wo = hz.wup;
         for (int i = hz.nP - 1; i >= 1; --i) {
             const int din = h.dims[i], dout = h.dims[i + 1];
             wo -= din * dout;
-            ho -= B * din;
-            const float* go = i == hz.nP - 1 ? HY + b * dout : HG + ho + B * din + b * dout;
+            ho -= din;
+            const float* go = i == hz.nP - 1 ? HY : HG + ho + din;
             const float* W = HWU + wo;
             for (int k = tid; k < din; k += NT) {
                 float s = 0.f;
 #pragma unroll 8
                 for (int j = 0; j < dout; ++j) s += go[j] * W[j * din + k];
-                HG[ho + b * din + k] = HH[ho + b * din + k] > 0.f ? s : 0.f;     // relu': hid = relu(.)
+                HG[ho + k] = HH[ho + k] > 0.f ? s : 0.f;     // relu': hid = relu(.)
             }
             __syncthreads();
         }
-        // publish this graph's hidden-layer gradients: entry e = values 2e, 2e + 1 of [grad hid[1] | grad hid[2] | ..]
-        const ScBuf hp = sc_buf(a.hpart, (size_t)B * hz.E * 16);
-        for (int e = tid; e < hz.E; e += NT) {
-            float v[2] = {0.f, 0.f};
-            for (int u = 0; u < 2; ++u) {
-                int t = 2 * e + u, blk = 0;
-                for (int i = 1; i < hz.nP && t >= 0; ++i) {
-                    if (t < h.dims[i]) v[u] = HG[blk + b * h.dims[i] + t];
-                    t -= h.dims[i];
-                    blk += B * h.dims[i];
-                }
-            }
-            sc_st16(hp, (unsigned)(((long)b * hz.E + e) * 16), sc_tagged(v[0], v[1], (seq << 4) | SM_HEAD_TAG));
-        }
+        // this graph's row of the [B][hup] hidden-layer gradients [grad hid[1] | grad hid[2] | ..]: plain stores, read
+        // by the step's final launch (k_reduce_slabs_head), which sums the head's dW / db over the batch
+        for (int e = tid; e < hz.hup; e += NT) a.hgrad[(long)b * hz.hup + e] = HG[e];
         // d features = g1 W0, and the max-readout scatter: this level's slice into the LDS running totals, the other
         // levels' into their dZe (zero on entry: the caller's contract; the kernel boundary publishes them)
-        const float* g1 = hz.nP == 1 ? HY + b * hz.C : HG + b * hz.d1;
+        const float* g1 = hz.nP == 1 ? HY : HG;
         for (int k = tid, it = 0; k < hz.d0; k += NT, ++it) {
             float s = 0.f;
 #pragma unroll 8
@@ -905,9 +887,6 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
         SM_STAMP(1, 19);
     }
 
-    // first probe of the head-gradient poll, issued before the first layer's row backward (below) and checked at the end
-    u32x4 hprobe = (u32x4){0u, 0u, 0u, 0u};
-    const unsigned htag = ((seq << 4) | SM_HEAD_TAG) ^ (a.target_bias ? 0x40000000u : 0u);   // (what the poll wants)
     int wo_end = a.wtot;
     for (int l = L - 1; l >= 0; --l) {
         const int din = a.dims[l], dout = a.dims[l + 1];
@@ -957,9 +936,6 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
                 }
             }
         }
-        // behind the last BatchNorm exchange (its poll loads have landed, so the vmcnt waits of the layer do not drain
-        // the probe): its round trip hides behind the first layer's work
-        if (a.fold && l == 0 && tid < B * hz.E) hprobe = sc_ld16(sc_buf(a.hpart, (size_t)B * hz.E * 16), (unsigned)tid * 16u);
         lds_barrier();
         // ---- dU = normalise^T relu^T bn^T dx, one team per row (uniform trip count: the bias sums reduce across
         // the four row teams of a wave)
@@ -1041,68 +1017,9 @@ __global__ __launch_bounds__(1024) void k_small_level_bwd(SmallLevelBwdArgs a) {
     if (a.dadj)
         for (int i = tid; i < n * n; i += NT) a.dadj[(long)b * n * n + i] = DA[i];
     SM_STAMP(1, 20);
-    if (a.fold) {
-        // ---- head parameter gradients: every graph's hidden-layer gradients, then this workgroup's fixed slice of the
-        // dW / db entries, each the b-ascending chain of k_head_bwd (bit-identical), written straight to grads.  The
-        // entries were published in the prologues; with BatchNorm the exchanges above have already waited for every
-        // workgroup, without it this poll is the level's one cross-workgroup wait (co-residency: small_level_fused_ok;
-        // bounded like sm_poll_row: on give-up the error word is raised and these gradients are NaN)
-        const HeadArgs& h = a.hb.h;
-        const ScBuf hp = sc_buf(a.hpart, (size_t)B * hz.E * 16);
-        bool ok = true;
-        for (int t = tid; t < B * hz.E; t += NT) {
-            const int bb = t / hz.E, e = t - bb * hz.E;
-            u32x4 q = hprobe;                      // (t == tid: the probe issued before layer 0)
-            for (int it = 0;; ++it) {
-                if (t != tid || it > 0) q = sc_ld16(hp, (unsigned)t * 16u);
-                if (q[1] == htag && q[3] == htag) break;
-                if (it > a.spin_limit) {
-                    __hip_atomic_store(a.bar + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    dev_err_raise(a.dev_err, DP_DEVERR_BARRIER);
-                    ok = false;
-                    break;
-                }
-                if (t != tid || it > 0) __builtin_amdgcn_s_sleep(2);
-            }
-            for (int u = 0; u < 2; ++u) {
-                int x = 2 * e + u, blk = 0;
-                for (int i = 1; i < hz.nP && x >= 0; ++i) {
-                    if (x < h.dims[i]) HG[blk + bb * h.dims[i] + x] = __uint_as_float(q[2 * u]);
-                    x -= h.dims[i];
-                    blk += B * h.dims[i];
-                }
-            }
-        }
-        ok = __syncthreads_and(ok);
-        SM_STAMP(1, 21);
-        const int lo = a.htot * b / B, hi = a.htot * (b + 1) / B;
-        for (int e = lo + tid; e < hi; e += NT) {
-            int i = 0, r = e, ho = 0;
-            for (; i < hz.nP - 1; ++i) {
-                const int seg = h.dims[i + 1] * (h.dims[i] + (h.b_off[i] >= 0 ? 1 : 0));
-                if (r < seg) break;
-                r -= seg;
-                if (i > 0) ho += B * h.dims[i];
-            }
-            const int din = h.dims[i], dout = h.dims[i + 1];
-            // go[bb][j]: d_ypred for the last Linear, else the gradient w.r.t. hid[i + 1];  hin[bb][k]: hid[i]
-            const float* go = i == hz.nP - 1 ? HY : HG + (i > 0 ? ho + B * din : 0);
-            const float* hin = i == 0 ? HF : HH + ho;
-            float s = 0.f;
-            if (r < dout * din) {
-                const int j = r / din, k = r - j * din;
-#pragma unroll 8
-                for (int bb = 0; bb < B; ++bb) s += go[bb * dout + j] * hin[bb * din + k];
-                a.hb.grads[h.w_off[i] + r] = ok ? s : __builtin_nanf("");
-            } else {
-                const int j = r - dout * din;
-#pragma unroll 8
-                for (int bb = 0; bb < B; ++bb) s += go[bb * dout + j];
-                a.hb.grads[h.b_off[i] + j] = ok ? s : __builtin_nanf("");
-            }
-        }
-        SM_STAMP(1, 22);
-    }
+    // (the head's parameter gradients are summed over the batch in the step's final launch, k_reduce_slabs_head, from
+    // the rows the prologues stored: nothing here waits for another workgroup.  With BatchNorm the exchanges above are
+    // the level's cross-workgroup waits; without it the kernel has none, and needs no co-residency at all)
     sm_finish(a.bar, a.seq, seq, a.B);
 }
 
@@ -1230,19 +1147,20 @@ bool small_level_fused_ok(int B, int n, const int* dims, int L, bool dadj) {
     return cus > 0 && B <= cus / 2 && B <= 16 * SM_BMAX16 && level_kernels_admitted();
 }
 size_t small_level_part_floats(int B, int n, int L) { return (size_t)(L > 1 ? L - 1 : 1) * B * n * 4; }
-static int head_grad_entries(const HeadArgs& h) {
-    int tot = 0;
-    for (int i = 0; i < h.n_pred; ++i) tot += h.dims[i + 1] * (h.dims[i] + (h.b_off[i] >= 0 ? 1 : 0));
+long head_grad_entries(const HeadArgs& h) {
+    long tot = 0;
+    for (int i = 0; i < h.n_pred; ++i) tot += (long)h.dims[i + 1] * (h.dims[i] + (h.b_off[i] >= 0 ? 1 : 0));
     return tot;
 }
+// the [B][hup] hidden-layer gradients between k_small_level_bwd and the final launch
 size_t small_head_fold_part_floats(const HeadArgs& h) {
     const SmHead z(h);
-    return (size_t)h.B * (z.E > 0 ? z.E : 1) * 4;
+    return (size_t)h.B * (z.hup > 0 ? z.hup : 1);
 }
-// the fused level's LDS with the head's operands added still fits (else the plan keeps k_head_bwd)
+// the fused level's LDS with one graph's head operands added still fits (else the plan keeps k_head_bwd)
 bool small_head_fold_fits(int B, int n, const int* dims, int L, bool dadj, const HeadArgs& h) {
-    if (h.n_pred < 1 || h.B != B || (long)head_grad_entries(h) * B >= (1L << 31)) return false;
-    return (small_level_lds_bwd(B, n, dims, L, dadj) + SmHead(h).lds_floats(B)) * sizeof(float) <= 150 * 1024;
+    if (h.n_pred < 1 || h.B != B || head_grad_entries(h) >= (1L << 30)) return false;
+    return (small_level_lds_bwd(B, n, dims, L, dadj) + SmHead(h).lds_floats()) * sizeof(float) <= 150 * 1024;
 }
 
 void small_level_fwd(Seq& q, const SmallLevelIO& io, int B, int n, const int* dims, int L, int add_self, int bn) {
@@ -1306,9 +1224,8 @@ void small_level_bwd(Seq& q, const SmallLevelIO& io, const float* dZe, float* dX
         a.hb = hf->hb;
         a.hlevel = hf->level;
         a.zcol = hf->zcol;
-        a.hpart = hf->part;
-        a.htot = head_grad_entries(hf->hb.h);
-        lds += SmHead(hf->hb.h).lds_floats(B);
+        a.hgrad = hf->part;
+        lds += SmHead(hf->hb.h).lds_floats();
     }
     hipLaunchKernelGGL(k_small_level_bwd, dim3(B), dim3(1024), lds * sizeof(float), q.stream, a);
     q.check_launch("small_level_bwd");
