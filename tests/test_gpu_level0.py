@@ -3,7 +3,8 @@ whole level-0 forward / backward of SoftPoolingGcnEncoder, encoders.py:1254-1279
 geometries — 16 / 32 / 48 / 64 rows per workgroup, ragged last row blocks, graphs of one node, no mask — plus the paths
 only some inputs take: a WEIGHTED adjacency (not bf16-exact: the in-kernel fp32 fallback), evaluation mode, the link loss
 arriving as d_assign.  Every case asserts through the library's launch counters that the persistent kernels really ran
-(the plan falls back to the per-phase kernels silently when a shape is outside their envelope)."""
+(the plan falls back to the per-phase kernels silently when a shape is outside their envelope).
+Width, depth, batch-slot and cluster-tier coverage, anchored to fp64, is in tests/test_gpu_level0_matrix.py."""
 import ctypes as C
 
 import numpy as np
