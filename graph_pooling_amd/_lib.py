@@ -92,6 +92,9 @@ AGG_FB_NONE, AGG_FB_PANEL, AGG_FB_GEMM = 0, 1, 2
 AGG_PLAN_INTS = 14
 AGG_DECLINED = -5
 
+# dp_linkpred_plan: (KT, CW, col_tiles, splits, split_tiles, forward tiles per graph, forward LDS bytes, backward LDS bytes)
+LINKPRED_PLAN_INTS = 8
+
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
 GEMM_PLAN_NONE, GEMM_PLAN_SPLIT_BF16 = 0, 1                           # DP_GEMM_PLAN_*
@@ -164,6 +167,7 @@ _PROTOS = {
     "dp_softmax_mask_fwd": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "dp_softmax_mask_bwd": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P]),
     "dp_colsum_batched": (_I, [_P, _I, _L, _I, _I, _P, _L, _I, _I, _P]),
+    "dp_linkpred_plan": (_I, [_I, _I, _I, C.POINTER(_I)]),
     "dp_linkpred_workspace_bytes": (_Z, [_I, _I, _I]),
     "dp_linkpred_loss_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_linkpred_loss_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),

@@ -899,6 +899,19 @@ size_t dp_linkpred_workspace_bytes(int B, int n, int K) {
     size_t b = sized([&](Seq& q) { linkpred_bwd(q, 0, K, 0, 0, 0, 0, K, B, n, K, 0); });
     return f > b ? f : b;
 }
+int dp_linkpred_plan(int B, int n, int K, int* plan_out) {
+    NOTNULL(plan_out);
+    NONNEG(B); NONNEG(n); NONNEG(K);
+    LinkPlan p;
+    if (!linkpred_plan(B, n, K, p)) {
+        set_error("linkpred: K=%d clusters exceed the fused tile kernel (max 256)", K);
+        return DP_ERR_UNSUPPORTED;
+    }
+    const int out[DP_LINKPRED_PLAN_INTS] = {p.kt, p.cw, p.col_tiles, p.splits, p.split_tiles, p.fwd_tiles,
+                                            (int)p.fwd_lds, (int)p.bwd_lds};
+    for (int i = 0; i < DP_LINKPRED_PLAN_INTS; ++i) plan_out[i] = out[i];
+    return DP_OK;
+}
 int dp_linkpred_loss_fwd(const float* S, const float* adj, const int* num_nodes, float* loss_out, int B, int n, int K,
                          void* workspace, size_t workspace_bytes, void* stream) {
     NOTNULL(S); NOTNULL(adj); NOTNULL(loss_out);

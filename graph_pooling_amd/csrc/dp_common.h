@@ -661,6 +661,14 @@ void segment_max_part(Seq& q, const float* Z, int ldz, const int* chunk_tab, int
 void set2set_prep_weights(Seq& q, const float* w_ih, const float* w_hh, float* wt, int d);
 
 // (dp_linkpred.hip)
+// what the link-loss launchers decide from (B, n, K), answered by the host function they themselves decide with
+struct LinkPlan {
+    int kt, cw;                      // K tier (16-column output tiles; 0: K > 256), backward column-tile width
+    int col_tiles, splits, split_tiles;   // backward: column tiles of cw, blockIdx.z extent (1: non-split), tiles per split
+    int fwd_tiles;                   // forward workgroups (and loss partials) per graph: ceil(n / 64)^2
+    size_t fwd_lds, bwd_lds;         // dynamic LDS bytes; bwd: the fp32 reader's (the packed one holds no A^T image)
+};
+bool linkpred_plan(int B, int n, int K, LinkPlan& p);          // false: K > 256 (no kernel)
 void linkpred_fwd(Seq& q, const float* S, int lds, const float* adj, const int* num_nodes, float* loss_out,
                   int B, int n, int K, const float* norm = nullptr /*device scalar replacing sum n_b^2*/);
 void linkpred_bwd(Seq& q, const float* S, int lds, const float* adj, const int* num_nodes, const float* dloss,

@@ -362,12 +362,38 @@ __global__ __launch_bounds__(256) void k_link_reduce(const float* part, int spli
     }
 }
 
+// ------------------------------------------------------------------ the plan (host only; dp_linkpred_plan)
+// dynamic LDS of the two kernels, shared by the launchers' constants and the plan
+constexpr size_t lk_fwd_lds(int kt) { return ((size_t)2 * 64 * (kt * 16 + 2) + 4) * sizeof(float); }
+constexpr size_t lk_bwd_lds(int kt, int cw, bool col_lds) {
+    return ((size_t)(64 + cw) * (kt * 16 + 2) + 64 * (cw + 4) + (col_lds ? cw * 65 : 0)) * sizeof(float);
+}
+
+// Everything link_fwd / link_bwd decide from (B, n, K), the same for both readers.  Small batches split the backward's
+// column tiles over extra workgroups (>= ~512 in all) whose partials k_link_reduce sums afterwards; splits == 1 is the
+// non-split form (no partials, k_link_bwd stores dS itself).  K > 256: kt = 0 and false; the sizes are still filled
+// in (as for the widest walk), so that a workspace query answers before the launchers refuse.
+bool linkpred_plan(int B, int n, int K, LinkPlan& p) {
+    p.kt = lk_kt(K);
+    p.cw = p.kt >= 12 ? 32 : 64;
+    p.col_tiles = (n + p.cw - 1) / p.cw;
+    const long base_wgs = (long)((n + 63) / 64) * B;
+    int splits = (int)((512 + base_wgs - 1) / base_wgs);
+    splits = splits < 1 ? 1 : (splits > p.col_tiles ? p.col_tiles : splits);
+    p.split_tiles = (p.col_tiles + splits - 1) / splits;
+    p.splits = (p.col_tiles + p.split_tiles - 1) / p.split_tiles;
+    p.fwd_tiles = ((n + 63) / 64) * ((n + 63) / 64);
+    p.fwd_lds = p.kt ? lk_fwd_lds(p.kt) : 0;
+    p.bwd_lds = p.kt ? lk_bwd_lds(p.kt, p.cw, LkAdjF32::kColLds) : 0;
+    return p.kt != 0;
+}
+
 // every instantiation is raised once per device to what it can ever need (static + dynamic LDS stay within 160 KiB)
 
 template <int KT, class Adj>
 static void launch_link_fwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num_nodes, int B, int n, int K,
                             int tiles, float* partial) {
-    constexpr size_t bytes = ((size_t)2 * 64 * (KT * 16 + 2) + 4) * sizeof(float);
+    constexpr size_t bytes = lk_fwd_lds(KT);
     static DynLdsOnce attr;
     if (bytes > 64 * 1024)
         ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_link_fwd<KT, Adj>), (int)bytes, "k_link_fwd");
@@ -380,11 +406,12 @@ template <class Adj>
 static void link_fwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num_nodes, float* loss_out, int B, int n,
                      int K, const float* norm) {
     if (q.err) return;
-    const int tiles = (n + 63) / 64;
-    float* partial = q.alloc<float>((size_t)B * tiles * tiles);
+    LinkPlan plan;
+    const bool fits = linkpred_plan(B, n, K, plan);
+    const int tiles = (n + 63) / 64, kt = plan.kt;
+    float* partial = q.alloc<float>((size_t)B * plan.fwd_tiles);
     if (!q.ok()) return;
-    const int kt = lk_kt(K);
-    if (!kt) {
+    if (!fits) {
         set_error("linkpred: K=%d clusters exceed the fused tile kernel (max 256)", K);
         q.err = DP_ERR_UNSUPPORTED;
         return;
@@ -403,8 +430,8 @@ template <int KT, int NJ, class Adj>
 static void launch_link_bwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num_nodes, const float* scale,
                             float* dS, int ldds, int B, int n, int K, int accumulate, float* part, int splits,
                             int split_tiles) {
-    constexpr int CW = 32 * NJ, KP = KT * 16 + 2;
-    constexpr size_t bytes = ((size_t)(64 + CW) * KP + 64 * (CW + 4) + (Adj::kColLds ? CW * 65 : 0)) * sizeof(float);
+    constexpr int CW = 32 * NJ;
+    constexpr size_t bytes = lk_bwd_lds(KT, CW, Adj::kColLds);
     static_assert(bytes <= 160 * 1024, "link_bwd LDS");
     static DynLdsOnce attr;
     if (bytes > 64 * 1024)
@@ -419,18 +446,12 @@ static void link_bwd(Seq& q, const float* S, int lds_ld, Adj adj, const int* num
                      int ldds, int B, int n, int K, int accumulate, const float* norm) {
     if (q.err) return;
     float* scale = q.alloc<float>(64);
-    const int kt = lk_kt(K);
-    // small batches: split the column tiles over extra workgroups (>= ~512 in all) and sum the partials afterwards
-    const int cw = kt >= 12 ? 32 : 64;
-    const int col_tiles = (n + cw - 1) / cw;
-    const long base_wgs = (long)((n + 63) / 64) * B;
-    int splits = (int)((512 + base_wgs - 1) / base_wgs);
-    splits = splits < 1 ? 1 : (splits > col_tiles ? col_tiles : splits);
-    const int split_tiles = (col_tiles + splits - 1) / splits;
-    splits = (col_tiles + split_tiles - 1) / split_tiles;
+    LinkPlan plan;
+    const bool fits = linkpred_plan(B, n, K, plan);
+    const int kt = plan.kt, splits = plan.splits, split_tiles = plan.split_tiles;
     float* part = splits > 1 ? q.alloc<float>((size_t)splits * B * n * K) : nullptr;
     if (!q.ok()) return;
-    if (!kt) {
+    if (!fits) {
         set_error("linkpred backward: K=%d clusters exceed the fused tile kernel (max 256)", K);
         q.err = DP_ERR_UNSUPPORTED;
         return;

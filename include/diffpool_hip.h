@@ -393,7 +393,23 @@ int dp_colsum_batched(const float* X, int ldx, long strideX, int rows, int cols,
  * The adjacency comes either as the dense fp32 batch adj [B,n,n] or, in the _packed entries, in the packed form of
  * dp_adj_pack / dp_build_batch_packed: bf16 rows [B, n, dp_adj_pack_ld(n)] of A (adj_pk) and of A^T (adj_pkt; the same
  * buffer for a symmetric adjacency), both 16-byte aligned.  The two forms run the same tile walk, so on a bf16-exact
- * adjacency (0/1) they give bit-identical loss and dS.  dp_linkpred_workspace_bytes covers both forms. */
+ * adjacency (0/1) they give bit-identical loss and dS.  dp_linkpred_workspace_bytes covers both forms.
+ * n_b = num_nodes[b] clamped to n (NULL: n).  A graph with n_b = 0 beside non-empty ones contributes nothing to the loss
+ * or to the normaliser, and its rows of dS are exactly 0 (left as they were under accumulate); a batch whose every n_b is
+ * 0 has no normaliser and is not a valid input.
+ *
+ * dp_linkpred_plan(B, n, K): the kernels and the split that shape runs, answered by the host function the launchers
+ * themselves decide with.  Host only: no GPU call; the same for both adjacency forms.
+ * plan_out[DP_LINKPRED_PLAN_INTS] = { KT (the kernels' K tier: 16-column tiles, one of 1 2 3 4 6 8 12 16), CW (width of
+ * the column tiles the backward walks: 64, or 32 for KT >= 12), col_tiles = ceil(n / CW), splits (column ranges the
+ * backward's grid is split into so that a small batch still fills the chip, aiming at 512 workgroups; 1 = the non-split
+ * form: no gradient partials, no reduce pass), split_tiles (column tiles per split; the last split may hold fewer),
+ * forward workgroups (= loss partials) per graph = ceil(n / 64)^2, the forward kernel's dynamic LDS bytes, the backward
+ * kernel's dynamic LDS bytes }.  The backward figure is the fp32 reader's: the packed reader holds no transposed A tile
+ * in LDS and needs CW * 65 * 4 bytes less.  DP_ERR_UNSUPPORTED for K > 256, DP_ERR_INVALID_ARG for a NULL plan_out or
+ * B, n, K < 1. */
+#define DP_LINKPRED_PLAN_INTS 8
+int dp_linkpred_plan(int B, int n, int K, int* plan_out);
 size_t dp_linkpred_workspace_bytes(int B, int n, int K);
 int dp_linkpred_loss_fwd(const float* S, const float* adj, const int* num_nodes, float* loss_out, int B,
                          int n, int K, void* workspace, size_t workspace_bytes, void* stream);

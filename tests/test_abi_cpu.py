@@ -124,6 +124,20 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     assert lib.dp_adj_aggregate_plan(20, 500, 40, 0, 0, 0, 0, 0.0, plan) == 0
     assert tuple(plan)[:6] == (_lib.AGG_FORM_PANEL_F32, 3, 32, 16, 320, 66048)
     assert lib.dp_adj_aggregate_plan(20, 500, 40, 0, 0, 0, 0, 0.0, None) == -1 and b"NULL" in lib.dp_last_error_string()
+    # the link loss's plan query (host only): the pinned plans of five shapes, then its refusals
+    assert "dp_linkpred_plan" in _lib.EXPORTED_SYMBOLS
+    lp = (C.c_int * _lib.LINKPRED_PLAN_INTS)()
+    for shape, want in (((20, 500, 50), (4, 64, 8, 4, 2)), ((1, 260, 256), (16, 32, 9, 9, 1)),
+                        ((256, 128, 8), (1, 64, 2, 1, 2)), ((512, 64, 192), (12, 32, 2, 1, 2)),
+                        ((30, 321, 20), (2, 64, 6, 3, 2))):
+        assert lib.dp_linkpred_plan(*shape, lp) == 0 and tuple(lp)[:5] == want, (shape, tuple(lp))
+    assert lib.dp_linkpred_plan(20, 500, 50, lp) == 0
+    assert tuple(lp)[5:] == (64, 4 * (2 * 64 * 66 + 4), 4 * (128 * 66 + 64 * 68 + 64 * 65))
+    assert lib.dp_linkpred_plan(20, 500, 257, lp) == -3 and b"K=257" in lib.dp_last_error_string()
+    assert lib.dp_linkpred_plan(20, 500, 256, lp) == 0 and tuple(lp)[:2] == (16, 32)
+    assert lib.dp_linkpred_plan(20, 500, 50, None) == -1 and b"NULL" in lib.dp_last_error_string()
+    for bad in ((0, 500, 50), (20, 0, 50), (20, 500, 0), (-1, 500, 50)):
+        assert lib.dp_linkpred_plan(*bad, lp) == -1 and b"must be positive" in lib.dp_last_error_string(), bad
     yp = _lib.GroupPtrs()
     rc = lib.dp_adj_aggregate_rownorm(None, None, None, None, None, 16, None, C.byref(g), None, C.byref(yp), None, None,
                                       1, 4, 1, 0, 0, None, 0, None)

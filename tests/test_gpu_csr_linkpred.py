@@ -4,8 +4,9 @@ n x n adjacency): the op against the direct formula in float64 on a densified ad
 against the oracle's dense restatement (PARITY UNPINNED by the reference, which drops such graphs, load_data.py:79),
 against the dense class, and as a bit-reproducible training loop.
 
-Tolerances are those of the dense link-loss test: loss rtol 1e-5 / atol 1e-6, dS rtol 1e-3 with an absolute floor of
-2e-5 x the largest reference entry.  Every op case first shows that the direct fp32 formula (the oracle's
+Tolerances are those of the dense link-loss test (test_gpu_ops.py::test_linkpred_loss): loss rtol 1e-5 / atol 1e-6,
+dS rtol 1e-3 with an absolute floor of 2e-5 x the largest reference entry.  The dense kernels this file compares with
+are themselves anchored to float64, at counted bounds, by tests/test_gpu_linkpred_matrix.py.  Every op case first shows that the direct fp32 formula (the oracle's
 link_pred_loss) meets the same tolerance against float64 on that input: where it does not, the input is wrong for a
 tolerance test (fp32 resolves 1 - p to 6e-8 when assignments are sharp) and belongs to the anchored test below."""
 import numpy as np

@@ -470,6 +470,8 @@ def test_masked_max(lib):
 
 
 # ------------------------------------------------------------------ A8 link loss
+# A first check against the fp32 torch oracle at loose tolerances.  The anchor of these kernels is
+# tests/test_gpu_linkpred_matrix.py: every K tier, tile edge and backward plan against float64 at counted bounds.
 @pytest.mark.parametrize("B,n,K", [(3, 16, 4), (2, 100, 10), (3, 200, 20), (2, 150, 40), (2, 132, 50), (2, 130, 90),
                                    (1, 200, 128), (1, 140, 150), (1, 260, 256)])
 def test_linkpred_loss(lib, B, n, K):
