@@ -14,7 +14,7 @@ mkdir -p $BUILD
 pids=()
 for s in $SRCS; do
   o=$BUILD/${s%.hip}.o
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ dp_common.h -nt "$o" ] || [ dp_link_tiles.h -nt "$o" ] || [ ../../include/diffpool_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ dp_common.h -nt "$o" ] || [ dp_entry.h -nt "$o" ] || [ dp_link_tiles.h -nt "$o" ] || [ ../../include/diffpool_hip.h -nt "$o" ]; then
     hipcc $FLAGS -c "$s" -o "$o" &
     pids+=($!)
   fi

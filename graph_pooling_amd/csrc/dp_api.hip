@@ -3,7 +3,7 @@
 
 #include <cmath>
 
-#include "dp_common.h"
+#include "dp_entry.h"
 
 namespace dp {
 
@@ -979,55 +979,53 @@ int dp_assign_entropy_bwd(const float* S, int lds, const int* num_nodes, const f
 }
 
 // ------------------------------------------------------------------ Frobenius link loss
-#define FROB_K(fn)                                                                                             \
-    do {                                                                                                       \
-        if (K > 256) {                                                                                         \
-            set_error(fn ": K=%d clusters: the Frobenius link kernels support K <= 256", K);                   \
-            return DP_ERR_UNSUPPORTED;                                                                         \
-        }                                                                                                      \
-    } while (0)
-#define FROB_WS(fn, need)                                                                                      \
-    do {                                                                                                       \
-        NOTNULL(workspace);                                                                                    \
-        DP_CHECK_ARG(workspace_bytes >= (need), fn ": workspace too small: need >= %zu bytes, have %zu", (need), \
-                     workspace_bytes);                                                                         \
+// The checked bodies below serve every exported name of their op; `fn` is that name, for the messages.
+#define FROB_K_OK(fn) \
+    DP_CHECK(K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d clusters: the Frobenius link kernels support K <= 256", fn, K)
+#define FROB_WS_OK(fn, need)                                                                                      \
+    do {                                                                                                          \
+        DP_NOTNULL(workspace);                                                                                    \
+        DP_CHECK(workspace_bytes >= (need), DP_ERR_INVALID_ARG, "%s: workspace too small: need >= %zu bytes, have %zu", \
+                 fn, (need), workspace_bytes);                                                                    \
     } while (0)
 
 size_t dp_frob_link_workspace_bytes(int B, int N, int K) {
     if (B < 1 || N < 1 || K < 1 || K > 256) return 0;
     return frob_link_ws_doubles((long long)B * N, B, K) * sizeof(double) + 3 * 256 + 256;
 }
-static int frob_link_fwd_dense(const char* fn, const float* S, int lds, const void* adj, const void* adj_t, int packed,
-                               const int* num_nodes, const float* link_norm, float* W, float* G, float* loss_out,
-                               float* total_inout, int B, int N, int K, void* workspace, size_t workspace_bytes,
-                               void* stream) {
+// adj_pk / adj_pkt: the packed planes, or (packed == 0) the fp32 adjacency and NULL
+static int frob_link_fwd_dense(const char* fn, const float* S, int lds, const void* adj_pk, const void* adj_pkt,
+                               int packed, const int* num_nodes, const float* link_norm, float* W, float* G,
+                               float* loss_out, float* total_inout, int B, int N, int K, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    DP_NOTNULL(S);
+    DP_CHECK(adj_pk != nullptr, DP_ERR_INVALID_ARG, "%s is NULL", packed ? "adj_pk" : "adj");
+    if (packed) DP_NOTNULL(adj_pkt);
+    DP_NOTNULL(W); DP_NOTNULL(G); DP_NOTNULL(loss_out);
+    NONNEG(B); NONNEG(N); NONNEG(K);
+    FROB_K_OK(fn);
+    DP_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", fn, lds, K);
+    if (packed) {
+        DP_ALIGNED16(adj_pk, true, "adj_pk is not 16-byte aligned");
+        DP_ALIGNED16(adj_pkt, true, "adj_pkt is not 16-byte aligned");
+    }
+    FROB_WS_OK(fn, dp_frob_link_workspace_bytes(B, N, K));
     Seq q(STREAM(stream), workspace, workspace_bytes);
     const int ld = packed ? adj_pack_ld(N) : N;
-    frob_link_w_dense(q, S, lds, adj, adj_t, packed, ld, num_nodes, W, B, N, K);
-    frob_link_fwd(q, S, lds, W, adj, packed ? 3 : 1, ld, num_nodes, nullptr, nullptr, link_norm, 1.f, G, loss_out,
+    frob_link_w_dense(q, S, lds, adj_pk, adj_pkt, packed, ld, num_nodes, W, B, N, K);
+    frob_link_fwd(q, S, lds, W, adj_pk, packed ? 3 : 1, ld, num_nodes, nullptr, nullptr, link_norm, 1.f, G, loss_out,
                   total_inout, B, N, (long long)B * N, K);
     return q.err;
 }
 int dp_frob_link_fwd(const float* S, int lds, const float* adj, const int* num_nodes, const float* link_norm, float* W,
                      float* G, float* loss_out, float* total_inout, int B, int N, int K, void* workspace,
                      size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(adj); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
-    NONNEG(B); NONNEG(N); NONNEG(K);
-    FROB_K("dp_frob_link_fwd");
-    DP_CHECK_ARG(lds >= K, "dp_frob_link_fwd: lds=%d smaller than K=%d", lds, K);
-    FROB_WS("dp_frob_link_fwd", dp_frob_link_workspace_bytes(B, N, K));
     return frob_link_fwd_dense("dp_frob_link_fwd", S, lds, adj, nullptr, 0, num_nodes, link_norm, W, G, loss_out,
                                total_inout, B, N, K, workspace, workspace_bytes, stream);
 }
 int dp_frob_link_fwd_packed(const float* S, int lds, const void* adj_pk, const void* adj_pkt, const int* num_nodes,
                             const float* link_norm, float* W, float* G, float* loss_out, float* total_inout, int B, int N,
                             int K, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(adj_pk); NOTNULL(adj_pkt); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
-    NONNEG(B); NONNEG(N); NONNEG(K);
-    FROB_K("dp_frob_link_fwd_packed");
-    DP_CHECK_ARG(lds >= K, "dp_frob_link_fwd_packed: lds=%d smaller than K=%d", lds, K);
-    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
-    FROB_WS("dp_frob_link_fwd_packed", dp_frob_link_workspace_bytes(B, N, K));
     return frob_link_fwd_dense("dp_frob_link_fwd_packed", S, lds, adj_pk, adj_pkt, 1, num_nodes, link_norm, W, G,
                                loss_out, total_inout, B, N, K, workspace, workspace_bytes, stream);
 }
@@ -1036,7 +1034,7 @@ int dp_frob_link_bwd(const float* S, int lds, const float* W, const float* G, co
                      void* stream) {
     NOTNULL(S); NOTNULL(W); NOTNULL(G); NOTNULL(dS);
     NONNEG(B); NONNEG(N); NONNEG(K);
-    FROB_K("dp_frob_link_bwd");
+    FROB_K_OK("dp_frob_link_bwd");
     DP_CHECK_ARG(lds >= K, "dp_frob_link_bwd: lds=%d smaller than K=%d", lds, K);
     DP_CHECK_ARG(ldds >= K, "dp_frob_link_bwd: ldds=%d smaller than K=%d", ldds, K);
     Seq q(STREAM(stream), nullptr, 0);
@@ -1054,11 +1052,29 @@ size_t dp_csr_frob_link_workspace_bytes(int n_total, int B, int K) {
     if (n_total < 1 || B < 1 || K < 1 || K > 256) return 0;
     return frob_link_ws_doubles(n_total, B, K) * sizeof(double) + 3 * 256 + 256;
 }
-static int csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
-                             const int* indices_t, const int* node_off, const float* link_norm, float* W, float* G,
+// batch: node_off and B are the caller's and n its n_total; else one graph of n rows (node_off NULL, B = 1)
+static int csr_frob_link_fwd(const char* fn, bool batch, const float* S, int lds, const int* indptr, const int* indices,
+                             const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
+                             bool weighted, const int* node_off, const float* link_norm, float* W, float* G,
                              float* loss_out, float* total_inout, int B, int n, int K, void* workspace,
-                             size_t workspace_bytes, void* stream, const float* values = nullptr,
-                             const float* values_t = nullptr) {
+                             size_t workspace_bytes, void* stream) {
+    DP_NOTNULL(S); DP_NOTNULL(indptr); DP_NOTNULL(indices);
+    DP_VALUES((void)0, "values is NULL");
+    if (batch) DP_NOTNULL(node_off);
+    DP_NOTNULL(W); DP_NOTNULL(G); DP_NOTNULL(loss_out);
+    if (batch) NONNEG(B);
+    DP_CHECK(n > 0, DP_ERR_INVALID_ARG, "%s=%d must be positive", batch ? "n_total" : "n", n);
+    NONNEG(K);
+    FROB_K_OK(fn);
+    if (batch)
+        DP_CHECK(B <= n, DP_ERR_INVALID_ARG, "%s: B=%d graphs over n_total=%d rows (every graph has >= 1 node)", fn, B, n);
+    DP_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", fn, lds, K);
+    DP_CHECK((indptr_t == nullptr) == (indices_t == nullptr), DP_ERR_INVALID_ARG,
+             "%s: indptr_t and indices_t go together (both NULL: undirected)", fn);
+    DP_VALUES_T((void)0, "%s: values_t is NULL but indices_t is a CSR of its own", fn);
+    FROB_WS_OK(fn, dp_csr_frob_link_workspace_bytes(n, B, K));
+    if (!weighted) values = nullptr;
+    values_t = weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr;
     Seq q(STREAM(stream), workspace, workspace_bytes);
     const bool directed = indptr_t && indices_t && !(indptr_t == indptr && indices_t == indices);
     csr_aggregate_fwd(q, S, lds, indptr, indices, W, K, n, K, 0, 0.f, values);                       // W = A S
@@ -1071,98 +1087,68 @@ static int csr_frob_link_fwd(const float* S, int lds, const int* indptr, const i
                       loss_out, total_inout, B, n, n, K);
     return q.err;
 }
+static int csr_frob_link_bwd(const char* fn, bool batch, const float* S, int lds, const float* W, const float* G,
+                             const int* node_off, const float* link_norm, const float* dloss, float* dS, int ldds,
+                             int accumulate, int symmetric, int B, int n, int K, void* stream) {
+    DP_NOTNULL(S); DP_NOTNULL(W); DP_NOTNULL(G);
+    if (batch) DP_NOTNULL(node_off);
+    DP_NOTNULL(dS);
+    if (batch) NONNEG(B);
+    DP_CHECK(n > 0, DP_ERR_INVALID_ARG, "%s=%d must be positive", batch ? "n_total" : "n", n);
+    NONNEG(K);
+    FROB_K_OK(fn);
+    DP_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", fn, lds, K);
+    DP_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", fn, ldds, K);
+    Seq q(STREAM(stream), nullptr, 0);
+    frob_link_bwd(q, S, lds, W, G, nullptr, node_off, link_norm, dloss, symmetric ? 2.f : 1.f, dS, ldds, accumulate, B, n,
+                  n, K);
+    return q.err;
+}
 int dp_csr_frob_link_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                          const int* indices_t, const float* link_norm, float* W, float* G, float* loss_out,
                          float* total_inout, int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
-    NONNEG(n); NONNEG(K);
-    FROB_K("dp_csr_frob_link_fwd");
-    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_fwd: lds=%d smaller than K=%d", lds, K);
-    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
-                 "dp_csr_frob_link_fwd: indptr_t and indices_t go together (both NULL: undirected)");
-    FROB_WS("dp_csr_frob_link_fwd", dp_csr_frob_link_workspace_bytes(n, 1, K));
-    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, nullptr, link_norm, W, G, loss_out,
-                             total_inout, 1, n, K, workspace, workspace_bytes, stream);
+    return csr_frob_link_fwd("dp_csr_frob_link_fwd", false, S, lds, indptr, indices, nullptr, indptr_t, indices_t,
+                             nullptr, false, nullptr, link_norm, W, G, loss_out, total_inout, 1, n, K, workspace,
+                             workspace_bytes, stream);
 }
 int dp_csr_frob_link_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
                            const int* indptr_t, const int* indices_t, const float* values_t, const float* link_norm,
                            float* W, float* G, float* loss_out, float* total_inout, int n, int K, void* workspace,
                            size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
-    NONNEG(n); NONNEG(K);
-    FROB_K("dp_csr_frob_link_fwd_w");
-    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_fwd_w: lds=%d smaller than K=%d", lds, K);
-    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
-                 "dp_csr_frob_link_fwd_w: indptr_t and indices_t go together (both NULL: undirected)");
-    DP_CHECK_ARG(!indices_t || indices_t == indices || values_t,
-                 "dp_csr_frob_link_fwd_w: values_t is NULL but indices_t is a CSR of its own");
-    FROB_WS("dp_csr_frob_link_fwd_w", dp_csr_frob_link_workspace_bytes(n, 1, K));
-    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, nullptr, link_norm, W, G, loss_out,
-                             total_inout, 1, n, K, workspace, workspace_bytes, stream, values,
-                             indices_t && indices_t != indices ? values_t : values);
+    return csr_frob_link_fwd("dp_csr_frob_link_fwd_w", false, S, lds, indptr, indices, values, indptr_t, indices_t,
+                             values_t, true, nullptr, link_norm, W, G, loss_out, total_inout, 1, n, K, workspace,
+                             workspace_bytes, stream);
 }
 int dp_csr_frob_link_bwd(const float* S, int lds, const float* W, const float* G, const float* link_norm,
                          const float* dloss, float* dS, int ldds, int accumulate, int symmetric, int n, int K,
                          void* stream) {
-    NOTNULL(S); NOTNULL(W); NOTNULL(G); NOTNULL(dS);
-    NONNEG(n); NONNEG(K);
-    FROB_K("dp_csr_frob_link_bwd");
-    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_bwd: lds=%d smaller than K=%d", lds, K);
-    DP_CHECK_ARG(ldds >= K, "dp_csr_frob_link_bwd: ldds=%d smaller than K=%d", ldds, K);
-    Seq q(STREAM(stream), nullptr, 0);
-    frob_link_bwd(q, S, lds, W, G, nullptr, nullptr, link_norm, dloss, symmetric ? 2.f : 1.f, dS, ldds, accumulate, 1, n,
-                  n, K);
-    return q.err;
+    return csr_frob_link_bwd("dp_csr_frob_link_bwd", false, S, lds, W, G, nullptr, link_norm, dloss, dS, ldds,
+                             accumulate, symmetric, 1, n, K, stream);
 }
 int dp_csr_frob_link_batch_fwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                                const int* indices_t, const int* node_off, const float* link_norm, float* W, float* G,
                                float* loss_out, float* total_inout, int B, int n_total, int K, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(node_off); NOTNULL(W); NOTNULL(G); NOTNULL(loss_out);
-    NONNEG(B); NONNEG(n_total); NONNEG(K);
-    FROB_K("dp_csr_frob_link_batch_fwd");
-    DP_CHECK_ARG(B <= n_total, "dp_csr_frob_link_batch_fwd: B=%d graphs over n_total=%d rows (every graph has >= 1 node)",
-                 B, n_total);
-    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_batch_fwd: lds=%d smaller than K=%d", lds, K);
-    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
-                 "dp_csr_frob_link_batch_fwd: indptr_t and indices_t go together (both NULL: undirected)");
-    FROB_WS("dp_csr_frob_link_batch_fwd", dp_csr_frob_link_workspace_bytes(n_total, B, K));
-    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, node_off, link_norm, W, G, loss_out,
-                             total_inout, B, n_total, K, workspace, workspace_bytes, stream);
+    return csr_frob_link_fwd("dp_csr_frob_link_batch_fwd", true, S, lds, indptr, indices, nullptr, indptr_t, indices_t,
+                             nullptr, false, node_off, link_norm, W, G, loss_out, total_inout, B, n_total, K, workspace,
+                             workspace_bytes, stream);
 }
 int dp_csr_frob_link_batch_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
                                  const int* indptr_t, const int* indices_t, const float* values_t, const int* node_off,
                                  const float* link_norm, float* W, float* G, float* loss_out, float* total_inout, int B,
                                  int n_total, int K, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(node_off); NOTNULL(W); NOTNULL(G);
-    NOTNULL(loss_out);
-    NONNEG(B); NONNEG(n_total); NONNEG(K);
-    FROB_K("dp_csr_frob_link_batch_fwd_w");
-    DP_CHECK_ARG(B <= n_total, "dp_csr_frob_link_batch_fwd_w: B=%d graphs over n_total=%d rows (every graph has >= 1 node)",
-                 B, n_total);
-    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_batch_fwd_w: lds=%d smaller than K=%d", lds, K);
-    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr),
-                 "dp_csr_frob_link_batch_fwd_w: indptr_t and indices_t go together (both NULL: undirected)");
-    DP_CHECK_ARG(!indices_t || indices_t == indices || values_t,
-                 "dp_csr_frob_link_batch_fwd_w: values_t is NULL but indices_t is a CSR of its own");
-    FROB_WS("dp_csr_frob_link_batch_fwd_w", dp_csr_frob_link_workspace_bytes(n_total, B, K));
-    return csr_frob_link_fwd(S, lds, indptr, indices, indptr_t, indices_t, node_off, link_norm, W, G, loss_out,
-                             total_inout, B, n_total, K, workspace, workspace_bytes, stream, values,
-                             indices_t && indices_t != indices ? values_t : values);
+    return csr_frob_link_fwd("dp_csr_frob_link_batch_fwd_w", true, S, lds, indptr, indices, values, indptr_t, indices_t,
+                             values_t, true, node_off, link_norm, W, G, loss_out, total_inout, B, n_total, K, workspace,
+                             workspace_bytes, stream);
 }
 int dp_csr_frob_link_batch_bwd(const float* S, int lds, const float* W, const float* G, const int* node_off,
                                const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate,
                                int symmetric, int B, int n_total, int K, void* stream) {
-    NOTNULL(S); NOTNULL(W); NOTNULL(G); NOTNULL(node_off); NOTNULL(dS);
-    NONNEG(B); NONNEG(n_total); NONNEG(K);
-    FROB_K("dp_csr_frob_link_batch_bwd");
-    DP_CHECK_ARG(lds >= K, "dp_csr_frob_link_batch_bwd: lds=%d smaller than K=%d", lds, K);
-    DP_CHECK_ARG(ldds >= K, "dp_csr_frob_link_batch_bwd: ldds=%d smaller than K=%d", ldds, K);
-    Seq q(STREAM(stream), nullptr, 0);
-    frob_link_bwd(q, S, lds, W, G, nullptr, node_off, link_norm, dloss, symmetric ? 2.f : 1.f, dS, ldds, accumulate, B,
-                  n_total, n_total, K);
-    return q.err;
+    return csr_frob_link_bwd("dp_csr_frob_link_batch_bwd", true, S, lds, W, G, node_off, link_norm, dloss, dS, ldds,
+                             accumulate, symmetric, B, n_total, K, stream);
 }
+#undef FROB_K_OK
+#undef FROB_WS_OK
 
 int dp_cross_entropy_fwd(const float* logits, const long long* label, float* loss_out, float* prob, int B, int C,
                          void* stream) {
@@ -1250,21 +1236,24 @@ int dp_bgemm_split_bf16(const float* A, const float* B, float* C, int batch, int
 }
 
 // ------------------------------------------------------------------ N4: CSR GraphConv
-int dp_csr_aggregate(const float* table, int ldt, const int* indptr, const int* indices, float* out, int ldo, int n_rows,
-                     int feat, int mean, float beta, void* stream) {
-    NOTNULL(table); NOTNULL(indptr); NOTNULL(indices); NOTNULL(out);
+static int csr_aggregate_entry(const float* table, int ldt, const int* indptr, const int* indices, const float* values,
+                               bool weighted, float* out, int ldo, int n_rows, int feat, int mean, float beta,
+                               void* stream) {
+    DP_NOTNULL(table); DP_NOTNULL(indptr); DP_NOTNULL(indices);
+    DP_VALUES((void)0, "values is NULL");
+    DP_NOTNULL(out);
     NONNEG(n_rows); NONNEG(feat);
     Seq q(STREAM(stream), nullptr, 0);
-    csr_aggregate_fwd(q, table, ldt, indptr, indices, out, ldo, n_rows, feat, mean, beta);
+    csr_aggregate_fwd(q, table, ldt, indptr, indices, out, ldo, n_rows, feat, mean, beta, weighted ? values : nullptr);
     return q.err;
+}
+int dp_csr_aggregate(const float* table, int ldt, const int* indptr, const int* indices, float* out, int ldo, int n_rows,
+                     int feat, int mean, float beta, void* stream) {
+    return csr_aggregate_entry(table, ldt, indptr, indices, nullptr, false, out, ldo, n_rows, feat, mean, beta, stream);
 }
 int dp_csr_aggregate_w(const float* table, int ldt, const int* indptr, const int* indices, const float* values,
                        float* out, int ldo, int n_rows, int feat, float beta, void* stream) {
-    NOTNULL(table); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(out);
-    NONNEG(n_rows); NONNEG(feat);
-    Seq q(STREAM(stream), nullptr, 0);
-    csr_aggregate_fwd(q, table, ldt, indptr, indices, out, ldo, n_rows, feat, 0, beta, values);
-    return q.err;
+    return csr_aggregate_entry(table, ldt, indptr, indices, values, true, out, ldo, n_rows, feat, 0, beta, stream);
 }
 namespace {
 void sparse_gcn_fwd_seq(Seq& q, const float* x, int ldx, const int* indptr, const int* indices, const float* W,
@@ -1307,57 +1296,66 @@ size_t dp_sparse_gcn_layer_workspace_bytes(int n, int Fin, int Fout) {
     });
     return f > b ? f : b;
 }
-int dp_sparse_gcn_layer_fwd(const float* x, int ldx, const int* indptr, const int* indices, const float* W,
-                            const float* bias, float* y, int ldy, float* ax, float* invnorm, int n, int Fin, int Fout,
-                            int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(x); NOTNULL(indptr); NOTNULL(indices); NOTNULL(W); NOTNULL(y); NOTNULL(ax); NOTNULL(invnorm);
+static int sparse_gcn_fwd_entry(const float* x, int ldx, const int* indptr, const int* indices, const float* values,
+                                bool weighted, const float* W, const float* bias, float* y, int ldy, float* ax,
+                                float* invnorm, int n, int Fin, int Fout, int flags, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    DP_NOTNULL(x); DP_NOTNULL(indptr); DP_NOTNULL(indices);
+    DP_VALUES((void)0, "values is NULL");
+    DP_NOTNULL(W); DP_NOTNULL(y); DP_NOTNULL(ax); DP_NOTNULL(invnorm);
     NONNEG(n); NONNEG(Fin); NONNEG(Fout);
     DP_CHECK_ARG(!(flags & DP_F_ADD_SELF) || ldx == Fin, "add_self needs a contiguous x (ldx == Fin)");
     Seq q(STREAM(stream), workspace, workspace_bytes);
-    sparse_gcn_fwd_seq(q, x, ldx, indptr, indices, W, bias, y, ldy, ax, invnorm, n, Fin, Fout, flags);
+    sparse_gcn_fwd_seq(q, x, ldx, indptr, indices, W, bias, y, ldy, ax, invnorm, n, Fin, Fout, flags,
+                       weighted ? values : nullptr);
     return q.err;
+}
+static int sparse_gcn_bwd_entry(const char* fn, const float* ax, const int* indptr, const int* indices,
+                                const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
+                                bool weighted, const float* W, const float* y, int ldy, const float* invnorm,
+                                const float* dy, int lddy, float* dx, int lddx, float* dW, float* db, int n, int Fin,
+                                int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    DP_NOTNULL(ax); DP_NOTNULL(indptr); DP_NOTNULL(indices);
+    DP_VALUES((void)0, "values is NULL");
+    DP_NOTNULL(W); DP_NOTNULL(y); DP_NOTNULL(invnorm); DP_NOTNULL(dy); DP_NOTNULL(dW);
+    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
+    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr), "indptr_t and indices_t come together");
+    DP_VALUES_T((void)0, "%s: values_t is NULL but indices_t is a CSR of its own", fn);
+    DP_CHECK_ARG(!dx || lddx == Fin, "dx must be contiguous (lddx == Fin)");
+    Seq q(STREAM(stream), workspace, workspace_bytes);
+    sparse_gcn_bwd_seq(q, ax, indptr, indices, indptr_t, indices_t, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n,
+                       Fin, Fout, flags, weighted ? values : nullptr,
+                       weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr);
+    return q.err;
+}
+int dp_sparse_gcn_layer_fwd(const float* x, int ldx, const int* indptr, const int* indices, const float* W,
+                            const float* bias, float* y, int ldy, float* ax, float* invnorm, int n, int Fin, int Fout,
+                            int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    return sparse_gcn_fwd_entry(x, ldx, indptr, indices, nullptr, false, W, bias, y, ldy, ax, invnorm, n, Fin, Fout,
+                                flags, workspace, workspace_bytes, stream);
+}
+int dp_sparse_gcn_layer_fwd_w(const float* x, int ldx, const int* indptr, const int* indices, const float* values,
+                              const float* W, const float* bias, float* y, int ldy, float* ax, float* invnorm, int n,
+                              int Fin, int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    return sparse_gcn_fwd_entry(x, ldx, indptr, indices, values, true, W, bias, y, ldy, ax, invnorm, n, Fin, Fout, flags,
+                                workspace, workspace_bytes, stream);
 }
 int dp_sparse_gcn_layer_bwd(const float* ax, const int* indptr, const int* indices, const int* indptr_t,
                             const int* indices_t, const float* W, const float* y, int ldy, const float* invnorm,
                             const float* dy, int lddy, float* dx, int lddx, float* dW, float* db, int n, int Fin,
                             int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(ax); NOTNULL(indptr); NOTNULL(indices); NOTNULL(W); NOTNULL(y); NOTNULL(invnorm); NOTNULL(dy); NOTNULL(dW);
-    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
-    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr), "indptr_t and indices_t come together");
-    DP_CHECK_ARG(!dx || lddx == Fin, "dx must be contiguous (lddx == Fin)");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    sparse_gcn_bwd_seq(q, ax, indptr, indices, indptr_t, indices_t, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n,
-                       Fin, Fout, flags);
-    return q.err;
-}
-
-int dp_sparse_gcn_layer_fwd_w(const float* x, int ldx, const int* indptr, const int* indices, const float* values,
-                              const float* W, const float* bias, float* y, int ldy, float* ax, float* invnorm, int n,
-                              int Fin, int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(x); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(W); NOTNULL(y); NOTNULL(ax);
-    NOTNULL(invnorm);
-    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
-    DP_CHECK_ARG(!(flags & DP_F_ADD_SELF) || ldx == Fin, "add_self needs a contiguous x (ldx == Fin)");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    sparse_gcn_fwd_seq(q, x, ldx, indptr, indices, W, bias, y, ldy, ax, invnorm, n, Fin, Fout, flags, values);
-    return q.err;
+    return sparse_gcn_bwd_entry("dp_sparse_gcn_layer_bwd", ax, indptr, indices, nullptr, indptr_t, indices_t, nullptr,
+                                false, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n, Fin, Fout, flags, workspace,
+                                workspace_bytes, stream);
 }
 int dp_sparse_gcn_layer_bwd_w(const float* ax, const int* indptr, const int* indices, const float* values,
                               const int* indptr_t, const int* indices_t, const float* values_t, const float* W,
                               const float* y, int ldy, const float* invnorm, const float* dy, int lddy, float* dx,
                               int lddx, float* dW, float* db, int n, int Fin, int Fout, int flags, void* workspace,
                               size_t workspace_bytes, void* stream) {
-    NOTNULL(ax); NOTNULL(indptr); NOTNULL(indices); NOTNULL(values); NOTNULL(W); NOTNULL(y); NOTNULL(invnorm);
-    NOTNULL(dy); NOTNULL(dW);
-    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
-    DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr), "indptr_t and indices_t come together");
-    DP_CHECK_ARG(!indices_t || indices_t == indices || values_t,
-                 "dp_sparse_gcn_layer_bwd_w: values_t is NULL but indices_t is a CSR of its own");
-    DP_CHECK_ARG(!dx || lddx == Fin, "dx must be contiguous (lddx == Fin)");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    sparse_gcn_bwd_seq(q, ax, indptr, indices, indptr_t, indices_t, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n,
-                       Fin, Fout, flags, values, indices_t && indices_t != indices ? values_t : values);
-    return q.err;
+    return sparse_gcn_bwd_entry("dp_sparse_gcn_layer_bwd_w", ax, indptr, indices, values, indptr_t, indices_t, values_t,
+                                true, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n, Fin, Fout, flags, workspace,
+                                workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------ model level

@@ -20,7 +20,7 @@
 // Every reduction has a fixed order and there are no float atomics: results are bit-reproducible run to run.
 #include <algorithm>
 
-#include "dp_common.h"
+#include "dp_entry.h"
 
 namespace dp {
 namespace {
@@ -29,8 +29,6 @@ constexpr float RB_BN_EPS = 1e-5f;      // BatchNorm1d eps (dp_rowops.hip BN_EPS
 constexpr float RB_L2_EPS = 1e-12f;     // F.normalize eps (dp_rowops.hip L2_EPS)
 constexpr int RB_WAVES = 4;             // node indices per 256-thread workgroup
 constexpr int SEG_ROW_LANES = 4;        // row lanes of a segment-max workgroup (x 64 feature lanes)
-
-inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 struct BnRaggedArgs {
     const float* x;         // [n_total, ldx] forward input (pre-ReLU)
@@ -307,25 +305,12 @@ void segment_max_part(Seq& q, const float* Z, int ldz, const int* chunk_tab, int
 
 using namespace dp;
 
-#define RB_CHECK(cond, code, ...)         \
-    do {                                  \
-        if (!(cond)) {                    \
-            ::dp::set_error(__VA_ARGS__); \
-            return code;                  \
-        }                                 \
-    } while (0)
-#define RB_PTR(p)                                                                             \
-    do {                                                                                      \
-        RB_CHECK((p) != nullptr, DP_ERR_INVALID_ARG, #p " is NULL");                          \
-        RB_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, #p " is not 4-byte aligned"); \
-    } while (0)
-
 namespace {
 int check_ragged(const char* entry, int B, int maxn, int F) {
-    RB_CHECK(B >= 1, DP_ERR_INVALID_ARG, "%s: B=%d must be positive", entry, B);
-    RB_CHECK(maxn >= 1, DP_ERR_INVALID_ARG, "%s: max_n=%d must be positive", entry, maxn);
-    RB_CHECK(F >= 1, DP_ERR_INVALID_ARG, "%s: F=%d must be positive", entry, F);
-    RB_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "%s: F=%d above the supported 2048", entry, F);
+    DP_CHECK(B >= 1, DP_ERR_INVALID_ARG, "%s: B=%d must be positive", entry, B);
+    DP_CHECK(maxn >= 1, DP_ERR_INVALID_ARG, "%s: max_n=%d must be positive", entry, maxn);
+    DP_CHECK(F >= 1, DP_ERR_INVALID_ARG, "%s: F=%d must be positive", entry, F);
+    DP_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "%s: F=%d above the supported 2048", entry, F);
     return DP_OK;
 }
 }  // namespace
@@ -339,9 +324,9 @@ size_t dp_bn_ragged_workspace_bytes(int max_n, int F) {
 
 int dp_bn_ragged_fwd(const float* x, int ldx, float* y, int ldy, float* stats, const int* node_off, const int* order,
                      const int* cnt, const float* pad, int B, int max_n, int F, int relu, void* stream) {
-    RB_PTR(x); RB_PTR(y); RB_PTR(stats); RB_PTR(node_off); RB_PTR(order); RB_PTR(cnt);
+    DP_PTR(x); DP_PTR(y); DP_PTR(stats); DP_PTR(node_off); DP_PTR(order); DP_PTR(cnt);
     if (int rc = check_ragged("dp_bn_ragged_fwd", B, max_n, F)) return rc;
-    RB_CHECK(ldx >= F && ldy >= F, DP_ERR_INVALID_ARG, "dp_bn_ragged_fwd: ldx=%d / ldy=%d smaller than F=%d", ldx, ldy, F);
+    DP_CHECK(ldx >= F && ldy >= F, DP_ERR_INVALID_ARG, "dp_bn_ragged_fwd: ldx=%d / ldy=%d smaller than F=%d", ldx, ldy, F);
     Seq q((hipStream_t)stream, nullptr, 0);
     BnRaggedArgs a{x, nullptr, nullptr, y, stats, node_off, order, cnt, pad, nullptr, ldx, ldy, 0, ldy, B, max_n, F,
                    relu ? 1 : 0};
@@ -354,11 +339,11 @@ int dp_bn_ragged_bwd(const float* x, int ldx, const float* y, int ldy, const flo
                      float* dx, int lddx, float* dpad, const int* node_off, const int* order, const int* cnt,
                      const float* pad, int B, int max_n, int F, int relu, void* workspace, size_t workspace_bytes,
                      void* stream) {
-    RB_PTR(y); RB_PTR(stats); RB_PTR(dy); RB_PTR(dx); RB_PTR(node_off); RB_PTR(order); RB_PTR(cnt);
-    RB_CHECK(!relu || x, DP_ERR_INVALID_ARG, "dp_bn_ragged_bwd: x is NULL but relu != 0");
-    RB_CHECK(!dpad || pad, DP_ERR_INVALID_ARG, "dp_bn_ragged_bwd: dpad asked for but pad is NULL");
+    DP_PTR(y); DP_PTR(stats); DP_PTR(dy); DP_PTR(dx); DP_PTR(node_off); DP_PTR(order); DP_PTR(cnt);
+    DP_CHECK(!relu || x, DP_ERR_INVALID_ARG, "dp_bn_ragged_bwd: x is NULL but relu != 0");
+    DP_CHECK(!dpad || pad, DP_ERR_INVALID_ARG, "dp_bn_ragged_bwd: dpad asked for but pad is NULL");
     if (int rc = check_ragged("dp_bn_ragged_bwd", B, max_n, F)) return rc;
-    RB_CHECK(ldy >= F && lddy >= F && lddx >= F && (!relu || ldx >= F), DP_ERR_INVALID_ARG,
+    DP_CHECK(ldy >= F && lddy >= F && lddx >= F && (!relu || ldx >= F), DP_ERR_INVALID_ARG,
              "dp_bn_ragged_bwd: a row stride is smaller than F=%d", F);
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     const int blocks = cdiv(max_n, RB_WAVES);
@@ -378,9 +363,9 @@ int dp_bn_ragged_bwd(const float* x, int ldx, const float* y, int ldy, const flo
 }
 
 int dp_gcn_pad_const_fwd(const float* bias, float* pad, int F, int flags, void* stream) {
-    RB_PTR(pad);
-    RB_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_pad_const_fwd: F=%d must be positive", F);
-    RB_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
+    DP_PTR(pad);
+    DP_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_pad_const_fwd: F=%d must be positive", F);
+    DP_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
              "dp_gcn_pad_const_fwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
     Seq q((hipStream_t)stream, nullptr, 0);
     hipLaunchKernelGGL(k_pad_const_fwd, dim3(1), dim3(256), 0, q.stream, bias, pad, F, (flags & DP_F_NORMALIZE) ? 1 : 0,
@@ -390,9 +375,9 @@ int dp_gcn_pad_const_fwd(const float* bias, float* pad, int F, int flags, void* 
 }
 
 int dp_gcn_pad_const_bwd(const float* bias, const float* dpad, float* dbias, int F, int flags, void* stream) {
-    RB_PTR(bias); RB_PTR(dpad); RB_PTR(dbias);
-    RB_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_pad_const_bwd: F=%d must be positive", F);
-    RB_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
+    DP_PTR(bias); DP_PTR(dpad); DP_PTR(dbias);
+    DP_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_pad_const_bwd: F=%d must be positive", F);
+    DP_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
              "dp_gcn_pad_const_bwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
     Seq q((hipStream_t)stream, nullptr, 0);
     hipLaunchKernelGGL(k_pad_const_bwd, dim3(1), dim3(256), 0, q.stream, bias, dpad, dbias, F,
@@ -402,9 +387,9 @@ int dp_gcn_pad_const_bwd(const float* bias, const float* dpad, float* dbias, int
 }
 
 int dp_gcn_row_const_fwd(const float* bias, float* c, int F, int flags, void* stream) {
-    RB_PTR(c);
-    RB_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_row_const_fwd: F=%d must be positive", F);
-    RB_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
+    DP_PTR(c);
+    DP_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_row_const_fwd: F=%d must be positive", F);
+    DP_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
              "dp_gcn_row_const_fwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
     Seq q((hipStream_t)stream, nullptr, 0);
     hipLaunchKernelGGL(k_pad_const_fwd, dim3(1), dim3(256), 0, q.stream, bias, c, F, (flags & DP_F_NORMALIZE) ? 1 : 0, 0);
@@ -413,9 +398,9 @@ int dp_gcn_row_const_fwd(const float* bias, float* c, int F, int flags, void* st
 }
 
 int dp_gcn_row_const_bwd(const float* bias, const float* dc, float* dbias, int F, int flags, void* stream) {
-    RB_PTR(bias); RB_PTR(dc); RB_PTR(dbias);
-    RB_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_row_const_bwd: F=%d must be positive", F);
-    RB_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
+    DP_PTR(bias); DP_PTR(dc); DP_PTR(dbias);
+    DP_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_gcn_row_const_bwd: F=%d must be positive", F);
+    DP_CHECK(!(flags & DP_F_ADD_SELF), DP_ERR_UNSUPPORTED,
              "dp_gcn_row_const_bwd: with DP_F_ADD_SELF a padded row is not a constant of the layer");
     Seq q((hipStream_t)stream, nullptr, 0);
     hipLaunchKernelGGL(k_pad_const_bwd, dim3(1), dim3(256), 0, q.stream, bias, dc, dbias, F,
@@ -432,11 +417,11 @@ size_t dp_segment_max_workspace_bytes(int n_chunks, int F) {
 int dp_segment_max_fwd(const float* Z, int ldz, const int* node_off, const int* chunk_tab, const int* chunk_off,
                        int n_chunks, const int* floor_flag, float* out, int ldo, int* argmax, int B, int F,
                        void* workspace, size_t workspace_bytes, void* stream) {
-    RB_PTR(Z); RB_PTR(node_off); RB_PTR(chunk_tab); RB_PTR(chunk_off); RB_PTR(out); RB_PTR(argmax);
-    RB_CHECK(B >= 1 && F >= 1 && n_chunks >= B, DP_ERR_INVALID_ARG,
+    DP_PTR(Z); DP_PTR(node_off); DP_PTR(chunk_tab); DP_PTR(chunk_off); DP_PTR(out); DP_PTR(argmax);
+    DP_CHECK(B >= 1 && F >= 1 && n_chunks >= B, DP_ERR_INVALID_ARG,
              "dp_segment_max_fwd: B=%d, F=%d, n_chunks=%d (every graph has at least one chunk)", B, F, n_chunks);
-    RB_CHECK(n_chunks <= 65535 && B <= 65535, DP_ERR_UNSUPPORTED, "dp_segment_max_fwd: more than 65535 chunks / graphs");
-    RB_CHECK(ldz >= F && ldo >= F, DP_ERR_INVALID_ARG, "dp_segment_max_fwd: ldz=%d / ldo=%d smaller than F=%d", ldz, ldo, F);
+    DP_CHECK(n_chunks <= 65535 && B <= 65535, DP_ERR_UNSUPPORTED, "dp_segment_max_fwd: more than 65535 chunks / graphs");
+    DP_CHECK(ldz >= F && ldo >= F, DP_ERR_INVALID_ARG, "dp_segment_max_fwd: ldz=%d / ldo=%d smaller than F=%d", ldz, ldo, F);
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     float* pv = q.alloc<float>((size_t)n_chunks * F);
     int* pi = q.alloc<int>((size_t)n_chunks * F);
@@ -452,9 +437,9 @@ int dp_segment_max_fwd(const float* Z, int ldz, const int* node_off, const int* 
 
 int dp_segment_max_bwd(const float* dout, int ldo, const int* argmax, const int* node_off, float* dZ, int lddz, int B,
                        int F, void* stream) {
-    RB_PTR(dout); RB_PTR(argmax); RB_PTR(node_off); RB_PTR(dZ);
-    RB_CHECK(B >= 1 && F >= 1, DP_ERR_INVALID_ARG, "dp_segment_max_bwd: B=%d, F=%d must be positive", B, F);
-    RB_CHECK(ldo >= F && lddz >= F, DP_ERR_INVALID_ARG, "dp_segment_max_bwd: ldo=%d / lddz=%d smaller than F=%d", ldo, lddz, F);
+    DP_PTR(dout); DP_PTR(argmax); DP_PTR(node_off); DP_PTR(dZ);
+    DP_CHECK(B >= 1 && F >= 1, DP_ERR_INVALID_ARG, "dp_segment_max_bwd: B=%d, F=%d must be positive", B, F);
+    DP_CHECK(ldo >= F && lddz >= F, DP_ERR_INVALID_ARG, "dp_segment_max_bwd: ldo=%d / lddz=%d smaller than F=%d", ldo, lddz, F);
     Seq q((hipStream_t)stream, nullptr, 0);
     hipLaunchKernelGGL(k_segment_max_bwd, dim3(cdiv((long)B * F, 256)), dim3(256), 0, q.stream, dout, ldo, argmax, F,
                        node_off, dZ, lddz, B, F);

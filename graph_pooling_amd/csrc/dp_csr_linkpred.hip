@@ -30,6 +30,7 @@
 // No float atomics anywhere and every reduction has a fixed order: loss and dS are bit-reproducible run to run.
 #include <algorithm>
 
+#include "dp_entry.h"
 #include "dp_link_tiles.h"
 
 namespace dp {
@@ -38,9 +39,6 @@ namespace {
 constexpr int LK_FWD_TARGET_WGS = 1024;   // dense forward: workgroups wanted (4 per CU) before column splits stop
 constexpr int LK_BWD_TARGET_WGS = 512;    // dense backward: as link_bwd (dp_linkpred.hip)
 constexpr int LK_TEAM_ROWS = 16;          // edge kernels: rows (16-lane teams) per 256-thread workgroup
-
-inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // fixed tree over the 256 threads of the workgroup
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
@@ -469,17 +467,6 @@ void csr_link_fwd_graph(Seq& q, const float* S, int lds, const int* indptr, cons
     else LK_EDGE_DISPATCH(k_csr_link_edge_fwd, v4, K, S, lds, indptr, indices, n, K, partial + n_dense);
     q.check_launch("csr_link_edge_fwd");
 }
-void csr_link_fwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
-                      int K, const float* values = nullptr) {
-    const int count = fwd_partials(n);
-    double* partial = q.alloc<double>((size_t)count);
-    if (!q.ok()) return;
-    csr_link_fwd_graph(q, S, lds, indptr, indices, n, K, partial, values);
-    if (!q.ok()) return;
-    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)partial, count,
-                       (double)n * (double)n, loss_out, (float*)nullptr, (const float*)nullptr);
-    q.check_launch("csr_link_final");
-}
 
 template <int KT, int NJ>
 void launch_dense_bwd(Seq& q, const float* S, int lds, const float* scale, float* dS, int ldds, int n, int K,
@@ -506,23 +493,6 @@ size_t bwd_part_floats(int n, int K, int* splits_out, int* split_tiles_out) {
     if (splits_out) *splits_out = splits;
     if (split_tiles_out) *split_tiles_out = split_tiles;
     return splits > 1 ? (size_t)splits * n * K : 0;
-}
-void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
-                        const int* indices_t, const float* scale, float* part, float* dS, int ldds, int accumulate,
-                        int n, int K, int directed, const float* values, const float* values_t);
-void csr_link_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
-                      const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n, int K,
-                      const float* values = nullptr, const float* values_t = nullptr) {
-    float* scale = q.alloc<float>(64);
-    float* part = nullptr;
-    if (const size_t pf = bwd_part_floats(n, K, nullptr, nullptr)) part = q.alloc<float>(pf);
-    if (!q.ok()) return;
-    hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)nullptr, 0,
-                       (double)n * (double)n, (float*)nullptr, scale, dloss);
-    q.check_launch("csr_link_scale");
-    const int directed = (indptr_t != indptr || indices_t != indices) ? 1 : 0;
-    csr_link_bwd_graph(q, S, lds, indptr, indices, indptr_t, indices_t, scale, part, dS, ldds, accumulate, n, K,
-                       directed, values, values_t);
 }
 // one graph's dS from the ready scale; `part`: bwd_part_floats(n, K) floats (null when that is 0)
 void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
@@ -558,15 +528,9 @@ void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, cons
     q.check_launch("csr_link_edge_bwd");
 }
 
-size_t sized_bytes(int n, int K) {
-    Seq f = Seq::sizing();
-    csr_link_fwd_seq(f, nullptr, K, nullptr, nullptr, nullptr, n, K);
-    Seq b = Seq::sizing();
-    csr_link_bwd_seq(b, nullptr, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, K, 0, n, K);
-    return std::max(f.ws_off, b.ws_off);
-}
-
-// ---- a ragged batch: loss = sum_b (graph b's sum) / sum_b n_b^2 (encoders.py:1326-1331).  Per-graph launches of the
+// ---- the launch sequences, written for a ragged batch: loss = sum_b (graph b's sum) / sum_b n_b^2
+// (encoders.py:1326-1331).  A lone graph of n rows is the batch B = 1, off = {0, n}: the single-graph entries build that
+// table on the stack and come here, so there is one forward and one backward sequence.  Per-graph launches of the
 // kernels above — the tile walk is n_b^2 work per graph anyway — into one partial array, one final launch for the
 // batch; the backward forms the scale once.  indptr is the batch's (row node_off[b] + i, GLOBAL edge offsets), the
 // column indices are graph-LOCAL.  Launch count grows with B (a batched tile table is the open item).
@@ -622,127 +586,72 @@ size_t batch_sized_bytes(const int* off, int B, int K) {
 
 using namespace dp;
 
-#define CL_CHECK(cond, code, ...)        \
-    do {                                 \
-        if (!(cond)) {                   \
-            ::dp::set_error(__VA_ARGS__); \
-            return code;                 \
-        }                                \
-    } while (0)
-#define CL_PTR(p)                                                                    \
-    do {                                                                             \
-        CL_CHECK((p) != nullptr, DP_ERR_INVALID_ARG, #p " is NULL");                 \
-        CL_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, #p " is not 4-byte aligned"); \
-    } while (0)
-
 namespace {
-int check_call(const char* entry, int n, int K, int lds, const void* workspace, size_t workspace_bytes) {
-    CL_CHECK(n >= 1, DP_ERR_INVALID_ARG, "%s: n=%d must be positive", entry, n);
-    CL_CHECK(K >= 1, DP_ERR_INVALID_ARG, "%s: K=%d must be positive", entry, K);
-    CL_CHECK(K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d clusters exceed the fused tile kernel (max 256)", entry, K);
-    CL_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", entry, lds, K);
-    CL_CHECK(workspace != nullptr && ((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG,
-             "%s: workspace is NULL or not 16-byte aligned", entry);
-    const size_t need = sized_bytes(n, K);
-    CL_CHECK(workspace_bytes >= need, DP_ERR_INVALID_ARG, "%s: workspace too small: need >= %zu bytes, have %zu", entry,
+
+// The checked bodies of all eight loss entries.  off_host: the batch's node offsets on the HOST; `single`: the caller
+// is a single-graph entry and off_host its {0, n}, so the refusals speak of n and of `indices`, not of the batch's
+// table and `indices_local`.
+int check_batch(const char* entry, bool single, const int* off, int B, int K, int lds, const void* workspace,
+                size_t workspace_bytes) {
+    if (single) {
+        DP_CHECK(off[1] >= 1, DP_ERR_INVALID_ARG, "%s: n=%d must be positive", entry, off[1]);
+    } else {
+        DP_CHECK(off != nullptr, DP_ERR_INVALID_ARG, "%s: node_off_host is NULL", entry);
+        DP_CHECK(B >= 1, DP_ERR_INVALID_ARG, "%s: B=%d must be positive", entry, B);
+    }
+    DP_CHECK(K >= 1, DP_ERR_INVALID_ARG, "%s: K=%d must be positive", entry, K);
+    DP_CHECK(K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d clusters exceed the fused tile kernel (max 256)", entry, K);
+    DP_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", entry, lds, K);
+    DP_CHECK(off[0] == 0, DP_ERR_INVALID_ARG, "%s: node_off[0] must be 0", entry);
+    for (int b = 0; b < B; ++b)
+        DP_CHECK(off[b + 1] > off[b], DP_ERR_INVALID_ARG, "%s: graph %d has no node (node_off must increase)", entry, b);
+    DP_ALIGNED16(workspace, false, "%s: workspace is NULL or not 16-byte aligned", entry);
+    const size_t need = batch_sized_bytes(off, B, K);
+    DP_CHECK(workspace_bytes >= need, DP_ERR_INVALID_ARG, "%s: workspace too small: need >= %zu bytes, have %zu", entry,
              need, workspace_bytes);
     return DP_OK;
 }
+// indices / indices_t under the name the entry's signature gives them
+#define LK_INDICES(p)                                                                                 \
+    do {                                                                                              \
+        const char* sfx_ = single ? "" : "_local";                                                    \
+        DP_CHECK((p) != nullptr, DP_ERR_INVALID_ARG, #p "%s is NULL", sfx_);                          \
+        DP_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, #p "%s is not 4-byte aligned", sfx_); \
+    } while (0)
+#define LK_ALIGNED4(p) DP_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, "%s: " #p " is not 4-byte aligned", entry)
+
+int link_fwd_entry(const char* entry, bool single, const float* S, int lds, const int* indptr, const int* indices,
+                   const float* values, bool weighted, const int* node_off_host, int B, float* loss_out, int K,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    DP_PTR(S); DP_PTR(indptr); LK_INDICES(indices); DP_PTR(loss_out);
+    DP_VALUES(LK_ALIGNED4(values), "%s: values is NULL", entry);
+    if (int rc = check_batch(entry, single, node_off_host, B, K, lds, workspace, workspace_bytes)) return rc;
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_batch_fwd_seq(q, S, lds, indptr, indices, node_off_host, B, loss_out, K, weighted ? values : nullptr);
+    return q.err;
+}
+int link_bwd_entry(const char* entry, bool single, const float* S, int lds, const int* indptr, const int* indices,
+                   const float* values, const int* indptr_t, const int* indices_t, const float* values_t, bool weighted,
+                   const int* node_off_host, int B, const float* dloss, float* dS, int ldds, int accumulate, int K,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    DP_PTR(S); DP_PTR(indptr); LK_INDICES(indices); DP_PTR(indptr_t); LK_INDICES(indices_t); DP_PTR(dS);
+    DP_VALUES(LK_ALIGNED4(values), "%s: values is NULL", entry);
+    DP_VALUES_T(LK_ALIGNED4(values_t), "%s: values_t is NULL but the transposed CSR is one of its own", entry);
+    DP_ALIGNED4(dloss);
+    if (int rc = check_batch(entry, single, node_off_host, B, K, lds, workspace, workspace_bytes)) return rc;
+    DP_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", entry, ldds, K);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_link_batch_bwd_seq(q, S, lds, indptr, indices, indptr_t, indices_t, node_off_host, B, dloss, dS, ldds, accumulate,
+                           K, weighted ? values : nullptr,
+                           weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr);
+    return q.err;
+}
+#undef LK_ALIGNED4
+#undef LK_INDICES
+
 }  // namespace
 
 extern "C" {
-
-size_t dp_csr_linkpred_workspace_bytes(int n, int K) {
-    if (n < 1 || K < 1 || K > 256) return 0;
-    return sized_bytes(n, K);
-}
-
-// a _w entry (weighted): values must be there; values_t next to a transposed CSR of its own
-#define CL_VALUES(entry)                                                                    \
-    do {                                                                                    \
-        if (weighted) {                                                                     \
-            CL_CHECK(values != nullptr, DP_ERR_INVALID_ARG, "%s: values is NULL", entry);   \
-            CL_CHECK(((uintptr_t)values & 3) == 0, DP_ERR_INVALID_ARG, "%s: values is not 4-byte aligned", entry); \
-        }                                                                                   \
-    } while (0)
-#define CL_VALUES_T(entry, ixt, ix)                                                         \
-    do {                                                                                    \
-        if (weighted && (ixt) != (ix)) {                                                    \
-            CL_CHECK(values_t != nullptr, DP_ERR_INVALID_ARG,                               \
-                     "%s: values_t is NULL but the transposed CSR is one of its own", entry); \
-            CL_CHECK(((uintptr_t)values_t & 3) == 0, DP_ERR_INVALID_ARG, "%s: values_t is not 4-byte aligned", entry); \
-        }                                                                                   \
-    } while (0)
-
-static int link_fwd_entry(const char* entry, const float* S, int lds, const int* indptr, const int* indices,
-                          const float* values, bool weighted, float* loss_out, int n, int K, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(loss_out);
-    CL_VALUES(entry);
-    if (int rc = check_call(entry, n, K, lds, workspace, workspace_bytes)) return rc;
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_fwd_seq(q, S, lds, indptr, indices, loss_out, n, K, weighted ? values : nullptr);
-    return q.err;
-}
-static int link_bwd_entry(const char* entry, const float* S, int lds, const int* indptr, const int* indices,
-                          const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
-                          bool weighted, const float* dloss, float* dS, int ldds, int accumulate, int n, int K,
-                          void* workspace, size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices); CL_PTR(indptr_t); CL_PTR(indices_t); CL_PTR(dS);
-    CL_VALUES(entry);
-    CL_VALUES_T(entry, indices_t, indices);
-    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
-    if (int rc = check_call(entry, n, K, lds, workspace, workspace_bytes)) return rc;
-    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", entry, ldds, K);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_bwd_seq(q, S, lds, indptr, indices, indptr_t, indices_t, dloss, dS, ldds, accumulate, n, K,
-                     weighted ? values : nullptr, weighted ? (indices_t != indices ? values_t : values) : nullptr);
-    return q.err;
-}
-
-int dp_csr_linkpred_loss_fwd(const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
-                             int K, void* workspace, size_t workspace_bytes, void* stream) {
-    return link_fwd_entry("dp_csr_linkpred_loss_fwd", S, lds, indptr, indices, nullptr, false, loss_out, n, K, workspace,
-                          workspace_bytes, stream);
-}
-int dp_csr_linkpred_loss_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
-                               float* loss_out, int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
-    return link_fwd_entry("dp_csr_linkpred_loss_fwd_w", S, lds, indptr, indices, values, true, loss_out, n, K, workspace,
-                          workspace_bytes, stream);
-}
-
-int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
-                             const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n,
-                             int K, void* workspace, size_t workspace_bytes, void* stream) {
-    return link_bwd_entry("dp_csr_linkpred_loss_bwd", S, lds, indptr, indices, nullptr, indptr_t, indices_t, nullptr,
-                          false, dloss, dS, ldds, accumulate, n, K, workspace, workspace_bytes, stream);
-}
-int dp_csr_linkpred_loss_bwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
-                               const int* indptr_t, const int* indices_t, const float* values_t, const float* dloss,
-                               float* dS, int ldds, int accumulate, int n, int K, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-    return link_bwd_entry("dp_csr_linkpred_loss_bwd_w", S, lds, indptr, indices, values, indptr_t, indices_t, values_t,
-                          true, dloss, dS, ldds, accumulate, n, K, workspace, workspace_bytes, stream);
-}
-
-// ---- the same loss on a ragged batch (node_off_host: int32 [B + 1] on the HOST)
-static int check_batch(const char* entry, const int* off, int B, int K, int lds, const void* workspace,
-                       size_t workspace_bytes) {
-    CL_CHECK(off != nullptr, DP_ERR_INVALID_ARG, "%s: node_off_host is NULL", entry);
-    CL_CHECK(B >= 1, DP_ERR_INVALID_ARG, "%s: B=%d must be positive", entry, B);
-    CL_CHECK(K >= 1, DP_ERR_INVALID_ARG, "%s: K=%d must be positive", entry, K);
-    CL_CHECK(K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d clusters exceed the fused tile kernel (max 256)", entry, K);
-    CL_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", entry, lds, K);
-    CL_CHECK(off[0] == 0, DP_ERR_INVALID_ARG, "%s: node_off[0] must be 0", entry);
-    for (int b = 0; b < B; ++b)
-        CL_CHECK(off[b + 1] > off[b], DP_ERR_INVALID_ARG, "%s: graph %d has no node (node_off must increase)", entry, b);
-    CL_CHECK(workspace != nullptr && ((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG,
-             "%s: workspace is NULL or not 16-byte aligned", entry);
-    const size_t need = batch_sized_bytes(off, B, K);
-    CL_CHECK(workspace_bytes >= need, DP_ERR_INVALID_ARG, "%s: workspace too small: need >= %zu bytes, have %zu", entry,
-             need, workspace_bytes);
-    return DP_OK;
-}
 
 size_t dp_csr_linkpred_batch_workspace_bytes(const int* node_off_host, int B, int K) {
     if (!node_off_host || B < 1 || K < 1 || K > 256 || node_off_host[0] != 0) return 0;
@@ -750,65 +659,69 @@ size_t dp_csr_linkpred_batch_workspace_bytes(const int* node_off_host, int B, in
         if (node_off_host[b + 1] <= node_off_host[b]) return 0;
     return batch_sized_bytes(node_off_host, B, K);
 }
-
-static int link_batch_fwd_entry(const char* entry, const float* S, int lds, const int* indptr,
-                                const int* indices_local, const float* values, bool weighted,
-                                const int* node_off_host, int B, float* loss_out, int K, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(loss_out);
-    CL_VALUES(entry);
-    if (int rc = check_batch(entry, node_off_host, B, K, lds, workspace, workspace_bytes)) return rc;
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_batch_fwd_seq(q, S, lds, indptr, indices_local, node_off_host, B, loss_out, K, weighted ? values : nullptr);
-    return q.err;
-}
-static int link_batch_bwd_entry(const char* entry, const float* S, int lds, const int* indptr,
-                                const int* indices_local, const float* values, const int* indptr_t,
-                                const int* indices_t_local, const float* values_t, bool weighted,
-                                const int* node_off_host, int B, const float* dloss, float* dS, int ldds,
-                                int accumulate, int K, void* workspace, size_t workspace_bytes, void* stream) {
-    CL_PTR(S); CL_PTR(indptr); CL_PTR(indices_local); CL_PTR(indptr_t); CL_PTR(indices_t_local); CL_PTR(dS);
-    CL_VALUES(entry);
-    CL_VALUES_T(entry, indices_t_local, indices_local);
-    CL_CHECK(((uintptr_t)dloss & 3) == 0, DP_ERR_INVALID_ARG, "dloss is not 4-byte aligned");
-    if (int rc = check_batch(entry, node_off_host, B, K, lds, workspace, workspace_bytes)) return rc;
-    CL_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", entry, ldds, K);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_link_batch_bwd_seq(q, S, lds, indptr, indices_local, indptr_t, indices_t_local, node_off_host, B, dloss, dS, ldds,
-                           accumulate, K, weighted ? values : nullptr,
-                           weighted ? (indices_t_local != indices_local ? values_t : values) : nullptr);
-    return q.err;
+size_t dp_csr_linkpred_workspace_bytes(int n, int K) {
+    const int off[2] = {0, n};
+    return dp_csr_linkpred_batch_workspace_bytes(off, 1, K);
 }
 
+// ---- one graph: the batch of one, off = {0, n}
+int dp_csr_linkpred_loss_fwd(const float* S, int lds, const int* indptr, const int* indices, float* loss_out, int n,
+                             int K, void* workspace, size_t workspace_bytes, void* stream) {
+    const int off[2] = {0, n};
+    return link_fwd_entry("dp_csr_linkpred_loss_fwd", true, S, lds, indptr, indices, nullptr, false, off, 1, loss_out, K,
+                          workspace, workspace_bytes, stream);
+}
+int dp_csr_linkpred_loss_fwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                               float* loss_out, int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
+    const int off[2] = {0, n};
+    return link_fwd_entry("dp_csr_linkpred_loss_fwd_w", true, S, lds, indptr, indices, values, true, off, 1, loss_out, K,
+                          workspace, workspace_bytes, stream);
+}
+int dp_csr_linkpred_loss_bwd(const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
+                             const int* indices_t, const float* dloss, float* dS, int ldds, int accumulate, int n,
+                             int K, void* workspace, size_t workspace_bytes, void* stream) {
+    const int off[2] = {0, n};
+    return link_bwd_entry("dp_csr_linkpred_loss_bwd", true, S, lds, indptr, indices, nullptr, indptr_t, indices_t,
+                          nullptr, false, off, 1, dloss, dS, ldds, accumulate, K, workspace, workspace_bytes, stream);
+}
+int dp_csr_linkpred_loss_bwd_w(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                               const int* indptr_t, const int* indices_t, const float* values_t, const float* dloss,
+                               float* dS, int ldds, int accumulate, int n, int K, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    const int off[2] = {0, n};
+    return link_bwd_entry("dp_csr_linkpred_loss_bwd_w", true, S, lds, indptr, indices, values, indptr_t, indices_t,
+                          values_t, true, off, 1, dloss, dS, ldds, accumulate, K, workspace, workspace_bytes, stream);
+}
+
+// ---- a ragged batch (node_off_host: int32 [B + 1] on the HOST)
 int dp_csr_linkpred_batch_loss_fwd(const float* S, int lds, const int* indptr, const int* indices_local,
                                    const int* node_off_host, int B, float* loss_out, int K, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-    return link_batch_fwd_entry("dp_csr_linkpred_batch_loss_fwd", S, lds, indptr, indices_local, nullptr, false,
-                                node_off_host, B, loss_out, K, workspace, workspace_bytes, stream);
+    return link_fwd_entry("dp_csr_linkpred_batch_loss_fwd", false, S, lds, indptr, indices_local, nullptr, false,
+                          node_off_host, B, loss_out, K, workspace, workspace_bytes, stream);
 }
 int dp_csr_linkpred_batch_loss_fwd_w(const float* S, int lds, const int* indptr, const int* indices_local,
                                      const float* values, const int* node_off_host, int B, float* loss_out, int K,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-    return link_batch_fwd_entry("dp_csr_linkpred_batch_loss_fwd_w", S, lds, indptr, indices_local, values, true,
-                                node_off_host, B, loss_out, K, workspace, workspace_bytes, stream);
+    return link_fwd_entry("dp_csr_linkpred_batch_loss_fwd_w", false, S, lds, indptr, indices_local, values, true,
+                          node_off_host, B, loss_out, K, workspace, workspace_bytes, stream);
 }
-
 int dp_csr_linkpred_batch_loss_bwd(const float* S, int lds, const int* indptr, const int* indices_local,
                                    const int* indptr_t, const int* indices_t_local, const int* node_off_host, int B,
                                    const float* dloss, float* dS, int ldds, int accumulate, int K, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-    return link_batch_bwd_entry("dp_csr_linkpred_batch_loss_bwd", S, lds, indptr, indices_local, nullptr, indptr_t,
-                                indices_t_local, nullptr, false, node_off_host, B, dloss, dS, ldds, accumulate, K,
-                                workspace, workspace_bytes, stream);
+    return link_bwd_entry("dp_csr_linkpred_batch_loss_bwd", false, S, lds, indptr, indices_local, nullptr, indptr_t,
+                          indices_t_local, nullptr, false, node_off_host, B, dloss, dS, ldds, accumulate, K, workspace,
+                          workspace_bytes, stream);
 }
 int dp_csr_linkpred_batch_loss_bwd_w(const float* S, int lds, const int* indptr, const int* indices_local,
                                      const float* values, const int* indptr_t, const int* indices_t_local,
                                      const float* values_t, const int* node_off_host, int B, const float* dloss,
                                      float* dS, int ldds, int accumulate, int K, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    return link_batch_bwd_entry("dp_csr_linkpred_batch_loss_bwd_w", S, lds, indptr, indices_local, values, indptr_t,
-                                indices_t_local, values_t, true, node_off_host, B, dloss, dS, ldds, accumulate, K,
-                                workspace, workspace_bytes, stream);
+    return link_bwd_entry("dp_csr_linkpred_batch_loss_bwd_w", false, S, lds, indptr, indices_local, values, indptr_t,
+                          indices_t_local, values_t, true, node_off_host, B, dloss, dS, ldds, accumulate, K, workspace,
+                          workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -20,7 +20,7 @@
 // per call by a small prologue launch (L2-resident afterwards).  No atomics: every row of dS / dZ has one writer.
 #include <algorithm>
 
-#include "dp_common.h"
+#include "dp_entry.h"
 
 namespace dp {
 namespace {
@@ -386,8 +386,6 @@ __global__ __launch_bounds__(256) void k_csr_pool_bwd_w(PoolBwdArgs a) {
     csr_pool_bwd_body<NI, VEC, true>(a);
 }
 
-inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
 // slab partition of the forward: >= FWD_TARGET_WGS workgroups when the rows allow, slabs a multiple of the stage
 void fwd_slabs(int n, int K, int D, int* nslab, int* rows_per_slab) {
     const int ntn = cdiv(K + D, FWD_TN);
@@ -398,8 +396,6 @@ void fwd_slabs(int n, int K, int D, int* nslab, int* rows_per_slab) {
     *nslab = cdiv(n, rows);
 }
 int bwd_ni(int K) { return K <= 64 ? 4 : (K <= 128 ? 8 : 16); }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // tab / slab_off / nslab_batch / B: the slab table of a batch (dp_csr_pool_batch_plan); null / 0: one graph of n rows
 void csr_pool_fwd_seq(Seq& q, const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
@@ -523,25 +519,76 @@ size_t batch_sized_bytes(int nslab, int B, int K, int D) {
 
 using namespace dp;
 
-#define CP_CHECK(cond, code, ...)        \
-    do {                                 \
-        if (!(cond)) {                   \
-            ::dp::set_error(__VA_ARGS__); \
-            return code;                 \
-        }                                \
-    } while (0)
-#define CP_NOTNULL(p) CP_CHECK((p) != nullptr, DP_ERR_INVALID_ARG, #p " is NULL")
-#define CP_ALIGNED(p) CP_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, #p " is not 4-byte aligned")
-
 namespace {
+
+// the tables of a batch (dp_csr_pool_batch_plan); a null PoolBatch: one graph of n rows
+struct PoolBatch {
+    const int* tab;         // forward: slab table; backward: row-block table
+    const int* slab_off;    // forward only
+    int count;              // slabs / row blocks
+    int B;
+};
+
 int check_shape(const char* entry, int n, int K, int D, int lds, int ldz) {
-    CP_CHECK(n > 0, DP_ERR_INVALID_ARG, "%s: n=%d must be positive", entry, n);
-    CP_CHECK(K >= 1 && K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d outside the supported 1..256", entry, K);
-    CP_CHECK(D >= 1 && D <= 512, DP_ERR_UNSUPPORTED, "%s: D=%d outside the supported 1..512", entry, D);
-    CP_CHECK(lds >= K && ldz >= D, DP_ERR_INVALID_ARG, "%s: lds=%d / ldz=%d smaller than K=%d / D=%d", entry, lds, ldz,
+    DP_CHECK(n > 0, DP_ERR_INVALID_ARG, "%s: n=%d must be positive", entry, n);
+    DP_CHECK(K >= 1 && K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d outside the supported 1..256", entry, K);
+    DP_CHECK(D >= 1 && D <= 512, DP_ERR_UNSUPPORTED, "%s: D=%d outside the supported 1..512", entry, D);
+    DP_CHECK(lds >= K && ldz >= D, DP_ERR_INVALID_ARG, "%s: lds=%d / ldz=%d smaller than K=%d / D=%d", entry, lds, ldz,
              K, D);
     return DP_OK;
 }
+
+// The checked bodies of all eight entries; bt: the batch entries' tables, null from the single-graph ones (n: n_total
+// of a batch).
+int pool_fwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
+                   const int* indices, const float* values, bool weighted, const PoolBatch* bt, float* Xp, float* Ap,
+                   int n, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
+    const int* fwd_tab = bt ? bt->tab : nullptr;
+    const int* slab_off = bt ? bt->slab_off : nullptr;
+    DP_NOTNULL(S); DP_NOTNULL(Z); DP_NOTNULL(indptr); DP_NOTNULL(indices);
+    if (bt) { DP_NOTNULL(fwd_tab); DP_NOTNULL(slab_off); }
+    DP_NOTNULL(Xp); DP_NOTNULL(Ap);
+    DP_VALUES(DP_ALIGNED4(values), "%s: values is NULL", entry);
+    DP_ALIGNED4(S); DP_ALIGNED4(Z); DP_ALIGNED4(indptr); DP_ALIGNED4(indices); DP_ALIGNED4(fwd_tab);
+    DP_ALIGNED4(slab_off); DP_ALIGNED4(Xp); DP_ALIGNED4(Ap);
+    if (int rc = check_shape(entry, n, K, D, lds, ldz)) return rc;
+    if (bt)
+        DP_CHECK(bt->B >= 1 && bt->B <= 65535 && bt->count >= bt->B && bt->count <= 65535, DP_ERR_INVALID_ARG,
+                 "%s: B=%d / n_slabs=%d outside 1..65535 (every graph has a slab)", entry, bt->B, bt->count);
+    DP_ALIGNED16(workspace, true, "%s: workspace is not 16-byte aligned", entry);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n, K, D, fwd_tab, slab_off, bt ? bt->count : 0,
+                     bt ? bt->B : 1, weighted ? values : nullptr);
+    return q.err;
+}
+
+int pool_bwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
+                   const int* indices, const float* values, const int* indptr_t, const int* indices_t,
+                   const float* values_t, bool weighted, const PoolBatch* bt, const float* dXp, const float* dAp,
+                   float* dS, int ldds, float* dZ, int lddz, int n, int K, int D, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    const int* bwd_tab = bt ? bt->tab : nullptr;
+    DP_NOTNULL(S); DP_NOTNULL(Z); DP_NOTNULL(indptr); DP_NOTNULL(indices); DP_NOTNULL(indptr_t); DP_NOTNULL(indices_t);
+    if (bt) DP_NOTNULL(bwd_tab);
+    DP_NOTNULL(dXp); DP_NOTNULL(dAp); DP_NOTNULL(dS); DP_NOTNULL(dZ);
+    DP_VALUES(DP_ALIGNED4(values), "%s: values is NULL", entry);
+    DP_VALUES_T(DP_ALIGNED4(values_t), "%s: values_t is NULL but indices_t is a CSR of its own", entry);
+    DP_ALIGNED4(S); DP_ALIGNED4(Z); DP_ALIGNED4(indptr); DP_ALIGNED4(indices); DP_ALIGNED4(indptr_t);
+    DP_ALIGNED4(indices_t); DP_ALIGNED4(bwd_tab); DP_ALIGNED4(dXp); DP_ALIGNED4(dAp); DP_ALIGNED4(dS); DP_ALIGNED4(dZ);
+    if (int rc = check_shape(entry, n, K, D, lds, ldz)) return rc;
+    DP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG, "%s: ldds=%d / lddz=%d smaller than K=%d / D=%d", entry, ldds,
+             lddz, K, D);
+    if (bt)
+        DP_CHECK(bt->B >= 1 && bt->B <= 65535 && bt->count >= bt->B, DP_ERR_INVALID_ARG,
+                 "%s: B=%d / n_blocks=%d (every graph has a row block)", entry, bt->B, bt->count);
+    DP_ALIGNED16(workspace, true, "%s: workspace is not 16-byte aligned", entry);
+    Seq q((hipStream_t)stream, workspace, workspace_bytes);
+    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n, K, D,
+                     bwd_tab, bt ? bt->count : 0, bt ? bt->B : 1, weighted ? values : nullptr,
+                     weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr);
+    return q.err;
+}
+
 }  // namespace
 
 extern "C" {
@@ -551,69 +598,15 @@ size_t dp_csr_pool_workspace_bytes(int n, int K, int D) {
     return sized_bytes(n, K, D);
 }
 
-// values == NULL with weighted set (a _w entry) is an argument error; values_t matters only next to a transposed CSR of
-// its own (indices_t != indices)
-#define CP_VALUES(entry)                                                                                      \
-    do {                                                                                                      \
-        if (weighted) {                                                                                       \
-            CP_CHECK(values != nullptr, DP_ERR_INVALID_ARG, "%s: values is NULL", entry);                     \
-            CP_ALIGNED(values);                                                                               \
-        }                                                                                                     \
-    } while (0)
-#define CP_VALUES_T(entry)                                                                                    \
-    do {                                                                                                      \
-        if (weighted && indices_t != indices) {                                                               \
-            CP_CHECK(values_t != nullptr, DP_ERR_INVALID_ARG,                                                 \
-                     "%s: values_t is NULL but indices_t is a CSR of its own", entry);                        \
-            CP_ALIGNED(values_t);                                                                             \
-        }                                                                                                     \
-    } while (0)
-
-static int pool_fwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
-                          const int* indices, const float* values, bool weighted, float* Xp, float* Ap, int n, int K,
-                          int D, void* workspace, size_t workspace_bytes, void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(Xp); CP_NOTNULL(Ap);
-    CP_VALUES(entry);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(Xp); CP_ALIGNED(Ap);
-    if (int rc = check_shape(entry, n, K, D, lds, ldz)) return rc;
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n, K, D, nullptr, nullptr, 0, 1,
-                     weighted ? values : nullptr);
-    return q.err;
-}
-
-static int pool_bwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
-                          const int* indices, const float* values, const int* indptr_t, const int* indices_t,
-                          const float* values_t, bool weighted, const float* dXp, const float* dAp, float* dS, int ldds,
-                          float* dZ, int lddz, int n, int K, int D, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(indptr_t); CP_NOTNULL(indices_t);
-    CP_NOTNULL(dXp); CP_NOTNULL(dAp); CP_NOTNULL(dS); CP_NOTNULL(dZ);
-    CP_VALUES(entry);
-    CP_VALUES_T(entry);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(indptr_t); CP_ALIGNED(indices_t);
-    CP_ALIGNED(dXp); CP_ALIGNED(dAp); CP_ALIGNED(dS); CP_ALIGNED(dZ);
-    if (int rc = check_shape(entry, n, K, D, lds, ldz)) return rc;
-    CP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG, "%s: ldds=%d / lddz=%d smaller than K=%d / D=%d", entry, ldds,
-             lddz, K, D);
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n, K, D,
-                     nullptr, 0, 1, weighted ? values : nullptr,
-                     weighted ? (indices_t != indices ? values_t : values) : nullptr);
-    return q.err;
-}
-
 int dp_csr_pool_fwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices, float* Xp,
                     float* Ap, int n, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    return pool_fwd_entry("dp_csr_pool_fwd", S, lds, Z, ldz, indptr, indices, nullptr, false, Xp, Ap, n, K, D,
+    return pool_fwd_entry("dp_csr_pool_fwd", S, lds, Z, ldz, indptr, indices, nullptr, false, nullptr, Xp, Ap, n, K, D,
                           workspace, workspace_bytes, stream);
 }
 int dp_csr_pool_fwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                       const float* values, float* Xp, float* Ap, int n, int K, int D, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    return pool_fwd_entry("dp_csr_pool_fwd_w", S, lds, Z, ldz, indptr, indices, values, true, Xp, Ap, n, K, D,
+    return pool_fwd_entry("dp_csr_pool_fwd_w", S, lds, Z, ldz, indptr, indices, values, true, nullptr, Xp, Ap, n, K, D,
                           workspace, workspace_bytes, stream);
 }
 
@@ -621,26 +614,26 @@ int dp_csr_pool_bwd(const float* S, int lds, const float* Z, int ldz, const int*
                     const int* indptr_t, const int* indices_t, const float* dXp, const float* dAp, float* dS, int ldds,
                     float* dZ, int lddz, int n, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
     return pool_bwd_entry("dp_csr_pool_bwd", S, lds, Z, ldz, indptr, indices, nullptr, indptr_t, indices_t, nullptr,
-                          false, dXp, dAp, dS, ldds, dZ, lddz, n, K, D, workspace, workspace_bytes, stream);
+                          false, nullptr, dXp, dAp, dS, ldds, dZ, lddz, n, K, D, workspace, workspace_bytes, stream);
 }
 int dp_csr_pool_bwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                       const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
                       const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int n, int K, int D,
                       void* workspace, size_t workspace_bytes, void* stream) {
     return pool_bwd_entry("dp_csr_pool_bwd_w", S, lds, Z, ldz, indptr, indices, values, indptr_t, indices_t, values_t,
-                          true, dXp, dAp, dS, ldds, dZ, lddz, n, K, D, workspace, workspace_bytes, stream);
+                          true, nullptr, dXp, dAp, dS, ldds, dZ, lddz, n, K, D, workspace, workspace_bytes, stream);
 }
 
 // ---- the same on a ragged batch of B graphs (rows concatenated, block-diagonal CSR with GLOBAL column indices)
 int dp_csr_pool_batch_plan(const int* node_off_host, int B, int K, int D, int* fwd_tab_host, int* slab_off_host,
                            int* bwd_tab_host, int* counts_host) {
-    CP_NOTNULL(node_off_host); CP_NOTNULL(counts_host);
-    CP_CHECK(B >= 1, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_plan: B=%d must be positive", B);
-    CP_CHECK(K >= 1 && K <= 256 && D >= 1 && D <= 512, DP_ERR_UNSUPPORTED,
+    DP_NOTNULL(node_off_host); DP_NOTNULL(counts_host);
+    DP_CHECK(B >= 1, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_plan: B=%d must be positive", B);
+    DP_CHECK(K >= 1 && K <= 256 && D >= 1 && D <= 512, DP_ERR_UNSUPPORTED,
              "dp_csr_pool_batch_plan: K=%d / D=%d outside the supported 1..256 / 1..512", K, D);
-    CP_CHECK(node_off_host[0] == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_plan: node_off[0] must be 0");
+    DP_CHECK(node_off_host[0] == 0, DP_ERR_INVALID_ARG, "dp_csr_pool_batch_plan: node_off[0] must be 0");
     for (int b = 0; b < B; ++b)
-        CP_CHECK(node_off_host[b + 1] > node_off_host[b], DP_ERR_INVALID_ARG,
+        DP_CHECK(node_off_host[b + 1] > node_off_host[b], DP_ERR_INVALID_ARG,
                  "dp_csr_pool_batch_plan: graph %d has no node (node_off must increase)", b);
     batch_plan(node_off_host, B, K, D, fwd_tab_host, slab_off_host, bwd_tab_host, counts_host);
     return DP_OK;
@@ -651,79 +644,40 @@ size_t dp_csr_pool_batch_workspace_bytes(int n_slabs, int B, int K, int D) {
     return batch_sized_bytes(n_slabs, B, K, D);
 }
 
-static int pool_batch_fwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
-                                const int* indices, const float* values, bool weighted, const int* fwd_tab,
-                                const int* slab_off, int n_slabs, float* Xp, float* Ap, int B, int n_total, int K, int D,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(fwd_tab); CP_NOTNULL(slab_off);
-    CP_NOTNULL(Xp); CP_NOTNULL(Ap);
-    CP_VALUES(entry);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(fwd_tab); CP_ALIGNED(slab_off);
-    CP_ALIGNED(Xp); CP_ALIGNED(Ap);
-    if (int rc = check_shape(entry, n_total, K, D, lds, ldz)) return rc;
-    CP_CHECK(B >= 1 && B <= 65535 && n_slabs >= B && n_slabs <= 65535, DP_ERR_INVALID_ARG,
-             "%s: B=%d / n_slabs=%d outside 1..65535 (every graph has a slab)", entry, B, n_slabs);
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_fwd_seq(q, S, lds, Z, ldz, indptr, indices, Xp, Ap, n_total, K, D, fwd_tab, slab_off, n_slabs, B,
-                     weighted ? values : nullptr);
-    return q.err;
-}
-
-static int pool_batch_bwd_entry(const char* entry, const float* S, int lds, const float* Z, int ldz, const int* indptr,
-                                const int* indices, const float* values, const int* indptr_t, const int* indices_t,
-                                const float* values_t, bool weighted, const int* bwd_tab, int n_blocks,
-                                const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int B,
-                                int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    CP_NOTNULL(S); CP_NOTNULL(Z); CP_NOTNULL(indptr); CP_NOTNULL(indices); CP_NOTNULL(indptr_t); CP_NOTNULL(indices_t);
-    CP_NOTNULL(bwd_tab); CP_NOTNULL(dXp); CP_NOTNULL(dAp); CP_NOTNULL(dS); CP_NOTNULL(dZ);
-    CP_VALUES(entry);
-    CP_VALUES_T(entry);
-    CP_ALIGNED(S); CP_ALIGNED(Z); CP_ALIGNED(indptr); CP_ALIGNED(indices); CP_ALIGNED(indptr_t); CP_ALIGNED(indices_t);
-    CP_ALIGNED(bwd_tab); CP_ALIGNED(dXp); CP_ALIGNED(dAp); CP_ALIGNED(dS); CP_ALIGNED(dZ);
-    if (int rc = check_shape(entry, n_total, K, D, lds, ldz)) return rc;
-    CP_CHECK(ldds >= K && lddz >= D, DP_ERR_INVALID_ARG, "%s: ldds=%d / lddz=%d smaller than K=%d / D=%d", entry, ldds,
-             lddz, K, D);
-    CP_CHECK(B >= 1 && B <= 65535 && n_blocks >= B, DP_ERR_INVALID_ARG,
-             "%s: B=%d / n_blocks=%d (every graph has a row block)", entry, B, n_blocks);
-    CP_CHECK(((uintptr_t)workspace & 15) == 0, DP_ERR_INVALID_ARG, "%s: workspace is not 16-byte aligned", entry);
-    Seq q((hipStream_t)stream, workspace, workspace_bytes);
-    csr_pool_bwd_seq(q, S, lds, Z, ldz, indptr, indices, indptr_t, indices_t, dXp, dAp, dS, ldds, dZ, lddz, n_total, K,
-                     D, bwd_tab, n_blocks, B, weighted ? values : nullptr,
-                     weighted ? (indices_t != indices ? values_t : values) : nullptr);
-    return q.err;
-}
-
 int dp_csr_pool_batch_fwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                           const int* fwd_tab, const int* slab_off, int n_slabs, float* Xp, float* Ap, int B,
                           int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    return pool_batch_fwd_entry("dp_csr_pool_batch_fwd", S, lds, Z, ldz, indptr, indices, nullptr, false, fwd_tab,
-                                slab_off, n_slabs, Xp, Ap, B, n_total, K, D, workspace, workspace_bytes, stream);
+    const PoolBatch bt{fwd_tab, slab_off, n_slabs, B};
+    return pool_fwd_entry("dp_csr_pool_batch_fwd", S, lds, Z, ldz, indptr, indices, nullptr, false, &bt, Xp, Ap,
+                          n_total, K, D, workspace, workspace_bytes, stream);
 }
 int dp_csr_pool_batch_fwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                             const float* values, const int* fwd_tab, const int* slab_off, int n_slabs, float* Xp,
                             float* Ap, int B, int n_total, int K, int D, void* workspace, size_t workspace_bytes,
                             void* stream) {
-    return pool_batch_fwd_entry("dp_csr_pool_batch_fwd_w", S, lds, Z, ldz, indptr, indices, values, true, fwd_tab,
-                                slab_off, n_slabs, Xp, Ap, B, n_total, K, D, workspace, workspace_bytes, stream);
+    const PoolBatch bt{fwd_tab, slab_off, n_slabs, B};
+    return pool_fwd_entry("dp_csr_pool_batch_fwd_w", S, lds, Z, ldz, indptr, indices, values, true, &bt, Xp, Ap,
+                          n_total, K, D, workspace, workspace_bytes, stream);
 }
 
 int dp_csr_pool_batch_bwd(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                           const int* indptr_t, const int* indices_t, const int* bwd_tab, int n_blocks,
                           const float* dXp, const float* dAp, float* dS, int ldds, float* dZ, int lddz, int B,
                           int n_total, int K, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    return pool_batch_bwd_entry("dp_csr_pool_batch_bwd", S, lds, Z, ldz, indptr, indices, nullptr, indptr_t, indices_t,
-                                nullptr, false, bwd_tab, n_blocks, dXp, dAp, dS, ldds, dZ, lddz, B, n_total, K, D,
-                                workspace, workspace_bytes, stream);
+    const PoolBatch bt{bwd_tab, nullptr, n_blocks, B};
+    return pool_bwd_entry("dp_csr_pool_batch_bwd", S, lds, Z, ldz, indptr, indices, nullptr, indptr_t, indices_t,
+                          nullptr, false, &bt, dXp, dAp, dS, ldds, dZ, lddz, n_total, K, D, workspace, workspace_bytes,
+                          stream);
 }
 int dp_csr_pool_batch_bwd_w(const float* S, int lds, const float* Z, int ldz, const int* indptr, const int* indices,
                             const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
                             const int* bwd_tab, int n_blocks, const float* dXp, const float* dAp, float* dS, int ldds,
                             float* dZ, int lddz, int B, int n_total, int K, int D, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    return pool_batch_bwd_entry("dp_csr_pool_batch_bwd_w", S, lds, Z, ldz, indptr, indices, values, indptr_t,
-                                indices_t, values_t, true, bwd_tab, n_blocks, dXp, dAp, dS, ldds, dZ, lddz, B, n_total,
-                                K, D, workspace, workspace_bytes, stream);
+    const PoolBatch bt{bwd_tab, nullptr, n_blocks, B};
+    return pool_bwd_entry("dp_csr_pool_batch_bwd_w", S, lds, Z, ldz, indptr, indices, values, indptr_t, indices_t,
+                          values_t, true, &bt, dXp, dAp, dS, ldds, dZ, lddz, n_total, K, D, workspace, workspace_bytes,
+                          stream);
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 // order.  No float atomics: every result is bit-reproducible.  Launch counts depend neither on B nor on max_n.
 #include <algorithm>
 
-#include "dp_common.h"
+#include "dp_entry.h"
 
 namespace dp {
 namespace {
@@ -27,8 +27,6 @@ constexpr float RR_BN_EPS = 1e-5f;      // BatchNorm1d eps (dp_csr_batch.hip RB_
 constexpr int RR_WAVES = 4;             // node indices per 256-thread workgroup
 constexpr int SUF_ROWS = 64;            // table rows per scan block
 constexpr int SUF_ROW_LANES = 4;        // row lanes of a block-maximum workgroup (x 64 feature lanes)
-
-inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // One wave per table row i in n_min .. n_idx - 1.  i < max_n: the statistics dp_bn_ragged_fwd wrote.  i == max_n (the
 // tail row): B * F values, B copies of pad — mean and biased variance over f of pad; written to stats row max_n.
@@ -293,27 +291,14 @@ __global__ __launch_bounds__(256) void k_readout_colsum(const float* part, int r
 
 using namespace dp;
 
-#define RR_CHECK(cond, code, ...)         \
-    do {                                  \
-        if (!(cond)) {                    \
-            ::dp::set_error(__VA_ARGS__); \
-            return code;                  \
-        }                                 \
-    } while (0)
-#define RR_PTR(p)                                                                             \
-    do {                                                                                      \
-        RR_CHECK((p) != nullptr, DP_ERR_INVALID_ARG, #p " is NULL");                          \
-        RR_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, #p " is not 4-byte aligned"); \
-    } while (0)
-
 namespace {
 // the table's row range: n_min = min_b n_b <= max_n, n_idx = max_n or max_n + 1 (the tail row)
 int check_table(const char* entry, int n_min, int max_n, int n_idx, int F) {
-    RR_CHECK(F >= 1, DP_ERR_INVALID_ARG, "%s: F=%d must be positive", entry, F);
-    RR_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "%s: F=%d above the supported 2048", entry, F);
-    RR_CHECK(max_n >= 1 && n_min >= 1 && n_min <= max_n, DP_ERR_INVALID_ARG,
+    DP_CHECK(F >= 1, DP_ERR_INVALID_ARG, "%s: F=%d must be positive", entry, F);
+    DP_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "%s: F=%d above the supported 2048", entry, F);
+    DP_CHECK(max_n >= 1 && n_min >= 1 && n_min <= max_n, DP_ERR_INVALID_ARG,
              "%s: n_min=%d, max_n=%d must satisfy 1 <= n_min <= max_n", entry, n_min, max_n);
-    RR_CHECK(n_idx == max_n || n_idx == max_n + 1, DP_ERR_INVALID_ARG,
+    DP_CHECK(n_idx == max_n || n_idx == max_n + 1, DP_ERR_INVALID_ARG,
              "%s: n_idx=%d must be max_n=%d or max_n + 1 (the tail row)", entry, n_idx, max_n);
     return DP_OK;
 }
@@ -323,9 +308,9 @@ extern "C" {
 
 int dp_ragged_padval_fwd(float* stats, const float* pad, float* padval, int ldp, int n_min, int max_n, int n_idx, int F,
                          void* stream) {
-    RR_PTR(stats); RR_PTR(padval);
+    DP_PTR(stats); DP_PTR(padval);
     if (int rc = check_table("dp_ragged_padval_fwd", n_min, max_n, n_idx, F)) return rc;
-    RR_CHECK(ldp >= F, DP_ERR_INVALID_ARG, "dp_ragged_padval_fwd: ldp=%d smaller than F=%d", ldp, F);
+    DP_CHECK(ldp >= F, DP_ERR_INVALID_ARG, "dp_ragged_padval_fwd: ldp=%d smaller than F=%d", ldp, F);
     if (n_idx == n_min) return DP_OK;       // no node index has a padded row
     Seq q((hipStream_t)stream, nullptr, 0);
     hipLaunchKernelGGL(k_ragged_padval, dim3(cdiv(n_idx - n_min, RR_WAVES)), dim3(256), 0, q.stream, stats, pad, padval,
@@ -341,16 +326,16 @@ size_t dp_ragged_suffix_max_workspace_bytes(int n_min, int n_idx, int F) {
 
 int dp_ragged_suffix_max(const float* padval, int ldp, float* sufv, int* sufi, int lds, int n_min, int n_idx, int F,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    RR_PTR(padval); RR_PTR(sufv); RR_PTR(sufi);
-    RR_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_ragged_suffix_max: F=%d must be positive", F);
-    RR_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "dp_ragged_suffix_max: F=%d above the supported 2048", F);
-    RR_CHECK(n_min >= 1 && n_idx >= n_min, DP_ERR_INVALID_ARG,
+    DP_PTR(padval); DP_PTR(sufv); DP_PTR(sufi);
+    DP_CHECK(F >= 1, DP_ERR_INVALID_ARG, "dp_ragged_suffix_max: F=%d must be positive", F);
+    DP_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "dp_ragged_suffix_max: F=%d above the supported 2048", F);
+    DP_CHECK(n_min >= 1 && n_idx >= n_min, DP_ERR_INVALID_ARG,
              "dp_ragged_suffix_max: n_min=%d, n_idx=%d must satisfy 1 <= n_min <= n_idx", n_min, n_idx);
-    RR_CHECK(ldp >= F && lds >= F, DP_ERR_INVALID_ARG, "dp_ragged_suffix_max: ldp=%d / lds=%d smaller than F=%d", ldp,
+    DP_CHECK(ldp >= F && lds >= F, DP_ERR_INVALID_ARG, "dp_ragged_suffix_max: ldp=%d / lds=%d smaller than F=%d", ldp,
              lds, F);
     if (n_idx == n_min) return DP_OK;
     const int n_blk = cdiv(n_idx - n_min, SUF_ROWS);
-    RR_CHECK(n_blk <= 65535, DP_ERR_UNSUPPORTED, "dp_ragged_suffix_max: more than 65535 scan blocks");
+    DP_CHECK(n_blk <= 65535, DP_ERR_UNSUPPORTED, "dp_ragged_suffix_max: more than 65535 scan blocks");
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     float* bv = q.alloc<float>((size_t)n_blk * F);
     int* bi = q.alloc<int>((size_t)n_blk * F);
@@ -368,21 +353,21 @@ int dp_segment_max_floor_fwd(const float* Z, int ldz, const int* node_off, const
                              int n_chunks, const int* floor_flag, const float* sufv, const int* sufi, int lds,
                              int n_min, int n_idx, const float* floor_row, float* out, int ldo, int* argmax, int B, int F, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    RR_PTR(Z); RR_PTR(node_off); RR_PTR(chunk_tab); RR_PTR(chunk_off); RR_PTR(out); RR_PTR(argmax);
-    RR_CHECK(B >= 1 && F >= 1 && n_chunks >= B, DP_ERR_INVALID_ARG,
+    DP_PTR(Z); DP_PTR(node_off); DP_PTR(chunk_tab); DP_PTR(chunk_off); DP_PTR(out); DP_PTR(argmax);
+    DP_CHECK(B >= 1 && F >= 1 && n_chunks >= B, DP_ERR_INVALID_ARG,
              "dp_segment_max_floor_fwd: B=%d, F=%d, n_chunks=%d (every graph has at least one chunk)", B, F, n_chunks);
-    RR_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "dp_segment_max_floor_fwd: F=%d above the supported 2048", F);
-    RR_CHECK(n_chunks <= 65535 && B <= 65535, DP_ERR_UNSUPPORTED,
+    DP_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "dp_segment_max_floor_fwd: F=%d above the supported 2048", F);
+    DP_CHECK(n_chunks <= 65535 && B <= 65535, DP_ERR_UNSUPPORTED,
              "dp_segment_max_floor_fwd: more than 65535 chunks / graphs");
-    RR_CHECK(ldz >= F && ldo >= F, DP_ERR_INVALID_ARG, "dp_segment_max_floor_fwd: ldz=%d / ldo=%d smaller than F=%d", ldz,
+    DP_CHECK(ldz >= F && ldo >= F, DP_ERR_INVALID_ARG, "dp_segment_max_floor_fwd: ldz=%d / ldo=%d smaller than F=%d", ldz,
              ldo, F);
-    RR_CHECK(!(sufv && floor_row), DP_ERR_INVALID_ARG,
+    DP_CHECK(!(sufv && floor_row), DP_ERR_INVALID_ARG,
              "dp_segment_max_floor_fwd: the floor is the suffix table or one constant row, not both");
-    RR_CHECK(!sufv == !sufi, DP_ERR_INVALID_ARG, "dp_segment_max_floor_fwd: sufv and sufi go together");
-    RR_CHECK(!sufv || (lds >= F && n_min >= 1 && n_idx > n_min), DP_ERR_INVALID_ARG,
+    DP_CHECK(!sufv == !sufi, DP_ERR_INVALID_ARG, "dp_segment_max_floor_fwd: sufv and sufi go together");
+    DP_CHECK(!sufv || (lds >= F && n_min >= 1 && n_idx > n_min), DP_ERR_INVALID_ARG,
              "dp_segment_max_floor_fwd: lds=%d, n_min=%d, n_idx=%d for a suffix table of F=%d columns", lds, n_min, n_idx,
              F);
-    RR_CHECK(!(sufv || floor_row) || floor_flag, DP_ERR_INVALID_ARG,
+    DP_CHECK(!(sufv || floor_row) || floor_flag, DP_ERR_INVALID_ARG,
              "dp_segment_max_floor_fwd: a floor needs floor_flag (which graphs have padded rows)");
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     float* pv = q.alloc<float>((size_t)n_chunks * F);
@@ -399,14 +384,14 @@ int dp_segment_max_floor_fwd(const float* Z, int ldz, const int* node_off, const
 
 int dp_segment_max_floor_bwd(const float* dout, int ldo, const int* argmax, const int* node_off, float* dZ, int lddz,
                              float* G, int ldg, int n_min, int n_idx, int table, int B, int F, void* stream) {
-    RR_PTR(dout); RR_PTR(argmax); RR_PTR(node_off); RR_PTR(dZ);
-    RR_CHECK(B >= 1 && F >= 1, DP_ERR_INVALID_ARG, "dp_segment_max_floor_bwd: B=%d, F=%d must be positive", B, F);
-    RR_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "dp_segment_max_floor_bwd: F=%d above the supported 2048", F);
-    RR_CHECK(ldo >= F && lddz >= F, DP_ERR_INVALID_ARG, "dp_segment_max_floor_bwd: ldo=%d / lddz=%d smaller than F=%d",
+    DP_PTR(dout); DP_PTR(argmax); DP_PTR(node_off); DP_PTR(dZ);
+    DP_CHECK(B >= 1 && F >= 1, DP_ERR_INVALID_ARG, "dp_segment_max_floor_bwd: B=%d, F=%d must be positive", B, F);
+    DP_CHECK(F <= 2048, DP_ERR_UNSUPPORTED, "dp_segment_max_floor_bwd: F=%d above the supported 2048", F);
+    DP_CHECK(ldo >= F && lddz >= F, DP_ERR_INVALID_ARG, "dp_segment_max_floor_bwd: ldo=%d / lddz=%d smaller than F=%d",
              ldo, lddz, F);
     if (G) {
-        RR_CHECK(((uintptr_t)G & 3) == 0, DP_ERR_INVALID_ARG, "G is not 4-byte aligned");
-        RR_CHECK(!table || (n_min >= 1 && n_idx >= n_min && ldg >= F), DP_ERR_INVALID_ARG,
+        DP_ALIGNED4(G);
+        DP_CHECK(!table || (n_min >= 1 && n_idx >= n_min && ldg >= F), DP_ERR_INVALID_ARG,
                  "dp_segment_max_floor_bwd: n_min=%d, n_idx=%d, ldg=%d for a table of F=%d columns", n_min, n_idx, ldg, F);
     }
     Seq q((hipStream_t)stream, nullptr, 0);
@@ -433,13 +418,13 @@ int dp_bn_ragged_g_bwd(const float* x, int ldx, const float* y, int ldy, const f
     if (!G)     // no padded row won anything: the plain backward over the real indices
         return dp_bn_ragged_bwd(x, ldx, y, ldy, stats, dy, lddy, dx, lddx, dpad, node_off, order, cnt, pad, B, max_n, F,
                                 relu, workspace, workspace_bytes, stream);
-    RR_PTR(y); RR_PTR(stats); RR_PTR(dy); RR_PTR(dx); RR_PTR(node_off); RR_PTR(order); RR_PTR(cnt);
-    RR_CHECK(((uintptr_t)G & 3) == 0, DP_ERR_INVALID_ARG, "G is not 4-byte aligned");
-    RR_CHECK(!relu || x, DP_ERR_INVALID_ARG, "dp_bn_ragged_g_bwd: x is NULL but relu != 0");
-    RR_CHECK(!dpad || pad, DP_ERR_INVALID_ARG, "dp_bn_ragged_g_bwd: dpad asked for but pad is NULL");
-    RR_CHECK(B >= 1, DP_ERR_INVALID_ARG, "dp_bn_ragged_g_bwd: B=%d must be positive", B);
+    DP_PTR(y); DP_PTR(stats); DP_PTR(dy); DP_PTR(dx); DP_PTR(node_off); DP_PTR(order); DP_PTR(cnt);
+    DP_ALIGNED4(G);
+    DP_CHECK(!relu || x, DP_ERR_INVALID_ARG, "dp_bn_ragged_g_bwd: x is NULL but relu != 0");
+    DP_CHECK(!dpad || pad, DP_ERR_INVALID_ARG, "dp_bn_ragged_g_bwd: dpad asked for but pad is NULL");
+    DP_CHECK(B >= 1, DP_ERR_INVALID_ARG, "dp_bn_ragged_g_bwd: B=%d must be positive", B);
     if (int rc = check_table("dp_bn_ragged_g_bwd", 1, max_n, n_idx, F)) return rc;
-    RR_CHECK(ldy >= F && lddy >= F && lddx >= F && ldg >= F && (!relu || ldx >= F), DP_ERR_INVALID_ARG,
+    DP_CHECK(ldy >= F && lddy >= F && lddx >= F && ldg >= F && (!relu || ldx >= F), DP_ERR_INVALID_ARG,
              "dp_bn_ragged_g_bwd: a row stride is smaller than F=%d", F);
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     const int blocks = cdiv(n_idx, RR_WAVES);

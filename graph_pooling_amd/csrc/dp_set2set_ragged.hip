@@ -19,7 +19,7 @@
 // dW_ih = DG^T QP, dW_hh = DG^T QP[:, :d] over the B T (graph, step) rows on the MFMA GEMM, and
 // demb_b = A_b^T DR_b + DE_b^T H_b per graph (k_s2sr_demb: M = n_b differs per graph, so one grid of (row tile, graph)
 // workgroups, each output a serial chain over t).  No atomics anywhere.
-#include "dp_common.h"
+#include "dp_entry.h"
 
 namespace dp {
 namespace {
@@ -505,19 +505,6 @@ struct SRBatch {
     int n_total, max_n, max_el, max_gl;      // max_el / max_gl: largest graph with / without its embedding in LDS, 0: none
 };
 
-#define SR_CHECK(cond, code, ...)         \
-    do {                                  \
-        if (!(cond)) {                    \
-            ::dp::set_error(__VA_ARGS__); \
-            return code;                  \
-        }                                 \
-    } while (0)
-#define SR_PTR(p)                                                                             \
-    do {                                                                                      \
-        SR_CHECK((p) != nullptr, DP_ERR_INVALID_ARG, #p " is NULL");                          \
-        SR_CHECK(((uintptr_t)(p) & 3) == 0, DP_ERR_INVALID_ARG, #p " is not 4-byte aligned"); \
-    } while (0)
-
 }  // namespace
 
 // The ONE place that picks the variant a graph of nb rows runs, for both passes (host only, no GPU call).
@@ -530,29 +517,29 @@ int set2set_ragged_plan(int nb, int d) {
 namespace {
 
 int sr_check_batch(const char* entry, const int* node_off_host, int B, int T, int d, SRBatch& s) {
-    SR_CHECK(node_off_host != nullptr, DP_ERR_INVALID_ARG, "%s: node_off_host is NULL", entry);
-    SR_CHECK(B >= 0, DP_ERR_INVALID_ARG, "%s: B=%d must not be negative", entry, B);
-    SR_CHECK(B <= 65535, DP_ERR_UNSUPPORTED, "%s: more than 65535 graphs", entry);
-    SR_CHECK(d >= 1, DP_ERR_INVALID_ARG, "%s: d=%d must be positive", entry, d);
-    SR_CHECK(d <= 256, DP_ERR_UNSUPPORTED, "%s: d=%d above the supported 256", entry, d);
-    SR_CHECK(T >= 1, DP_ERR_INVALID_ARG, "%s: T=%d must be positive", entry, T);
-    SR_CHECK(node_off_host[0] >= 0, DP_ERR_INVALID_ARG, "%s: node_off_host[0]=%d is negative", entry, node_off_host[0]);
+    DP_CHECK(node_off_host != nullptr, DP_ERR_INVALID_ARG, "%s: node_off_host is NULL", entry);
+    DP_CHECK(B >= 0, DP_ERR_INVALID_ARG, "%s: B=%d must not be negative", entry, B);
+    DP_CHECK(B <= 65535, DP_ERR_UNSUPPORTED, "%s: more than 65535 graphs", entry);
+    DP_CHECK(d >= 1, DP_ERR_INVALID_ARG, "%s: d=%d must be positive", entry, d);
+    DP_CHECK(d <= 256, DP_ERR_UNSUPPORTED, "%s: d=%d above the supported 256", entry, d);
+    DP_CHECK(T >= 1, DP_ERR_INVALID_ARG, "%s: T=%d must be positive", entry, T);
+    DP_CHECK(node_off_host[0] >= 0, DP_ERR_INVALID_ARG, "%s: node_off_host[0]=%d is negative", entry, node_off_host[0]);
     s = SRBatch{0, 0, 0, 0};
     for (int b = 0; b < B; ++b) {
         const long nb = (long)node_off_host[b + 1] - node_off_host[b];
-        SR_CHECK(nb >= 1, DP_ERR_INVALID_ARG, "%s: graph %d has %ld rows (every graph needs at least one)", entry, b, nb);
-        SR_CHECK(nb <= SR_MAX_ROWS, DP_ERR_UNSUPPORTED, "%s: graph %d has %ld rows, above the supported %d", entry, b, nb,
+        DP_CHECK(nb >= 1, DP_ERR_INVALID_ARG, "%s: graph %d has %ld rows (every graph needs at least one)", entry, b, nb);
+        DP_CHECK(nb <= SR_MAX_ROWS, DP_ERR_UNSUPPORTED, "%s: graph %d has %ld rows, above the supported %d", entry, b, nb,
                  SR_MAX_ROWS);
-        SR_CHECK(nb <= T, DP_ERR_INVALID_ARG, "%s: T=%d is below graph %d's %ld rows", entry, T, b, nb);
+        DP_CHECK(nb <= T, DP_ERR_INVALID_ARG, "%s: T=%d is below graph %d's %ld rows", entry, T, b, nb);
         const int plan = set2set_ragged_plan((int)nb, d);
-        SR_CHECK(plan >= 0, DP_ERR_UNSUPPORTED, "%s: graph %d (%ld rows, d=%d) outside the persistent kernel's limits",
+        DP_CHECK(plan >= 0, DP_ERR_UNSUPPORTED, "%s: graph %d (%ld rows, d=%d) outside the persistent kernel's limits",
                  entry, b, nb, d);
         s.max_n = nb > s.max_n ? (int)nb : s.max_n;
         int& mx = (plan & SR_EL) ? s.max_el : s.max_gl;
         mx = nb > mx ? (int)nb : mx;
     }
     s.n_total = B > 0 ? node_off_host[B] - node_off_host[0] : 0;
-    SR_CHECK((long)B * T < (1L << 31), DP_ERR_UNSUPPORTED, "%s: B * T = %ld (graph, step) rows, above 2^31 - 1", entry,
+    DP_CHECK((long)B * T < (1L << 31), DP_ERR_UNSUPPORTED, "%s: B * T = %ld (graph, step) rows, above 2^31 - 1", entry,
              (long)B * T);
     return DP_OK;
 }
@@ -669,14 +656,14 @@ size_t dp_set2set_ragged_bwd_workspace_bytes(const int* node_off_host, int B, in
 int dp_set2set_ragged_fwd(const float* emb, int lde, const int* node_off, const int* node_off_host, int B, int T, int d,
                           const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* Wp,
                           const float* bp, float* out, void* save, size_t save_bytes, void* stream) {
-    SR_PTR(emb); SR_PTR(node_off); SR_PTR(w_ih); SR_PTR(w_hh); SR_PTR(b_ih); SR_PTR(b_hh); SR_PTR(Wp); SR_PTR(bp);
-    SR_PTR(out);
+    DP_PTR(emb); DP_PTR(node_off); DP_PTR(w_ih); DP_PTR(w_hh); DP_PTR(b_ih); DP_PTR(b_hh); DP_PTR(Wp); DP_PTR(bp);
+    DP_PTR(out);
     SRBatch s;
     if (int rc = sr_check_batch("dp_set2set_ragged_fwd", node_off_host, B, T, d, s)) return rc;
-    SR_CHECK(lde >= d, DP_ERR_INVALID_ARG, "dp_set2set_ragged_fwd: lde=%d smaller than the row width d=%d", lde, d);
+    DP_CHECK(lde >= d, DP_ERR_INVALID_ARG, "dp_set2set_ragged_fwd: lde=%d smaller than the row width d=%d", lde, d);
     if (save) {
-        SR_CHECK(((uintptr_t)save & 3) == 0, DP_ERR_INVALID_ARG, "save is not 4-byte aligned");
-        SR_CHECK(save_bytes >= sr_save_bytes(s, B, T, d), DP_ERR_INVALID_ARG,
+        DP_ALIGNED4(save);
+        DP_CHECK(save_bytes >= sr_save_bytes(s, B, T, d), DP_ERR_INVALID_ARG,
                  "dp_set2set_ragged_fwd: save buffer too small: %zu < %zu", save_bytes, sr_save_bytes(s, B, T, d));
     }
     if (B == 0) return DP_OK;                          // (an empty batch has no output row: nothing to launch)
@@ -706,14 +693,14 @@ int dp_set2set_ragged_bwd(const float* emb, int lde, const int* node_off, const 
                           const float* bp, const float* out, const float* dout, float* demb, int ldde, float* dw_ih,
                           float* dw_hh, float* db_ih, float* db_hh, float* dWp, float* dbp, const void* save,
                           size_t save_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-    SR_PTR(emb); SR_PTR(node_off); SR_PTR(w_ih); SR_PTR(w_hh); SR_PTR(Wp); SR_PTR(out); SR_PTR(dout); SR_PTR(demb);
-    SR_PTR(dw_ih); SR_PTR(dw_hh); SR_PTR(db_ih); SR_PTR(db_hh); SR_PTR(dWp); SR_PTR(dbp); SR_PTR(save);
+    DP_PTR(emb); DP_PTR(node_off); DP_PTR(w_ih); DP_PTR(w_hh); DP_PTR(Wp); DP_PTR(out); DP_PTR(dout); DP_PTR(demb);
+    DP_PTR(dw_ih); DP_PTR(dw_hh); DP_PTR(db_ih); DP_PTR(db_hh); DP_PTR(dWp); DP_PTR(dbp); DP_PTR(save);
     (void)b_ih; (void)b_hh; (void)bp;                  // (the biases enter no gradient but their own)
     SRBatch s;
     if (int rc = sr_check_batch("dp_set2set_ragged_bwd", node_off_host, B, T, d, s)) return rc;
-    SR_CHECK(lde >= d && ldde >= d, DP_ERR_INVALID_ARG,
+    DP_CHECK(lde >= d && ldde >= d, DP_ERR_INVALID_ARG,
              "dp_set2set_ragged_bwd: lde=%d / ldde=%d smaller than the row width d=%d", lde, ldde, d);
-    SR_CHECK(save_bytes >= sr_save_bytes(s, B, T, d), DP_ERR_INVALID_ARG,
+    DP_CHECK(save_bytes >= sr_save_bytes(s, B, T, d), DP_ERR_INVALID_ARG,
              "dp_set2set_ragged_bwd: save buffer too small: %zu < %zu", save_bytes, sr_save_bytes(s, B, T, d));
     Seq q((hipStream_t)stream, workspace, workspace_bytes);
     sr_bwd_seq(q, s, emb, lde, node_off, node_off_host[0], w_ih, w_hh, Wp, out, dout, demb, ldde, dw_ih, dw_hh, db_ih,
