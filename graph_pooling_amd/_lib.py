@@ -94,6 +94,9 @@ AGG_DECLINED = -5
 
 # dp_linkpred_plan: (KT, CW, col_tiles, splits, split_tiles, forward tiles per graph, forward LDS bytes, backward LDS bytes)
 LINKPRED_PLAN_INTS = 8
+# dp_csr_linkpred_plan: (KT, T, pairs, Z, dense partials, edge partials, CW, col_tiles, splits, split_tiles,
+# forward edge VEC, NCH, backward edge VEC, NCH, dense forward LDS bytes, dense backward LDS bytes)
+CSR_LINKPRED_PLAN_INTS = 16
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -210,6 +213,7 @@ _PROTOS = {
     "dp_csr_pool_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_csr_pool_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "dp_csr_linkpred_workspace_bytes": (_Z, [_I, _I]),
+    "dp_csr_linkpred_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "dp_csr_linkpred_loss_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _Z, _P]),
     "dp_csr_linkpred_loss_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     # ragged batches of CSR graphs (host pointers — node_off_host, the plan's tables — are passed as addresses too)

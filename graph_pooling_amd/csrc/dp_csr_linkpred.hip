@@ -412,15 +412,57 @@ __global__ __launch_bounds__(256) void k_csr_link_edge_bwd_w(const float* S, int
                                            directed, values, values_t);
 }
 
-// ------------------------------------------------------------------ launch sequences
-int fwd_splits(int T) {
-    const int pairs = (T + 1) / 2;
-    return std::max(1, std::min(T, cdiv(LK_FWD_TARGET_WGS, pairs)));
+// ------------------------------------------------------------------ the plan (host only; dp_csr_linkpred_plan)
+// Everything the host decides for one graph, in one place: the launchers below act on this record and
+// dp_csr_linkpred_plan reports it, so what is reported is what runs.
+constexpr size_t dense_fwd_lds(int kt) { return (size_t)2 * 64 * (kt * 16 + 2) * sizeof(float); }
+constexpr size_t dense_bwd_lds(int kt, int cw) {
+    return ((size_t)(64 + cw) * (kt * 16 + 2) + 64 * (cw + 4)) * sizeof(float);
+}
+struct CsrLinkPlan {
+    int kt;                                      // K tier of both dense kernels
+    int T, pairs, Z;                             // forward: row blocks, row-block pairs (grid y), column splits (grid x)
+    int n_dense, n_edge;                         // forward partials: pairs * Z, then one per edge workgroup
+    int cw, col_tiles, splits, split_tiles;      // backward: column tile width, tiles, grid z, tiles per split
+    int fwd_vec, fwd_nch, bwd_vec, bwd_nch;      // edge kernels: floats per lane load, chunks of 16 lanes per row
+    size_t fwd_lds, bwd_lds;                     // dynamic LDS of the dense kernels
+    size_t part_floats;                          // backward partial buffer (0: no split)
+};
+// (VEC, NCH) of the edge kernels: 16-byte lanes cover 64 columns per chunk, 4-byte lanes 16
+void edge_form(bool v4, int K, int& vec, int& nch) {
+    vec = v4 ? 4 : 1;
+    nch = v4 ? (K <= 64 ? 1 : K <= 128 ? 2 : 4) : (K <= 16 ? 1 : K <= 64 ? 4 : 16);
+}
+// s_al16 / ds_al16: S / dS of this graph are 16-byte aligned.  The forward reads neither ldds nor ds_al16.
+CsrLinkPlan csr_link_plan(int n, int K, int lds, int ldds, bool s_al16, bool ds_al16) {
+    CsrLinkPlan p;
+    p.kt = lk_kt(K);
+    p.T = cdiv(n, 64);
+    p.pairs = (p.T + 1) / 2;
+    p.Z = std::max(1, std::min(p.T, cdiv(LK_FWD_TARGET_WGS, p.pairs)));
+    p.n_dense = p.pairs * p.Z;
+    p.n_edge = cdiv(n, LK_TEAM_ROWS);
+    // few row blocks: the column tiles are split over extra workgroups and the partials summed afterwards (link_bwd's
+    // rule, dp_linkpred.hip)
+    p.cw = p.kt >= 12 ? 32 : 64;
+    p.col_tiles = cdiv(n, p.cw);
+    const int row_blocks = cdiv(n, 64);
+    const int want = std::max(1, std::min(p.col_tiles, cdiv(LK_BWD_TARGET_WGS, row_blocks)));
+    p.split_tiles = cdiv(p.col_tiles, want);
+    p.splits = cdiv(p.col_tiles, p.split_tiles);
+    p.part_floats = p.splits > 1 ? (size_t)p.splits * n * K : 0;
+    const bool v4f = K % 4 == 0 && lds % 4 == 0 && s_al16;
+    edge_form(v4f, K, p.fwd_vec, p.fwd_nch);
+    edge_form(v4f && ldds % 4 == 0 && ds_al16, K, p.bwd_vec, p.bwd_nch);
+    p.fwd_lds = dense_fwd_lds(p.kt);
+    p.bwd_lds = dense_bwd_lds(p.kt, p.cw);
+    return p;
 }
 
+// ------------------------------------------------------------------ launch sequences
 template <int KT>
 void launch_dense_fwd(Seq& q, const float* S, int lds, int n, int K, int T, int Z, double* partial) {
-    constexpr size_t bytes = (size_t)2 * 64 * (KT * 16 + 2) * sizeof(float);
+    constexpr size_t bytes = dense_fwd_lds(KT);
     static_assert(bytes + 256 * sizeof(double) <= 160 * 1024, "csr_link_dense_fwd LDS");
     static DynLdsOnce attr;
     if (bytes > 64 * 1024)
@@ -431,48 +473,47 @@ void launch_dense_fwd(Seq& q, const float* S, int lds, int n, int K, int T, int 
                        partial);
 }
 
-// (VEC, NCH) of the edge kernels: 16-byte lanes cover 64 columns per chunk, 4-byte lanes 16
-#define LK_EDGE_DISPATCH(KERNEL, v4, K, ...)                                                                \
+// the edge kernel of the plan's form
+#define LK_EDGE_DISPATCH(KERNEL, vec, nch, ...)                                                             \
     do {                                                                                                    \
         const dim3 grid_(cdiv(n, LK_TEAM_ROWS));                                                            \
-        if (v4) {                                                                                           \
-            if (K <= 64) hipLaunchKernelGGL((KERNEL<4, 1>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);    \
-            else if (K <= 128) hipLaunchKernelGGL((KERNEL<4, 2>), grid_, dim3(256), 0, q.stream, __VA_ARGS__); \
+        if (vec == 4) {                                                                                     \
+            if (nch == 1) hipLaunchKernelGGL((KERNEL<4, 1>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);   \
+            else if (nch == 2) hipLaunchKernelGGL((KERNEL<4, 2>), grid_, dim3(256), 0, q.stream, __VA_ARGS__); \
             else hipLaunchKernelGGL((KERNEL<4, 4>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);            \
         } else {                                                                                            \
-            if (K <= 16) hipLaunchKernelGGL((KERNEL<1, 1>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);    \
-            else if (K <= 64) hipLaunchKernelGGL((KERNEL<1, 4>), grid_, dim3(256), 0, q.stream, __VA_ARGS__); \
+            if (nch == 1) hipLaunchKernelGGL((KERNEL<1, 1>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);   \
+            else if (nch == 4) hipLaunchKernelGGL((KERNEL<1, 4>), grid_, dim3(256), 0, q.stream, __VA_ARGS__); \
             else hipLaunchKernelGGL((KERNEL<1, 16>), grid_, dim3(256), 0, q.stream, __VA_ARGS__);           \
         }                                                                                                   \
     } while (0)
 
 int fwd_partials(int n) {
-    const int T = cdiv(n, 64);
-    return ((T + 1) / 2) * fwd_splits(T) + cdiv(n, LK_TEAM_ROWS);
+    const CsrLinkPlan p = csr_link_plan(n, 1, 1, 1, true, true);      // neither count depends on K or the strides
+    return p.n_dense + p.n_edge;
 }
 // the dense and the edge partials of one graph -> partial[0 .. fwd_partials(n) - 1]
 void csr_link_fwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, int n, int K,
                         double* partial, const float* values) {
-    const int T = cdiv(n, 64), Z = fwd_splits(T);
-    const int n_dense = ((T + 1) / 2) * Z;
+    const CsrLinkPlan p = csr_link_plan(n, K, lds, K, aligned16(S), true);
     if (!q.ok()) return;
 #define LK_FWD(KT_) \
-    case KT_: launch_dense_fwd<KT_>(q, S, lds, n, K, T, Z, partial); break;
-    switch (lk_kt(K)) { LK_FWD(1) LK_FWD(2) LK_FWD(3) LK_FWD(4) LK_FWD(6) LK_FWD(8) LK_FWD(12) LK_FWD(16) }
+    case KT_: launch_dense_fwd<KT_>(q, S, lds, n, K, p.T, p.Z, partial); break;
+    switch (p.kt) { LK_FWD(1) LK_FWD(2) LK_FWD(3) LK_FWD(4) LK_FWD(6) LK_FWD(8) LK_FWD(12) LK_FWD(16) }
 #undef LK_FWD
     q.check_launch("csr_link_dense_fwd");
     if (!q.ok()) return;
-    const bool v4 = K % 4 == 0 && lds % 4 == 0 && aligned16(S);
-    if (values) LK_EDGE_DISPATCH(k_csr_link_edge_fwd_w, v4, K, S, lds, indptr, indices, values, n, K, partial + n_dense);
-    else LK_EDGE_DISPATCH(k_csr_link_edge_fwd, v4, K, S, lds, indptr, indices, n, K, partial + n_dense);
+    if (values)
+        LK_EDGE_DISPATCH(k_csr_link_edge_fwd_w, p.fwd_vec, p.fwd_nch, S, lds, indptr, indices, values, n, K,
+                         partial + p.n_dense);
+    else LK_EDGE_DISPATCH(k_csr_link_edge_fwd, p.fwd_vec, p.fwd_nch, S, lds, indptr, indices, n, K, partial + p.n_dense);
     q.check_launch("csr_link_edge_fwd");
 }
 
 template <int KT, int NJ>
 void launch_dense_bwd(Seq& q, const float* S, int lds, const float* scale, float* dS, int ldds, int n, int K,
                       int accumulate, float* part, int splits, int split_tiles) {
-    constexpr int CW = 32 * NJ, KP = KT * 16 + 2;
-    constexpr size_t bytes = ((size_t)(64 + CW) * KP + 64 * (CW + 4)) * sizeof(float);
+    constexpr size_t bytes = dense_bwd_lds(KT, 32 * NJ);
     static_assert(bytes <= 160 * 1024, "csr_link_dense_bwd LDS");
     static DynLdsOnce attr;
     if (bytes > 64 * 1024)
@@ -483,48 +524,35 @@ void launch_dense_bwd(Seq& q, const float* S, int lds, const float* scale, float
                        q.stream, S, lds, scale, dS, ldds, n, K, accumulate, part, split_tiles);
 }
 
-// column splits of the dense backward and their partial buffer (floats; 0: no split)
-size_t bwd_part_floats(int n, int K, int* splits_out, int* split_tiles_out) {
-    const int cw = lk_kt(K) >= 12 ? 32 : 64;
-    const int col_tiles = cdiv(n, cw), row_blocks = cdiv(n, 64);
-    int splits = std::max(1, std::min(col_tiles, cdiv(LK_BWD_TARGET_WGS, row_blocks)));
-    const int split_tiles = cdiv(col_tiles, splits);
-    splits = cdiv(col_tiles, split_tiles);
-    if (splits_out) *splits_out = splits;
-    if (split_tiles_out) *split_tiles_out = split_tiles;
-    return splits > 1 ? (size_t)splits * n * K : 0;
-}
+// the dense backward's partial buffer (floats; 0: no split)
+size_t bwd_part_floats(int n, int K) { return csr_link_plan(n, K, K, K, true, true).part_floats; }
 // one graph's dS from the ready scale; `part`: bwd_part_floats(n, K) floats (null when that is 0)
 void csr_link_bwd_graph(Seq& q, const float* S, int lds, const int* indptr, const int* indices, const int* indptr_t,
                         const int* indices_t, const float* scale, float* part, float* dS, int ldds, int accumulate,
                         int n, int K, int directed, const float* values, const float* values_t) {
-    const int kt = lk_kt(K);
-    int splits, split_tiles;
-    if (!bwd_part_floats(n, K, &splits, &split_tiles)) part = nullptr;
+    const CsrLinkPlan p = csr_link_plan(n, K, lds, ldds, aligned16(S), aligned16(dS));
+    if (!p.part_floats) part = nullptr;
     if (!q.ok()) return;
-    // few row blocks: the column tiles are split over extra workgroups and the partials summed afterwards (link_bwd's
-    // rule, bwd_part_floats)
-#define LK_BWD(KT_, NJ_)                                                                                      \
-    case KT_:                                                                                                 \
-        launch_dense_bwd<KT_, NJ_>(q, S, lds, scale, dS, ldds, n, K, accumulate, part, splits, split_tiles);  \
+#define LK_BWD(KT_, NJ_)                                                                                          \
+    case KT_:                                                                                                     \
+        launch_dense_bwd<KT_, NJ_>(q, S, lds, scale, dS, ldds, n, K, accumulate, part, p.splits, p.split_tiles);  \
         break;
-    switch (kt) { LK_BWD(1, 2) LK_BWD(2, 2) LK_BWD(3, 2) LK_BWD(4, 2) LK_BWD(6, 2) LK_BWD(8, 2) LK_BWD(12, 1) LK_BWD(16, 1) }
+    switch (p.kt) { LK_BWD(1, 2) LK_BWD(2, 2) LK_BWD(3, 2) LK_BWD(4, 2) LK_BWD(6, 2) LK_BWD(8, 2) LK_BWD(12, 1) LK_BWD(16, 1) }
 #undef LK_BWD
     q.check_launch("csr_link_dense_bwd");
     if (!q.ok()) return;
     if (part) {
         const int blocks = std::min(cdiv((long)n * K, 256), 2048);
-        hipLaunchKernelGGL(k_csr_link_reduce, dim3(blocks), dim3(256), 0, q.stream, (const float*)part, splits, dS, ldds,
-                           n, K, accumulate);
+        hipLaunchKernelGGL(k_csr_link_reduce, dim3(blocks), dim3(256), 0, q.stream, (const float*)part, p.splits, dS,
+                           ldds, n, K, accumulate);
         q.check_launch("csr_link_reduce");
     }
-    const bool v4 = K % 4 == 0 && lds % 4 == 0 && ldds % 4 == 0 && aligned16(S) && aligned16(dS);
     if (values)
-        LK_EDGE_DISPATCH(k_csr_link_edge_bwd_w, v4, K, S, lds, indptr, indices, values, indptr_t, indices_t, values_t,
-                         (const float*)scale, dS, ldds, n, K, directed);
+        LK_EDGE_DISPATCH(k_csr_link_edge_bwd_w, p.bwd_vec, p.bwd_nch, S, lds, indptr, indices, values, indptr_t,
+                         indices_t, values_t, (const float*)scale, dS, ldds, n, K, directed);
     else
-        LK_EDGE_DISPATCH(k_csr_link_edge_bwd, v4, K, S, lds, indptr, indices, indptr_t, indices_t, (const float*)scale, dS,
-                         ldds, n, K, directed);
+        LK_EDGE_DISPATCH(k_csr_link_edge_bwd, p.bwd_vec, p.bwd_nch, S, lds, indptr, indices, indptr_t, indices_t,
+                         (const float*)scale, dS, ldds, n, K, directed);
     q.check_launch("csr_link_edge_bwd");
 }
 
@@ -561,7 +589,7 @@ void csr_link_batch_bwd_seq(Seq& q, const float* S, int lds, const int* indptr, 
                             int accumulate, int K, const float* values = nullptr, const float* values_t = nullptr) {
     float* scale = q.alloc<float>(64);
     size_t pf = 0;
-    for (int b = 0; b < B; ++b) pf = std::max(pf, bwd_part_floats(off[b + 1] - off[b], K, nullptr, nullptr));
+    for (int b = 0; b < B; ++b) pf = std::max(pf, bwd_part_floats(off[b + 1] - off[b], K));
     float* part = pf ? q.alloc<float>(pf) : nullptr;       // reused graph after graph: the launches are stream-ordered
     if (!q.ok()) return;
     hipLaunchKernelGGL(k_csr_link_final, dim3(1), dim3(256), 0, q.stream, (const double*)nullptr, 0, batch_norm(off, B),
@@ -662,6 +690,21 @@ size_t dp_csr_linkpred_batch_workspace_bytes(const int* node_off_host, int B, in
 size_t dp_csr_linkpred_workspace_bytes(int n, int K) {
     const int off[2] = {0, n};
     return dp_csr_linkpred_batch_workspace_bytes(off, 1, K);
+}
+int dp_csr_linkpred_plan(int n, int K, int lds, int ldds, int s_misaligned, int ds_misaligned, int* plan_out) {
+    const char* entry = "dp_csr_linkpred_plan";
+    DP_CHECK(plan_out != nullptr, DP_ERR_INVALID_ARG, "%s: plan_out is NULL", entry);
+    DP_CHECK(n >= 1, DP_ERR_INVALID_ARG, "%s: n=%d must be positive", entry, n);
+    DP_CHECK(K >= 1, DP_ERR_INVALID_ARG, "%s: K=%d must be positive", entry, K);
+    DP_CHECK(K <= 256, DP_ERR_UNSUPPORTED, "%s: K=%d clusters exceed the fused tile kernel (max 256)", entry, K);
+    DP_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", entry, lds, K);
+    DP_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", entry, ldds, K);
+    const CsrLinkPlan p = csr_link_plan(n, K, lds, ldds, !s_misaligned, !ds_misaligned);
+    const int out[DP_CSR_LINKPRED_PLAN_INTS] = {p.kt, p.T, p.pairs, p.Z, p.n_dense, p.n_edge, p.cw, p.col_tiles,
+                                                p.splits, p.split_tiles, p.fwd_vec, p.fwd_nch, p.bwd_vec, p.bwd_nch,
+                                                (int)p.fwd_lds, (int)p.bwd_lds};
+    for (int i = 0; i < DP_CSR_LINKPRED_PLAN_INTS; ++i) plan_out[i] = out[i];
+    return DP_OK;
 }
 
 // ---- one graph: the batch of one, off = {0, n}

@@ -675,6 +675,20 @@ int dp_csr_pool_bwd_w(const float* S, int lds, const float* Z, int ldz, const in
  * summation is decomposed).  The workspace is O(n K): dp_csr_linkpred_workspace_bytes covers both directions; a short
  * or NULL workspace, n < 1, lds < K and NULL pointers are DP_ERR_INVALID_ARG before any launch. */
 size_t dp_csr_linkpred_workspace_bytes(int n, int K);
+/* dp_csr_linkpred_plan: what the host decides for one graph of n rows (a batch runs it per graph, n = n_b, on the graph's
+ * own S / dS pointers), answered by the function the launchers themselves act on.  Host only: no stream, no GPU call.
+ * s_misaligned / ds_misaligned: non-zero when the graph's S / dS is not 16-byte aligned.
+ * plan_out[DP_CSR_LINKPRED_PLAN_INTS] = { KT (K tier of both dense kernels: 1 2 3 4 6 8 12 16), T = ceil(n / 64) row
+ * blocks, the forward's row-block pairs (T + 1) / 2 (grid y), its column splits Z (grid x; a workgroup walks every Z-th
+ * column tile), dense loss partials = pairs * Z, edge loss partials = ceil(n / 16); the backward's column tile width CW
+ * (64, or 32 for KT >= 12), col_tiles = ceil(n / CW), splits (grid z; 1: no gradient partials and no reduce launch),
+ * split_tiles (column tiles per split; the last may hold fewer); the forward edge kernel's VEC (floats per lane load:
+ * 4 when K % 4 == 0, lds % 4 == 0 and S is 16-byte aligned, else 1) and NCH (16-lane chunks per row), the backward edge
+ * kernel's VEC (4 needs ldds % 4 == 0 and an aligned dS as well) and NCH; the dense forward's and the dense backward's
+ * dynamic LDS bytes }.  DP_ERR_UNSUPPORTED for K > 256; DP_ERR_INVALID_ARG for n < 1, K < 1, lds < K, ldds < K or a NULL
+ * plan_out. */
+#define DP_CSR_LINKPRED_PLAN_INTS 16
+int dp_csr_linkpred_plan(int n, int K, int lds, int ldds, int s_misaligned, int ds_misaligned, int* plan_out);
 int dp_csr_linkpred_loss_fwd(const float* S, int lds, const int* indptr, const int* indices, float* loss_out,
                              int n, int K, void* workspace, size_t workspace_bytes, void* stream);
 /* dS (+)= dloss * dloss/dS; dloss: device scalar or NULL = 1; indptr_t/indices_t: CSR of A^T (the forward's arrays

@@ -174,16 +174,22 @@ def pool_ref(a, S, Z, dXp, dAp, dz_old, deg, deg_t):
 
 
 # ------------------------------------------------------------------ link loss (one graph; a batch sums the graphs)
-def link_terms(a, S, deg, deg_t):
-    """(sum of the n^2 terms, bound of that sum, d sum / dS, its bound) in float64 for one graph."""
+def link_terms(a, S, deg, deg_t, exact=None):
+    """(sum of the n^2 terms, bound of that sum, d sum / dS, its bound) in float64 for one graph.  The gate is
+    torch.minimum's: 1 below raw = 1, 1/2 at raw == 1 exactly, 0 above.  `exact`: bool [n, n], True where the fp32 p equals
+    the float64 one (one-hot rows, a quarter grid): there the (K + 4) u p term is 0 and 1 - p is exact, so only the
+    relative roundings of the two sums with eps remain (2 u absolute on either logarithm, inside the 4 u of a
+    quotient).  None: no entry is exact."""
     S = np.asarray(S, dtype=np.float64)
     n, K = S.shape
-    p = np.minimum(S @ S.T, 1.0)
-    gate = (S @ S.T <= 1.0).astype(np.float64)
+    raw = S @ S.T
+    p = np.minimum(raw, 1.0)
+    gate = np.where(raw < 1.0, 1.0, np.where(raw == 1.0, 0.5, 0.0))
+    inexact = np.ones_like(p) if exact is None else (~np.asarray(exact, dtype=bool)).astype(np.float64)
     lp, lq = np.log(p + EPS), np.log(1.0 - p + EPS)
     tot = float((-a * lp - (1.0 - a) * lq).sum())
-    dq = ((K + 4) * U * p + 2 * U) / (1.0 - p + EPS) + 4 * U * np.abs(lq)
-    dp_ = ((K + 4) * U * p + 2 * U) / (p + EPS) + 4 * U * np.abs(lp)
+    dq = np.where(inexact > 0, ((K + 4) * U * p + 2 * U) / (1.0 - p + EPS), 2 * U) + 4 * U * np.abs(lq)
+    dp_ = np.where(inexact > 0, ((K + 4) * U * p + 2 * U) / (p + EPS), 2 * U) + 4 * U * np.abs(lp)
     aa = np.abs(a)
     bt = float((dq + aa * (dq + dp_ + 4 * U * (np.abs(lp) + np.abs(lq)))).sum())
     # gradient: d/dp of the dense term g' = 1 / (1 - p + eps), of the edge term c = -1/(p + eps) - 1/(1 - p + eps)
@@ -191,8 +197,8 @@ def link_terms(a, S, deg, deg_t):
     c = gate * (-1.0 / (p + EPS) - 1.0 / (1.0 - p + EPS))
     coef = g1 + a * c
     dS = (coef + coef.T) @ S
-    dg = (K + 4) * U * (p + 1.0) / (1.0 - p + EPS) ** 2 + 4 * U * g1
-    dc = (K + 4) * U * (p / (p + EPS) ** 2 + (p + 1.0) / (1.0 - p + EPS) ** 2) + 4 * U * np.abs(c)
+    dg = inexact * (K + 4) * U * (p + 1.0) / (1.0 - p + EPS) ** 2 + 4 * U * g1
+    dc = inexact * (K + 4) * U * (p / (p + EPS) ** 2 + (p + 1.0) / (1.0 - p + EPS) ** 2) + 4 * U * np.abs(c)
     dmax = int(max(deg.max(), deg_t.max())) if n else 0
     bS = 2.0 * (dg + (n + K + 8) * U * g1) @ S
     edge = aa * (dc + (dmax + 8) * U * np.abs(c))
@@ -201,7 +207,7 @@ def link_terms(a, S, deg, deg_t):
 
 
 def link_ref(graphs, dloss=1.0):
-    """graphs: [(a, S, deg, deg_t)] -> dict(loss, loss_bound, dS [n_total, K], dS_bound)."""
+    """graphs: [(a, S, deg, deg_t)] or [(a, S, deg, deg_t, exact)] -> dict(loss, loss_bound, dS [n_total, K], dS_bound)."""
     terms = [link_terms(*g) for g in graphs]
     nn = float(sum(g[1].shape[0] ** 2 for g in graphs))
     loss = sum(t[0] for t in terms) / nn

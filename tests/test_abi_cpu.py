@@ -138,6 +138,20 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     assert lib.dp_linkpred_plan(20, 500, 50, None) == -1 and b"NULL" in lib.dp_last_error_string()
     for bad in ((0, 500, 50), (20, 0, 50), (20, 500, 0), (-1, 500, 50)):
         assert lib.dp_linkpred_plan(*bad, lp) == -1 and b"must be positive" in lib.dp_last_error_string(), bad
+    # the CSR link loss's plan query (host only): DD's largest graph at K = 50, an ENZYMES-sized one, the refusals
+    assert "dp_csr_linkpred_plan" in _lib.EXPORTED_SYMBOLS
+    cp = (C.c_int * _lib.CSR_LINKPRED_PLAN_INTS)()
+    assert lib.dp_csr_linkpred_plan(5748, 50, 50, 50, 0, 0, cp) == 0
+    assert tuple(cp) == (4, 90, 45, 23, 1035, 360, 64, 90, 6, 15, 1, 4, 1, 4, 4 * 2 * 64 * 66, 4 * (128 * 66 + 64 * 68))
+    assert lib.dp_csr_linkpred_plan(126, 28, 28, 28, 0, 0, cp) == 0 and tuple(cp)[:4] + tuple(cp)[6:14] == (
+        2, 2, 1, 2, 64, 2, 2, 1, 4, 1, 4, 1)
+    assert lib.dp_csr_linkpred_plan(126, 28, 28, 30, 0, 0, cp) == 0 and tuple(cp)[10:14] == (4, 1, 1, 4)
+    assert lib.dp_csr_linkpred_plan(126, 28, 28, 28, 1, 0, cp) == 0 and tuple(cp)[10:14] == (1, 4, 1, 4)
+    assert lib.dp_csr_linkpred_plan(126, 257, 257, 257, 0, 0, cp) == -3 and b"K=257" in lib.dp_last_error_string()
+    assert lib.dp_csr_linkpred_plan(126, 28, 28, 28, 0, 0, None) == -1 and b"NULL" in lib.dp_last_error_string()
+    for bad, text in (((0, 28, 28, 28), b"must be positive"), ((126, 0, 28, 28), b"must be positive"),
+                      ((126, 28, 27, 28), b"lds=27 smaller"), ((126, 28, 28, 27), b"ldds=27 smaller")):
+        assert lib.dp_csr_linkpred_plan(*bad, 0, 0, cp) == -1 and text in lib.dp_last_error_string(), bad
     yp = _lib.GroupPtrs()
     rc = lib.dp_adj_aggregate_rownorm(None, None, None, None, None, 16, None, C.byref(g), None, C.byref(yp), None, None,
                                       1, 4, 1, 0, 0, None, 0, None)
