@@ -279,7 +279,7 @@ void head_fwd(Seq& q, const HeadArgs& a) {
 // 50 and 2 above it): its weight-gradient columns, its share of d(features) and the max-readout scatter of those
 // features.  The layers above are a few hundred MACs per graph; every workgroup recomputes them from LDS instead of
 // waiting for a neighbour (no inter-workgroup dependency), and workgroup 0 stores their gradients.  All sums over the
-// batch are plain loops in b: deterministic.
+// batch are plain loops in b: deterministic (the bias gradients' in fp64, rounded once).
 constexpr int HEAD_SLICE = 16;
 __global__ __launch_bounds__(256) void k_head_bwd(HeadBwdArgs a) {
     extern __shared__ float lds[];
@@ -369,10 +369,13 @@ __global__ __launch_bounds__(256) void k_head_bwd(HeadBwdArgs a) {
             }
             if (a.h.b_off[i] >= 0)
                 for (int j = threadIdx.x; j < dout; j += 256) {
-                    float s = 0.f;
+                    // a bias gradient is a sum of B terms of both signs, most of which cancel: a serial fp32 chain
+                    // over B = 1024 graphs was 25-50 times further from fp64 than a blocked fp32 sum.  fp64 adds here
+                    // (dout chains per launch) cost nothing; k_reduce_slabs_head's bias entries do the same.
+                    double s = 0.0;
 #pragma unroll 8
-                    for (int b = 0; b < B; ++b) s += go[b * dout + j];
-                    a.grads[a.h.b_off[i] + j] = s;
+                    for (int b = 0; b < B; ++b) s += (double)go[b * dout + j];
+                    a.grads[a.h.b_off[i] + j] = (float)s;
                 }
         }
         // gi[b][k] = relu'(hin) * sum_j go[b][j] W[j][k]   (hin = relu(.), so hin > 0 decides)
@@ -398,10 +401,10 @@ __global__ __launch_bounds__(256) void k_head_bwd(HeadBwdArgs a) {
     }
     if (blockIdx.x == 0 && a.h.b_off[0] >= 0)
         for (int j = threadIdx.x; j < d1; j += 256) {
-            float s = 0.f;
+            double s = 0.0;                       // (as the upper layers' bias gradients)
 #pragma unroll 8
-            for (int b = 0; b < B; ++b) s += go[b * d1 + j];
-            a.grads[a.h.b_off[0] + j] = s;
+            for (int b = 0; b < B; ++b) s += (double)go[b * d1 + j];
+            a.grads[a.h.b_off[0] + j] = (float)s;
         }
     // d(features) of the slice and its max-readout scatter: dZ[b, argmax, f] += dfeat  (dZ zero-initialised by the caller)
     HEAD_STAMP(11);

@@ -2041,8 +2041,8 @@ void argmax_rows(Seq& q, const float* X, int ldx, long long* out, int rows, int 
 //
 // The step's final launch also finishes the prediction head when its backward rode in the last level's kernel
 // (SmallHeadFold; k_reduce_slabs_head below): workgroups past the `tiles` slab tiles take entries of pred_model's
-// dW / db, one per thread, each the b-ascending chain of k_head_bwd ( s += go[b][j] * hin[b][k], s += go[b][j] for a
-// bias ), operands straight from global memory -- d_ypred, the saved hid[i] and the [B][hup] hidden-layer gradients
+// dW / db, one per thread, each the b-ascending chain of k_head_bwd ( s += go[b][j] * hin[b][k], s += go[b][j] in fp64
+// for a bias ), operands straight from global memory -- d_ypred, the saved hid[i] and the [B][hup] hidden-layer gradients
 // k_small_level_bwd stored, all complete since that launch ended.  Every load of a chunk of HG_CHUNK graphs is issued
 // before the chunk's adds, so a batch of up to HG_CHUNK graphs costs these workgroups ONE memory round trip, as a slab
 // tile costs its own; and only HG_THREADS threads of a workgroup take an entry (the other waves leave at once),
@@ -2100,6 +2100,7 @@ __device__ inline void head_grad_entry(const HeadGradArgs& a, int e) {
     const float* xp = hin + (weight ? k : 0);
     const int xs = weight ? din : 0;        // (a bias entry loads hin[0][0] for nothing: no branch around the loads)
     float s = 0.f;
+    double sb = 0.0;                        // a bias entry's chain, in fp64 as k_head_bwd's: the same bits
     for (int b0 = 0; b0 < B; b0 += HG_CHUNK) {
         float g[HG_CHUNK], x[HG_CHUNK];
         // groups of eight graphs behind a uniform test, rows clamped inside the last group: every load of the chunk
@@ -2122,11 +2123,11 @@ __device__ inline void head_grad_entry(const HeadGradArgs& a, int e) {
         } else {
 #pragma unroll
             for (int u = 0; u < HG_CHUNK; ++u)
-                if (b0 + u < B) s += g[u];
+                if (b0 + u < B) sb += (double)g[u];
         }
     }
     if (weight) a.grads[woff + r] = s;
-    else a.grads[boff + j] = s;
+    else a.grads[boff + j] = (float)sb;
 }
 
 __device__ inline void reduce_slab_tile(const float* slabs, long stride, int B, float* out, long count, int accumulate,

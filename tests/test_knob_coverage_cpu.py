@@ -14,7 +14,8 @@ API = os.path.join(CSRC, "dp_api.hip")
 
 # knobs that select no alternate plan of the encoder, or whose plan has a test of its own
 EXCLUDED = {
-    "DP_NO_HEAD_FOLD": "its plan is held bit-identical to the folded head by tests/test_gpu_head_fold.py",
+    "DP_NO_HEAD_FOLD": "its plan is held bit-identical to the folded head by tests/test_gpu_head_fold.py and checked "
+                       "against fp64 at every edge of k_head_bwd by tests/test_gpu_head.py",
     "DP_GEMM_TRACE": "only writes a host-side log of the GEMM shapes; it selects no kernel",
     "DP_AGG_DEBUG": "read only in DP_STAMP diagnostic builds, where it ablates phases of the panel kernel on purpose "
                     "(timing only, wrong results)",
