@@ -97,6 +97,8 @@ LINKPRED_PLAN_INTS = 8
 # dp_csr_linkpred_plan: (KT, T, pairs, Z, dense partials, edge partials, CW, col_tiles, splits, split_tiles,
 # forward edge VEC, NCH, backward edge VEC, NCH, dense forward LDS bytes, dense backward LDS bytes)
 CSR_LINKPRED_PLAN_INTS = 16
+# dp_csr_sddmm_plan: (lanes per entry, floats per lane load, register-held visits, column tail, row chunk, rows per workgroup)
+CSR_SDDMM_PLAN_INTS = 6
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -259,6 +261,14 @@ _PROTOS = {
     "dp_csr_linkpred_batch_loss_bwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "dp_csr_frob_link_fwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
     "dp_csr_frob_link_batch_fwd_w": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    # gradients to the stored values: the SDDMM family (node_off_host is a host pointer, passed as an address)
+    "dp_csr_sddmm_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "dp_csr_sddmm": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _P, _F, _P]),
+    "dp_csr_link_dvalues": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P]),
+    "dp_csr_pool_dvalues_workspace_bytes": (_Z, [_I, _I]),
+    "dp_csr_pool_dvalues": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _Z, _P]),
+    "dp_sparse_gcn_layer_bwd_dv": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P,
+                                        _I, _I, _I, _I, _P, _Z, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

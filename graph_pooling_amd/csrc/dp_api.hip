@@ -167,6 +167,9 @@ void set2set_bwd(Seq& q, const float* emb, int lde, const float* w_ih, const flo
                  float* dbp, int B, int n, int d, const void* save);
 size_t set2set_save_bytes(int B, int n, int d);
 int set2set_plan(int n, int d);
+// dp_csr_edge_grad.hip: out[e] = P_i . Q_indices[e] over the stored entries
+void csr_sddmm_identity(Seq& q, const float* P, int ldp, const float* Q, int ldq, const int* indptr, const int* indices,
+                        float* out, int n_rows, int F);
 // dp_meanagg.hip
 void mean_aggregate_fwd(Seq& q, const float* table, int ldt, const int* indptr, const int* indices, float* out,
                         int ldo, int n_rows, int feat);
@@ -1270,23 +1273,28 @@ void sparse_gcn_fwd_seq(Seq& q, const float* x, int ldx, const int* indptr, cons
 void sparse_gcn_bwd_seq(Seq& q, const float* ax, const int* indptr, const int* indices, const int* indptr_t,
                         const int* indices_t, const float* W, const float* y, int ldy, const float* invn,
                         const float* dy, int lddy, float* dx, int lddx, float* dW, float* db, int n, int Fin, int Fout,
-                        int flags, const float* values = nullptr, const float* values_t = nullptr) {
+                        int flags, const float* values = nullptr, const float* values_t = nullptr,
+                        const float* x = nullptr, int ldx = 0, float* dvalues = nullptr) {
     float* dU = q.alloc<float>((size_t)n * Fout);
-    float* dax = dx ? q.alloc<float>((size_t)n * Fin) : nullptr;
+    float* dax = (dx || dvalues) ? q.alloc<float>((size_t)n * Fin) : nullptr;
     if (q.err) return;
     rownorm_bwd(q, gcp(dy, lddy), gcp(nullptr, 0), gcp(y, ldy), invn, nullptr, nullptr, one_group(Fout), dU, Fout,
                 nullptr, 1, n, 0, 0, (flags & DP_F_NORMALIZE) ? 1 : 0);
     if (db) colsum_batched(q, dU, Fout, 0, n, Fout, db, 0, 1);
     bgemm(q, ax, dU, dW, nullptr, 1, Fin, Fout, n, Fin, Fout, Fout, 0, 0, 0, true, false, 1.f, 0.f, 0);
-    if (!dx) return;
+    if (!dax) return;
     bgemm(q, dU, W, dax, nullptr, 1, n, Fin, Fout, Fout, Fout, Fin, 0, 0, 0, false, true, 1.f, 0.f, 0);
-    if (indptr_t && indices_t) {
-        csr_aggregate_fwd(q, dax, Fin, indptr_t, indices_t, dx, lddx, n, Fin, 0, 0.f, values_t);      // dx = A^T dax, a gather
-    } else {
-        zero_fill(q, dx, (size_t)n * Fin * sizeof(float));
-        csr_aggregate_bwd_scatter(q, dax, Fin, indptr, indices, dx, lddx, n, Fin, 0, values);
+    if (dx) {
+        if (indptr_t && indices_t) {
+            csr_aggregate_fwd(q, dax, Fin, indptr_t, indices_t, dx, lddx, n, Fin, 0, 0.f, values_t);      // dx = A^T dax, a gather
+        } else {
+            zero_fill(q, dx, (size_t)n * Fin * sizeof(float));
+            csr_aggregate_bwd_scatter(q, dax, Fin, indptr, indices, dx, lddx, n, Fin, 0, values);
+        }
+        if (flags & DP_F_ADD_SELF) axpy(q, dx, dax, 1.f, (long)n * Fin);
     }
-    if (flags & DP_F_ADD_SELF) axpy(q, dx, dax, 1.f, (long)n * Fin);
+    // dvalues[e] = dax_i . x_j: every stored entry of A x is its own variable (add_self's + x does not read A)
+    if (dvalues) csr_sddmm_identity(q, dax, Fin, x, ldx, indptr, indices, dvalues, n, Fin);
 }
 }  // namespace
 size_t dp_sparse_gcn_layer_workspace_bytes(int n, int Fin, int Fout) {
@@ -1310,11 +1318,13 @@ static int sparse_gcn_fwd_entry(const float* x, int ldx, const int* indptr, cons
                        weighted ? values : nullptr);
     return q.err;
 }
+// x / ldx / dvalues: the gradient to the stored values (dp_sparse_gcn_layer_bwd_dv: want_dv); NULL from the others
 static int sparse_gcn_bwd_entry(const char* fn, const float* ax, const int* indptr, const int* indices,
                                 const float* values, const int* indptr_t, const int* indices_t, const float* values_t,
                                 bool weighted, const float* W, const float* y, int ldy, const float* invnorm,
                                 const float* dy, int lddy, float* dx, int lddx, float* dW, float* db, int n, int Fin,
-                                int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+                                int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream,
+                                bool want_dv = false, const float* x = nullptr, int ldx = 0, float* dvalues = nullptr) {
     DP_NOTNULL(ax); DP_NOTNULL(indptr); DP_NOTNULL(indices);
     DP_VALUES((void)0, "values is NULL");
     DP_NOTNULL(W); DP_NOTNULL(y); DP_NOTNULL(invnorm); DP_NOTNULL(dy); DP_NOTNULL(dW);
@@ -1322,10 +1332,15 @@ static int sparse_gcn_bwd_entry(const char* fn, const float* ax, const int* indp
     DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr), "indptr_t and indices_t come together");
     DP_VALUES_T((void)0, "%s: values_t is NULL but indices_t is a CSR of its own", fn);
     DP_CHECK_ARG(!dx || lddx == Fin, "dx must be contiguous (lddx == Fin)");
+    if (want_dv) {
+        DP_NOTNULL(x); DP_NOTNULL(dvalues);
+        DP_CHECK_ARG(ldx >= Fin, "ldx=%d smaller than Fin=%d", ldx, Fin);
+    }
     Seq q(STREAM(stream), workspace, workspace_bytes);
     sparse_gcn_bwd_seq(q, ax, indptr, indices, indptr_t, indices_t, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n,
                        Fin, Fout, flags, weighted ? values : nullptr,
-                       weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr);
+                       weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr, want_dv ? x : nullptr, ldx,
+                       want_dv ? dvalues : nullptr);
     return q.err;
 }
 int dp_sparse_gcn_layer_fwd(const float* x, int ldx, const int* indptr, const int* indices, const float* W,
@@ -1356,6 +1371,15 @@ int dp_sparse_gcn_layer_bwd_w(const float* ax, const int* indptr, const int* ind
     return sparse_gcn_bwd_entry("dp_sparse_gcn_layer_bwd_w", ax, indptr, indices, values, indptr_t, indices_t, values_t,
                                 true, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n, Fin, Fout, flags, workspace,
                                 workspace_bytes, stream);
+}
+int dp_sparse_gcn_layer_bwd_dv(const float* ax, const int* indptr, const int* indices, const float* values,
+                               const int* indptr_t, const int* indices_t, const float* values_t, const float* W,
+                               const float* y, int ldy, const float* invnorm, const float* dy, int lddy, float* dx,
+                               int lddx, float* dW, float* db, const float* x, int ldx, float* dvalues, int n, int Fin,
+                               int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    return sparse_gcn_bwd_entry("dp_sparse_gcn_layer_bwd_dv", ax, indptr, indices, values, indptr_t, indices_t, values_t,
+                                true, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n, Fin, Fout, flags, workspace,
+                                workspace_bytes, stream, true, x, ldx, dvalues);
 }
 
 // ------------------------------------------------------------------ model level

@@ -150,9 +150,43 @@ def _call(lib, name, *args):
     _lib.check(getattr(lib, name)(*args), name)
 
 
+def _grad_values(graph):
+    """The container's `values` when a gradient is wanted for them (they require grad and grad mode is on), else None:
+    the one more tensor input of the Functions that read the adjacency.  With None the entries called are those of a
+    container whose values are data."""
+    v = getattr(graph, "values", None)
+    return v if v is not None and v.requires_grad and torch.is_grad_enabled() else None
+
+
+def _link_dvalues(lib, s, g, objective, dloss):
+    """dloss * dL/dvalues of a link term (objective 0: cross entropy, 1: Frobenius) of s [n, k] on container `g`, in the
+    order of `g.values` — dp_csr_link_dvalues: one launch for a graph or a batch (the block-diagonal CSR, global
+    columns), 1 / sum_b n_b^2 from the host."""
+    n, k = s.shape
+    dv = torch.empty_like(g.values)
+    sizes = g.node_off_host.astype("int64")
+    inv_norm = 1.0 / float(((sizes[1:] - sizes[:-1]) ** 2).sum())
+    _call(lib, "dp_csr_link_dvalues", s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(), g.values.data_ptr(),
+          dv.data_ptr(), n, k, objective, inv_norm, dloss.data_ptr(), _lib.current_stream())
+    return dv
+
+
+def _pool_dvalues(lib, s, g, dap):
+    """dvalues of A' = S^T A S for the gradient dap [B, k, k] ([k, k] for one graph): dp_csr_pool_dvalues."""
+    n, k = s.shape
+    dv = torch.empty_like(g.values)
+    batch = hasattr(g, "indices_local")
+    wsb = lib.dp_csr_pool_dvalues_workspace_bytes(n, k)
+    ws = _workspace(wsb, s)
+    _call(lib, "dp_csr_pool_dvalues", s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(), dap.data_ptr(),
+          g.node_off_host.ctypes.data if batch else None, g.num_graphs, dv.data_ptr(), n, k, ws.data_ptr(), wsb,
+          _lib.current_stream())
+    return dv
+
+
 class _CsrGraphConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, g, flags):
+    def forward(ctx, x, weight, bias, g, flags, vals=None):
         lib = _lib.load()
         _lib.require_gpu_tensor(x, "x")
         x = x.contiguous().float()
@@ -165,14 +199,14 @@ class _CsrGraphConvFn(torch.autograd.Function):
         sfx, a, _ = _csr_args(g)
         _call(lib, "dp_sparse_gcn_layer_fwd" + sfx, x.data_ptr(), fin, *a, w.data_ptr(), _lib.ptr(bias), y.data_ptr(),
               fout, ax.data_ptr(), invn.data_ptr(), n, fin, fout, flags, ws.data_ptr(), wsb, _lib.current_stream())
-        ctx.save_for_backward(ax, w, y, invn)
+        ctx.save_for_backward(ax, w, y, invn, *((x,) if vals is not None else ()))      # dvalues[e] = dax_i . x_j
         ctx.g, ctx.flags, ctx.ws, ctx.has_bias = g, flags, ws, bias is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = _lib.load()
-        ax, w, y, invn = ctx.saved_tensors
+        ax, w, y, invn = ctx.saved_tensors[:4]
         g = ctx.g
         n, fin = ax.shape
         fout = w.shape[1]
@@ -181,17 +215,25 @@ class _CsrGraphConvFn(torch.autograd.Function):
         dw = torch.empty_like(w)
         db = _f32(ax, fout) if ctx.has_bias else None
         sfx, a, at = _csr_args(g)
+        if ctx.needs_input_grad[5]:
+            x = ctx.saved_tensors[4]
+            dv = torch.empty_like(g.values)
+            _call(lib, "dp_sparse_gcn_layer_bwd_dv", ax.data_ptr(), *a, *at, w.data_ptr(), y.data_ptr(), fout,
+                  invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin, dw.data_ptr(), _lib.ptr(db), x.data_ptr(), fin,
+                  dv.data_ptr(), n, fin, fout, ctx.flags, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+            return dx, dw, db, None, None, dv
         _call(lib, "dp_sparse_gcn_layer_bwd" + sfx, ax.data_ptr(), *a, *at, w.data_ptr(), y.data_ptr(), fout,
               invn.data_ptr(), dy.data_ptr(), fout, _lib.ptr(dx), fin, dw.data_ptr(), _lib.ptr(db), n, fin, fout,
               ctx.flags, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None
 
 
 def csr_graph_conv(x, weight, bias, graph, flags):
     """`graph_conv` on node rows x [n, F] with the adjacency as CSR: `graph` (a CsrGraph, or a CsrBatch with its
     block-diagonal CSR and n = n_total) carries int32 indptr / indices of A and of A^T (the neighbour sum A x is the
-    gather of dp_csr_aggregate, the backward gathers over A^T) and, when it is `weighted`, their fp32 values."""
-    return _CsrGraphConvFn.apply(x, weight, bias, graph, flags)
+    gather of dp_csr_aggregate, the backward gathers over A^T) and, when it is `weighted`, their fp32 values.  Values that
+    require grad receive dvalues[e] = dax_i . x_j (dp_sparse_gcn_layer_bwd_dv); `values_t` stays data."""
+    return _CsrGraphConvFn.apply(x, weight, bias, graph, flags, _grad_values(graph))
 
 
 # ----------------------------------------------------------------------------- row ops on one graph (B = 1)
@@ -313,7 +355,7 @@ def assign_softmax(z, weight, bias):
 
 class _CsrPoolFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, s, z, g):
+    def forward(ctx, s, z, g, vals=None):
         lib = _lib.load()
         s, z = s.contiguous(), z.contiguous()
         n, k = s.shape
@@ -341,12 +383,12 @@ class _CsrPoolFn(torch.autograd.Function):
         sfx, a, at = _csr_args(g)
         _call(lib, "dp_csr_pool_bwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, *at, dxp.data_ptr(), dap.data_ptr(),
               ds.data_ptr(), k, dz.data_ptr(), d, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        return ds, dz, None
+        return ds, dz, None, _pool_dvalues(lib, s, g, dap) if ctx.needs_input_grad[3] else None
 
 
 def csr_pool(s, z, graph):
     """Level-0 pooling X' = S^T Z [k, d], A' = S^T A S [k, k] (encoders.py:1278-1279) with A as CSR: dp_csr_pool_*."""
-    return _CsrPoolFn.apply(s, z, graph)
+    return _CsrPoolFn.apply(s, z, graph, _grad_values(graph))
 
 
 class _DensePoolFn(torch.autograd.Function):
@@ -651,7 +693,7 @@ def segment_max_floor(z, floor, batch):
 
 class _CsrPoolBatchFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, s, z, batch):
+    def forward(ctx, s, z, batch, vals=None):
         lib = _lib.load()
         s, z = s.contiguous(), z.contiguous()
         n, k = s.shape
@@ -683,18 +725,18 @@ class _CsrPoolBatchFn(torch.autograd.Function):
         _call(lib, "dp_csr_pool_batch_bwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, *at, plan.bwd_tab.data_ptr(),
               plan.n_blocks, dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d, g.num_graphs, n, k, d,
               ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        return ds, dz, None
+        return ds, dz, None, _pool_dvalues(lib, s, g, dap) if ctx.needs_input_grad[3] else None
 
 
 def csr_pool_batch(s, z, batch):
     """`csr_pool` for every graph of a ragged batch: X' [B, k, d], A' [B, k, k] from s [n_total, k], z [n_total, d] —
     dp_csr_pool_batch_*, two launches per direction whatever B."""
-    return _CsrPoolBatchFn.apply(s, z, batch)
+    return _CsrPoolBatchFn.apply(s, z, batch, _grad_values(batch))
 
 
 class _CsrLinkLossBatchFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, s, g):
+    def forward(ctx, s, g, vals=None):
         lib = _lib.load()
         _lib.require_gpu_tensor(s, "s")
         s = s.contiguous().float()
@@ -722,13 +764,13 @@ class _CsrLinkLossBatchFn(torch.autograd.Function):
         _call(lib, "dp_csr_linkpred_batch_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, g.node_off_host.ctypes.data,
               g.num_graphs, dloss.data_ptr(), ds.data_ptr(), k, 0, k, ctx.ws.data_ptr(), ctx.ws.numel(),
               _lib.current_stream())
-        return ds, None
+        return ds, None, _link_dvalues(lib, s, g, 0, dloss) if ctx.needs_input_grad[2] else None
 
 
 def csr_link_loss_batch(s, batch):
     """The link-prediction loss of a ragged batch, sum_b sum_{i,j < n_b} l_ij / sum_b n_b^2 (encoders.py:1326-1331), of
     s [n_total, k]: dp_csr_linkpred_batch_* (per-graph launches of the single-graph kernels, one final launch)."""
-    return _CsrLinkLossBatchFn.apply(s, batch)
+    return _CsrLinkLossBatchFn.apply(s, batch, _grad_values(batch))
 
 
 # ----------------------------------------------------------------------------- Set2Set on ragged rows
@@ -820,7 +862,7 @@ def cross_entropy(logits, label):
 
 class _CsrLinkLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, s, g):
+    def forward(ctx, s, g, vals=None):
         lib = _lib.load()
         _lib.require_gpu_tensor(s, "s")
         s = s.contiguous().float()
@@ -846,7 +888,7 @@ class _CsrLinkLossFn(torch.autograd.Function):
         sfx, a, at = _csr_args(g)
         _call(lib, "dp_csr_linkpred_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, dloss.data_ptr(), ds.data_ptr(), k, 0, n,
               k, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        return ds, None
+        return ds, None, _link_dvalues(lib, s, g, 0, dloss) if ctx.needs_input_grad[2] else None
 
 
 def csr_link_loss(s, graph):
@@ -854,7 +896,7 @@ def csr_link_loss(s, graph):
     (0/1 adjacency, or the stored values of a weighted graph; each edge listed once): dp_csr_linkpred_loss_* — a tile
     walk over s for the n^2 term that does not depend on the adjacency plus a gather over the edges, O(n k) memory.
     Returns the device scalar."""
-    return _CsrLinkLossFn.apply(s, graph)
+    return _CsrLinkLossFn.apply(s, graph, _grad_values(graph))
 
 
 # ----------------------------------------------------------------------------- assignment entropy
@@ -913,7 +955,7 @@ class _FrobLinkFn(torch.autograd.Function):
     backward reads no adjacency."""
 
     @staticmethod
-    def forward(ctx, s, adj, num_nodes, kind):
+    def forward(ctx, s, adj, num_nodes, kind, vals=None):
         lib = _lib.load()
         _lib.require_gpu_tensor(s, "s")
         s = s.contiguous().float()
@@ -949,7 +991,8 @@ class _FrobLinkFn(torch.autograd.Function):
                       loss.data_ptr(), None, n, k, ws.data_ptr(), wsb, st)
             ctx.sym = int(at[0] is None)          # an undirected container: W = A S
         ctx.save_for_backward(s, w, g)
-        ctx.kind, ctx.num_nodes, ctx.adj, ctx.b = kind, num_nodes, adj if kind == "batch" else None, b
+        ctx.kind, ctx.num_nodes, ctx.b = kind, num_nodes, b
+        ctx.adj = adj if kind == "batch" or vals is not None else None
         return loss
 
     @staticmethod
@@ -972,7 +1015,7 @@ class _FrobLinkFn(torch.autograd.Function):
         else:
             _lib.check(lib.dp_csr_frob_link_bwd(*head, None, dloss.data_ptr(), ds.data_ptr(), k, 0, ctx.sym, s.shape[0], k,
                                                 st), "dp_csr_frob_link_bwd")
-        return ds, None, None, None
+        return ds, None, None, None, _link_dvalues(lib, s, ctx.adj, 1, dloss) if ctx.needs_input_grad[4] else None
 
 
 def frob_link_loss(s, adj, num_nodes=None):
@@ -1012,4 +1055,4 @@ def frob_link_loss(s, adj, num_nodes=None):
         raise TypeError(f"frob_link_loss: s [n, K] goes with a CsrGraph or a CsrBatch, got {type(adj).__name__}")
     if adj.n != s.shape[0]:
         raise ValueError(f"frob_link_loss: the {adj.ARG} has n = {adj.n} rows but s has {s.shape[0]}")
-    return _FrobLinkFn.apply(s, adj, None, "batch" if hasattr(adj, "indices_local") else "csr")
+    return _FrobLinkFn.apply(s, adj, None, "batch" if hasattr(adj, "indices_local") else "csr", _grad_values(adj))

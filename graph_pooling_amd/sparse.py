@@ -148,6 +148,40 @@ def _normalized_values(n, h, what):
     return new, ((valt * inv[h.indices_t]) * inv[rows(h.indptr_t)]).astype(np.float32)      # (r, c) of A^T is a_cr
 
 
+def _transpose_perm(g):
+    """For a container with a transposed CSR of its own: int64 [nnz] on the device with values_t = values[perm] — entry k
+    of the transposed CSR, (r, c) of A^T, is the stored entry (c, r) of A.  Computed on the host from the two CSRs (one
+    read-back); raises when they are not each other's transpose."""
+    h = _read_back(g)
+    n = h.indptr.size - 1
+    rows = lambda ip: np.repeat(np.arange(ip.size - 1, dtype=np.int64), np.diff(ip.astype(np.int64)))
+    key = rows(h.indptr) * n + h.indices.astype(np.int64)               # (i, j) of every stored entry of A
+    key_t = h.indices_t.astype(np.int64) * n + rows(h.indptr_t)         # ... and of every entry of A^T, as (c, r)
+    order = np.argsort(key, kind="stable")
+    pos = np.minimum(np.searchsorted(key[order], key_t), max(key.size - 1, 0))
+    if key.size != key_t.size or (key.size and (key[order][pos] != key_t).any()):
+        raise ValueError(f"{type(g).__name__}.with_values: indptr_t / indices_t are not the transpose of indptr / indices")
+    return torch.from_numpy(order[pos]).to(g.indices.device)
+
+
+def _with_values(g, values):
+    """`CsrGraph.with_values` / `CsrBatch.with_values`: a shallow copy of container `g` that shares every index array and
+    table and stores `values` (which may carry autograd history)."""
+    what = f"{type(g).__name__}.with_values: values"
+    nnz = g.nnz
+    if nnz == 0 and isinstance(values, torch.Tensor) and values.numel() == 0:      # an edgeless batch keeps its pad
+        _check_values(values, g.indices[:0], what)
+        values = torch.zeros(g.indices.numel(), device=g.indices.device, dtype=torch.float32)
+    else:
+        values = _check_values(values, g.indices[:nnz] if nnz else g.indices, what)
+    perm = None if g.indices_t is g.indices else g._t_perm          # cached on `g` BEFORE the copy: shared from then on
+    new = copy.copy(g)
+    new.weighted = True
+    new.values = values
+    new.values_t = values if perm is None else values.detach()[perm]      # data: it only feeds the dx / dS gathers
+    return new
+
+
 class CsrGraph:
     """CSR of one graph's adjacency on the device: int32 indptr [n + 1], indices [nnz] — row i lists the j with
     A[i, j] != 0 (0/1 adjacency, graph_sampler.py:26) — plus the CSR of A^T for the backward gather (the same arrays
@@ -190,6 +224,18 @@ class CsrGraph:
 
     def rows(self):
         return f"[n, F] with n = {self.n}"
+
+    nnz = cached_property(lambda self: int(self.indptr[-1]))          # stored entries (one read-back, then cached)
+    _t_perm = cached_property(_transpose_perm)
+
+    def with_values(self, values):
+        """A new container with the same index arrays (shared, not copied) and `values` — fp32 [nnz] on the indices'
+        device, in the order of `indices` — as its stored entries; a 0/1 container becomes weighted.  `values` may carry
+        autograd history: every op that reads the adjacency then returns its gradient (each stored entry an independent
+        variable, also (i, j) and (j, i) of an undirected container).  `values_t` stays data: `values` itself
+        for an undirected container, else `values[perm]` with the permutation between the two CSRs computed once on the
+        host and cached.  An edgeless batch keeps its one-element pad (pass an empty tensor)."""
+        return _with_values(self, values)
 
     def bn_relu(self, h, layer):
         """apply_bn after ReLU behind GraphConv `layer`: dp_bn_node_* with B = 1."""
@@ -379,6 +425,18 @@ class CsrBatch:
         if plan is None:
             plan = self._pool_plans[(k, d)] = _PoolPlan(self.node_off_host, k, d, self.device)
         return plan
+
+    nnz = cached_property(lambda self: int(self.indptr[-1]))          # stored entries (one read-back, then cached)
+    _t_perm = cached_property(_transpose_perm)
+
+    def with_values(self, values):
+        """A new container with the same index arrays (shared, not copied) and `values` — fp32 [nnz] on the indices'
+        device, in the order of `indices` — as its stored entries; a 0/1 container becomes weighted.  `values` may carry
+        autograd history: every op that reads the adjacency then returns its gradient (each stored entry an independent
+        variable, also (i, j) and (j, i) of an undirected container).  `values_t` stays data: `values` itself
+        for an undirected container, else `values[perm]` with the permutation between the two CSRs computed once on the
+        host and cached.  An edgeless batch keeps its one-element pad (pass an empty tensor)."""
+        return _with_values(self, values)
 
     # -- the four steps of the DiffPool model that differ from a single CsrGraph's
     def rows(self):
@@ -691,7 +749,9 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
     Both containers may carry one fp32 value per stored entry (`values`, and `values_t` for the CSR of A^T): the
     weighted adjacency of the dense path, e.g. the reference sampler's default D^-1/2 A D^-1/2 (graph_sampler.py:27-29),
     which `normalized()` builds.  Every op then takes its `_w` entry (`graph.weighted`), with the launches of the 0/1
-    call; the values are data, no gradient flows to them.
+    call.  Values that do not require grad are data; `graph.with_values(v)` with `v.requires_grad` makes every stored
+    entry a variable: GraphConv, the level-0 pooling and both link objectives then return `v.grad` (one SDDMM launch
+    each, dp_csr_sddmm's kernel).  `normalized()` is host float64 and not differentiated.
 
     A linkpred=True model (the constructor default, train.py --linkpred) trains here too: `loss(pred, label, graph)`
     adds the link-prediction term on dp_csr_linkpred_loss_* (per graph of a batch: dp_csr_linkpred_batch_*) — the n^2

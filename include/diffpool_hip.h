@@ -1050,6 +1050,54 @@ int dp_clip_adam_step_counted(float* params, float* grads, float* exp_avg, float
                               float lr, float beta1, float beta2, float eps, float max_norm, float* total_norm_out,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ N4  gradients to the stored values of a CSR
+ * Every stored entry e = (i, j), j = indices[e], of a CsrGraph / CsrBatch is an independent variable a_e (the gradient
+ * torch gives for a dense A built with index_put from `values`); its gradient is delivered in the order of `values`.
+ * All four come from ONE kernel family, a sampled dense-dense product over the stored entries,
+ *     out[e] = beta * out[e] + alpha * d * epi( sum_f P[i,f] Q[indices[e],f], a_e ),
+ * P [n_rows,F] (ldp), Q [.,F] (ldq) row-major fp32, d = dscale[0] (device scalar; NULL: 1), epi the identity
+ * (dp_csr_sddmm), the cross-entropy link derivative log(1 - p + 1e-7) - log(p + 1e-7) with p = min(t, 1), or the
+ * Frobenius derivative 2 (a_e - t).  A group of 4 / 16 / 64 lanes serves one entry, P_i stays in registers over the
+ * row's entries, a row is cut into chunks of 512 entries taken by separate waves, and every out[e] is one dot product
+ * summed in a fixed order: no atomics, no temporary, bit-reproducible.  beta == 0: out is not read.  Any F >= 1;
+ * F == 0 or n_rows == 0 writes nothing and returns DP_OK.  No gradient flows to P or Q through these entries.
+ *
+ * dp_csr_sddmm_plan (host only): plan_out[DP_CSR_SDDMM_PLAN_INTS] = { lanes per entry (4 / 16 / 64: the smallest group
+ * that covers F in one visit, 64 above), floats per lane load (4 when F % 4 == 0, ldp % 4 == 0, ldq % 4 == 0 and
+ * neither base is misaligned to 16 bytes; else 1), visits of lanes * floats columns whose P_i is held in registers
+ * (1 .. 4), 1 when columns beyond those are walked with P_i re-read from the cache, entries per row chunk (512), rows per
+ * workgroup (4) }, answered by the function the launcher acts on.  F < 1, ldp < F, ldq < F, NULL plan_out:
+ * DP_ERR_INVALID_ARG. */
+#define DP_CSR_SDDMM_PLAN_INTS 6
+int dp_csr_sddmm_plan(int F, int ldp, int ldq, int p_misaligned, int q_misaligned, int* plan_out);
+int dp_csr_sddmm(const float* P, int ldp, const float* Q, int ldq, const int* indptr, const int* indices, float* out,
+                 int n_rows, int F, float alpha, const float* dscale, float beta, void* stream);
+/* dvalues[e] OVERWRITTEN = dloss * dL/da_e of the link loss of dp_csr_linkpred_* (objective 0) or dp_csr_frob_link_*
+ * (objective 1): inv_norm * (log(1 - p + 1e-7) - log(p + 1e-7)), or inv_norm * 2 (a_e - s_i . s_j) with a_e = values[e]
+ * (NULL values: a 0/1 container, a_e = 1).  inv_norm = 1 / sum_b n_b^2 comes from the host; dloss: device scalar or
+ * NULL = 1.  One launch serves one graph or a whole batch: indices are rows of S (the block-diagonal CSR with GLOBAL
+ * columns and the concatenated S).  K >= 1 (no limit above), lds >= K. */
+int dp_csr_link_dvalues(const float* S, int lds, const int* indptr, const int* indices, const float* values,
+                        float* dvalues, int n_rows, int K, int objective, float inv_norm, const float* dloss,
+                        void* stream);
+/* dvalues[e] OVERWRITTEN = (S dAp_b)_i . s_j of the pooling Ap_b = S_b^T A_b S_b (dp_csr_pool_* / dp_csr_pool_batch_*),
+ * b the graph that owns row i.  dAp [B,K,K]; node_off_host: host int32 [B+1], or NULL for one graph (B must be 1).  The
+ * workspace receives P = S dAp_b [n_total,K] (one GEMM for one graph, grouped GEMMs of up to 4 graphs for a batch), then
+ * one SDDMM launch with Q = S runs over the block-diagonal CSR (GLOBAL columns).  K >= 1, lds >= K. */
+size_t dp_csr_pool_dvalues_workspace_bytes(int n_total, int K);
+int dp_csr_pool_dvalues(const float* S, int lds, const int* indptr, const int* indices, const float* dAp,
+                        const int* node_off_host, int B, float* dvalues, int n_total, int K, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* dp_sparse_gcn_layer_bwd_w that also returns dvalues[e] OVERWRITTEN = dax_i . x_j, dax = dU W^T as the backward forms
+ * it (add_self changes nothing here): the same launches in the same order, then one SDDMM with P = dax, Q = x (ldx).
+ * dax is formed whenever dvalues is wanted, also with dx == NULL; dp_sparse_gcn_layer_workspace_bytes covers it.  dx,
+ * dW, db are the bits of dp_sparse_gcn_layer_bwd_w.  A 0/1 container has no values: only the weighted form exists. */
+int dp_sparse_gcn_layer_bwd_dv(const float* ax, const int* indptr, const int* indices, const float* values,
+                               const int* indptr_t, const int* indices_t, const float* values_t, const float* W,
+                               const float* y, int ldy, const float* invnorm, const float* dy, int lddy, float* dx,
+                               int lddx, float* dW, float* db, const float* x, int ldx, float* dvalues, int n, int Fin,
+                               int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
