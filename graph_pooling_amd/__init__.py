@@ -3,13 +3,14 @@
     from graph_pooling_amd.encoders import SoftPoolingGcnEncoder, GcnEncoderGraph, GcnSet2SetEncoder
     from graph_pooling_amd.set2set import Set2Set
     from graph_pooling_amd import SparseGcnSet2SetEncoder      # GCN + Set2Set on CSR graphs and ragged batches (sparse.py)
+    from graph_pooling_amd import EdgeAttention                # learned edge weights in front of the CSR encoders
 
 The arithmetic lives in libdiffpool_hip.so (graph_pooling_amd/csrc, C ABI in include/diffpool_hip.h).
 Importing this package does not load the library; the first forward does, and raises if it is missing.
 """
 __version__ = "0.1.0"
 
-__all__ = ["SparseGcnSet2SetEncoder"]
+__all__ = ["SparseGcnSet2SetEncoder", "EdgeAttention"]
 
 
 def __getattr__(name):
@@ -17,4 +18,7 @@ def __getattr__(name):
     if name == "SparseGcnSet2SetEncoder":
         from .sparse import SparseGcnSet2SetEncoder
         return SparseGcnSet2SetEncoder
+    if name == "EdgeAttention":
+        from .sparse import EdgeAttention
+        return EdgeAttention
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -99,6 +99,8 @@ LINKPRED_PLAN_INTS = 8
 CSR_LINKPRED_PLAN_INTS = 16
 # dp_csr_sddmm_plan: (lanes per entry, floats per lane load, register-held visits, column tail, row chunk, rows per workgroup)
 CSR_SDDMM_PLAN_INTS = 6
+# dp_csr_edge_plan: (lanes per row, entries a lane keeps in registers, rows per workgroup, longest row read once)
+CSR_EDGE_PLAN_INTS = 4
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -269,6 +271,12 @@ _PROTOS = {
     "dp_csr_pool_dvalues": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _Z, _P]),
     "dp_sparse_gcn_layer_bwd_dv": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P,
                                         _I, _I, _I, _I, _P, _Z, _P]),
+    # learned edge weights: softmax over each CSR row, D^-1/2 A D^-1/2 on the device, both with their backward
+    "dp_csr_edge_plan": (_I, [_I, _I, C.POINTER(_I)]),
+    "dp_csr_edge_softmax_fwd": (_I, [_P, _P, _P, _I, _I, _P]),
+    "dp_csr_edge_softmax_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "dp_csr_sym_norm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "dp_csr_sym_norm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

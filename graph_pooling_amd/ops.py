@@ -1056,3 +1056,148 @@ def frob_link_loss(s, adj, num_nodes=None):
     if adj.n != s.shape[0]:
         raise ValueError(f"frob_link_loss: the {adj.ARG} has n = {adj.n} rows but s has {s.shape[0]}")
     return _FrobLinkFn.apply(s, adj, None, "batch" if hasattr(adj, "indices_local") else "csr", _grad_values(adj))
+
+
+# ----------------------------------------------------------------------------- learned edge weights on a CSR
+def _edge_vec(t, g, what):
+    """An fp32 [nnz] tensor of container `g` (one number per stored entry, in the order of `indices`), contiguous."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() != g.nnz:
+        got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what} must hold one number per stored entry [{g.nnz}], got {got}")
+    if g.nnz:
+        _lib.require_gpu_tensor(t, what)
+    return t.contiguous().float()
+
+
+class _CsrSddmmFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, q, g, alpha):
+        lib = _lib.load()
+        p, q = p.contiguous().float(), q.contiguous().float()
+        f = p.shape[1]
+        out = _f32(p, g.nnz)
+        _call(lib, "dp_csr_sddmm", p.data_ptr(), f, q.data_ptr(), f, g.indptr.data_ptr(), g.indices.data_ptr(),
+              out.data_ptr(), g.n, f, alpha, None, 0.0, _lib.current_stream())
+        ctx.save_for_backward(p, q)
+        ctx.g, ctx.alpha = g, alpha
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        p, q = ctx.saved_tensors
+        g, f = ctx.g, p.shape[1]
+        dv = dout.contiguous() if ctx.alpha == 1.0 else dout * ctx.alpha      # A(alpha dout): one [nnz] scaling
+        dp = dq = None
+        if ctx.needs_input_grad[0]:          # dP = A(dout) Q: the weighted gather with the gradient as the values
+            dp = torch.empty_like(p)
+            _call(lib, "dp_csr_aggregate_w", q.data_ptr(), f, g.indptr.data_ptr(), g.indices.data_ptr(), dv.data_ptr(),
+                  dp.data_ptr(), f, g.n, f, 0.0, _lib.current_stream())
+        if ctx.needs_input_grad[1]:          # dQ = A(dout)^T P: the same entry on the transposed CSR, dout[mirror]
+            dq = torch.empty_like(q)
+            dvt = dv[g.mirror_perm.long()]
+            _call(lib, "dp_csr_aggregate_w", p.data_ptr(), f, g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
+                  dvt.data_ptr(), dq.data_ptr(), f, g.n, f, 0.0, _lib.current_stream())
+        return dp, dq, None, None
+
+
+def csr_sddmm(p, q, graph, alpha=1.0):
+    """alpha * p_i . q_j on every stored entry (i, j) of a CsrGraph / CsrBatch -> [graph.nnz] in the order of `indices`
+    (dp_csr_sddmm; p, q [n, F], for a batch the concatenated rows).  Differentiable in p and q without a new kernel and
+    without an atomic scatter: dP = A(dout) Q is dp_csr_aggregate_w with the gradient as the values, dQ = A(dout)^T P the
+    same entry on the transposed CSR with dout[mirror_perm]."""
+    for name, t in (("p", p), ("q", q)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"csr_sddmm: expected {name} {graph.rows()}, got {got}")
+    if p.shape[1] != q.shape[1] or p.shape[1] < 1:
+        raise ValueError(f"csr_sddmm: p and q must share a width F >= 1, got {p.shape[1]} and {q.shape[1]}")
+    if graph.nnz == 0:                       # an edgeless batch: nothing stored, nothing launched
+        return _f32(p, 0)
+    _lib.require_gpu_tensor(p, "p")
+    _lib.require_gpu_tensor(q, "q")
+    return _CsrSddmmFn.apply(p, q, graph, float(alpha))
+
+
+class _CsrEdgeSoftmaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, g):
+        lib = _lib.load()
+        out = torch.empty_like(scores)
+        _call(lib, "dp_csr_edge_softmax_fwd", scores.data_ptr(), g.indptr.data_ptr(), out.data_ptr(), g.n, g.nnz,
+              _lib.current_stream())
+        ctx.save_for_backward(out)
+        ctx.g = g
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        (out,) = ctx.saved_tensors
+        g = ctx.g
+        dout = dout.contiguous()
+        ds = torch.empty_like(out)
+        _call(lib, "dp_csr_edge_softmax_bwd", out.data_ptr(), dout.data_ptr(), g.indptr.data_ptr(), ds.data_ptr(), g.n,
+              g.nnz, _lib.current_stream())
+        return ds, None
+
+
+def csr_edge_softmax(scores, graph):
+    """Softmax of scores [nnz] over each node's neighbour list (each row of the CSR; for a batch its block-diagonal
+    CSR) -> [nnz]: dp_csr_edge_softmax_*.  A row with one entry gives exactly 1."""
+    scores = _edge_vec(scores, graph, "csr_edge_softmax: scores")
+    return scores if graph.nnz == 0 else _CsrEdgeSoftmaxFn.apply(scores, graph)
+
+
+class _CsrSymNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, g):
+        lib = _lib.load()
+        dev = g.indptr.device
+        out = torch.empty(g.nnz, device=dev, dtype=torch.float32)
+        rdeg = torch.empty(g.n, device=dev, dtype=torch.float32)
+        undirected = g.indices_t is g.indices
+        # an undirected container stores a_ij = a_ji: its own order serves as the transposed one (no mirror read)
+        mirror = None if undirected else g.mirror_perm.data_ptr()
+        _call(lib, "dp_csr_sym_norm_fwd", g.indptr.data_ptr(), g.indices.data_ptr(), _lib.ptr(values),
+              g.indptr_t.data_ptr(), g.indices_t.data_ptr(), mirror, rdeg.data_ptr(), out.data_ptr(), g.n, g.nnz,
+              _lib.current_stream())
+        if values is not None:
+            ctx.save_for_backward(values, rdeg)
+        ctx.g = g
+        ctx.mark_non_differentiable(rdeg)
+        return out, rdeg
+
+    @staticmethod
+    def backward(ctx, dout, _drdeg):
+        lib = _lib.load()
+        values, rdeg = ctx.saved_tensors
+        g = ctx.g
+        dout = dout.contiguous()
+        dv, gdeg = torch.empty_like(values), torch.empty_like(rdeg)
+        _call(lib, "dp_csr_sym_norm_bwd", g.indptr.data_ptr(), g.indices.data_ptr(), values.data_ptr(),
+              g.indptr_t.data_ptr(), g.indices_t.data_ptr(), g.mirror_perm.data_ptr(), rdeg.data_ptr(), dout.data_ptr(),
+              gdeg.data_ptr(), dv.data_ptr(), g.n, g.nnz, _lib.current_stream())
+        return dv, None
+
+
+def csr_sym_normalize_rdeg(values, graph):
+    """(D^-1/2 A D^-1/2 as [nnz] values, r = d^-1/2 [n]) of container `graph` with the stored `values` ([nnz], or None for
+    a 0/1 container: ones) — dp_csr_sym_norm_*: d is the column sum of the values as the reference takes it
+    (graph_sampler.py:27-29), on the device, differentiable in `values` (every stored entry its own variable)."""
+    if values is not None:
+        values = _edge_vec(values, graph, "csr_sym_normalize: values")
+    dev = graph.indptr.device
+    if graph.nnz == 0:
+        out = torch.empty(0, device=dev, dtype=torch.float32) if values is None else values
+        return out, torch.full((graph.n,), float("inf"), device=dev, dtype=torch.float32)
+    _lib.require_gpu_tensor(graph.indptr, "the container's index arrays")
+    if values is None:
+        with torch.no_grad():
+            return _CsrSymNormFn.apply(None, graph)
+    return _CsrSymNormFn.apply(values, graph)
+
+
+def csr_sym_normalize(values, graph):
+    """`csr_sym_normalize_rdeg` without the degrees: the [nnz] values of D^-1/2 A D^-1/2."""
+    return csr_sym_normalize_rdeg(values, graph)[0]

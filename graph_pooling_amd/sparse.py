@@ -32,6 +32,10 @@ encoders.py:1278-1279 — (dp_csr_pool_* / dp_csr_pool_batch_*) and `link_loss` 
 an n x n adjacency — (dp_csr_linkpred_loss_* / dp_csr_linkpred_batch_*).  A single graph is NOT a batch of one: it
 keeps its own kernels.  The small pooled levels run on the dense per-op entries as a dense batch [B, K, .], B = 1
 behind a CsrGraph.
+
+`EdgeAttention` computes the stored values of either container from the node features — scores on the stored entries
+(dp_csr_sddmm), a softmax over each neighbour list (dp_csr_edge_softmax_*) or a symmetric gate under D^-1/2 A D^-1/2
+(dp_csr_sym_norm_*) — and hands the three encoders a weighted container through which its projections train.
 """
 from __future__ import annotations
 
@@ -164,6 +168,50 @@ def _transpose_perm(g):
     return torch.from_numpy(order[pos]).to(g.indices.device)
 
 
+def _mirror_perm(g):
+    """int32 [nnz] on the device: entry k of the transposed CSR is the stored entry mirror_perm[k].  A container with a
+    transposed CSR of its own has it as `_t_perm`; an undirected one's transposed CSR is its own arrays, so entry k =
+    (r, c) maps to the stored (c, r) (one read-back; raises when the stored pattern is not symmetric)."""
+    if g.indices_t is not g.indices:
+        return g._t_perm.to(torch.int32)
+    h = _read_back(g)
+    n = h.indptr.size - 1
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(h.indptr.astype(np.int64)))
+    key = rows * n + h.indices.astype(np.int64)               # sorted: rows ascending, columns ascending within a row
+    key_t = h.indices.astype(np.int64) * n + rows
+    pos = np.minimum(np.searchsorted(key, key_t), max(key.size - 1, 0))
+    if key.size and (key[pos] != key_t).any():
+        raise ValueError(f"{type(g).__name__}.mirror_perm: an undirected container (no transposed CSR of its own) must "
+                         "store (j, i) beside every (i, j)")
+    return torch.from_numpy(pos.astype(np.int32)).to(g.indices.device)
+
+
+def _directed(g):
+    """`CsrGraph.directed` / `CsrBatch.directed`."""
+    if g.indices_t is not g.indices:
+        return g
+    perm = g.mirror_perm.long()
+    new = copy.copy(g)
+    new.indptr_t, new.indices_t = g.indptr.clone(), g.indices.clone()
+    if hasattr(g, "indices_local"):
+        new.indices_t_local = g.indices_local.clone()
+    if g.weighted:
+        new.values_t = g.values.detach()[perm] if g.nnz else g.values.detach().clone()
+    new.__dict__["_t_perm"], new.__dict__["mirror_perm"] = perm, g.mirror_perm      # the same pattern: nothing to redo
+    return new
+
+
+def _sym_normalized(g, check):
+    """`CsrGraph.sym_normalized` / `CsrBatch.sym_normalized`."""
+    stored = None if not g.weighted else (g.values if g.values.numel() == g.nnz else g.values[:g.nnz])
+    values, rdeg = ops.csr_sym_normalize_rdeg(stored, g)
+    if check and not bool(torch.isfinite(rdeg).all()):                              # the one flag read back
+        bad = torch.nonzero(~torch.isfinite(rdeg)).reshape(-1)
+        raise ValueError(f"{type(g).__name__}.sym_normalized(): node {int(bad[0])} has degree <= 0 (column sum of the "
+                         f"stored values; {bad.numel()} such node(s)): D^-1/2 A D^-1/2 is not defined there")
+    return g.with_values(values)
+
+
 def _with_values(g, values):
     """`CsrGraph.with_values` / `CsrBatch.with_values`: a shallow copy of container `g` that shares every index array and
     table and stores `values` (which may carry autograd history)."""
@@ -227,6 +275,21 @@ class CsrGraph:
 
     nnz = cached_property(lambda self: int(self.indptr[-1]))          # stored entries (one read-back, then cached)
     _t_perm = cached_property(_transpose_perm)
+    mirror_perm = cached_property(_mirror_perm)
+
+    def directed(self):
+        """A container of the same class with a transposed CSR of its OWN: cloned index arrays and `values_t =
+        values[mirror_perm]` (data).  Values that are not symmetric — a softmax over each row — must not ride an
+        undirected container, whose dx gathers and factor-2 link form assume a_ij = a_ji.  A container that already has
+        a transposed CSR returns itself."""
+        return _directed(self)
+
+    def sym_normalized(self, check=False):
+        """`self.with_values(ops.csr_sym_normalize(self.values, self))`: D^-1/2 A D^-1/2 of the stored values (ones for a
+        0/1 container) on the device (dp_csr_sym_norm_*), the degree the column sum as in `normalized()`; no read-back,
+        and differentiable when `values` require grad.  check=True reads one flag back and raises ValueError as
+        `normalized()` does for a node of degree <= 0; without it such a node gives inf / NaN as the reference does."""
+        return _sym_normalized(self, check)
 
     def with_values(self, values):
         """A new container with the same index arrays (shared, not copied) and `values` — fp32 [nnz] on the indices'
@@ -428,6 +491,21 @@ class CsrBatch:
 
     nnz = cached_property(lambda self: int(self.indptr[-1]))          # stored entries (one read-back, then cached)
     _t_perm = cached_property(_transpose_perm)
+    mirror_perm = cached_property(_mirror_perm)
+
+    def directed(self):
+        """A container of the same class with a transposed CSR of its OWN: cloned index arrays and `values_t =
+        values[mirror_perm]` (data).  Values that are not symmetric — a softmax over each row — must not ride an
+        undirected container, whose dx gathers and factor-2 link form assume a_ij = a_ji.  A container that already has
+        a transposed CSR returns itself."""
+        return _directed(self)
+
+    def sym_normalized(self, check=False):
+        """`self.with_values(ops.csr_sym_normalize(self.values, self))`: D^-1/2 A D^-1/2 of the stored values (ones for a
+        0/1 container) on the device (dp_csr_sym_norm_*), the degree the column sum as in `normalized()`; no read-back,
+        and differentiable when `values` require grad.  check=True reads one flag back and raises ValueError as
+        `normalized()` does for a node of degree <= 0; without it such a node gives inf / NaN as the reference does."""
+        return _sym_normalized(self, check)
 
     def with_values(self, values):
         """A new container with the same index arrays (shared, not copied) and `values` — fp32 [nnz] on the indices'
@@ -907,3 +985,41 @@ class SparseSoftPoolingGcnEncoder(SoftPoolingGcnEncoder):
         if not isinstance(self._saved.get("graph"), CsrBatch) and what != "readout_argmax" and t.dim() == 2:
             return t.unsqueeze(0)                    # a single graph's level-0 'assign' / 'embedding' [n, .]
         return t
+
+
+# ----------------------------------------------------------------------------- learned edge weights
+class EdgeAttention(torch.nn.Module):
+    """Edge weights computed from the node features, on the stored entries of a CsrGraph / CsrBatch: forward(x, graph)
+    returns a weighted container that the three sparse encoders take unchanged — `ypred = model(x, att(x, g))` — and
+    through which the projections train (`ops.csr_sddmm`, `ops.csr_edge_softmax`, `ops.csr_sym_normalize`).
+
+    norm="softmax": two bias-free Linear layers q, k [att_dim, input_dim] on `hip_linear`; the scores
+    q(x)_i . k(x)_j / sqrt(att_dim) of every stored (i, j) go through a softmax over each node's neighbour list.  The
+    rows then sum to 1 and a_ij != a_ji, so the result rides `graph.directed()`.
+    norm="sym": one projection q; the gate sigmoid(q(x)_i . q(x)_j / sqrt(att_dim)) is symmetric bit for bit (the
+    products commute and the summation order is fixed), is multiplied by the stored values of a weighted container, and
+    is normalised as D^-1/2 A D^-1/2 with the gated degrees; the result keeps the container's form."""
+
+    def __init__(self, input_dim, att_dim, norm="softmax"):
+        super().__init__()
+        if norm not in ("softmax", "sym"):
+            raise ValueError(f"EdgeAttention: norm must be 'softmax' or 'sym', got {norm!r}")
+        self.input_dim, self.att_dim, self.norm = input_dim, att_dim, norm
+        self.q = torch.nn.Linear(input_dim, att_dim, bias=False)
+        if norm == "softmax":
+            self.k = torch.nn.Linear(input_dim, att_dim, bias=False)
+
+    def forward(self, x, graph):
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError(f"EdgeAttention.forward(x, graph: CsrGraph or CsrBatch), got {type(graph).__name__}")
+        _check_node_rows(graph, x, self.input_dim)
+        x = x.contiguous().float()
+        scale = float(self.att_dim) ** -0.5
+        qx = hip_linear(x, self.q.weight)
+        if self.norm == "softmax":
+            a = ops.csr_edge_softmax(ops.csr_sddmm(qx, hip_linear(x, self.k.weight), graph, scale), graph)
+            return graph.directed().with_values(a)
+        gate = torch.sigmoid(ops.csr_sddmm(qx, qx, graph, scale))
+        if graph.weighted:
+            gate = gate * (graph.values if graph.values.numel() == graph.nnz else graph.values[:graph.nnz])
+        return graph.with_values(ops.csr_sym_normalize(gate, graph))

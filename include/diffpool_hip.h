@@ -1098,6 +1098,46 @@ int dp_sparse_gcn_layer_bwd_dv(const float* ax, const int* indptr, const int* in
                                int lddx, float* dW, float* db, const float* x, int ldx, float* dvalues, int n, int Fin,
                                int Fout, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ N5  learned edge weights on a CSR: edge softmax
+ * and D^-1/2 A D^-1/2 on the device, both with their backward.  Segmented passes over the stored entries
+ * of each row of a CsrGraph / CsrBatch (a batch is its block-diagonal CSR with GLOBAL columns: one launch sequence
+ * serves both).  A group of 4 / 16 / 64 lanes serves one row, chosen from the mean row length nnz / n_rows; the lanes of
+ * a group take consecutive entries (coalesced index and value loads) and a row longer than the group loops.  Every sum
+ * has one order — the lane's entries ascending, then a DPP tree over the group — so a second run gives the same bits.
+ * No atomics, no workspace.  n_rows == 0 or nnz == 0 writes nothing and returns DP_OK; every refusal
+ * (DP_ERR_INVALID_ARG: a NULL or misaligned pointer, a negative count) comes before any launch.
+ *
+ * dp_csr_edge_plan (host only): plan_out[DP_CSR_EDGE_PLAN_INTS] = { lanes per row (4 while nnz <= 8 n_rows, 16 while
+ * nnz <= 32 n_rows, 64 above), entries a lane of the softmax kernels keeps in registers (8 / 4 / 4), rows per workgroup
+ * (256 / lanes), the longest row that is read once (lanes * entries per lane) }, answered by the function the launchers
+ * act on.  n_rows < 0, nnz < 0, NULL plan_out: DP_ERR_INVALID_ARG. */
+#define DP_CSR_EDGE_PLAN_INTS 4
+int dp_csr_edge_plan(int n_rows, int nnz, int* plan_out);
+/* Softmax over each row's stored entries: out[e] = exp(s_e - m_i) / sum_{e' in row i} exp(s_e' - m_i), m_i the row
+ * maximum; scores, out fp32 [nnz] in the order of indices (which the entry does not need).  A row with one entry gives
+ * exactly 1.0, a row with none is not touched.  A row that fits the registers is read once; a longer one runs a
+ * per-lane running maximum and sum and is read a second time.  One launch. */
+int dp_csr_edge_softmax_fwd(const float* scores, const int* indptr, float* out, int n_rows, int nnz, void* stream);
+/* dscores[e] OVERWRITTEN = out_e (dout_e - sum_{row} out dout); a one-entry row gives exactly 0.  One launch. */
+int dp_csr_edge_softmax_bwd(const float* out, const float* dout, const int* indptr, float* dscores, int n_rows, int nnz,
+                            void* stream);
+/* out[e] = values[e] * (r_i * r_j), j = indices[e], r = d^-1/2 (1 / sqrt, plain IEEE) written to rdeg [n] and kept for
+ * the backward; d_c is the COLUMN sum of the stored values (graph_sampler.py:27-29: np.sum(adj, axis=0)), taken as the
+ * sum of row c of the transposed CSR, whose entry k is the stored entry mirror[k] (int32 [nnz]).  The product order
+ * makes symmetric values give out_ij == out_ji bit for bit.  values NULL: all ones (a 0/1 container).  mirror may be
+ * NULL only when indices_t == indices: an undirected container, whose contract is a_ij = a_ji.  d_c <= 0 with entries
+ * present gives inf or NaN as the reference does; a node with no entry in its row and none in its column has
+ * rdeg = inf and touches no out[e].  Two launches. */
+int dp_csr_sym_norm_fwd(const int* indptr, const int* indices, const float* values, const int* indptr_t,
+                        const int* indices_t, const int* mirror, float* rdeg, float* out, int n, int nnz, void* stream);
+/* dvalues[e] OVERWRITTEN = dout_e r_i r_j + G_j, G_c = -1/2 r_c^3 t_c (0 for a node with no entries), t_c =
+ * sum_{e in row c} dout_e v_e r_col(e) + sum_{e in column c} dout_e v_e r_row(e) (a self loop counts in both sums): the
+ * gradient torch gives for a dense A built with index_put and normalised with A.sum(0).  mirror is always required;
+ * gdeg [n] is the workspace that receives G.  Two launches. */
+int dp_csr_sym_norm_bwd(const int* indptr, const int* indices, const float* values, const int* indptr_t,
+                        const int* indices_t, const int* mirror, const float* rdeg, const float* dout, float* gdeg,
+                        float* dvalues, int n, int nnz, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
