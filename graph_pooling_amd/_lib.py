@@ -101,6 +101,10 @@ CSR_LINKPRED_PLAN_INTS = 16
 CSR_SDDMM_PLAN_INTS = 6
 # dp_csr_edge_plan: (lanes per row, entries a lane keeps in registers, rows per workgroup, longest row read once)
 CSR_EDGE_PLAN_INTS = 4
+# dp_csr_gat_plan: (lanes per row, floats per v load, entries a lane keeps in registers, rows per workgroup, longest row
+# read once)
+CSR_GAT_PLAN_INTS = 5
+CSR_GAT_MAX_HEADS = 8
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -277,6 +281,10 @@ _PROTOS = {
     "dp_csr_edge_softmax_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dp_csr_sym_norm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dp_csr_sym_norm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    # multi-head additive (GAT) edge attention, fused: scores, softmax over each CSR row and the mean over the heads
+    "dp_csr_gat_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "dp_csr_gat_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "dp_csr_gat_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

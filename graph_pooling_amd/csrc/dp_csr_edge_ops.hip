@@ -16,63 +16,26 @@
 // of the normalisation; a second run gives the same bits.
 #include <math.h>
 
+#include "dp_csr_edge_seg.h"
 #include "dp_entry.h"
 
 namespace dp {
 namespace {
 
-constexpr int EO_THREADS = 256;
-
 struct EdgePick {
     int lanes, regs, rows_per_wg;
 };
 
-// The one place that decides the launch form.  The group is the smallest of 4 / 16 / 64 lanes that covers the MEAN row
-// in two visits (mean <= 8: 4 lanes, <= 32: 16 lanes, 64 above); a narrow group holds more entries per lane, so that a
-// row several times the mean still fits the registers: 4 x 8, 16 x 4, 64 x 4 entries.
+// The one place that decides the launch form.  The group is eo_lanes' (dp_csr_edge_seg.h: the smallest of 4 / 16 / 64
+// lanes that covers the MEAN row in two visits); a narrow group holds more entries per lane, so that a row several times
+// the mean still fits the registers: 4 x 8, 16 x 4, 64 x 4 entries.
 constexpr int eo_regs(int lanes) { return lanes == 4 ? 8 : 4; }
 EdgePick edge_pick(long n_rows, long nnz) {
     EdgePick k;
-    k.lanes = nnz <= 8 * n_rows ? 4 : (nnz <= 32 * n_rows ? 16 : 64);
+    k.lanes = eo_lanes(n_rows, nnz);
     k.regs = eo_regs(k.lanes);
     k.rows_per_wg = EO_THREADS / k.lanes;
     return k;
-}
-
-template <int L>
-__device__ __forceinline__ float eo_sum(float v) {
-    if constexpr (L == 4) return quad4_sum(v);
-    else if constexpr (L == 16) return row16_sum(v);
-    else return wave64_sum(v);
-}
-template <int L>
-__device__ __forceinline__ float eo_max(float v) {
-    if constexpr (L == 4) {
-        v = fmaxf(v, dpp_src<0xB1, 0xF, true>(v, v));      // quad_perm [1,0,3,2]
-        v = fmaxf(v, dpp_src<0x4E, 0xF, true>(v, v));      // quad_perm [2,3,0,1]
-        return v;
-    } else if constexpr (L == 16) {
-        return row16_max(v);
-    } else {
-        return wave64_max(v);
-    }
-}
-
-// the row of this lane's group: its stored entries [beg, end) (none for a row beyond n_rows) and the lane's place
-struct Seg {
-    int row, beg, end, sub;
-    bool live;
-};
-template <int L>
-__device__ __forceinline__ Seg eo_seg(const int* __restrict__ indptr, int n_rows) {
-    Seg g;
-    const long row = (long)blockIdx.x * (EO_THREADS / L) + threadIdx.x / L;
-    g.sub = threadIdx.x % L;
-    g.live = row < n_rows;
-    g.row = g.live ? (int)row : 0;
-    g.beg = g.live ? indptr[g.row] : 0;
-    g.end = g.live ? indptr[g.row + 1] : 0;
-    return g;
 }
 
 template <int L>

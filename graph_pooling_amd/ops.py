@@ -1201,3 +1201,53 @@ def csr_sym_normalize_rdeg(values, graph):
 def csr_sym_normalize(values, graph):
     """`csr_sym_normalize_rdeg` without the degrees: the [nnz] values of D^-1/2 A D^-1/2."""
     return csr_sym_normalize_rdeg(values, graph)[0]
+
+
+# ----------------------------------------------------------------------------- additive multi-head attention (DESIGN §4.8)
+class _CsrGatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, v, g, slope):
+        lib = _lib.load()
+        u, v = u.contiguous().float(), v.contiguous().float()
+        heads = u.shape[1]
+        out, rowstat = _f32(u, g.nnz), _f32(u, g.n, 2 * heads)
+        _call(lib, "dp_csr_gat_fwd", u.data_ptr(), heads, v.data_ptr(), heads, g.indptr.data_ptr(), g.indices.data_ptr(),
+              out.data_ptr(), rowstat.data_ptr(), g.n, g.nnz, heads, slope, _lib.current_stream())
+        ctx.save_for_backward(u, v, rowstat)
+        ctx.g, ctx.slope = g, slope
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        u, v, rowstat = ctx.saved_tensors
+        g, heads = ctx.g, u.shape[1]
+        dout = dout.contiguous()
+        du, dv, tdot = torch.empty_like(u), torch.empty_like(v), torch.empty_like(u)
+        _call(lib, "dp_csr_gat_bwd", u.data_ptr(), heads, v.data_ptr(), heads, g.indptr.data_ptr(), g.indices.data_ptr(),
+              g.indptr_t.data_ptr(), g.indices_t.data_ptr(), g.mirror_perm.data_ptr(), rowstat.data_ptr(),
+              dout.data_ptr(), tdot.data_ptr(), du.data_ptr(), heads, dv.data_ptr(), heads, g.n, g.nnz, heads,
+              ctx.slope, _lib.current_stream())
+        return du, dv, None, None
+
+
+def csr_gat_attention(u, v, graph, negative_slope=0.2):
+    """The mean over H heads of softmax_j(leaky_relu(u_ih + v_jh)) on every stored entry (i, j) of a CsrGraph / CsrBatch
+    -> fp32 [graph.nnz] in the order of `indices`: dp_csr_gat_fwd / _bwd, one fused pass (u, v [n, H], 1 <= H <= 8, for a
+    batch the concatenated rows).  Nothing of size nnz * H is written: the backward recomputes the coefficients from u, v
+    and the [n, 2H] row maxima and sums, and returns du, dv.  A row with one entry gives exactly 1."""
+    for name, t in (("u", u), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"csr_gat_attention: expected {name} [n, H] with n = {graph.n}, got {got}")
+    if u.shape[1] != v.shape[1] or not 1 <= u.shape[1] <= _lib.CSR_GAT_MAX_HEADS:
+        raise ValueError(f"csr_gat_attention: u and v must share H heads, 1 <= H <= {_lib.CSR_GAT_MAX_HEADS}, got "
+                         f"{u.shape[1]} and {v.shape[1]}")
+    slope = float(negative_slope)
+    if slope != slope or slope in (float("inf"), float("-inf")):
+        raise ValueError(f"csr_gat_attention: negative_slope must be finite, got {negative_slope!r}")
+    if graph.nnz == 0:                       # an edgeless container: nothing stored, nothing launched
+        return _f32(u, 0)
+    _lib.require_gpu_tensor(u, "u")
+    _lib.require_gpu_tensor(v, "v")
+    return _CsrGatFn.apply(u, v, graph, slope)

@@ -35,7 +35,8 @@ behind a CsrGraph.
 
 `EdgeAttention` computes the stored values of either container from the node features — scores on the stored entries
 (dp_csr_sddmm), a softmax over each neighbour list (dp_csr_edge_softmax_*) or a symmetric gate under D^-1/2 A D^-1/2
-(dp_csr_sym_norm_*) — and hands the three encoders a weighted container through which its projections train.
+(dp_csr_sym_norm_*), or GAT's additive multi-head scores with their softmax and head mean in one fused pass
+(dp_csr_gat_*) — and hands the three encoders a weighted container through which its projections train.
 """
 from __future__ import annotations
 
@@ -998,13 +999,37 @@ class EdgeAttention(torch.nn.Module):
     rows then sum to 1 and a_ij != a_ji, so the result rides `graph.directed()`.
     norm="sym": one projection q; the gate sigmoid(q(x)_i . q(x)_j / sqrt(att_dim)) is symmetric bit for bit (the
     products commute and the summation order is fixed), is multiplied by the stored values of a weighted container, and
-    is normalised as D^-1/2 A D^-1/2 with the gated degrees; the result keeps the container's form."""
+    is normalised as D^-1/2 A D^-1/2 with the gated degrees; the result keeps the container's form.
 
-    def __init__(self, input_dim, att_dim, norm="softmax"):
+    score="additive" (with norm="softmax"): GAT's scores on `heads` heads, the mean over the heads of
+    softmax_j(leaky_relu(a_src_h . q_h(x_i) + a_dst_h . q_h(x_j), negative_slope)), in one fused pass
+    (`ops.csr_gat_attention`).  One bias-free q: Linear(input_dim, heads * att_dim) and a_src, a_dst [heads, att_dim];
+    the per-head vectors q.weight.view(H, d, F)^T a are [H, F] matrices, so u and v are two `hip_linear` calls and
+    [n, heads * att_dim] is never formed.  The result rides `graph.directed()`."""
+
+    def __init__(self, input_dim, att_dim, norm="softmax", score="dot", heads=1, negative_slope=0.2):
         super().__init__()
         if norm not in ("softmax", "sym"):
             raise ValueError(f"EdgeAttention: norm must be 'softmax' or 'sym', got {norm!r}")
+        if score not in ("dot", "additive"):
+            raise ValueError(f"EdgeAttention: score must be 'dot' or 'additive', got {score!r}")
+        if score == "additive" and norm != "softmax":
+            raise ValueError(f"EdgeAttention: score='additive' goes with norm='softmax', got norm={norm!r}")
+        if not isinstance(heads, int) or not 1 <= heads <= 8:
+            raise ValueError(f"EdgeAttention: heads must be 1 .. 8, got {heads!r}")
+        if heads > 1 and score == "dot":
+            raise ValueError(f"EdgeAttention: heads={heads} needs score='additive' (the dot-product score has one head)")
         self.input_dim, self.att_dim, self.norm = input_dim, att_dim, norm
+        self.score, self.heads, self.negative_slope = score, heads, float(negative_slope)
+        if score == "additive":
+            self.q = torch.nn.Linear(input_dim, heads * att_dim, bias=False)
+            self.a_src = torch.nn.Parameter(torch.empty(heads, att_dim))
+            self.a_dst = torch.nn.Parameter(torch.empty(heads, att_dim))
+            gain = torch.nn.init.calculate_gain("relu")              # GAT's initialisation: Xavier, ReLU gain
+            torch.nn.init.xavier_uniform_(self.q.weight, gain=gain)
+            torch.nn.init.xavier_uniform_(self.a_src, gain=gain)
+            torch.nn.init.xavier_uniform_(self.a_dst, gain=gain)
+            return
         self.q = torch.nn.Linear(input_dim, att_dim, bias=False)
         if norm == "softmax":
             self.k = torch.nn.Linear(input_dim, att_dim, bias=False)
@@ -1014,6 +1039,12 @@ class EdgeAttention(torch.nn.Module):
             raise TypeError(f"EdgeAttention.forward(x, graph: CsrGraph or CsrBatch), got {type(graph).__name__}")
         _check_node_rows(graph, x, self.input_dim)
         x = x.contiguous().float()
+        if self.score == "additive":
+            w = self.q.weight.view(self.heads, self.att_dim, self.input_dim)
+            wu = torch.einsum("hdf,hd->hf", w, self.a_src)           # [H, F]: a_src_h . q_h(x) = (W_h^T a_src_h) . x
+            wv = torch.einsum("hdf,hd->hf", w, self.a_dst)
+            a = ops.csr_gat_attention(hip_linear(x, wu), hip_linear(x, wv), graph, self.negative_slope)
+            return graph.directed().with_values(a)
         scale = float(self.att_dim) ** -0.5
         qx = hip_linear(x, self.q.weight)
         if self.norm == "softmax":

@@ -1138,6 +1138,48 @@ int dp_csr_sym_norm_bwd(const int* indptr, const int* indices, const float* valu
                         const int* indices_t, const int* mirror, const float* rdeg, const float* dout, float* gdeg,
                         float* dvalues, int n, int nnz, void* stream);
 
+/* ------------------------------------------------------------------ N6  multi-head additive (GAT) edge attention on a
+ * CSR, fused.  For every stored entry e = (i, j), j = indices[e], of a CsrGraph / CsrBatch (a batch is its
+ * block-diagonal CSR with GLOBAL columns) and every head h < H:
+ *     pre_eh = u_ih + v_jh,   s_eh = pre_eh > 0 ? pre_eh : slope * pre_eh   (torch's leaky_relu: derivative `slope` AT 0)
+ *     a_eh   = exp(s_eh - m_ih) / z_ih,   m_ih the maximum of s over row i, z_ih = sum_{row i} exp(s - m_ih)
+ *     out_e  = (sum_h a_eh) / H            heads summed h ascending, one IEEE division
+ * u, v fp32 [n, H] at leading dimensions ldu, ldv >= H, 1 <= H <= DP_CSR_GAT_MAX_HEADS.  Scores, softmax and the mean run
+ * in one pass over the stored entries; nothing of size nnz * H is written, and the backward recomputes every coefficient
+ * from u, v and rowstat [n, 2H].  The launch form is N5's: a group of 4 / 16 / 64 lanes per row from the mean row length,
+ * the lanes of a group on consecutive entries, a row longer than the group loops.  Every sum has one order — the lane's
+ * entries ascending, then a DPP tree over the group — so a second run gives the same bits.  No atomics, no LDS.  A row
+ * with one entry gives out = 1.0 exactly and contributes exactly 0 to every gradient; rows of 2^k entries whose v_j are
+ * equal give exactly 2^-k (H = 1, 2, 4, 8).  n_rows == 0 or nnz == 0 writes nothing and returns DP_OK (the backward with
+ * nnz == 0 and n > 0 still writes the zero du and dv); every refusal (DP_ERR_INVALID_ARG: a NULL or misaligned pointer,
+ * an ld below H, a negative count, H outside 1 .. 8, a slope that is not finite) comes before any launch.
+ *
+ * dp_csr_gat_plan (host only): plan_out[DP_CSR_GAT_PLAN_INTS] = { lanes per row (4 while nnz <= 8 n_rows, 16 while
+ * nnz <= 32 n_rows, 64 above), floats per load of the H contiguous values of v_j (4: H / 4 loads of 16 bytes, taken when
+ * H % 4 == 0, ldv % 4 == 0 and the base is 16-byte aligned — v_misaligned == 0 —; 1 otherwise), entries a lane of the
+ * forward and of the row pass of the backward keeps in registers (min(8 | 4 | 4, 16 / H): 16 scores at the most), rows
+ * per workgroup (256 / lanes), the longest row that is read once (lanes * entries per lane) }, answered by the function
+ * the launchers act on. */
+#define DP_CSR_GAT_MAX_HEADS 8
+#define DP_CSR_GAT_PLAN_INTS 5
+int dp_csr_gat_plan(int n_rows, int nnz, int H, int ldv, int v_misaligned, int* plan_out);
+/* out fp32 [nnz] in the order of indices; rowstat fp32 [n_rows, 2H] OVERWRITTEN: m_i0 .. m_i(H-1), z_i0 .. z_i(H-1), zeros
+ * for a row without entries (which touches no out).  A row that fits the registers is read once; a longer one runs a
+ * per-lane running maximum and sum per head and is read a second time.  One launch. */
+int dp_csr_gat_fwd(const float* u, int ldu, const float* v, int ldv, const int* indptr, const int* indices, float* out,
+                   float* rowstat, int n_rows, int nnz, int H, float slope, void* stream);
+/* With g_e = dout_e / H:  t_ih = sum_{row i} a_eh g_e,  dpre_eh = a_eh (g_e - t_ih) (pre_eh > 0 ? 1 : slope),
+ * du_ih OVERWRITTEN = sum_{row i} dpre_eh (zeros for a row without entries),  dv_ch OVERWRITTEN = sum_{column c} dpre_eh
+ * (zeros for a column without entries), the column sum taken as row c of the transposed CSR, whose entry k is the stored
+ * entry mirror[k] (int32 [nnz], always required) from row indices_t[k].  rowstat is the forward's; tdot fp32 [n, H] is the
+ * workspace that receives t.  Two launches: over the rows (t, du), then over the transposed rows (dv, each coefficient
+ * recomputed from u_r, v_c and the SOURCE row's rowstat_r and t_r; 16-byte loads there when H % 4 == 0, ldu % 4 == 0 and
+ * u, rowstat and tdot are 16-byte aligned). */
+int dp_csr_gat_bwd(const float* u, int ldu, const float* v, int ldv, const int* indptr, const int* indices,
+                   const int* indptr_t, const int* indices_t, const int* mirror, const float* rowstat,
+                   const float* dout, float* tdot, float* du, int lddu, float* dv, int lddv, int n, int nnz, int H,
+                   float slope, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
