@@ -4,13 +4,14 @@
     from graph_pooling_amd.set2set import Set2Set
     from graph_pooling_amd import SparseGcnSet2SetEncoder      # GCN + Set2Set on CSR graphs and ragged batches (sparse.py)
     from graph_pooling_amd import EdgeAttention                # learned edge weights in front of the CSR encoders
+    from graph_pooling_amd import GatConv                      # multi-head graph-attention layer on CSR graphs / batches
 
 The arithmetic lives in libdiffpool_hip.so (graph_pooling_amd/csrc, C ABI in include/diffpool_hip.h).
 Importing this package does not load the library; the first forward does, and raises if it is missing.
 """
 __version__ = "0.1.0"
 
-__all__ = ["SparseGcnSet2SetEncoder", "EdgeAttention"]
+__all__ = ["SparseGcnSet2SetEncoder", "EdgeAttention", "GatConv"]
 
 
 def __getattr__(name):
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name == "EdgeAttention":
         from .sparse import EdgeAttention
         return EdgeAttention
+    if name == "GatConv":
+        from .sparse import GatConv
+        return GatConv
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -105,6 +105,10 @@ CSR_EDGE_PLAN_INTS = 4
 # read once)
 CSR_GAT_PLAN_INTS = 5
 CSR_GAT_MAX_HEADS = 8
+# dp_csr_gat_conv_plan: (floats per load of a gathered row, column chunks per lane, one coefficient per 16-byte quad, rows
+# per workgroup, columns per lane, lanes per row of the forward's statistics pass)
+CSR_GAT_CONV_PLAN_INTS = 6
+CSR_GAT_CONV_MAX_WIDTH = 512
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -285,6 +289,11 @@ _PROTOS = {
     "dp_csr_gat_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "dp_csr_gat_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
     "dp_csr_gat_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P]),
+    # multi-head GAT convolution: the coefficients multiplied into the gathered neighbour rows, per head
+    "dp_csr_gat_conv_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "dp_csr_gat_conv_fwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _I, _P]),
+    "dp_csr_gat_conv_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I,
+                                 _I, _I, _F, _I, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -1251,3 +1251,68 @@ def csr_gat_attention(u, v, graph, negative_slope=0.2):
     _lib.require_gpu_tensor(u, "u")
     _lib.require_gpu_tensor(v, "v")
     return _CsrGatFn.apply(u, v, graph, slope)
+
+
+# ----------------------------------------------------------------------------- multi-head GAT convolution
+class _CsrGatConvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, u, v, g, heads, slope, mean):
+        lib = _lib.load()
+        z, u, v = z.contiguous().float(), u.contiguous().float(), v.contiguous().float()
+        width = z.shape[1]
+        c = width // heads
+        y, rowstat = _f32(z, g.n, c if mean else width), _f32(z, g.n, 2 * heads)
+        _call(lib, "dp_csr_gat_conv_fwd", z.data_ptr(), width, u.data_ptr(), heads, v.data_ptr(), heads,
+              g.indptr.data_ptr(), g.indices.data_ptr(), y.data_ptr(), y.shape[1], rowstat.data_ptr(), g.n, g.nnz, heads,
+              c, slope, mean, _lib.current_stream())
+        ctx.save_for_backward(z, u, v, rowstat)
+        ctx.g, ctx.heads, ctx.slope, ctx.mean = g, heads, slope, mean
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        z, u, v, rowstat = ctx.saved_tensors
+        g, heads = ctx.g, ctx.heads
+        dy = dy.contiguous()
+        dz, du, dv, tdot = torch.empty_like(z), torch.empty_like(u), torch.empty_like(v), torch.empty_like(u)
+        _call(lib, "dp_csr_gat_conv_bwd", z.data_ptr(), z.shape[1], u.data_ptr(), heads, v.data_ptr(), heads,
+              g.indptr.data_ptr(), g.indices.data_ptr(), g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
+              rowstat.data_ptr(), dy.data_ptr(), dy.shape[1], tdot.data_ptr(), du.data_ptr(), heads, dv.data_ptr(), heads,
+              dz.data_ptr(), z.shape[1], g.n, g.nnz, heads, z.shape[1] // heads, ctx.slope, ctx.mean,
+              _lib.current_stream())
+        return dz, du, dv, None, None, None, None
+
+
+def csr_gat_conv(z, u, v, graph, heads, negative_slope=0.2, concat=True):
+    """One graph-attention layer's aggregation on a CsrGraph / CsrBatch: per head h the softmax over node i's stored
+    entries of leaky_relu(u_ih + v_jh) multiplied into the neighbours' head-h features, y_i^h = sum_j a_ijh z_j^h
+    (dp_csr_gat_conv_fwd / _bwd; z [n, heads * C] with head h in columns h C .. h C + C - 1, u, v [n, heads],
+    1 <= heads <= 8, heads * C <= 512; for a batch the concatenated rows).  concat=True returns [n, heads * C], the heads
+    side by side; concat=False their mean [n, C].  The container's stored values are not read.  Nothing of size nnz is
+    written or saved: the backward recomputes every coefficient from u, v and the [n, 2 heads] row maxima and sums, and
+    returns dz, du, dv.  A node without stored entries gets a zero row.  An edgeless container returns zeros without a
+    launch and without an autograd node: z, u and v then receive NO gradient (None, not zeros)."""
+    if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= _lib.CSR_GAT_MAX_HEADS:
+        raise ValueError(f"csr_gat_conv: heads must be 1 .. {_lib.CSR_GAT_MAX_HEADS}, got {heads!r}")
+    for name, t, cols in (("z", z, "heads * C"), ("u", u, "heads"), ("v", v, "heads")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"csr_gat_conv: expected {name} [n, {cols}] with n = {graph.n}, got {got}")
+    if u.shape[1] != heads or v.shape[1] != heads:
+        raise ValueError(f"csr_gat_conv: u and v must be [n, heads] with heads = {heads}, got {tuple(u.shape)} and "
+                         f"{tuple(v.shape)}")
+    width = z.shape[1]
+    if width == 0 or width % heads:
+        raise ValueError(f"csr_gat_conv: z has {width} columns, not a positive multiple of heads = {heads}")
+    if width > _lib.CSR_GAT_CONV_MAX_WIDTH:
+        raise ValueError(f"csr_gat_conv: z has {width} columns, more than the supported heads * C <= "
+                         f"{_lib.CSR_GAT_CONV_MAX_WIDTH}")
+    slope = float(negative_slope)
+    if slope != slope or slope in (float("inf"), float("-inf")):
+        raise ValueError(f"csr_gat_conv: negative_slope must be finite, got {negative_slope!r}")
+    if graph.nnz == 0:                       # an edgeless container: every node gets a zero row, nothing launched
+        return z.new_zeros((graph.n, width if concat else width // heads), dtype=torch.float32)
+    for name, t in (("z", z), ("u", u), ("v", v)):
+        _lib.require_gpu_tensor(t, name)
+    return _CsrGatConvFn.apply(z, u, v, graph, heads, slope, 0 if concat else 1)

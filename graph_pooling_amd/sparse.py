@@ -1054,3 +1054,54 @@ class EdgeAttention(torch.nn.Module):
         if graph.weighted:
             gate = gate * (graph.values if graph.values.numel() == graph.nnz else graph.values[:graph.nnz])
         return graph.with_values(ops.csr_sym_normalize(gate, graph))
+
+
+# ----------------------------------------------------------------------------- graph-attention layer
+class GatConv(torch.nn.Module):
+    """One multi-head graph-attention (GAT) layer on a CsrGraph / CsrBatch: forward(x, graph) returns
+    [n, heads * out_dim] (concat=True, the heads side by side) or [n, out_dim] (concat=False, their mean), plus `bias`.
+
+    z = lin(x) with lin: Linear(input_dim, heads * out_dim, bias=False) on `hip_linear`; per head h the scores
+    leaky_relu(a_src_h . z_i^h + a_dst_h . z_j^h, negative_slope) go through a softmax over node i's stored entries and the
+    coefficients are multiplied into the neighbours' z_j^h in one fused pass (`ops.csr_gat_conv`): nothing of size nnz is
+    written, the only temporaries are [n, heads * out_dim].  a_src, a_dst are [heads, out_dim] (Xavier-uniform with the
+    ReLU gain, as `EdgeAttention`'s additive form), bias [heads * out_dim] or [out_dim], zero at the start.
+
+    The layer adds NO self loops and does not read the container's stored values: a node attends exactly its stored
+    entries, and a node without any gets `bias`.  GAT's usual self-attention comes from listing (i, i) in the edge list,
+    which `CsrGraph.from_edges` / `CsrBatch.from_edge_lists` accept.  Layers stack, and their output feeds the three
+    sparse encoders unchanged.  Limits: 1 <= heads <= 8, heads * out_dim <= 512."""
+
+    def __init__(self, input_dim, out_dim, heads=1, concat=True, negative_slope=0.2, bias=True):
+        super().__init__()
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= 8:
+            raise ValueError(f"GatConv: heads must be 1 .. 8, got {heads!r}")
+        if not isinstance(out_dim, int) or out_dim < 1 or heads * out_dim > _lib.CSR_GAT_CONV_MAX_WIDTH:
+            raise ValueError(f"GatConv: heads * out_dim must be 1 .. {_lib.CSR_GAT_CONV_MAX_WIDTH}, got heads={heads}, "
+                             f"out_dim={out_dim!r}")
+        slope = float(negative_slope)
+        if slope != slope or slope in (float("inf"), float("-inf")):
+            raise ValueError(f"GatConv: negative_slope must be finite, got {negative_slope!r}")
+        self.input_dim, self.out_dim, self.heads = input_dim, out_dim, heads
+        self.concat, self.negative_slope = bool(concat), slope
+        self.lin = torch.nn.Linear(input_dim, heads * out_dim, bias=False)
+        self.a_src = torch.nn.Parameter(torch.empty(heads, out_dim))
+        self.a_dst = torch.nn.Parameter(torch.empty(heads, out_dim))
+        gain = torch.nn.init.calculate_gain("relu")                  # GAT's initialisation: Xavier, ReLU gain
+        torch.nn.init.xavier_uniform_(self.lin.weight, gain=gain)
+        torch.nn.init.xavier_uniform_(self.a_src, gain=gain)
+        torch.nn.init.xavier_uniform_(self.a_dst, gain=gain)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(heads * out_dim if self.concat else out_dim))
+        else:
+            self.register_parameter("bias", None)
+
+    def forward(self, x, graph):
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError(f"GatConv.forward(x, graph: CsrGraph or CsrBatch), got {type(graph).__name__}")
+        _check_node_rows(graph, x, self.input_dim)
+        z = hip_linear(x.contiguous().float(), self.lin.weight)
+        zh = z.view(graph.n, self.heads, self.out_dim)
+        u, v = (zh * self.a_src).sum(-1), (zh * self.a_dst).sum(-1)
+        y = ops.csr_gat_conv(z, u, v, graph, self.heads, self.negative_slope, self.concat)
+        return y if self.bias is None else y + self.bias

@@ -1180,6 +1180,55 @@ int dp_csr_gat_bwd(const float* u, int ldu, const float* v, int ldv, const int* 
                    const float* dout, float* tdot, float* du, int lddu, float* dv, int lddv, int n, int nnz, int H,
                    float slope, void* stream);
 
+/* ------------------------------------------------------------------ N7  multi-head GAT convolution on a CSR, attention
+ * and aggregation fused.  z fp32 [n, H C] at ldz >= H C (head h: columns h C .. h C + C - 1), u, v fp32
+ * [n, H] at ldu, ldv >= H, the CSR of a CsrGraph / CsrBatch (a batch is its block-diagonal CSR with GLOBAL columns).  The
+ * stored values are NOT read: the coefficients a_eh of N6 (the same pre, s, m, z, a_eh = exp(s_eh - m_ih) / zsum_ih)
+ * replace them, and are multiplied into the gathered neighbour rows in the pass that computes them:
+ *     Y_ih = sum_{e in row i} a_eh z_j^h,     j = indices[e]
+ *     mean_heads == 0:  y [n, H C],  y_i[h C + c] = Y_ih[c]
+ *     mean_heads == 1:  y [n, C],    y_i[c] = (sum_h Y_ih[c]) / H      heads added h ascending, one IEEE division
+ * Nothing of size nnz is written or saved; beyond the outputs only rowstat [n, 2H] (N6's layout: m, then zsum) and
+ * tdot [n, H] exist.  Apart from the statistics pass: one wavefront per row, lanes across the H C columns, a
+ * neighbour's row gathered as whole 256-byte (or, by 16-byte loads, 1 KiB) requests; a row of any length stays on its
+ * wave.  Every sum has one order (stated in dp_csr_gat_conv.hip), so a second run gives the same bits.  No atomics, no
+ * LDS.  A row with one entry gives y_i = z_j bit for bit (concat); rows of 2^k entries with equal v_j have a = 2^-k
+ * exactly.  Limits: 1 <= H <= DP_CSR_GAT_MAX_HEADS, C >= 1 (DP_ERR_INVALID_ARG), H C <= DP_CSR_GAT_CONV_MAX_WIDTH
+ * (DP_ERR_UNSUPPORTED above).  Every refusal (also: a NULL or misaligned pointer, an ld below its width, a negative
+ * count, a slope that is not finite, mean_heads not 0 / 1) comes before any launch.  n_rows == 0 writes nothing;
+ * nnz == 0 with n > 0 still writes the zero outputs.
+ *
+ * dp_csr_gat_conv_plan (host only): plan_out[DP_CSR_GAT_CONV_PLAN_INTS] = { floats per load of a gathered row (4: 16-byte
+ * loads, taken when H C % 4 == 0, ldz % 4 == 0 and the base is 16-byte aligned — z_misaligned == 0 —; 1 otherwise),
+ * column chunks per lane (the chunk is 64 floats-per-load columns; 1, 2, 4 or 8: the smallest that covers H C), 1 when
+ * every 16-byte quad lies in one head (4-float loads and C % 4 == 0: one coefficient per quad, else one per column),
+ * rows per workgroup (4), columns per lane, lanes per row of the forward's statistics pass (N6's rule: 4 while nnz <=
+ * 8 n_rows, 16 while nnz <= 32 n_rows, 64 above) }, answered by the function the launchers act on.  The backward gathers z
+ * (row pass) and dy (column pass) with one form: ask with ldz | lddy and with z_misaligned set when z or dy is off the
+ * 16-byte grid, or when mean_heads and C % 4 != 0. */
+#define DP_CSR_GAT_CONV_MAX_WIDTH 512
+#define DP_CSR_GAT_CONV_PLAN_INTS 6
+int dp_csr_gat_conv_plan(int n_rows, int nnz, int H, int C, int ldz, int z_misaligned, int* plan_out);
+/* y OVERWRITTEN at ldy >= H C (concat) or >= C (mean), rowstat fp32 [n_rows, 2H] OVERWRITTEN; a row without entries gets
+ * a zero y row and zero rowstat.  Two launches: the rows' statistics in N5's segmented form (a group of 4 / 16 / 64 lanes
+ * per row, lanes across the entries, head after head), then the aggregation (one wave per row, lanes across the columns,
+ * four neighbour rows in flight). */
+int dp_csr_gat_conv_fwd(const float* z, int ldz, const float* u, int ldu, const float* v, int ldv, const int* indptr,
+                        const int* indices, float* y, int ldy, float* rowstat, int n_rows, int nnz, int H, int C,
+                        float slope, int mean_heads, void* stream);
+/* With dY_ih = dy_i[h C ..] (concat, lddy >= H C) or dy_i / H (mean, lddy >= C):  g_eh = dY_ih . z_j^h,
+ * t_ih = sum_{row i} a_eh g_eh,  dpre_eh = a_eh (g_eh - t_ih) (pre_eh > 0 ? 1 : slope),  du_ih = sum_{row i} dpre_eh,
+ * dv_ch = sum_{column c} dpre_eh,  dz_c^h = sum_{column c} a_eh dY_r^h,  all OVERWRITTEN (zeros for a row / column
+ * without entries); tdot fp32 [n, H] is the workspace that receives t.  The column sums run over row c of the transposed
+ * CSR (indptr_t, indices_t; an undirected container passes the forward's arrays), whose entry k comes from source row
+ * r = indices_t[k]: every coefficient is recomputed from u_r, v_c, rowstat_r, t_r, dy_r and z_c, so there is no mirror
+ * argument.  rowstat is the forward's.  A row with one entry contributes exactly 0 to du and dv and dY_r to dz.  Two
+ * launches: over the rows (t, then du: the row is gathered twice), then over the transposed rows (dv, dz). */
+int dp_csr_gat_conv_bwd(const float* z, int ldz, const float* u, int ldu, const float* v, int ldv, const int* indptr,
+                        const int* indices, const int* indptr_t, const int* indices_t, const float* rowstat,
+                        const float* dy, int lddy, float* tdot, float* du, int lddu, float* dv, int lddv, float* dz,
+                        int lddz, int n, int nnz, int H, int C, float slope, int mean_heads, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
