@@ -76,6 +76,46 @@ __device__ __forceinline__ void lds_barrier() {
 }
 #endif
 
+// ----------------------------------------------------------------- bulk staging by LDS-DMA (dp_small.hip, dp_head.hip)
+// dst[e] <- *src_of(e) for e < count: 64 dwords per wave instruction, no register round trip.  The LDS destination of
+// an instruction is wave-uniform (M0) + 4 * lane, the source address is per lane.  Nothing is waited for here: the
+// caller issues every region it needs and then passes ONE __syncthreads() (whose fence drains vmcnt while a DMA is in
+// flight); the staged cells are read only after that barrier.  The 64-float pieces are dealt round-robin to the
+// workgroup's waves, the first to wave `first_wave` (< blockDim.x / 64), so that several short regions do not all
+// land on wave 0.
+#ifdef __HIPCC__
+__device__ __forceinline__ void sm_dma_piece(const float* src, float* lds_piece) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)lds_piece, 4, 0, 0);
+}
+template <typename SrcFn>
+__device__ inline void sm_dma(float* dst, int count, SrcFn src_of, int first_wave = 0) {
+    const int lane = threadIdx.x & 63;
+    const int nw = blockDim.x >> 6;
+    int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) - first_wave;
+    if (wave < 0) wave += nw;
+    for (int c0 = wave * 64; c0 < count; c0 += nw * 64) {
+        const int e = c0 + lane;
+        if (e < count) sm_dma_piece(src_of(e), dst + c0);
+    }
+}
+// `rows` rows of `len` floats (row r at row_src(r)) into an LDS image of row stride `ld` >= len: every row arrives as
+// pieces of its own, so the cells between two rows (an odd stride against bank conflicts) are simply not written.  Rows
+// are dealt to the waves; no division anywhere.
+template <typename RowFn>
+__device__ inline void sm_dma_rows(float* dst, int ld, int rows, int len, RowFn row_src, int first_wave = 0) {
+    const int lane = threadIdx.x & 63;
+    const int nw = blockDim.x >> 6;
+    int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) - first_wave;
+    if (wave < 0) wave += nw;
+    for (int r = wave; r < rows; r += nw) {
+        const float* src = row_src(r);
+        for (int c0 = 0; c0 < len; c0 += 64)
+            if (c0 + lane < len) sm_dma_piece(src + c0 + lane, dst + r * ld + c0);
+    }
+}
+#endif
+
 // ----------------------------------------------------------------- cross-lane reductions on DPP
 // __shfl_xor compiles to ds_bpermute_b32 (an LDS-pipe round trip per step); these run in the VALU.  A DPP row is 16
 // lanes: two quad permutes, then the half-row and the row mirror, leave the row's total in every lane.  The wave

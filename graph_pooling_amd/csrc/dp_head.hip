@@ -4,6 +4,8 @@
 //   backward: the whole pred_model backward (weight, bias and input gradients) + the max-readout scatter of every
 //             level — one workgroup for the batch, so the weight gradients are plain deterministic sums over b.
 // At B = 20 these were 3 + 7 kernels of 4-6 us each, all of them at the launch floor.
+// The forward asks for every operand in one LDS-DMA burst laid out by the host (head_fwd_plan); the backward stages its
+// gathered slices through registers (stage_issue / stage_commit).
 #include "dp_common.h"
 
 namespace dp {
@@ -23,29 +25,21 @@ __device__ unsigned long long g_head_stamps[16];
 
 constexpr int HEAD_FWD_LDS_FLOATS = 30 * 1024;    // weights + biases + two activation vectors + readout scratch
 constexpr int HEAD_BWD_LDS_FLOATS = 38 * 1024;    // weights + saved activations of the batch + two gradient blocks
+// Threads of a k_head_fwd workgroup: eight waves issue its staging burst, and two groups of four run the MLP.  Stamps at
+// the DD shape, cycles of the whole kernel: 256 threads 14.9 k, 512 13.6 k, 1024 13.9 k (profiles/hfwd_head_stamps.txt);
+// ER, the same kernel at B = 256, stays within its pairs' spread at 512 (profiles/hfwd_ab_bench.txt).
+constexpr int HEAD_FWD_THREADS = 512;
+constexpr int HEAD_FWD_WAVES = HEAD_FWD_THREADS / 64;
+static_assert(HEAD_FWD_WAVES == 8, "k_head_fwd: four readout waves, two MLP groups of four, wave rotation by & 7");
 
 __device__ inline float head_wave_sum(float v) {
     return wave64_sum(v);
 }
 
-// dst[i] = src[i] for i < cnt, 16 loads per thread in flight (clamped addresses, no branch around the loads)
-template <int NT>
-__device__ inline void head_stage(float* dst, const float* src, int cnt) {
-    for (int e0 = 0; e0 < cnt; e0 += NT * 16) {
-        float t[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) t[u] = src[min(e0 + u * NT + (int)threadIdx.x, cnt - 1)];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int i = e0 + u * NT + (int)threadIdx.x;
-            if (i < cnt) dst[i] = t[u];
-        }
-    }
-}
-
-// Split form of head_stage: `issue` asks for round `e0` of a segment (16 elements per thread, clamped addresses, gather
-// through idx), `commit` writes it to LDS.  Several segments are issued before the first commit, so their loads share
-// one memory round trip; segments longer than one round finish with stage_rest.
+// Register staging of k_head_bwd (its slices are gathers; the forward stages by LDS-DMA, dp_common.h): `issue` asks for
+// round `e0` of a segment (16 elements per thread, clamped addresses, gather through idx), `commit` writes it to LDS.
+// Several segments are issued before the first commit, so their loads share one memory round trip; segments longer than
+// one round finish with stage_rest.
 template <int NT, typename Idx>
 __device__ __forceinline__ void stage_issue(float (&t)[16], const float* src, int cnt, int e0, Idx idx) {
     // only the slots the segment has (uniform early exit): most segments are a few hundred floats, and sixteen clamped
@@ -89,110 +83,160 @@ __host__ __device__ inline HeadSizes head_sizes(const HeadArgs& a) {
     }
     return z;
 }
+// LDS row stride of a forward weight matrix [dout][din].  In the MLP lane j reads word j * stride + k: with an even
+// stride the 64 lanes share 64 / gcd(stride, 64) banks (8 of them at din = 120), with an odd one every lane has its
+// own.  Rows shorter than 16 floats stay dense: their k-loop is four steps per wave, and a DMA piece per row would carry
+// under a quarter of its lanes.
+constexpr int HEAD_PAD_MIN_DIN = 16;
+static int head_w_stride(int din, bool padded) {
+    return padded && !(din & 1) && din >= HEAD_PAD_MIN_DIN ? din + 1 : din;
+}
+// What k_head_fwd needs, laid out by the host (head_fwd_plan).  A layer is one aligned record, so it costs the kernel
+// one scalar load: HeadArgs' arrays indexed by a runtime i were a dependent scalar load per field and layer, and the
+// size sums (head_sizes) two more loops of them, all in front of the first request for data.
+struct alignas(32) HeadFwdLayer {
+    const float* W;          // [dout][din]
+    const float* bias;       // [dout], or null
+    float* out;              // hid[i + 1] of graph 0
+    int din, dout;
+    int ws, wo;              // LDS row stride and offset of the weights
+};
+struct HeadFwdArgs {
+    HeadFwdLayer L[DP_MAX_PRED + 1];
+    const float* Z;          // as HeadArgs
+    int ldz, n, rw, featoff;
+    int* argmax;
+    int lda;
+    float* feat;             // hid[0] of graph 0, [B][d0]
+    long long* labels;
+    const int* poison[DP_MAX_LEVELS + 1];   // every entry a readable address: those past n_poison repeat one
+    int n_poison;
+    int n_pred, d0, wtot, btot, mx;         // LDS floats of the weights (with their strides) and biases; widest layer
+};
 
 // Both kernels are latency problems, not throughput problems (a 120-50-2 MLP on 20 graphs): every global operand is
 // requested up front in bulk, coalesced loops into LDS, and all arithmetic then runs out of LDS.
 
+// One k-quarter of an output, k ascending, with the rounding of every step written out: the first n % 8 products are
+// fused multiply-adds, the others go in blocks of eight as rounded products added one at a time.  `s += x[k] * w[k]`
+// leaves that choice to the compiler (contraction, and how `unroll 8` splits the loop), and moving the loop into this
+// kernel's new surroundings changed it: ypred and every gradient behind it moved in the last bit.  This is the form
+// the logits have had; what holds it to them is the bit comparison of bench.py's dumps against the previous library
+// (profiles/hfwd_ab_bench.txt) and the bit tests of tests/test_gpu_head_fold.py, not this comment.
+__device__ __forceinline__ float head_dot(const float* x, const float* w, int n) {
+    float s = 0.f;
+    n = max(n, 0);
+    int k = 0;
+    for (; k < (n & 7); ++k) s = __builtin_fmaf(x[k], w[k], s);
+    {
+#pragma clang fp contract(off)
+        for (; k < n; k += 8) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const float p = x[k + u] * w[k + u];
+                s = s + p;
+            }
+        }
+    }
+    return s;
+}
+
 // ------------------------------------------------------------------ forward  (one workgroup per graph)
-__global__ __launch_bounds__(256) void k_head_fwd(HeadArgs a) {
+// Forward staging is ONE burst: the graph's feature row, every layer's weights and biases all travel by LDS-DMA
+// (sm_dma, dp_common.h), spread over all the workgroup's waves, next to the readout's loads and the poison words, and
+// one vmcnt(0) + barrier retires the lot -- one memory round trip.  (Through registers it was three dependent ones on
+// four waves: 16 clamped loads per thread and round, a segment's second round behind the commit of its first, the next
+// layer behind that.)  Staged cells are read only after that barrier.
+__global__ __launch_bounds__(HEAD_FWD_THREADS) void k_head_fwd(HeadFwdArgs a) {
     extern __shared__ float lds[];
-    const HeadSizes z = head_sizes(a);
-    float* Wl = lds;                       // all layers' weights, layer after layer
-    float* bl = Wl + z.wtot;               // all biases (zeros where a layer has none)
-    float* h0 = bl + z.btot;               // activations, ping
-    float* h1 = h0 + z.mx;                 // pong
-    float* sv = h1 + z.mx;                 // readout partials [4][64] values
+    float* Wl = lds;                       // all layers' weights, layer after layer (row strides: HeadFwdLayer::ws)
+    float* bl = Wl + a.wtot;               // all biases (zeros where a layer has none)
+    float* h0 = bl + a.btot;               // activations, ping
+    float* h1 = h0 + a.mx;                 // pong
+    float* sv = h1 + a.mx;                 // readout partials [4][64] values + [4][64] rows; MLP partials [2][4][64]
     int* si = reinterpret_cast<int*>(sv + 256);
     const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* feat = a.hid[0] + (long)b * a.dims[0];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int nw = HEAD_FWD_WAVES;
+    float* feat = a.feat + (long)b * a.d0;
     HEAD_STAMP(0);
-    // (1) readout loads go out first (16 rows per thread in flight: one pass for a level of <= 64 nodes, clamped addresses, no branches) ...
+    // the error words of this forward's grid barriers: written by earlier launches, wanted by the last layer only.
+    // Plain loads that join the burst (an atomic load is waited for on the spot: a round trip each).
+    int pz[DP_MAX_LEVELS + 1];
+#pragma unroll
+    for (int i = 0; i < DP_MAX_LEVELS + 1; ++i) pz[i] = *a.poison[i];
+    // (1) readout loads, on the first four waves (16 rows per thread in flight: one pass for a level of <= 64 nodes,
+    //     clamped addresses, no branches) ...
     constexpr int RU = 16;
     float zv[RU];
     const bool one_pass = a.Z && a.rw <= 64 && a.n <= 4 * RU;
-    if (one_pass) {
+    if (one_pass && wave < 4) {
         const float* zc = a.Z + (long)b * a.n * a.ldz + min(lane, a.rw - 1);
 #pragma unroll
         for (int u = 0; u < RU; ++u) zv[u] = zc[(long)min(wave + 4 * u, a.n - 1) * a.ldz];
     }
-    // (2) ... then the weights, biases and lower-level features stream into LDS behind them
-    //     The first round of layer i+1 (and of the features) is in flight while layer i's is committed, so the
-    //     staging is about as many round trips as the longest segment has rounds, not their sum.
+    // (2) ... and the burst beside them.  The feature row is copied whole: its columns [featoff, featoff + rw) are stale
+    //     here (this launch produces them) and are overwritten below, AFTER the barrier that retires the burst.  The
+    //     pieces start behind the four readout waves and go round the workgroup from there.
     {
-        const auto ident = [](int e) { return e; };
-        float tf[16], tw[16], tb[16];
-        stage_issue<256>(tf, feat, a.dims[0], 0, ident);
-        int wo = 0, bo = 0;
-        {
-            const int cnt0 = a.dims[0] * a.dims[1];
-            stage_issue<256>(tw, a.params + a.w_off[0], cnt0, 0, ident);
-        }
+        int fw = 4 & (nw - 1);
+        const auto next = [&](int floats) { fw = (fw + ((floats + 63) >> 6)) & (nw - 1); };
+        sm_dma(h0, a.d0, [&](int e) { return feat + e; }, fw);
+        next(a.d0);
+        int bo = 0;
         for (int i = 0; i < a.n_pred; ++i) {
-            const int cnt = a.dims[i] * a.dims[i + 1], bc = a.dims[i + 1];
-            const float* W = a.params + a.w_off[i];
-            const float* bsrc = a.b_off[i] >= 0 ? a.params + a.b_off[i] : W;      // a valid address either way
-            stage_issue<256>(tb, bsrc, bc, 0, ident);
-            float tn[16];                                                          // next layer's first round
-            const bool more = i + 1 < a.n_pred;
-            if (more) stage_issue<256>(tn, a.params + a.w_off[i + 1], a.dims[i + 1] * a.dims[i + 2], 0, ident);
-            stage_commit<256>(Wl + wo, tw, cnt, 0);
-            if (a.b_off[i] < 0) {
-#pragma unroll
-                for (int u = 0; u < 16; ++u) tb[u] = 0.f;
+            const HeadFwdLayer l = a.L[i];
+            if (l.ws == l.din) {
+                sm_dma(Wl + l.wo, l.din * l.dout, [&](int e) { return l.W + e; }, fw);
+                next(l.din * l.dout);
+            } else {
+                sm_dma_rows(Wl + l.wo, l.ws, l.dout, l.din, [&](int r) { return l.W + (long)r * l.din; }, fw);
+                fw = (fw + l.dout) & (nw - 1);
             }
-            stage_commit<256>(bl + bo, tb, bc, 0);
-            stage_rest<256>(Wl + wo, W, cnt, ident);
-            if (a.b_off[i] >= 0) stage_rest<256>(bl + bo, bsrc, bc, ident);
-            else
-                for (int e = 4096 + threadIdx.x; e < bc; e += 256) bl[bo + e] = 0.f;
-            if (more) {
-#pragma unroll
-                for (int u = 0; u < 16; ++u) tw[u] = tn[u];
+            if (l.bias) {
+                sm_dma(bl + bo, l.dout, [&](int e) { return l.bias + e; }, fw);
+                next(l.dout);
+            } else {
+                for (int e = threadIdx.x; e < l.dout; e += blockDim.x) bl[bo + e] = 0.f;    // cells no DMA writes
             }
-            wo += cnt;
-            bo += bc;
+            bo += l.dout;
         }
-        // features of the lower levels (the readout columns of this level are produced below)
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int k = u * 256 + (int)threadIdx.x;
-            if (k < a.dims[0] && (!a.Z || k < a.featoff || k >= a.featoff + a.rw)) h0[k] = tf[u];
-        }
-        for (int k = 4096 + threadIdx.x; k < a.dims[0]; k += 256)
-            if (!a.Z || k < a.featoff || k >= a.featoff + a.rw) h0[k] = feat[k];
     }
-    HEAD_STAMP(1);
-    if (a.Z) {
+    HEAD_STAMP(4);
+    if (a.Z && a.rw > 0) {
         // unmasked max over the nodes of the last level; ties -> lowest row (torch CPU max).  Four row groups x 64
-        // columns per pass, combined through LDS.
+        // columns per pass, combined through LDS.  (The readout stays on four waves: eight row groups would need twice
+        // the scratch, and the scratch is part of the LDS size head_supported admits by.  Not tried.)
         for (int c0 = 0; c0 < a.rw; c0 += 64) {
             const int c = c0 + lane;
             float best = -INFINITY;
             int bi = -1;
-            if (one_pass) {
+            if (wave < 4) {
+                if (one_pass) {
 #pragma unroll
-                for (int u = 0; u < RU; ++u) {
-                    const int r = wave + 4 * u;
-                    if (r < a.n && zv[u] > best) {
-                        best = zv[u];
-                        bi = r;
+                    for (int u = 0; u < RU; ++u) {
+                        const int r = wave + 4 * u;
+                        if (r < a.n && zv[u] > best) {
+                            best = zv[u];
+                            bi = r;
+                        }
                     }
-                }
-            } else if (c < a.rw) {
-                const float* zc = a.Z + (long)b * a.n * a.ldz + c;
+                } else if (c < a.rw) {
+                    const float* zc = a.Z + (long)b * a.n * a.ldz + c;
 #pragma unroll 4
-                for (int r = wave; r < a.n; r += 4) {
-                    const float v = zc[(long)r * a.ldz];
-                    if (v > best) {
-                        best = v;
-                        bi = r;
+                    for (int r = wave; r < a.n; r += 4) {
+                        const float v = zc[(long)r * a.ldz];
+                        if (v > best) {
+                            best = v;
+                            bi = r;
+                        }
                     }
                 }
+                sv[wave * 64 + lane] = best;
+                si[wave * 64 + lane] = bi;
             }
-            sv[wave * 64 + lane] = best;
-            si[wave * 64 + lane] = bi;
-            __syncthreads();
+            __syncthreads();               // the first pass's: vmcnt(0) + barrier, the burst has landed
+            if (c0 == 0) HEAD_STAMP(1);
             if (wave == 0 && c < a.rw) {
                 for (int k = 1; k < 4; ++k) {
                     const float v = sv[k * 64 + lane];
@@ -206,52 +250,57 @@ __global__ __launch_bounds__(256) void k_head_fwd(HeadArgs a) {
                 feat[a.featoff + c] = best;
                 a.argmax[(long)b * a.lda + c] = bi;
             }
-            __syncthreads();
+            lds_barrier();
         }
+    } else {
+        __syncthreads();                   // vmcnt(0) + barrier: the burst has landed
+        HEAD_STAMP(1);
     }
-    __syncthreads();
     HEAD_STAMP(2);
+    // From here on the barriers order LDS traffic only (lds_barrier): the stores of the features, winners and
+    // activations to global memory are read by later launches, and no barrier below waits for them.
     float* cur = h0;
     float* nxt = h1;
-    int wo = 0, bo = 0;
+    int bo = 0;
     bool poisoned = false;
-    for (int i = 0; i < a.n_poison; ++i)
-        poisoned |= __hip_atomic_load(a.poison[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+#pragma unroll
+    for (int i = 0; i < DP_MAX_LEVELS + 1; ++i) poisoned |= pz[i] != 0;
+    poisoned &= a.n_poison > 0;
+    // lane = output (64 per pass), four waves split k; partial sums meet in LDS.  (A wave-per-output dot product costs a
+    // 6-step cross-lane reduction per output: 13 serial ones for the 50-wide hidden layer.)  The second group of four
+    // waves takes the next 64 outputs of a wide layer (the scratch holds two groups' partials).
+    const int grp = wave >> 2, kw = wave & 3;
+    constexpr int ngrp = 2;
+    float* sg = sv + grp * 256;
     for (int i = 0; i < a.n_pred; ++i) {
-        const int din = a.dims[i], dout = a.dims[i + 1];
+        const HeadFwdLayer l = a.L[i];
+        const int din = l.din, dout = l.dout, ws = l.ws, wo = l.wo;
         const bool last = i == a.n_pred - 1;
-        float* out = a.hid[i + 1] + (long)b * dout;
-        // lane = output (64 per pass), the four waves split k; partial sums meet in LDS.  (A wave-per-output dot
-        // product costs a 6-step cross-lane reduction per output: 13 serial ones for the 50-wide hidden layer.)
-        for (int j0 = 0; j0 < dout; j0 += 64) {
-            const int j = j0 + lane;
-            const int kq = (din + 3) / 4, kb = wave * kq, ke = min(din, kb + kq);
+        float* out = l.out + (long)b * dout;
+        for (int j0 = 0; j0 < dout; j0 += 64 * ngrp) {
+            const int j = j0 + grp * 64 + lane;
+            const bool mine = j < dout;
+            const int kq = (din + 3) / 4, kb = kw * kq, ke = min(din, kb + kq);
             float s = 0.f;
-            if (j < dout) {
-                const float* w = Wl + wo + j * din;
-#pragma unroll 8
-                for (int k = kb; k < ke; ++k) s += cur[k] * w[k];
-            }
-            sv[wave * 64 + lane] = s;
-            __syncthreads();
-            if (wave == 0 && j < dout) {
-                s = sv[lane] + sv[64 + lane] + sv[128 + lane] + sv[192 + lane] + bl[bo + j];
+            if (mine) s = head_dot(cur + kb, Wl + wo + j * ws + kb, ke - kb);
+            sg[kw * 64 + lane] = s;
+            lds_barrier();
+            if (kw == 0 && mine) {
+                s = sg[lane] + sg[64 + lane] + sg[128 + lane] + sg[192 + lane] + bl[bo + j];
                 if (!last) s = fmaxf(s, 0.f);
                 else if (poisoned) s = __builtin_nanf("");
                 nxt[j] = s;
                 out[j] = s;
             }
-            __syncthreads();
+            lds_barrier();
         }
-        __syncthreads();
         float* t = cur; cur = nxt; nxt = t;
-        wo += din * dout;
         bo += dout;
     }
     // evaluation: the predicted class leaves the device as ONE integer per graph (`torch.max(ypred, 1)` +
     // `.cpu()` of B x C logits in the reference's evaluate(), train.py:42-44); first index on ties
     if (a.labels && threadIdx.x == 0) {
-        const int C = a.dims[a.n_pred];
+        const int C = a.L[a.n_pred - 1].dout;
         int best = 0;
         for (int c = 1; c < C; ++c)
             if (cur[c] > cur[best]) best = c;
@@ -260,9 +309,43 @@ __global__ __launch_bounds__(256) void k_head_fwd(HeadArgs a) {
     HEAD_STAMP(3);
 }
 
-static size_t head_fwd_lds_floats(const HeadArgs& a) {
+// LDS floats of k_head_fwd with dense weight rows (`padded` false: what head_supported admits by) or with the odd row
+// strides of head_w_stride
+static size_t head_fwd_lds_floats(const HeadArgs& a, bool padded) {
     const HeadSizes z = head_sizes(a);
-    return (size_t)z.wtot + z.btot + 2 * z.mx + 512;
+    size_t w = 0;
+    for (int i = 0; i < a.n_pred; ++i) w += (size_t)head_w_stride(a.dims[i], padded) * a.dims[i + 1];
+    return w + z.btot + 2 * z.mx + 512;
+}
+// The layout a launch uses: odd strides where they fit the limit, dense rows where they do not -- the padding never
+// decides whether a head is taken.
+static bool head_fwd_padded(const HeadArgs& a) {
+    return head_fwd_lds_floats(a, true) <= (size_t)HEAD_FWD_LDS_FLOATS;
+}
+static HeadFwdArgs head_fwd_plan(const HeadArgs& a, bool padded) {
+    HeadFwdArgs k{};
+    const HeadSizes z = head_sizes(a);
+    int wo = 0;
+    for (int i = 0; i < a.n_pred; ++i) {
+        HeadFwdLayer& l = k.L[i];
+        l.W = a.params + a.w_off[i];
+        l.bias = a.b_off[i] >= 0 ? a.params + a.b_off[i] : nullptr;
+        l.out = a.hid[i + 1];
+        l.din = a.dims[i];
+        l.dout = a.dims[i + 1];
+        l.ws = head_w_stride(l.din, padded);
+        l.wo = wo;
+        wo += l.ws * l.dout;
+    }
+    k.Z = a.Z, k.ldz = a.ldz, k.n = a.n, k.rw = a.rw, k.featoff = a.featoff;
+    k.argmax = a.argmax, k.lda = a.lda;
+    k.feat = a.hid[0];
+    k.labels = a.labels;
+    for (int i = 0; i <= DP_MAX_LEVELS; ++i)
+        k.poison[i] = a.n_poison > 0 ? a.poison[i < a.n_poison ? i : 0] : reinterpret_cast<const int*>(a.params);
+    k.n_poison = a.n_poison;
+    k.n_pred = a.n_pred, k.d0 = a.dims[0], k.wtot = wo, k.btot = z.btot, k.mx = z.mx;
+    return k;
 }
 void head_fwd(Seq& q, const HeadArgs& a) {
     if (!q.ok()) return;
@@ -270,7 +353,9 @@ void head_fwd(Seq& q, const HeadArgs& a) {
     ensure_dyn_lds(q, attr, reinterpret_cast<const void*>(&k_head_fwd), HEAD_FWD_LDS_FLOATS * (int)sizeof(float),
                    "k_head_fwd");
     if (!q.ok()) return;
-    hipLaunchKernelGGL(k_head_fwd, dim3(a.B), dim3(256), head_fwd_lds_floats(a) * sizeof(float), q.stream, a);
+    const bool padded = head_fwd_padded(a);
+    hipLaunchKernelGGL(k_head_fwd, dim3(a.B), dim3(HEAD_FWD_THREADS), head_fwd_lds_floats(a, padded) * sizeof(float),
+                       q.stream, head_fwd_plan(a, padded));
     q.check_launch("head_fwd");
 }
 
@@ -440,7 +525,7 @@ static size_t head_bwd_lds_floats(const HeadArgs& a) {
 bool head_supported(const HeadArgs& a) {
     if (a.n_pred < 1 || a.B < 1 || a.B > 1024) return false;
     // everything the kernels touch repeatedly must fit LDS (they are latency-, not throughput-shaped)
-    return head_fwd_lds_floats(a) <= HEAD_FWD_LDS_FLOATS && head_bwd_lds_floats(a) <= HEAD_BWD_LDS_FLOATS;
+    return head_fwd_lds_floats(a, false) <= HEAD_FWD_LDS_FLOATS && head_bwd_lds_floats(a) <= HEAD_BWD_LDS_FLOATS;
 }
 
 void head_bwd(Seq& q, const HeadBwdArgs& a) {

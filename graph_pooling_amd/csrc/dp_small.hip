@@ -36,9 +36,8 @@ __device__ inline float sm_team_sum(float v) {
 
 typedef float sm_f32x4 __attribute__((ext_vector_type(4)));
 
-// Bulk staging by LDS-DMA: dst[e] <- *src_of(e) for e < count, 64 dwords per wave instruction, no register round
-// trip; every request of every region is in flight before the single barrier that follows (whose fence drains
-// vmcnt).  The LDS destination is wave-uniform (M0) + 4 * lane.
+// Bulk staging by LDS-DMA (sm_dma, dp_common.h): every request of every region is in flight before the single barrier
+// that follows (whose fence drains vmcnt).
 // In-kernel stamps (DP_STAMP build, tools/small_kernel_stamps.py) put the opening burst at ~10k of the backward
 // kernel's ~29k cycles and ~7.5k of the forward's ~15k whichever way it is written — plain load/store loops, this
 // DMA form, or registers with all loads issued first: one workgroup pulls ~180 KB through ONE CU's vector-memory
@@ -55,18 +54,6 @@ struct SmDiv {
     __device__ inline int rem(int e) const { return e - quot(e) * d; }
 };
 static SmDiv sm_div(int d) { return SmDiv{(unsigned)(0x100000000ull / (unsigned)d + 1), d}; }
-
-template <typename SrcFn>
-__device__ inline void sm_dma(float* dst, int count, SrcFn src_of) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-    for (int c0 = wave * 64; c0 < count; c0 += nw * 64) {
-        const int e = c0 + lane;
-        if (e < count)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_of(e),
-                                             (__attribute__((address_space(3))) void*)(dst + c0), 4, 0, 0);
-    }
-}
 
 // C[M x N] = op(A)[M x K] · op(B)[K x N] with both operands in LDS, on the fp32 MFMA (16x16x4), tiles dealt
 // round-robin to the workgroup's waves.  Reads outside the logical matrices return 0, so nothing needs

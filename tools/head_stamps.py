@@ -23,7 +23,7 @@ buf = (C.c_ulonglong * 16)()
 lib.dp_debug_head_stamps.restype = C.c_int
 assert lib.dp_debug_head_stamps(buf) == 0
 t = list(buf)
-print("forward  (cycles): staging issue+commit", t[1] - t[0], "| readout + barrier", t[2] - t[1], "| MLP", t[3] - t[2],
-      "| total", t[3] - t[0])
+print("forward  (cycles): staging", t[1] - t[0], "(burst issued after", t[4] - t[0], ") | readout combine + barrier",
+      t[2] - t[1], "| MLP", t[3] - t[2], "| total", t[3] - t[0])
 print("backward (cycles): staging", t[9] - t[8], "| upper layers", t[10] - t[9], "| first-layer dW + bias", t[11] - t[10],
       "| d(features) + scatter", t[12] - t[11], "| total", t[12] - t[8])
