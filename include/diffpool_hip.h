@@ -1036,14 +1036,19 @@ int dp_gather_labels(const long long* graph_label, long long* label_out, int B, 
  *   total = ||grads||_2;  grads *= min(1, max_norm / (total + 1e-6))   (max_norm <= 0: no clipping)
  *   exp_avg = b1 exp_avg + (1-b1) g;  exp_avg_sq = b2 exp_avg_sq + (1-b2) g^2
  *   params -= lr / (1 - b1^step) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - b2^step) + eps)
- * step >= 1 is the 1-based count of this update.  total_norm_out: device float or NULL.  Two launches. */
+ * step >= 1 is the 1-based count of this update.  total_norm_out: device float or NULL.  Two launches.
+ * With max_norm <= 0 AND total_norm_out == NULL no norm is taken by either entry (this one then makes one launch), so
+ * nothing looks at the gradient's finiteness: a non-finite gradient is NOT skipped and DP_DEVERR_NONFINITE_GRAD is not raised — the
+ * update goes through and writes NaN into the elements concerned, as torch.optim.Adam alone would.  Give either
+ * argument to keep the skip. */
 size_t dp_clip_adam_workspace_bytes(void);
 int dp_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, int step, float lr,
                       float beta1, float beta2, float eps, float max_norm, float* total_norm_out, void* workspace,
                       size_t workspace_bytes, void* stream);
 /* The same update with the step count kept ON THE DEVICE: step_counter (device int, the number of updates done so far;
  * zero it once) is incremented by the call and the bias corrections of the new count are computed by the kernel (in
- * double, as above).  No argument changes from step to step, so the call can sit inside a captured hipGraph together
+ * double, as above).  The count goes up on a step that is skipped for a non-finite norm too: the norm kernel counts,
+ * one launch ahead of the kernel that finds the norm non-finite.  No argument changes from step to step, so the call can sit inside a captured hipGraph together
  * with dp_build_batch_packed, dp_encoder_forward_packed, dp_loss_forward (dp_loss_forward_packed with the
  * link-prediction loss) and dp_encoder_backward_packed: one graph launch per training step (train.py:197-210). */
 int dp_clip_adam_step_counted(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, int* step_counter,
