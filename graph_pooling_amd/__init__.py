@@ -5,13 +5,14 @@
     from graph_pooling_amd import SparseGcnSet2SetEncoder      # GCN + Set2Set on CSR graphs and ragged batches (sparse.py)
     from graph_pooling_amd import EdgeAttention                # learned edge weights in front of the CSR encoders
     from graph_pooling_amd import GatConv                      # multi-head graph-attention layer on CSR graphs / batches
+    from graph_pooling_amd import SageConv, SageEncoder        # GraphSAGE layer, the neighbour sample drawn on the device
 
 The arithmetic lives in libdiffpool_hip.so (graph_pooling_amd/csrc, C ABI in include/diffpool_hip.h).
 Importing this package does not load the library; the first forward does, and raises if it is missing.
 """
 __version__ = "0.1.0"
 
-__all__ = ["SparseGcnSet2SetEncoder", "EdgeAttention", "GatConv"]
+__all__ = ["SparseGcnSet2SetEncoder", "EdgeAttention", "GatConv", "SageConv", "SageEncoder"]
 
 
 def __getattr__(name):
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name == "GatConv":
         from .sparse import GatConv
         return GatConv
+    if name in ("SageConv", "SageEncoder"):
+        from . import sparse
+        return getattr(sparse, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

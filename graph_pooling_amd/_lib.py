@@ -109,6 +109,11 @@ CSR_GAT_MAX_HEADS = 8
 # per workgroup, columns per lane, lanes per row of the forward's statistics pass)
 CSR_GAT_CONV_PLAN_INTS = 6
 CSR_GAT_CONV_MAX_WIDTH = 512
+# dp_csr_sample_mean_plan: (rows per workgroup, forward workgroups, backward workgroups, tier of a row of d entries
+# (0 A / 1 B / 2 C), its key chunks, of those in registers, 64-column forward passes, 256-column backward passes)
+CSR_SAMPLE_PLAN_INTS = 8
+CSR_SAMPLE_ALL, CSR_SAMPLE_MAX_K = 0, 64
+CSR_SAMPLE_SELF = {"none": 0, "gcn": 1, "concat": 2}      # DP_CSR_SAMPLE_SELF_*
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -294,6 +299,10 @@ _PROTOS = {
     "dp_csr_gat_conv_fwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _I, _P]),
     "dp_csr_gat_conv_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I,
                                  _I, _I, _F, _I, _P]),
+    # GraphSAGE neighbour sampling fused with the mean: the sample a function of (seed, i, j), re-derived in the backward
+    "dp_csr_sample_mean_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "dp_csr_sample_mean_fwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _L, _P]),
+    "dp_csr_sample_mean_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

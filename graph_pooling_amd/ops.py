@@ -1316,3 +1316,123 @@ def csr_gat_conv(z, u, v, graph, heads, negative_slope=0.2, concat=True):
     for name, t in (("z", z), ("u", u), ("v", v)):
         _lib.require_gpu_tensor(t, name)
     return _CsrGatConvFn.apply(z, u, v, graph, heads, slope, 0 if concat else 1)
+
+
+# ----------------------------------------------------------------------------- sampled neighbour mean
+class _CsrSampleMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, g, nodes, k, seed, mode):
+        lib = _lib.load()
+        x = x.contiguous().float()
+        n, feat = x.shape
+        m = n if nodes is None else nodes.numel()
+        width = 2 * feat if mode == _lib.CSR_SAMPLE_SELF["concat"] else feat
+        y = _f32(x, m, width)
+        thr = torch.empty(m, device=x.device, dtype=torch.int64)
+        cnt = torch.empty(m, device=x.device, dtype=torch.int32)
+        indices = g.indices if g.indices.numel() else g.indptr          # an edgeless CsrGraph: never read, never NULL
+        _call(lib, "dp_csr_sample_mean_fwd", x.data_ptr(), feat, g.indptr.data_ptr(), indices.data_ptr(), _lib.ptr(nodes),
+              y.data_ptr(), width, thr.data_ptr(), cnt.data_ptr(), m, n, feat, k, mode, seed, _lib.current_stream())
+        ctx.save_for_backward(thr, cnt)
+        ctx.g, ctx.nodes, ctx.seed, ctx.mode, ctx.shape = g, nodes, seed, mode, (n, feat)
+        ctx.mark_non_differentiable(thr, cnt)
+        ctx.set_materialize_grads(False)                                 # no zero-filled "gradients" of thr and cnt
+        return y, thr, cnt
+
+    @staticmethod
+    def backward(ctx, dy, _dthr, _dcnt):
+        if dy is None:
+            return None, None, None, None, None, None
+        lib = _lib.load()
+        thr, cnt = ctx.saved_tensors
+        g, nodes, (n, feat) = ctx.g, ctx.nodes, ctx.shape
+        dy = dy.contiguous()
+        slot = None
+        if nodes is not None:                                            # plumbing: one scatter
+            slot = torch.full((n,), -1, device=dy.device, dtype=torch.int32)
+            slot[nodes.long()] = torch.arange(nodes.numel(), device=dy.device, dtype=torch.int32)
+        dx = _f32(dy, n, feat)
+        indices_t = g.indices_t if g.indices_t.numel() else g.indptr_t
+        _call(lib, "dp_csr_sample_mean_bwd", dy.data_ptr(), dy.shape[1], g.indptr_t.data_ptr(), indices_t.data_ptr(),
+              _lib.ptr(slot), thr.data_ptr(), cnt.data_ptr(), dx.data_ptr(), feat, n, feat, ctx.mode, ctx.seed,
+              _lib.current_stream())
+        return dx, None, None, None, None, None
+
+
+def _sample_args(who, num_sample, seed, self_mode):
+    """(k of the C entries, the seed as the signed 64-bit word they take, DP_CSR_SAMPLE_SELF_*) or ValueError."""
+    if num_sample is None:
+        k = _lib.CSR_SAMPLE_ALL
+    elif isinstance(num_sample, int) and not isinstance(num_sample, bool) and 1 <= num_sample <= _lib.CSR_SAMPLE_MAX_K:
+        k = num_sample
+    else:
+        raise ValueError(f"{who}: num_sample must be 1 .. {_lib.CSR_SAMPLE_MAX_K} or None (all neighbours), got "
+                         f"{num_sample!r}")
+    if not isinstance(seed, int) or isinstance(seed, bool) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"{who}: seed must be a Python int in [0, 2^64), got {seed!r}")
+    if self_mode not in _lib.CSR_SAMPLE_SELF:
+        raise ValueError(f"{who}: self_mode must be 'none', 'gcn' or 'concat', got {self_mode!r}")
+    return k, seed - (1 << 64) if seed >= 1 << 63 else seed, _lib.CSR_SAMPLE_SELF[self_mode]
+
+
+def check_target_nodes(who, nodes, n):
+    """`nodes` of `csr_sample_mean` as host numbers: integers, distinct, in 0 .. n - 1, else ValueError."""
+    a = torch.as_tensor(nodes).detach().cpu()
+    if a.dim() != 1 or a.is_floating_point() or a.is_complex() or a.dtype == torch.bool:
+        raise ValueError(f"{who}: nodes must be a 1-d list of integer node ids, got shape {tuple(a.shape)} of {a.dtype}")
+    a = a.long()
+    if a.numel() and (int(a.min()) < 0 or int(a.max()) >= n):
+        raise ValueError(f"{who}: node id outside 0 .. {n - 1}")
+    if torch.unique(a).numel() != a.numel():
+        raise ValueError(f"{who}: nodes must be distinct")
+    return a
+
+
+def csr_sample_mean_stats(x, graph, num_sample, seed, nodes=None, self_mode="none", nodes_checked=False):
+    """`csr_sample_mean` with what it saves: (y, thr int64 [m], cnt int32 [m]).  thr holds the bits of each target row's
+    64-bit threshold (-1: every neighbour taken), cnt the divisor; both are data."""
+    k, seed64, mode = _sample_args("csr_sample_mean", num_sample, seed, self_mode)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != graph.n:
+        got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"csr_sample_mean: expected x [n, F] with n = {graph.n}, got {got}")
+    if nodes is not None:
+        if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int32 or nodes.dim() != 1:
+            raise ValueError("csr_sample_mean: nodes must be None or an int32 tensor [m] of distinct node ids")
+        if not nodes_checked:
+            check_target_nodes("csr_sample_mean", nodes, graph.n)
+    m = graph.n if nodes is None else nodes.numel()
+    feat = x.shape[1]
+    width = 2 * feat if self_mode == "concat" else feat
+    if (graph.nnz == 0 and self_mode == "none") or m == 0 or feat == 0:   # nothing to gather: zeros, nothing launched
+        y = x.new_zeros((m, width), dtype=torch.float32)
+        return (y, torch.full((m,), -1, device=x.device, dtype=torch.int64),
+                torch.zeros(m, device=x.device, dtype=torch.int32))
+    _lib.require_gpu_tensor(x, "x")
+    _lib.require_gpu_tensor(graph.indptr, "the container's index arrays")
+    if nodes is not None:
+        _lib.require_gpu_tensor(nodes, "nodes")
+        nodes = nodes.contiguous()
+    return _CsrSampleMeanFn.apply(x, graph, nodes, k, seed64, mode)
+
+
+def csr_sample_mean(x, graph, num_sample, seed, nodes=None, self_mode="none", nodes_checked=False):
+    """GraphSAGE's sampled neighbour mean on a CsrGraph / CsrBatch, drawn and taken in one fused launch
+    (dp_csr_sample_mean_fwd / _bwd; MeanAggregator.forward with num_sample, aggregators.py:30-63).
+
+    x fp32 [n, F] (for a batch the concatenated rows); `num_sample` = k in 1 .. 64, or None for every neighbour; `seed` a
+    Python int in [0, 2^64); `nodes` None (row r of the result is node r) or an int32 device tensor [m] of DISTINCT node
+    ids (row r is node nodes[r]; range and distinctness are checked on the host, ValueError — one read-back, which a
+    caller that built `nodes` from host numbers it has checked itself skips with nodes_checked=True).  A node with at
+    most k stored neighbours takes all of them; otherwise the k entries with the smallest
+    key(i, j) = (h(seed, i, j) << 32) | j, h word 0 of Philox4x32-10 with the seed as its key and (i, j, 0, 0) as its counter — uniform without replacement,
+    independent from row to row, and a pure function of (seed, i, j): the same seed gives the same sample and the same
+    bits.  The container's stored values are not read (the sampled mean is unweighted, as the reference's).
+
+    self_mode 'none': the mean over the sample, [m, F].  'gcn': the node joins its own sample as in the reference's
+    gcn=True (`set | {i}`; a stored and sampled self loop is not counted twice), [m, F].  'concat': [x_i | mean], [m, 2F],
+    GraphSAGE's own combination.  A node whose sample is empty gets ZEROS in the mean part, not the reference's
+    0 / 0 = NaN.  Nothing of size nnz is written or saved: the backward re-derives the sample from the saved [m] thresholds
+    over the transposed CSR, in a fixed order and without atomics (a second run gives the same bits).  An edgeless
+    container with 'none' (and a call without target rows or columns) returns zeros without a launch and without an
+    autograd node.  Not for hipGraph capture: the seed is a kernel argument and would be frozen."""
+    return csr_sample_mean_stats(x, graph, num_sample, seed, nodes, self_mode, nodes_checked)[0]

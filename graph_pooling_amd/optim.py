@@ -19,6 +19,44 @@ import torch
 from . import _lib
 
 
+class _FlatModule:
+    """The encoders' flat-buffer protocol (`_ensure_flat`, `_flat`, `_flat_params`, `_flat_index`) for a module that
+    lacks it — `SupervisedGraphSage` over a `SageEncoder`, a stack of `SageConv` / `GatConv` layers: every parameter
+    becomes a view into ONE fp32 buffer, in `parameters()` order, re-flattened after .cuda() / load_state_dict re-bound
+    the tensors."""
+
+    def __init__(self, module):
+        self.module = module
+        self._flat, self._flat_index, self._flat_params = None, [], []
+        self._last_flat_grad = None
+
+    def parameters(self):
+        return self.module.parameters()
+
+    def zero_grad(self, set_to_none: bool = True):
+        self.module.zero_grad(set_to_none=set_to_none)
+
+    def _ensure_flat(self, device):
+        params = list(self.module.parameters())
+        ok = self._flat is not None and self._flat.device == device and len(params) == len(self._flat_index)
+        if ok:
+            base = self._flat.data_ptr()
+            ok = all(p is q and p.data_ptr() == base + 4 * off and p.dtype == torch.float32
+                     for p, q, (off, _, _) in zip(params, self._flat_params, self._flat_index))
+        if ok:
+            return
+        flat = torch.empty(sum(p.numel() for p in params), device=device, dtype=torch.float32)
+        index, off = [], 0
+        for p in params:
+            n = p.numel()
+            flat[off:off + n].copy_(p.data.reshape(-1).to(device=device, dtype=torch.float32))
+            index.append((off, n, tuple(p.shape)))
+            off += n
+        for p, (o, n, shape) in zip(params, index):
+            p.data = flat[o:o + n].view(shape)
+        self._flat, self._flat_index, self._flat_params = flat, index, params
+
+
 class FusedClipAdam:
     """opt = FusedClipAdam(model, lr=1e-3, clip=2.0);  loss.backward();  opt.step()"""
 
@@ -28,6 +66,8 @@ class FusedClipAdam:
         (dp_clip_adam_step_counted) instead of passing it from the host — nothing about the call changes from step to
         step, so `step()` can be captured in a hipGraph (train_step.CapturedTrainStep)."""
         self.model = getattr(model, "model", model)          # accept a DataParallelEncoder wrapper too
+        if not hasattr(self.model, "_ensure_flat"):          # any other module: its parameters in one flat buffer
+            self.model = _FlatModule(self.model)
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.clip = float(clip) if clip is not None else 0.0
         self.step_count = 0

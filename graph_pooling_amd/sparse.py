@@ -37,6 +37,9 @@ behind a CsrGraph.
 (dp_csr_sddmm), a softmax over each neighbour list (dp_csr_edge_softmax_*) or a symmetric gate under D^-1/2 A D^-1/2
 (dp_csr_sym_norm_*), or GAT's additive multi-head scores with their softmax and head mean in one fused pass
 (dp_csr_gat_*) — and hands the three encoders a weighted container through which its projections train.
+
+`SageConv` / `SageEncoder` are GraphSAGE's mean-aggregator layer and the encoder `SupervisedGraphSage` expects, on either
+container, with the neighbour sample drawn on the device in the launch that takes its mean (dp_csr_sample_mean_*).
 """
 from __future__ import annotations
 
@@ -1105,3 +1108,84 @@ class GatConv(torch.nn.Module):
         u, v = (zh * self.a_src).sum(-1), (zh * self.a_dst).sum(-1)
         y = ops.csr_gat_conv(z, u, v, graph, self.heads, self.negative_slope, self.concat)
         return y if self.bias is None else y + self.bias
+
+
+# ----------------------------------------------------------------------------- GraphSAGE layer
+class SageConv(torch.nn.Module):
+    """One GraphSAGE layer with the mean aggregator on a CsrGraph / CsrBatch, the neighbour sample drawn on the device:
+    forward(x, graph, nodes=None, seed=None) = relu(W [x_i | mean_{j in S(i)} x_j])  (gcn=False, the reference's Encoder
+    over its MeanAggregator, aggregators.py:30-63)  or  relu(W mean_{S(i) u {i}} x_j)  (gcn=True), [m, out_dim].
+
+    S(i) is `num_sample` of node i's stored neighbours without replacement (all of them when it has no more, or with
+    num_sample=None), drawn and averaged in ONE fused launch (`ops.csr_sample_mean`): no Python loop over the nodes, no
+    host-to-device copy, nothing of size nnz written.  `weight` is [out_dim, 2 input_dim] ([out_dim, input_dim] under
+    gcn), Xavier-uniform, applied on `hip_linear`; `bias` [out_dim] is off by default, as in the reference.
+
+    `seed`: a Python int in [0, 2^64) fixes the sample; None draws one from torch's CPU generator (no device sync,
+    reproducible under `torch.manual_seed`).  The layer samples in training AND in evaluation, as the reference does.
+    `nodes`: None for every node (layers stack on the whole graph), or an int32 device tensor of distinct node ids —
+    the last layer of a stack may take the mini-batch.  Nested mini-batch sampling across layers (a sample of the
+    sample's neighbourhood) is out of scope, as are weighted sampling, num_sample > 64 and hipGraph capture of the op
+    (the seed is a kernel argument and would be frozen).  A node without neighbours gets a zero mean, not NaN."""
+
+    def __init__(self, input_dim, out_dim, num_sample=10, gcn=False, bias=False):
+        super().__init__()
+        if num_sample is not None and (not isinstance(num_sample, int) or isinstance(num_sample, bool)
+                                       or not 1 <= num_sample <= _lib.CSR_SAMPLE_MAX_K):
+            raise ValueError(f"SageConv: num_sample must be 1 .. {_lib.CSR_SAMPLE_MAX_K} or None, got {num_sample!r}")
+        if not isinstance(input_dim, int) or not isinstance(out_dim, int) or input_dim < 1 or out_dim < 1:
+            raise ValueError(f"SageConv: input_dim and out_dim must be positive, got {input_dim!r} and {out_dim!r}")
+        self.input_dim, self.out_dim, self.num_sample, self.gcn = input_dim, out_dim, num_sample, bool(gcn)
+        self.weight = torch.nn.Parameter(torch.empty(out_dim, input_dim if self.gcn else 2 * input_dim))
+        torch.nn.init.xavier_uniform_(self.weight)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(out_dim))
+        else:
+            self.register_parameter("bias", None)
+
+    def forward(self, x, graph, nodes=None, seed=None, nodes_checked=False):
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError(f"SageConv.forward(x, graph: CsrGraph or CsrBatch), got {type(graph).__name__}")
+        _check_node_rows(graph, x, self.input_dim)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # the CPU generator: no device sync
+        h = ops.csr_sample_mean(x, graph, self.num_sample, seed, nodes, "gcn" if self.gcn else "concat",
+                                nodes_checked)
+        return torch.relu(hip_linear(h, self.weight, self.bias))
+
+
+class SageEncoder(torch.nn.Module):
+    """The reference's Encoder for `SupervisedGraphSage` on the device: forward(nodes) -> [len(nodes), embed_dim], the
+    `SageConv` layer `conv` over `graph` on the features of ALL nodes, evaluated at `nodes`.
+
+    `features`: an fp32 tensor [n, F] (kept as a buffer), an `nn.Embedding` (its weight trains), or a callable / module
+    mapping a LongTensor of node ids to their features.  `nodes`: a list, a numpy array or a tensor of distinct node
+    ids (checked on the host: ValueError).  `seed` as in `SageConv.forward`."""
+
+    def __init__(self, features, graph, conv):
+        super().__init__()
+        if not isinstance(conv, SageConv):
+            raise TypeError(f"SageEncoder: conv must be a SageConv, got {type(conv).__name__}")
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError(f"SageEncoder: graph must be a CsrGraph or CsrBatch, got {type(graph).__name__}")
+        if isinstance(features, torch.Tensor) and not isinstance(features, torch.nn.Parameter):
+            self.register_buffer("features", features, persistent=False)
+        elif isinstance(features, (torch.nn.Module, torch.nn.Parameter)) or callable(features):
+            self.features = features
+        else:
+            raise TypeError(f"SageEncoder: features must be a tensor, an nn.Embedding or a callable, got "
+                            f"{type(features).__name__}")
+        self.graph, self.conv, self.embed_dim = graph, conv, conv.out_dim
+
+    def _x(self):
+        f = self.features
+        if isinstance(f, torch.Tensor):
+            return f
+        if isinstance(f, torch.nn.Embedding):
+            return f.weight
+        return f(torch.arange(self.graph.n, device=self.graph.indptr.device))
+
+    def forward(self, nodes, seed=None):
+        ids = ops.check_target_nodes("SageEncoder", nodes, self.graph.n)
+        dev = self.graph.indptr.device
+        return self.conv(self._x(), self.graph, ids.to(device=dev, dtype=torch.int32), seed, nodes_checked=True)

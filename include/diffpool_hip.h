@@ -1234,6 +1234,58 @@ int dp_csr_gat_conv_bwd(const float* z, int ldz, const float* u, int ldu, const 
                         const float* dy, int lddy, float* tdot, float* du, int lddu, float* dv, int lddv, float* dz,
                         int lddz, int n, int nnz, int H, int C, float slope, int mean_heads, void* stream);
 
+/* ------------------------------------------------------------------ N8  GraphSAGE neighbour sampling fused with the mean
+ * (DESIGN §4.10): MeanAggregator.forward(nodes, to_neighs, num_sample), aggregators.py:30-63 — the reference's
+ * random.sample per node on the host (aggregators.py:38-42), its `set | {node}` under gcn (aggregators.py:44-47) and the
+ * row-normalised mask times the embedding matrix (aggregators.py:50-62) — on the CSR of a CsrGraph / CsrBatch (GLOBAL
+ * columns, unique and ascending in every row; the stored values are NOT read).  x fp32 [n, F] at ldx >= F.  Row r of the
+ * result belongs to node i = nodes[r] (int32 [n_rows], distinct, in 0 .. n - 1; not checked here) or, with nodes == NULL
+ * (then n_rows == n), to node r.  With d = the row's stored entries and k the sample size:
+ *     key(i, j) = (h << 32) | j,  h = word 0 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *                 (i, j, 0, 0)  (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85)
+ *     d <= k or k == DP_CSR_SAMPLE_ALL:  S(i) = N(i), thr_i = all-ones;   else thr_i = the k-th smallest key of the row
+ *     and S(i) = { j : key(i, j) <= thr_i }: exactly k entries, uniform without replacement.
+ *     self_mode DP_CSR_SAMPLE_SELF_NONE:    y_r = sum_{S(i)} x_j / cnt_i,  cnt_i = |S(i)|                       y [n_rows, F]
+ *               DP_CSR_SAMPLE_SELF_GCN:     y_r = (sum_{S(i)} x_j + [i not in S(i)] x_i) / cnt_i,  cnt_i = |S(i) u {i}|
+ *               DP_CSR_SAMPLE_SELF_CONCAT:  y_r = [x_i | sum_{S(i)} x_j / cnt_i],  cnt_i = |S(i)|              y [n_rows, 2F]
+ * A row with cnt_i == 0 gets ZEROS in the mean part (the reference: 0 / 0 = NaN).  Saved for the backward: thr [n_rows]
+ * (64-bit) and cnt [n_rows]; nothing of size nnz is written.  The order of every sum is fixed (dp_csr_sample.hip), no
+ * atomics, a second run gives the same bits; with DP_CSR_SAMPLE_SELF_NONE a row with d <= k gives the bits of
+ * dp_mean_aggregate_fwd.  Every refusal (k outside 1 .. DP_CSR_SAMPLE_MAX_K and not DP_CSR_SAMPLE_ALL, a self_mode that
+ * is none of the three, a NULL or misaligned pointer, an ld below its width, a negative count, n_rows > n, n_rows != n
+ * without nodes) comes before any launch; n_rows == 0 (forward), n == 0 (backward) or F == 0 returns without one.
+ *
+ * dp_csr_sample_mean_plan (host only, aggregators.py:30-63): plan_out[DP_CSR_SAMPLE_PLAN_INTS] = { rows per workgroup
+ * (4: one wavefront each), workgroups of the forward, workgroups of the backward, the tier of a row of d entries (0: A,
+ * d <= k, no hash; 1: B, k < d <= 64, one key per lane; 2: C, d > 64, chunks of 64), the row's key chunks (0 in tier A),
+ * how many of them stay in registers (4 at most, the rest are recomputed), 64-column passes of the forward, 256-column
+ * passes of the backward (the membership is evaluated once per pass) }, answered by the functions the launchers and the
+ * kernels act on. */
+#define DP_CSR_SAMPLE_ALL 0
+#define DP_CSR_SAMPLE_MAX_K 64
+#define DP_CSR_SAMPLE_SELF_NONE 0
+#define DP_CSR_SAMPLE_SELF_GCN 1
+#define DP_CSR_SAMPLE_SELF_CONCAT 2
+#define DP_CSR_SAMPLE_PLAN_INTS 8
+int dp_csr_sample_mean_plan(int n_rows, int n, int F, int k, int self_mode, int d, int* plan_out);
+/* MeanAggregator.forward, aggregators.py:30-63.  y OVERWRITTEN at ldy >= F (2F under concat), thr (8-byte aligned) and
+ * cnt OVERWRITTEN; `seed` carries the 64 bits of the seed.  One launch: a wavefront per target row draws the row's
+ * sample once, then gathers it, lanes across the columns. */
+int dp_csr_sample_mean_fwd(const float* x, int ldx, const int* indptr, const int* indices, const int* nodes, float* y,
+                           int ldy, unsigned long long* thr, int* cnt, int n_rows, int n, int F, int k, int self_mode,
+                           long seed, void* stream);
+/* The backward of MeanAggregator.forward, aggregators.py:30-63 (autograd through aggregators.py:50-62 in the reference).
+ *     dx_j = sum_{i in N^T(j), slot_i >= 0, key(i, j) <= thr_i} dy_slot(i) / cnt_i      sources ascending, one chain
+ *            + dy_slot(j) / cnt_j   under gcn when j is a target and (j, j) was not sampled
+ *            + dy_slot(j)[0 .. F)   under concat when j is a target (the neighbour terms then read dy[F .. 2F))
+ * over the transposed CSR (indptr_t, indices_t; an undirected container passes the forward's arrays).  slot: int32 [n],
+ * slot[nodes[r]] = r and -1 elsewhere, or NULL when every node is its own target row.  thr, cnt, seed: the forward's; an
+ * all-ones thr_i skips the hash.  dx [n, F] at lddx >= F: EVERY row OVERWRITTEN (no zero-fill needed).  dy at lddy >= F
+ * (2F under concat).  One launch, no atomics, a second run gives the same bits. */
+int dp_csr_sample_mean_bwd(const float* dy, int lddy, const int* indptr_t, const int* indices_t, const int* slot,
+                           const unsigned long long* thr, const int* cnt, float* dx, int lddx, int n, int F,
+                           int self_mode, long seed, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
