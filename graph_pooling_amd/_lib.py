@@ -114,6 +114,10 @@ CSR_GAT_CONV_MAX_WIDTH = 512
 CSR_SAMPLE_PLAN_INTS = 8
 CSR_SAMPLE_ALL, CSR_SAMPLE_MAX_K = 0, 64
 CSR_SAMPLE_SELF = {"none": 0, "gcn": 1, "concat": 2}      # DP_CSR_SAMPLE_SELF_*
+# dp_csr_topk_plan: (threads of the select workgroup, tier of a graph of n_b nodes keeping k_b (0 all kept / 1 keys in
+# registers / 2 keys recomputed), its keys per thread, its radix passes, the chunks of its prefix count, workgroups of the
+# select, of an induce count / fill launch, chunks of the scan, workgroups of the gather forward, of the backward)
+CSR_TOPK_PLAN_INTS = 10
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -303,6 +307,14 @@ _PROTOS = {
     "dp_csr_sample_mean_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "dp_csr_sample_mean_fwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _L, _P]),
     "dp_csr_sample_mean_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _P]),
+    # top-k (gPool / SAGPool) pooling: select + renumber, the induced CSR, gather * gate (node_off_host / kb_host are host
+    # pointers, passed as addresses)
+    "dp_csr_topk_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "dp_csr_topk_workspace_bytes": (_Z, [_I]),
+    "dp_csr_topk_select": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dp_csr_topk_induce": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "dp_csr_topk_gather_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dp_csr_topk_gather_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -1,13 +1,14 @@
 """The per-op layer: one autograd wrapper per dp_*_fwd / dp_*_bwd pair of libdiffpool_hip.so that the package calls
 outside the whole-model entries (dp_encoder_* / dp_loss_*, encoders.py), each exposed as a plain function.
 
-Sits below `encoders`, `sparse` and `graphsage`: it imports only `_lib` and torch.  Every wrapper makes its inputs
+Sits below `encoders`, `sparse` and `graphsage`: it imports only `_lib`, numpy and torch.  Every wrapper makes its inputs
 contiguous, allocates the outputs and the workspace the C entry asks for, and keeps for the backward what the forward
 wrote (the workspace included, where the backward entry reads it).  No torch arithmetic, no CPU path.  Line numbers
 cite the reference's encoders.py.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1436,3 +1437,150 @@ def csr_sample_mean(x, graph, num_sample, seed, nodes=None, self_mode="none", no
     container with 'none' (and a call without target rows or columns) returns zeros without a launch and without an
     autograd node.  Not for hipGraph capture: the seed is a kernel argument and would be frozen."""
     return csr_sample_mean_stats(x, graph, num_sample, seed, nodes, self_mode, nodes_checked)[0]
+
+
+# ----------------------------------------------------------------------------- top-k pooling (DESIGN §4.11)
+class _CsrTopkGatherFn(torch.autograd.Function):
+    """x_out = x[perm] * gate[perm] and its gradients to x and gate (dp_csr_topk_gather_fwd / _bwd): one launch each."""
+
+    @staticmethod
+    def forward(ctx, x, gate, perm, new_id):
+        lib = _lib.load()
+        x = x.contiguous().float()
+        gate = None if gate is None else gate.contiguous().float()
+        n, feat = x.shape
+        y = _f32(x, perm.numel(), feat)
+        _call(lib, "dp_csr_topk_gather_fwd", x.data_ptr(), feat, _lib.ptr(gate), perm.data_ptr(), y.data_ptr(), feat, n,
+              perm.numel(), feat, _lib.current_stream())
+        ctx.save_for_backward(*((x, gate) if gate is not None else ()))
+        ctx.new_id, ctx.shape, ctx.n_out = new_id, (n, feat), perm.numel()
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        n, feat = ctx.shape
+        x, gate = ctx.saved_tensors if ctx.saved_tensors else (None, None)
+        dy = dy.contiguous()
+        dx = _f32(dy, n, feat)
+        want_dgate = gate is not None and ctx.needs_input_grad[1]
+        dgate = (_f32(dy, n) if feat else torch.zeros(n, device=dy.device)) if want_dgate else None
+        _call(lib, "dp_csr_topk_gather_bwd", dy.data_ptr(), feat, _lib.ptr(x) if want_dgate else None, feat, _lib.ptr(gate),
+              ctx.new_id.data_ptr(), dx.data_ptr(), feat, _lib.ptr(dgate), n, ctx.n_out, feat, _lib.current_stream())
+        return dx, dgate, None, None
+
+
+def topk_counts(num_nodes, ratio=None, k=None):
+    """The kept count of every graph, on the host: k_b = min(n_b, max(1, ceil(float64(ratio) * n_b))) for 0 < ratio <= 1,
+    or min(k, n_b) for an integer k >= 1 — exactly one of the two — as int64 [B]."""
+    if (ratio is None) == (k is None):
+        raise ValueError("csr_topk_pool: give exactly one of ratio and k")
+    nn = np.asarray(num_nodes, dtype=np.int64).reshape(-1)
+    if k is not None:
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+            raise ValueError(f"csr_topk_pool: k must be an integer >= 1, got {k!r}")
+        return np.minimum(k, nn)
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < float(ratio) <= 1.0:
+        raise ValueError(f"csr_topk_pool: ratio must lie in (0, 1], got {ratio!r}")
+    kb = np.ceil(np.float64(ratio) * nn.astype(np.float64)).astype(np.int64)
+    return np.minimum(nn, np.maximum(1, kb))
+
+
+def csr_topk_pool_stats(x, score, graph, ratio=None, k=None, gate=None):
+    """`csr_topk_pool` with what it computes on the way: (x_out, graph_out, perm, new_id int32 [n] (-1: dropped), thr
+    int64 [B] (the bits of every graph's threshold key; 0 where everything is kept), edge_map int32 [nnz'], edge_map_t
+    (the same tensor for an undirected container)).  All but x_out are data."""
+    batch = hasattr(graph, "indices_local")
+    sizes = np.asarray(graph.num_nodes if batch else [graph.n], dtype=np.int64)
+    kb = topk_counts(sizes, ratio, k)
+    n = graph.n
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != n:
+        got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"csr_topk_pool: expected x [n, F] with n = {n}, got {got}")
+    for name, t in (("score", score), ("gate", gate)):
+        if t is None and name == "gate":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n:
+            got = (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"csr_topk_pool: {name} must be a float32 tensor [n] with n = {n}, got {got}")
+    if n == 0:
+        raise ValueError("csr_topk_pool: the container has no node")
+    _lib.require_gpu_tensor(x, "x")
+    _lib.require_gpu_tensor(score, "score")
+    _lib.require_gpu_tensor(graph.indptr, "the container's index arrays")
+    if gate is not None:
+        _lib.require_gpu_tensor(gate, "gate")
+    lib = _lib.load()
+    dev, stream = x.device, _lib.current_stream()
+    nb, n_out = int(sizes.size), int(kb.sum())
+    node_off_host = np.ascontiguousarray(graph.node_off_host, dtype=np.int32)
+    kb_host = np.ascontiguousarray(kb, dtype=np.int32)
+    new_off_host = np.concatenate([[0], np.cumsum(kb)]).astype(np.int32)
+    new_off = torch.from_numpy(new_off_host).to(dev)
+    i32 = lambda m: torch.empty(m, device=dev, dtype=torch.int32)
+    new_id, perm, thr = i32(n), i32(n_out), torch.empty(nb, device=dev, dtype=torch.int64)
+    sc = score.detach().contiguous()
+    _call(lib, "dp_csr_topk_select", sc.data_ptr(), graph.node_off.data_ptr(), new_off.data_ptr(),
+          node_off_host.ctypes.data, kb_host.ctypes.data, new_id.data_ptr(), perm.data_ptr(), thr.data_ptr(), n, n_out, nb,
+          stream)
+    wsb = lib.dp_csr_topk_workspace_bytes(n_out)
+    ws = _workspace(wsb, x)
+
+    def induce(indptr, indices):
+        nnz = indices.numel()                                   # the stored entries, or the pad of an edgeless batch
+        cap = max(nnz, 1)
+        ip, ix, em = i32(n_out + 1), i32(cap), i32(cap)
+        il = i32(cap) if batch else None
+        _call(lib, "dp_csr_topk_induce", indptr.data_ptr(), (indices if nnz else indptr).data_ptr(), new_id.data_ptr(),
+              perm.data_ptr(), new_off.data_ptr(), ip.data_ptr(), ix.data_ptr(), _lib.ptr(il), em.data_ptr(), n, n_out, nb,
+              nnz, cap, ws.data_ptr(), wsb, stream)
+        return ip, ix, il, em
+
+    directed = graph.indices_t is not graph.indices
+    fwd = induce(graph.indptr, graph.indices)
+    bwd = induce(graph.indptr_t, graph.indices_t) if directed else None
+
+    def narrowed(arrs):
+        ip, ix, il, em = arrs
+        m = int(ip[-1])                                         # the one read-back of this direction
+        keep = max(m, 1) if batch else m                        # an edgeless batch keeps its one-element pad
+        return m, ip, ix[:keep], None if il is None else il[:keep], em[:m]
+
+    nnz_out, ip, ix, il, em = narrowed(fwd)
+    ipt = ixt = ilt = None
+    em_t = em
+    if directed:
+        _, ipt, ixt, ilt, em_t = narrowed(bwd)
+    values = values_t = None
+    if graph.weighted:
+        def picked(v, m):
+            if m.numel() == 0 and batch:
+                return torch.zeros(1, device=dev, dtype=torch.float32)
+            return v[m.long()]
+        values = picked(graph.values, em)
+        values_t = picked(graph.values_t.detach(), em_t) if directed else None
+    if batch:
+        pad_to = int(topk_counts([graph.pad_to], ratio, k)[0])
+        out = type(graph).from_device_csr(kb, ip, ix, il, ipt, ixt, ilt, values, values_t, pad_to=pad_to, nnz=nnz_out,
+                                          node_off=new_off)
+    else:
+        out = type(graph).from_device_csr(n_out, ip, ix, ipt, ixt, values, values_t, nnz=nnz_out)
+    x_out = _CsrTopkGatherFn.apply(x, gate, perm, new_id)
+    return x_out, out, perm, new_id, thr, em, em_t
+
+
+def csr_topk_pool(x, score, graph, ratio=None, k=None, gate=None):
+    """Top-k pooling (gPool of Graph U-Nets; SAGPool when the score comes from a GraphConv) on a CsrGraph / CsrBatch:
+    (x_out, graph_out, perm) with the k_b best-scored nodes of every graph kept — `topk_counts`: ceil(ratio * n_b), or
+    min(k, n_b) — `graph_out` the induced subgraph A[perm][:, perm] as a container of the input's class, built on the
+    device, and perm int32 [n'] the old global id of every new row.
+
+    x fp32 [n, F], score fp32 [n], gate fp32 [n] or None.  Node i beats node j of its graph when score_i > score_j, or
+    on equal scores when i < j; -0.0 ties with +0.0, a positive NaN ranks above +inf and a negative one below -inf, so
+    exactly k_b nodes are kept whatever the scores hold.  The kept nodes keep their relative order (ascending old id),
+    so rows stay sorted and an undirected container stays undirected.  x_out[r] = x[perm[r]] * gate[perm[r]] (one fp32
+    multiply; a copy without gate) with gradients to x and to gate — `score` gets none through the selection; pass
+    gate = tanh(score) for gPool's.  A weighted container's values' = values[edge_map] by torch indexing, so values with
+    autograd history (`with_values`) receive their gradient.  The host reads back 4 bytes (nnz') per call, 8 for a
+    directed container; 5 launches forward (8 directed), 1 backward, whatever B and n.  Not for hipGraph capture."""
+    return csr_topk_pool_stats(x, score, graph, ratio, k, gate)[:3]

@@ -40,6 +40,10 @@ behind a CsrGraph.
 
 `SageConv` / `SageEncoder` are GraphSAGE's mean-aggregator layer and the encoder `SupervisedGraphSage` expects, on either
 container, with the neighbour sample drawn on the device in the launch that takes its mean (dp_csr_sample_mean_*).
+
+`TopKPooling` is the hard pooling next to DiffPool's soft one (gPool / SAGPool): it keeps the best-scored nodes of every
+graph and returns the induced subgraph as a container of the input's class, built on the device (dp_csr_topk_*) and
+wrapped by `CsrGraph.from_device_csr` / `CsrBatch.from_device_csr`, so it feeds everything above.
 """
 from __future__ import annotations
 
@@ -332,6 +336,30 @@ class CsrGraph:
         return CsrGraph(*(None if a is None else torch.from_numpy(a).to(device) for a in h))
 
     @staticmethod
+    def from_device_csr(n, indptr, indices, indptr_t=None, indices_t=None, values=None, values_t=None, nnz=None):
+        """One graph from index arrays that already live on a device (`ops.csr_topk_pool` builds them there): int32
+        `indptr` [n + 1] and `indices` (ascending and unique in a row), the transposed pair for a directed graph, `values`
+        / `values_t` beside them for a weighted one.  Nothing is read back and nothing is checked beyond shapes, dtypes
+        and devices.  `nnz`: the stored entries when the caller knows them (it fills the `nnz` cache)."""
+        if (indptr_t is None) != (indices_t is None):
+            raise ValueError("CsrGraph.from_device_csr: indptr_t and indices_t come together")
+        for name, t in (("indptr", indptr), ("indices", indices), ("indptr_t", indptr_t), ("indices_t", indices_t)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f"CsrGraph.from_device_csr: {name} must be a contiguous 1-d int32 tensor")
+            if t.device != indptr.device:
+                raise ValueError(f"CsrGraph.from_device_csr: {name} is on {t.device}, indptr on {indptr.device}")
+            if name.startswith("indptr") and t.numel() != int(n) + 1:
+                raise ValueError(f"CsrGraph.from_device_csr: {name} must hold n + 1 = {int(n) + 1} offsets, got {t.numel()}")
+        if nnz is not None and int(nnz) != indices.numel():
+            raise ValueError(f"CsrGraph.from_device_csr: nnz = {nnz} but indices holds {indices.numel()} entries")
+        g = CsrGraph(indptr, indices, indptr_t, indices_t, values, values_t)
+        if nnz is not None:
+            g.__dict__["nnz"] = int(nnz)
+        return g
+
+    @staticmethod
     def from_dense(adj, weighted=False):
         """[n, n] tensor (any device) -> CSR on adj's device (testing aid); weighted=True keeps the nonzero values."""
         a = adj.detach().cpu().numpy()
@@ -396,24 +424,7 @@ class CsrBatch:
         """`parts`: per graph a `HostCsr`, or a plain (indptr, indices, indptr_t, indices_t[, values, values_t]): host
         arrays with graph-local columns, the transposed pair None for an undirected graph; values (float, one per stored
         entry; values_t next to a transposed pair) or None / absent for a 0/1 graph.  Use the from_* constructors."""
-        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
-        if sizes.size == 0:
-            raise ValueError("CsrBatch: no graph")
-        if (sizes < 1).any():
-            raise ValueError(f"CsrBatch: every graph needs at least one node, got sizes {sizes.tolist()}")
-        if len(parts) != sizes.size:
-            raise ValueError(f"CsrBatch: {sizes.size} sizes but {len(parts)} graphs")
-        if int(sizes.sum()) >= 2 ** 31:
-            raise ValueError("CsrBatch: more than 2^31 - 1 nodes in one batch")
-        self.num_graphs = int(sizes.size)
-        self.num_nodes = sizes.astype(np.int64)
-        self.max_n = int(sizes.max())
-        self.pad_to = self.max_n if pad_to is None else int(pad_to)
-        if self.pad_to < self.max_n:
-            raise ValueError(f"CsrBatch: pad_to = {self.pad_to} is below the largest graph ({self.max_n} nodes)")
-        self.node_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-        self.n_total = self.n = int(self.node_off_host[-1])
-        self.device = torch.device(device)
+        sizes = self._init_sizes(sizes, len(parts), device, pad_to)
         parts = [p if isinstance(p, HostCsr) else HostCsr(*p) for p in parts]
         directed = any(p.indptr_t is not None for p in parts)
         self.weighted = any(p.values is not None for p in parts)
@@ -461,7 +472,37 @@ class CsrBatch:
         else:
             self.indptr_t, self.indices_t, self.indices_t_local = self.indptr, self.indices, self.indices_local
             self.values_t = self.values
-        self.node_off = torch.from_numpy(self.node_off_host).to(self.device)
+        self._init_tables()
+
+    def _init_sizes(self, sizes, n_parts, device, pad_to):
+        """The checks and host numbers every constructor starts with -> sizes as int64 [B].  `n_parts`: how many graphs
+        the caller brought (None: it brings device arrays of the whole batch)."""
+        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+        if sizes.size == 0:
+            raise ValueError("CsrBatch: no graph")
+        if (sizes < 1).any():
+            raise ValueError(f"CsrBatch: every graph needs at least one node, got sizes {sizes.tolist()}")
+        if n_parts is not None and n_parts != sizes.size:
+            raise ValueError(f"CsrBatch: {sizes.size} sizes but {n_parts} graphs")
+        if int(sizes.sum()) >= 2 ** 31:
+            raise ValueError("CsrBatch: more than 2^31 - 1 nodes in one batch")
+        self.num_graphs = int(sizes.size)
+        self.num_nodes = sizes.astype(np.int64)
+        self.max_n = int(sizes.max())
+        self.pad_to = self.max_n if pad_to is None else int(pad_to)
+        if self.pad_to < self.max_n:
+            raise ValueError(f"CsrBatch: pad_to = {self.pad_to} is below the largest graph ({self.max_n} nodes)")
+        self.node_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        self.n_total = self.n = int(self.node_off_host[-1])
+        self.device = torch.device(device)
+        return sizes
+
+    def _init_tables(self, node_off=None):
+        """The host-made tables of the kernels, from the sizes alone: `node_off`, the size order and owner counts of the
+        node-index BatchNorm, the floor flags, the row chunks of the segmented max, the pool-plan cache.  `node_off`: the
+        offsets when the caller already has them on the device."""
+        sizes = self.num_nodes
+        self.node_off = torch.from_numpy(self.node_off_host).to(self.device) if node_off is None else node_off
         # node-index BatchNorm: graphs by size, largest first; cnt[i] = graphs with n_b > i
         order = np.argsort(-sizes, kind="stable")
         asc = np.sort(sizes)
@@ -569,6 +610,65 @@ class CsrBatch:
             raise ValueError("CsrBatch.from_edge_lists: sizes, srcs, dsts (and weights) must have one entry per graph")
         parts = [_host_csr(int(n), src, dst, symmetric, w) for n, src, dst, w in zip(sizes, srcs, dsts, weights)]
         return CsrBatch(sizes, parts, device, pad_to=pad_to)
+
+    @staticmethod
+    def from_device_csr(sizes, indptr, indices, indices_local, indptr_t=None, indices_t=None, indices_t_local=None,
+                        values=None, values_t=None, pad_to=None, nnz=None, node_off=None):
+        """A batch from index arrays that already live on a device (`ops.csr_topk_pool` builds them there) plus the host
+        sizes: the block-diagonal CSR as the class stores it — int32 `indptr` [n_total + 1], `indices` (GLOBAL columns,
+        ascending and unique in a row, inside the row's graph), `indices_local` (minus the graph's offset), an edgeless
+        batch padded to one element — and, for a directed batch, the transposed trio; `values` / `values_t` beside them
+        for a weighted one.  Nothing is read back and nothing is checked beyond shapes, dtypes and devices: the arrays
+        are trusted as the kernels' own output is.  `nnz`: the stored entries when the caller knows them (it fills the
+        `nnz` cache); `node_off`: int32 [B + 1] on the device when the caller has it.  Every host table is made from
+        `sizes` exactly as the other constructors make it."""
+        self = CsrBatch.__new__(CsrBatch)
+        self._init_sizes(sizes, None, indptr.device, pad_to)
+        trios = [("indptr", indptr, "indices", indices, "indices_local", indices_local)]
+        if (indptr_t is None) != (indices_t is None) or (indptr_t is None) != (indices_t_local is None):
+            raise ValueError("CsrBatch.from_device_csr: indptr_t, indices_t and indices_t_local come together")
+        if indptr_t is not None:
+            trios.append(("indptr_t", indptr_t, "indices_t", indices_t, "indices_t_local", indices_t_local))
+        for pn, ip, gn, ix, ln, il in trios:
+            for name, t in ((pn, ip), (gn, ix), (ln, il)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                    raise ValueError(f"CsrBatch.from_device_csr: {name} must be a contiguous 1-d int32 tensor")
+                if t.device != indptr.device:
+                    raise ValueError(f"CsrBatch.from_device_csr: {name} is on {t.device}, indptr on {indptr.device}")
+            if ip.numel() != self.n_total + 1:
+                raise ValueError(f"CsrBatch.from_device_csr: {pn} must hold n_total + 1 = {self.n_total + 1} offsets, got "
+                                 f"{ip.numel()}")
+            if ix.numel() != il.numel() or ix.numel() < 1:
+                raise ValueError(f"CsrBatch.from_device_csr: {gn} and {ln} must hold the same entries, one at least (an "
+                                 f"edgeless batch keeps a one-element pad), got {ix.numel()} and {il.numel()}")
+        if nnz is not None and not (int(nnz) == indices.numel() or (int(nnz) == 0 and indices.numel() == 1)):
+            raise ValueError(f"CsrBatch.from_device_csr: nnz = {nnz} but indices holds {indices.numel()} entries")
+        self.indptr, self.indices, self.indices_local = indptr, indices, indices_local
+        self.weighted = values is not None
+        self.values = self.values_t = None
+        if values is None and values_t is not None:
+            raise ValueError("CsrBatch.from_device_csr: values_t without values")
+        if values is not None:
+            self.values = _check_values(values, indices, "CsrBatch.from_device_csr: values")
+        if indptr_t is None:
+            if values_t is not None and values_t is not values:
+                raise ValueError("CsrBatch.from_device_csr: an undirected batch stores a_ij = a_ji: values_t must be "
+                                 "values or None")
+            self.indptr_t, self.indices_t, self.indices_t_local = indptr, indices, indices_local
+            self.values_t = self.values
+        else:
+            self.indptr_t, self.indices_t, self.indices_t_local = indptr_t, indices_t, indices_t_local
+            if self.weighted:
+                if values_t is None:
+                    raise ValueError("CsrBatch.from_device_csr: a weighted batch with a transposed CSR needs values_t")
+                self.values_t = _check_values(values_t, indices_t, "CsrBatch.from_device_csr: values_t")
+        if node_off is not None and (node_off.dtype != torch.int32 or node_off.numel() != self.num_graphs + 1
+                                     or node_off.device != indptr.device):
+            raise ValueError("CsrBatch.from_device_csr: node_off must be int32 [B + 1] on the arrays' device")
+        self._init_tables(node_off)
+        if nnz is not None:
+            self.__dict__["nnz"] = int(nnz)
+        return self
 
     def normalized(self):
         """A new weighted batch holding D^-1/2 A D^-1/2 of every graph (`CsrGraph.normalized`: column sums of the stored
@@ -1189,3 +1289,48 @@ class SageEncoder(torch.nn.Module):
         ids = ops.check_target_nodes("SageEncoder", nodes, self.graph.n)
         dev = self.graph.indptr.device
         return self.conv(self._x(), self.graph, ids.to(device=dev, dtype=torch.int32), seed, nodes_checked=True)
+
+
+# ----------------------------------------------------------------------------- top-k pooling
+class TopKPooling(torch.nn.Module):
+    """Hard top-k pooling on a CsrGraph / CsrBatch: forward(x, graph) -> (x', graph', perm) keeps the
+    ceil(ratio * n_b) best-scored nodes of every graph (`ops.csr_topk_pool`), gates their features with tanh(score) and
+    returns the induced subgraph as a container of the input's class, so layers stack to any depth at O(n + nnz).
+
+    score="proj": gPool of Graph U-Nets, s = x . p / ||p|| with a learned p [input_dim] (on `hip_linear`).
+    score="gcn": SAGPool, s = (A x + x) W + b with W [input_dim, 1] on `ops.csr_graph_conv` (the container's stored
+    values weigh the sum; pass a `normalized()` container for the usual D^-1/2 A D^-1/2).
+    The selection itself passes no gradient; the score trains through the gate.  perm int32 [n'] holds the old global id
+    of every new row, in ascending order within a graph.  Not on this path: `min_score`, unpooling, hipGraph capture."""
+
+    def __init__(self, input_dim, ratio=0.5, score="proj"):
+        super().__init__()
+        if not isinstance(input_dim, int) or isinstance(input_dim, bool) or input_dim < 1:
+            raise ValueError(f"TopKPooling: input_dim must be a positive integer, got {input_dim!r}")
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < float(ratio) <= 1.0:
+            raise ValueError(f"TopKPooling: ratio must lie in (0, 1], got {ratio!r}")
+        if score not in ("proj", "gcn"):
+            raise ValueError(f"TopKPooling: score must be 'proj' or 'gcn', got {score!r}")
+        self.input_dim, self.ratio, self.score = input_dim, float(ratio), score
+        if score == "proj":
+            self.p = torch.nn.Parameter(torch.empty(input_dim))
+            bound = float(input_dim) ** -0.5
+            torch.nn.init.uniform_(self.p, -bound, bound)
+        else:
+            self.weight = torch.nn.Parameter(torch.empty(input_dim, 1))
+            torch.nn.init.xavier_uniform_(self.weight)
+            self.bias = torch.nn.Parameter(torch.zeros(1))
+
+    def scores(self, x, graph):
+        """The score of every node, fp32 [n], with autograd history."""
+        if self.score == "proj":
+            return hip_linear(x, (self.p / self.p.norm()).view(1, -1)).view(-1)
+        return ops.csr_graph_conv(x, self.weight, self.bias, graph, _lib.F_ADD_SELF).view(-1)
+
+    def forward(self, x, graph):
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError(f"TopKPooling.forward(x, graph: CsrGraph or CsrBatch), got {type(graph).__name__}")
+        _check_node_rows(graph, x, self.input_dim)
+        x = x.contiguous().float()
+        s = self.scores(x, graph)
+        return ops.csr_topk_pool(x, s, graph, ratio=self.ratio, gate=torch.tanh(s))

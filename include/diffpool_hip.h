@@ -1286,6 +1286,55 @@ int dp_csr_sample_mean_bwd(const float* dy, int lddy, const int* indptr_t, const
                            const unsigned long long* thr, const int* cnt, float* dx, int lddx, int n, int F,
                            int self_mode, long seed, void* stream);
 
+/* ------------------------------------------------------------------ N9  top-k (gPool / SAGPool) pooling on CSR
+ * (DESIGN §4.11): keep the k_b best-scored nodes of every graph of a CsrGraph / CsrBatch, gate their features and build
+ * the induced subgraph A' = A[perm][:, perm] as CSR on the device.  Graph b owns rows node_off[b] .. node_off[b+1]-1 and,
+ * pooled, rows new_off[b] .. new_off[b+1]-1 with new_off[b+1] - new_off[b] = k_b, 1 <= k_b <= n_b, decided by the host.
+ *     key_i = (ord(score_i) << 32) | (0xffffffff - local_i);  ord(bits) = ~bits for a set sign bit, bits | 0x80000000
+ *             otherwise, after -0.0 is made +0.0 — every bit pattern has a place (a positive NaN above +inf, a negative
+ *             one below -inf), so no score can send the selection out of bounds
+ *     thr_b = the k_b-th largest key of graph b;  0 when k_b == n_b (no select: everything is kept)
+ *     kept: key_i >= thr_b, exactly k_b nodes; new rows in ASCENDING old id: new_id[i] (int32 [n], -1 dropped) and
+ *     perm[r] (int32 [n_out], the old global id of new row r)
+ * Every refusal (a NULL or misaligned pointer, an ld below its width, a negative count, k_b outside 1 .. n_b, host tables
+ * that do not add up, a capacity below the input's nnz, a workspace below the queried size) comes before any launch.
+ *
+ * dp_csr_topk_plan (host only): plan_out[DP_CSR_TOPK_PLAN_INTS] = { threads of the select workgroup (64 * ceil(max_n /
+ * 256), 64 .. 1024), the tier of a graph of n_b nodes keeping k_b (0: k_b == n_b, no select; 1: at most 4 keys per
+ * thread, held in registers; 2: the keys recomputed from score on every pass), its keys per thread (0 in tier 0), its
+ * radix passes (4 for the score word + one per byte of n_b - 1; 0 in tier 0), the chunks of its prefix count, the
+ * workgroups of the select (B), of an induce count / fill launch (32 kept rows each), the chunks of the one-workgroup
+ * scan, the workgroups of the gather forward and of the backward (4 rows each) }, answered by the functions the
+ * launchers and the kernels act on. */
+#define DP_CSR_TOPK_PLAN_INTS 10
+int dp_csr_topk_plan(int n, int n_out, int B, int max_n, int n_b, int k_b, int F, int* plan_out);
+/* Workspace of dp_csr_topk_induce for n_out kept rows (one int per 32 rows, and the total). */
+size_t dp_csr_topk_workspace_bytes(int n_out);
+/* Select + renumber, ONE launch, one workgroup per graph.  score fp32 [n]; node_off / new_off int32 [B + 1] on the
+ * DEVICE, node_off_host [B + 1] / kb_host [B] the same numbers on the HOST (checked here: 0 .. n, k_b in 1 .. n_b, the
+ * k_b summing to n_out).  new_id [n], perm [n_out], thr [B] (8-byte aligned) OVERWRITTEN. */
+int dp_csr_topk_select(const float* score, const int* node_off, const int* new_off, const int* node_off_host,
+                       const int* kb_host, int* new_id, int* perm, unsigned long long* thr, int n, int n_out, int B,
+                       void* stream);
+/* The induced CSR of one direction, THREE launches (count per 32 kept rows; one workgroup scans the sums; recount,
+ * offset and fill): indptr_out [n_out + 1], and for each kept entry, in stored order, indices_out (new GLOBAL column),
+ * indices_local_out (minus new_off of the row's graph; NULL for a single graph: new_off and B are then not read) and
+ * edge_map (its old position).  The three arrays hold `cap` entries, cap >= nnz = the entries of `indices`; the kept
+ * count arrives in indptr_out[n_out].  A transposed CSR of its own takes a second call on indptr_t / indices_t. */
+int dp_csr_topk_induce(const int* indptr, const int* indices, const int* new_id, const int* perm, const int* new_off,
+                       int* indptr_out, int* indices_out, int* indices_local_out, int* edge_map, int n, int n_out, int B,
+                       int nnz, int cap, void* workspace, size_t workspace_bytes, void* stream);
+/* y[r] = x[perm[r]] * gate[perm[r]] (one fp32 multiply; gate NULL: a copy), y [n_out, F] at ldy OVERWRITTEN.  One
+ * launch; n_out == 0 or F == 0 returns without one. */
+int dp_csr_topk_gather_fwd(const float* x, int ldx, const float* gate, const int* perm, float* y, int ldy, int n, int n_out,
+                           int F, void* stream);
+/* dx[i] = dy[new_id[i]] * gate[i] and dgate[i] = sum_f dy[new_id[i], f] x[i, f] for a kept node, zeros for a dropped one:
+ * EVERY row of dx [n, F] and dgate [n] OVERWRITTEN (no zero-fill, no atomics).  dgate: a lane sums its columns f = lane,
+ * lane + 64, .. in one fma chain, then a butterfly over the 64 lanes — ceil(F / 64) + 6 roundings.  gate NULL: dx is the
+ * scattered copy and dgate must be NULL; dgate NULL: x is not read.  One launch; n == 0 or F == 0 returns without one. */
+int dp_csr_topk_gather_bwd(const float* dy, int lddy, const float* x, int ldx, const float* gate, const int* new_id,
+                           float* dx, int lddx, float* dgate, int n, int n_out, int F, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
