@@ -1,7 +1,7 @@
 """The per-op layer: one autograd wrapper per dp_*_fwd / dp_*_bwd pair of libdiffpool_hip.so that the package calls
 outside the whole-model entries (dp_encoder_* / dp_loss_*, encoders.py), each exposed as a plain function.
 
-Sits below `encoders`, `sparse` and `graphsage`: it imports only `_lib`, numpy and torch.  Every wrapper makes its inputs
+Sits below `encoders`, `csr`, `sparse` and `graphsage`: it imports only `_lib`, numpy and torch.  Every wrapper makes its inputs
 contiguous, allocates the outputs and the workspace the C entry asks for, and keeps for the backward what the forward
 wrote (the workspace included, where the backward entry reads it).  No torch arithmetic, no CPU path.  Line numbers
 cite the reference's encoders.py.
@@ -139,11 +139,41 @@ def _csr_args(g, local=False, null_t=False):
     entry when `g` stores values.  `local`: the graph-local index arrays of a CsrBatch (link loss).  `null_t`: NULL for
     the transposed group of an undirected container (the Frobenius entries then skip the A^T S gather)."""
     ix, ix_t = (g.indices_local, g.indices_t_local) if local else (g.indices, g.indices_t)
-    null = null_t and g.indptr_t is g.indptr and g.indices_t is g.indices
+    null = null_t and g.undirected
     if _weighted(g):
         return ("_w", (g.indptr.data_ptr(), ix.data_ptr(), g.values.data_ptr()),
                 (None, None, None) if null else (g.indptr_t.data_ptr(), ix_t.data_ptr(), g.values_t.data_ptr()))
     return "", (g.indptr.data_ptr(), ix.data_ptr()), (None, None) if null else (g.indptr_t.data_ptr(), ix_t.data_ptr())
+
+
+def _csr_index_args(g, mirror=None):
+    """`_csr_args` for the entries that read no stored values: ((indptr, indices), (indptr_t, indices_t[, mirror_perm])) as
+    device pointers, no suffix.  An edgeless CsrGraph has empty `indices`: `indptr` goes in their place — never read, never
+    NULL (an edgeless CsrBatch keeps a one-element pad).  `mirror`: 'always' appends the container's `mirror_perm`
+    (built on first use), 'own' NULL for an undirected container, whose own order serves as the transposed one."""
+    ix = g.indices if g.indices.numel() else g.indptr
+    ix_t = g.indices_t if g.indices_t.numel() else g.indptr_t
+    at = (g.indptr_t.data_ptr(), ix_t.data_ptr())
+    if mirror is not None:
+        at += (None if mirror == "own" and g.undirected else g.mirror_perm.data_ptr(),)
+    return (g.indptr.data_ptr(), ix.data_ptr()), at
+
+
+def check_rows(who, graph, name, t, cols=None):
+    """`t` is a tensor [n, cols] with n = graph.n, else ValueError.  `who` opens the message ('csr_sddmm: ', or '');
+    cols None: the rows as the container words them (`graph.rows()`)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
+        got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+        want = graph.rows() if cols is None else f"[n, {cols}] with n = {graph.n}"
+        raise ValueError(f"{who}expected {name} {want}, got {got}")
+
+
+def finite_slope(who, negative_slope):
+    """A leaky-ReLU slope as a finite float, else ValueError."""
+    slope = float(negative_slope)
+    if slope != slope or slope in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: negative_slope must be finite, got {negative_slope!r}")
+    return slope
 
 
 def _call(lib, name, *args):
@@ -167,8 +197,8 @@ def _link_dvalues(lib, s, g, objective, dloss):
     dv = torch.empty_like(g.values)
     sizes = g.node_off_host.astype("int64")
     inv_norm = 1.0 / float(((sizes[1:] - sizes[:-1]) ** 2).sum())
-    _call(lib, "dp_csr_link_dvalues", s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(), g.values.data_ptr(),
-          dv.data_ptr(), n, k, objective, inv_norm, dloss.data_ptr(), _lib.current_stream())
+    _call(lib, "dp_csr_link_dvalues", s.data_ptr(), k, *_csr_args(g)[1], dv.data_ptr(), n, k, objective, inv_norm,
+          dloss.data_ptr(), _lib.current_stream())
     return dv
 
 
@@ -176,11 +206,10 @@ def _pool_dvalues(lib, s, g, dap):
     """dvalues of A' = S^T A S for the gradient dap [B, k, k] ([k, k] for one graph): dp_csr_pool_dvalues."""
     n, k = s.shape
     dv = torch.empty_like(g.values)
-    batch = hasattr(g, "indices_local")
     wsb = lib.dp_csr_pool_dvalues_workspace_bytes(n, k)
     ws = _workspace(wsb, s)
-    _call(lib, "dp_csr_pool_dvalues", s.data_ptr(), k, g.indptr.data_ptr(), g.indices.data_ptr(), dap.data_ptr(),
-          g.node_off_host.ctypes.data if batch else None, g.num_graphs, dv.data_ptr(), n, k, ws.data_ptr(), wsb,
+    _call(lib, "dp_csr_pool_dvalues", s.data_ptr(), k, *_csr_args(g)[1][:2], dap.data_ptr(),
+          g.node_off_host.ctypes.data if g.is_batch else None, g.num_graphs, dv.data_ptr(), n, k, ws.data_ptr(), wsb,
           _lib.current_stream())
     return dv
 
@@ -355,35 +384,54 @@ def assign_softmax(z, weight, bias):
 
 
 class _CsrPoolFn(torch.autograd.Function):
+    """One node for both containers: a CsrGraph takes dp_csr_pool_*, a CsrBatch dp_csr_pool_batch_* on its slab tables
+    (`CsrBatch.pool_plan`)."""
+
     @staticmethod
     def forward(ctx, s, z, g, vals=None):
         lib = _lib.load()
         s, z = s.contiguous(), z.contiguous()
         n, k = s.shape
         d = z.shape[1]
-        xp, ap = _f32(s, k, d), _f32(s, k, k)
-        wsb = lib.dp_csr_pool_workspace_bytes(n, k, d)
-        ws = _workspace(wsb, s)
         sfx, a, _ = _csr_args(g)
-        _call(lib, "dp_csr_pool_fwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, xp.data_ptr(), ap.data_ptr(), n, k, d,
-              ws.data_ptr(), wsb, _lib.current_stream())
+        head = (s.data_ptr(), k, z.data_ptr(), d, *a)
+        if g.is_batch:
+            b, plan = g.num_graphs, g.pool_plan(k, d)
+            xp, ap = _f32(s, b, k, d), _f32(s, b, k, k)
+            wsb = lib.dp_csr_pool_batch_workspace_bytes(plan.n_slabs, b, k, d)
+            ws = _workspace(wsb, s)
+            _call(lib, "dp_csr_pool_batch_fwd" + sfx, *head, plan.fwd_tab.data_ptr(), plan.slab_off.data_ptr(),
+                  plan.n_slabs, xp.data_ptr(), ap.data_ptr(), b, n, k, d, ws.data_ptr(), wsb, _lib.current_stream())
+        else:
+            plan = None
+            xp, ap = _f32(s, k, d), _f32(s, k, k)
+            wsb = lib.dp_csr_pool_workspace_bytes(n, k, d)
+            ws = _workspace(wsb, s)
+            _call(lib, "dp_csr_pool_fwd" + sfx, *head, xp.data_ptr(), ap.data_ptr(), n, k, d, ws.data_ptr(), wsb,
+                  _lib.current_stream())
         ctx.save_for_backward(s, z)
-        ctx.g, ctx.ws = g, ws
+        ctx.g, ctx.plan, ctx.ws = g, plan, ws
         return xp, ap
 
     @staticmethod
     def backward(ctx, dxp, dap):
         lib = _lib.load()
         s, z = ctx.saved_tensors
-        g = ctx.g
+        g, plan = ctx.g, ctx.plan
         n, k = s.shape
         d = z.shape[1]
         dxp, dap = dxp.contiguous(), dap.contiguous()
         ds = torch.empty_like(s)
         dz = torch.zeros_like(z)
         sfx, a, at = _csr_args(g)
-        _call(lib, "dp_csr_pool_bwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, *at, dxp.data_ptr(), dap.data_ptr(),
-              ds.data_ptr(), k, dz.data_ptr(), d, n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+        head = (s.data_ptr(), k, z.data_ptr(), d, *a, *at)
+        grads = (dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d)
+        tail = (n, k, d, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+        if g.is_batch:
+            _call(lib, "dp_csr_pool_batch_bwd" + sfx, *head, plan.bwd_tab.data_ptr(), plan.n_blocks, *grads, g.num_graphs,
+                  *tail)
+        else:
+            _call(lib, "dp_csr_pool_bwd" + sfx, *head, *grads, *tail)
         return ds, dz, None, _pool_dvalues(lib, s, g, dap) if ctx.needs_input_grad[3] else None
 
 
@@ -692,86 +740,16 @@ def segment_max_floor(z, floor, batch):
     return _SegmentMaxFloorFn.apply(z, floor, batch)
 
 
-class _CsrPoolBatchFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, s, z, batch, vals=None):
-        lib = _lib.load()
-        s, z = s.contiguous(), z.contiguous()
-        n, k = s.shape
-        d = z.shape[1]
-        b = batch.num_graphs
-        plan = batch.pool_plan(k, d)
-        xp, ap = _f32(s, b, k, d), _f32(s, b, k, k)
-        wsb = lib.dp_csr_pool_batch_workspace_bytes(plan.n_slabs, b, k, d)
-        ws = _workspace(wsb, s)
-        sfx, a, _ = _csr_args(batch)
-        _call(lib, "dp_csr_pool_batch_fwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, plan.fwd_tab.data_ptr(),
-              plan.slab_off.data_ptr(), plan.n_slabs, xp.data_ptr(), ap.data_ptr(), b, n, k, d, ws.data_ptr(), wsb,
-              _lib.current_stream())
-        ctx.save_for_backward(s, z)
-        ctx.batch, ctx.plan, ctx.ws = batch, plan, ws
-        return xp, ap
-
-    @staticmethod
-    def backward(ctx, dxp, dap):
-        lib = _lib.load()
-        s, z = ctx.saved_tensors
-        g, plan = ctx.batch, ctx.plan
-        n, k = s.shape
-        d = z.shape[1]
-        dxp, dap = dxp.contiguous(), dap.contiguous()
-        ds = torch.empty_like(s)
-        dz = torch.zeros_like(z)
-        sfx, a, at = _csr_args(g)
-        _call(lib, "dp_csr_pool_batch_bwd" + sfx, s.data_ptr(), k, z.data_ptr(), d, *a, *at, plan.bwd_tab.data_ptr(),
-              plan.n_blocks, dxp.data_ptr(), dap.data_ptr(), ds.data_ptr(), k, dz.data_ptr(), d, g.num_graphs, n, k, d,
-              ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
-        return ds, dz, None, _pool_dvalues(lib, s, g, dap) if ctx.needs_input_grad[3] else None
-
-
 def csr_pool_batch(s, z, batch):
     """`csr_pool` for every graph of a ragged batch: X' [B, k, d], A' [B, k, k] from s [n_total, k], z [n_total, d] —
     dp_csr_pool_batch_*, two launches per direction whatever B."""
-    return _CsrPoolBatchFn.apply(s, z, batch, _grad_values(batch))
-
-
-class _CsrLinkLossBatchFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, s, g, vals=None):
-        lib = _lib.load()
-        _lib.require_gpu_tensor(s, "s")
-        s = s.contiguous().float()
-        n, k = s.shape
-        off = g.node_off_host.ctypes.data
-        loss = _f32(s, ())
-        wsb = lib.dp_csr_linkpred_batch_workspace_bytes(off, g.num_graphs, k)
-        ws = _workspace(wsb, s)
-        sfx, a, _ = _csr_args(g, local=True)
-        _call(lib, "dp_csr_linkpred_batch_loss_fwd" + sfx, s.data_ptr(), k, *a, off, g.num_graphs, loss.data_ptr(), k,
-              ws.data_ptr(), wsb, _lib.current_stream())
-        ctx.save_for_backward(s)
-        ctx.g, ctx.ws = g, ws
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        lib = _lib.load()
-        (s,) = ctx.saved_tensors
-        g = ctx.g
-        n, k = s.shape
-        dloss = dloss.contiguous().float()
-        ds = torch.empty_like(s)
-        sfx, a, at = _csr_args(g, local=True)
-        _call(lib, "dp_csr_linkpred_batch_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, g.node_off_host.ctypes.data,
-              g.num_graphs, dloss.data_ptr(), ds.data_ptr(), k, 0, k, ctx.ws.data_ptr(), ctx.ws.numel(),
-              _lib.current_stream())
-        return ds, None, _link_dvalues(lib, s, g, 0, dloss) if ctx.needs_input_grad[2] else None
+    return _CsrPoolFn.apply(s, z, batch, _grad_values(batch))
 
 
 def csr_link_loss_batch(s, batch):
     """The link-prediction loss of a ragged batch, sum_b sum_{i,j < n_b} l_ij / sum_b n_b^2 (encoders.py:1326-1331), of
     s [n_total, k]: dp_csr_linkpred_batch_* (per-graph launches of the single-graph kernels, one final launch)."""
-    return _CsrLinkLossBatchFn.apply(s, batch, _grad_values(batch))
+    return _CsrLinkLossFn.apply(s, batch, _grad_values(batch))
 
 
 # ----------------------------------------------------------------------------- Set2Set on ragged rows
@@ -823,8 +801,7 @@ def set2set_ragged(emb, graph, w_ih, w_hh, b_ih, b_hh, wp, bp):
     kernels give on the batch zero-padded to `pad_to` rows (that many steps, the padded rows' zero logits in every
     softmax), on dp_set2set_ragged_*; a CsrGraph is the batch of one without padding -> [1, d].  Parameters in nn.LSTM /
     nn.Linear layout.  Under torch.no_grad() no per-step state is kept (the entry gets no save buffer)."""
-    if emb.dim() != 2 or emb.shape[0] != graph.n:
-        raise ValueError(f"set2set_ragged: expected embedding [n, d] with n = {graph.n}, got {tuple(emb.shape)}")
+    check_rows("set2set_ragged: ", graph, "embedding", emb, "d")
     keep = torch.is_grad_enabled() and any(t.requires_grad for t in (emb, w_ih, w_hh, b_ih, b_hh, wp, bp))
     return _Set2SetRaggedFn.apply(emb, graph, keep, w_ih, w_hh, b_ih, b_hh, wp, bp)
 
@@ -862,6 +839,9 @@ def cross_entropy(logits, label):
 
 
 class _CsrLinkLossFn(torch.autograd.Function):
+    """One node for both containers: a CsrGraph takes dp_csr_linkpred_loss_*, a CsrBatch dp_csr_linkpred_batch_* with its
+    graph-local columns and the host offsets in the place of n."""
+
     @staticmethod
     def forward(ctx, s, g, vals=None):
         lib = _lib.load()
@@ -869,11 +849,18 @@ class _CsrLinkLossFn(torch.autograd.Function):
         s = s.contiguous().float()
         n, k = s.shape
         loss = _f32(s, ())
-        wsb = lib.dp_csr_linkpred_workspace_bytes(n, k)
-        ws = _workspace(wsb, s)
-        sfx, a, _ = _csr_args(g)
-        _call(lib, "dp_csr_linkpred_loss_fwd" + sfx, s.data_ptr(), k, *a, loss.data_ptr(), n, k, ws.data_ptr(), wsb,
-              _lib.current_stream())
+        sfx, a, _ = _csr_args(g, local=g.is_batch)
+        if g.is_batch:
+            off = g.node_off_host.ctypes.data
+            wsb = lib.dp_csr_linkpred_batch_workspace_bytes(off, g.num_graphs, k)
+            ws = _workspace(wsb, s)
+            _call(lib, "dp_csr_linkpred_batch_loss_fwd" + sfx, s.data_ptr(), k, *a, off, g.num_graphs, loss.data_ptr(), k,
+                  ws.data_ptr(), wsb, _lib.current_stream())
+        else:
+            wsb = lib.dp_csr_linkpred_workspace_bytes(n, k)
+            ws = _workspace(wsb, s)
+            _call(lib, "dp_csr_linkpred_loss_fwd" + sfx, s.data_ptr(), k, *a, loss.data_ptr(), n, k, ws.data_ptr(), wsb,
+                  _lib.current_stream())
         ctx.save_for_backward(s)
         ctx.g, ctx.ws = g, ws
         return loss
@@ -886,9 +873,14 @@ class _CsrLinkLossFn(torch.autograd.Function):
         n, k = s.shape
         dloss = dloss.contiguous().float()
         ds = torch.empty_like(s)
-        sfx, a, at = _csr_args(g)
-        _call(lib, "dp_csr_linkpred_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, dloss.data_ptr(), ds.data_ptr(), k, 0, n,
-              k, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+        sfx, a, at = _csr_args(g, local=g.is_batch)
+        tail = (k, ctx.ws.data_ptr(), ctx.ws.numel(), _lib.current_stream())
+        if g.is_batch:
+            _call(lib, "dp_csr_linkpred_batch_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, g.node_off_host.ctypes.data,
+                  g.num_graphs, dloss.data_ptr(), ds.data_ptr(), k, 0, *tail)
+        else:
+            _call(lib, "dp_csr_linkpred_loss_bwd" + sfx, s.data_ptr(), k, *a, *at, dloss.data_ptr(), ds.data_ptr(), k, 0, n,
+                  *tail)
         return ds, None, _link_dvalues(lib, s, g, 0, dloss) if ctx.needs_input_grad[2] else None
 
 
@@ -1056,7 +1048,7 @@ def frob_link_loss(s, adj, num_nodes=None):
         raise TypeError(f"frob_link_loss: s [n, K] goes with a CsrGraph or a CsrBatch, got {type(adj).__name__}")
     if adj.n != s.shape[0]:
         raise ValueError(f"frob_link_loss: the {adj.ARG} has n = {adj.n} rows but s has {s.shape[0]}")
-    return _FrobLinkFn.apply(s, adj, None, "batch" if hasattr(adj, "indices_local") else "csr", _grad_values(adj))
+    return _FrobLinkFn.apply(s, adj, None, "batch" if adj.is_batch else "csr", _grad_values(adj))
 
 
 # ----------------------------------------------------------------------------- learned edge weights on a CSR
@@ -1077,8 +1069,8 @@ class _CsrSddmmFn(torch.autograd.Function):
         p, q = p.contiguous().float(), q.contiguous().float()
         f = p.shape[1]
         out = _f32(p, g.nnz)
-        _call(lib, "dp_csr_sddmm", p.data_ptr(), f, q.data_ptr(), f, g.indptr.data_ptr(), g.indices.data_ptr(),
-              out.data_ptr(), g.n, f, alpha, None, 0.0, _lib.current_stream())
+        _call(lib, "dp_csr_sddmm", p.data_ptr(), f, q.data_ptr(), f, *_csr_index_args(g)[0], out.data_ptr(), g.n, f, alpha,
+              None, 0.0, _lib.current_stream())
         ctx.save_for_backward(p, q)
         ctx.g, ctx.alpha = g, alpha
         return out
@@ -1090,15 +1082,16 @@ class _CsrSddmmFn(torch.autograd.Function):
         g, f = ctx.g, p.shape[1]
         dv = dout.contiguous() if ctx.alpha == 1.0 else dout * ctx.alpha      # A(alpha dout): one [nnz] scaling
         dp = dq = None
+        a, at = _csr_index_args(g)
         if ctx.needs_input_grad[0]:          # dP = A(dout) Q: the weighted gather with the gradient as the values
             dp = torch.empty_like(p)
-            _call(lib, "dp_csr_aggregate_w", q.data_ptr(), f, g.indptr.data_ptr(), g.indices.data_ptr(), dv.data_ptr(),
-                  dp.data_ptr(), f, g.n, f, 0.0, _lib.current_stream())
+            _call(lib, "dp_csr_aggregate_w", q.data_ptr(), f, *a, dv.data_ptr(), dp.data_ptr(), f, g.n, f, 0.0,
+                  _lib.current_stream())
         if ctx.needs_input_grad[1]:          # dQ = A(dout)^T P: the same entry on the transposed CSR, dout[mirror]
             dq = torch.empty_like(q)
             dvt = dv[g.mirror_perm.long()]
-            _call(lib, "dp_csr_aggregate_w", p.data_ptr(), f, g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
-                  dvt.data_ptr(), dq.data_ptr(), f, g.n, f, 0.0, _lib.current_stream())
+            _call(lib, "dp_csr_aggregate_w", p.data_ptr(), f, *at, dvt.data_ptr(), dq.data_ptr(), f, g.n, f, 0.0,
+                  _lib.current_stream())
         return dp, dq, None, None
 
 
@@ -1108,9 +1101,7 @@ def csr_sddmm(p, q, graph, alpha=1.0):
     without an atomic scatter: dP = A(dout) Q is dp_csr_aggregate_w with the gradient as the values, dQ = A(dout)^T P the
     same entry on the transposed CSR with dout[mirror_perm]."""
     for name, t in (("p", p), ("q", q)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
-            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"csr_sddmm: expected {name} {graph.rows()}, got {got}")
+        check_rows("csr_sddmm: ", graph, name, t)
     if p.shape[1] != q.shape[1] or p.shape[1] < 1:
         raise ValueError(f"csr_sddmm: p and q must share a width F >= 1, got {p.shape[1]} and {q.shape[1]}")
     if graph.nnz == 0:                       # an edgeless batch: nothing stored, nothing launched
@@ -1125,7 +1116,7 @@ class _CsrEdgeSoftmaxFn(torch.autograd.Function):
     def forward(ctx, scores, g):
         lib = _lib.load()
         out = torch.empty_like(scores)
-        _call(lib, "dp_csr_edge_softmax_fwd", scores.data_ptr(), g.indptr.data_ptr(), out.data_ptr(), g.n, g.nnz,
+        _call(lib, "dp_csr_edge_softmax_fwd", scores.data_ptr(), _csr_index_args(g)[0][0], out.data_ptr(), g.n, g.nnz,
               _lib.current_stream())
         ctx.save_for_backward(out)
         ctx.g = g
@@ -1138,8 +1129,8 @@ class _CsrEdgeSoftmaxFn(torch.autograd.Function):
         g = ctx.g
         dout = dout.contiguous()
         ds = torch.empty_like(out)
-        _call(lib, "dp_csr_edge_softmax_bwd", out.data_ptr(), dout.data_ptr(), g.indptr.data_ptr(), ds.data_ptr(), g.n,
-              g.nnz, _lib.current_stream())
+        _call(lib, "dp_csr_edge_softmax_bwd", out.data_ptr(), dout.data_ptr(), _csr_index_args(g)[0][0], ds.data_ptr(),
+              g.n, g.nnz, _lib.current_stream())
         return ds, None
 
 
@@ -1157,11 +1148,9 @@ class _CsrSymNormFn(torch.autograd.Function):
         dev = g.indptr.device
         out = torch.empty(g.nnz, device=dev, dtype=torch.float32)
         rdeg = torch.empty(g.n, device=dev, dtype=torch.float32)
-        undirected = g.indices_t is g.indices
         # an undirected container stores a_ij = a_ji: its own order serves as the transposed one (no mirror read)
-        mirror = None if undirected else g.mirror_perm.data_ptr()
-        _call(lib, "dp_csr_sym_norm_fwd", g.indptr.data_ptr(), g.indices.data_ptr(), _lib.ptr(values),
-              g.indptr_t.data_ptr(), g.indices_t.data_ptr(), mirror, rdeg.data_ptr(), out.data_ptr(), g.n, g.nnz,
+        a, at = _csr_index_args(g, mirror="own")
+        _call(lib, "dp_csr_sym_norm_fwd", *a, _lib.ptr(values), *at, rdeg.data_ptr(), out.data_ptr(), g.n, g.nnz,
               _lib.current_stream())
         if values is not None:
             ctx.save_for_backward(values, rdeg)
@@ -1176,9 +1165,9 @@ class _CsrSymNormFn(torch.autograd.Function):
         g = ctx.g
         dout = dout.contiguous()
         dv, gdeg = torch.empty_like(values), torch.empty_like(rdeg)
-        _call(lib, "dp_csr_sym_norm_bwd", g.indptr.data_ptr(), g.indices.data_ptr(), values.data_ptr(),
-              g.indptr_t.data_ptr(), g.indices_t.data_ptr(), g.mirror_perm.data_ptr(), rdeg.data_ptr(), dout.data_ptr(),
-              gdeg.data_ptr(), dv.data_ptr(), g.n, g.nnz, _lib.current_stream())
+        a, at = _csr_index_args(g, mirror="always")
+        _call(lib, "dp_csr_sym_norm_bwd", *a, values.data_ptr(), *at, rdeg.data_ptr(), dout.data_ptr(), gdeg.data_ptr(),
+              dv.data_ptr(), g.n, g.nnz, _lib.current_stream())
         return dv, None
 
 
@@ -1212,8 +1201,8 @@ class _CsrGatFn(torch.autograd.Function):
         u, v = u.contiguous().float(), v.contiguous().float()
         heads = u.shape[1]
         out, rowstat = _f32(u, g.nnz), _f32(u, g.n, 2 * heads)
-        _call(lib, "dp_csr_gat_fwd", u.data_ptr(), heads, v.data_ptr(), heads, g.indptr.data_ptr(), g.indices.data_ptr(),
-              out.data_ptr(), rowstat.data_ptr(), g.n, g.nnz, heads, slope, _lib.current_stream())
+        _call(lib, "dp_csr_gat_fwd", u.data_ptr(), heads, v.data_ptr(), heads, *_csr_index_args(g)[0], out.data_ptr(),
+              rowstat.data_ptr(), g.n, g.nnz, heads, slope, _lib.current_stream())
         ctx.save_for_backward(u, v, rowstat)
         ctx.g, ctx.slope = g, slope
         return out
@@ -1225,8 +1214,8 @@ class _CsrGatFn(torch.autograd.Function):
         g, heads = ctx.g, u.shape[1]
         dout = dout.contiguous()
         du, dv, tdot = torch.empty_like(u), torch.empty_like(v), torch.empty_like(u)
-        _call(lib, "dp_csr_gat_bwd", u.data_ptr(), heads, v.data_ptr(), heads, g.indptr.data_ptr(), g.indices.data_ptr(),
-              g.indptr_t.data_ptr(), g.indices_t.data_ptr(), g.mirror_perm.data_ptr(), rowstat.data_ptr(),
+        a, at = _csr_index_args(g, mirror="always")
+        _call(lib, "dp_csr_gat_bwd", u.data_ptr(), heads, v.data_ptr(), heads, *a, *at, rowstat.data_ptr(),
               dout.data_ptr(), tdot.data_ptr(), du.data_ptr(), heads, dv.data_ptr(), heads, g.n, g.nnz, heads,
               ctx.slope, _lib.current_stream())
         return du, dv, None, None
@@ -1238,15 +1227,11 @@ def csr_gat_attention(u, v, graph, negative_slope=0.2):
     batch the concatenated rows).  Nothing of size nnz * H is written: the backward recomputes the coefficients from u, v
     and the [n, 2H] row maxima and sums, and returns du, dv.  A row with one entry gives exactly 1."""
     for name, t in (("u", u), ("v", v)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
-            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"csr_gat_attention: expected {name} [n, H] with n = {graph.n}, got {got}")
+        check_rows("csr_gat_attention: ", graph, name, t, "H")
     if u.shape[1] != v.shape[1] or not 1 <= u.shape[1] <= _lib.CSR_GAT_MAX_HEADS:
         raise ValueError(f"csr_gat_attention: u and v must share H heads, 1 <= H <= {_lib.CSR_GAT_MAX_HEADS}, got "
                          f"{u.shape[1]} and {v.shape[1]}")
-    slope = float(negative_slope)
-    if slope != slope or slope in (float("inf"), float("-inf")):
-        raise ValueError(f"csr_gat_attention: negative_slope must be finite, got {negative_slope!r}")
+    slope = finite_slope("csr_gat_attention", negative_slope)
     if graph.nnz == 0:                       # an edgeless container: nothing stored, nothing launched
         return _f32(u, 0)
     _lib.require_gpu_tensor(u, "u")
@@ -1264,8 +1249,8 @@ class _CsrGatConvFn(torch.autograd.Function):
         c = width // heads
         y, rowstat = _f32(z, g.n, c if mean else width), _f32(z, g.n, 2 * heads)
         _call(lib, "dp_csr_gat_conv_fwd", z.data_ptr(), width, u.data_ptr(), heads, v.data_ptr(), heads,
-              g.indptr.data_ptr(), g.indices.data_ptr(), y.data_ptr(), y.shape[1], rowstat.data_ptr(), g.n, g.nnz, heads,
-              c, slope, mean, _lib.current_stream())
+              *_csr_index_args(g)[0], y.data_ptr(), y.shape[1], rowstat.data_ptr(), g.n, g.nnz, heads, c, slope, mean,
+              _lib.current_stream())
         ctx.save_for_backward(z, u, v, rowstat)
         ctx.g, ctx.heads, ctx.slope, ctx.mean = g, heads, slope, mean
         return y
@@ -1277,8 +1262,8 @@ class _CsrGatConvFn(torch.autograd.Function):
         g, heads = ctx.g, ctx.heads
         dy = dy.contiguous()
         dz, du, dv, tdot = torch.empty_like(z), torch.empty_like(u), torch.empty_like(v), torch.empty_like(u)
-        _call(lib, "dp_csr_gat_conv_bwd", z.data_ptr(), z.shape[1], u.data_ptr(), heads, v.data_ptr(), heads,
-              g.indptr.data_ptr(), g.indices.data_ptr(), g.indptr_t.data_ptr(), g.indices_t.data_ptr(),
+        a, at = _csr_index_args(g)
+        _call(lib, "dp_csr_gat_conv_bwd", z.data_ptr(), z.shape[1], u.data_ptr(), heads, v.data_ptr(), heads, *a, *at,
               rowstat.data_ptr(), dy.data_ptr(), dy.shape[1], tdot.data_ptr(), du.data_ptr(), heads, dv.data_ptr(), heads,
               dz.data_ptr(), z.shape[1], g.n, g.nnz, heads, z.shape[1] // heads, ctx.slope, ctx.mean,
               _lib.current_stream())
@@ -1297,9 +1282,7 @@ def csr_gat_conv(z, u, v, graph, heads, negative_slope=0.2, concat=True):
     if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= _lib.CSR_GAT_MAX_HEADS:
         raise ValueError(f"csr_gat_conv: heads must be 1 .. {_lib.CSR_GAT_MAX_HEADS}, got {heads!r}")
     for name, t, cols in (("z", z, "heads * C"), ("u", u, "heads"), ("v", v, "heads")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != graph.n:
-            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"csr_gat_conv: expected {name} [n, {cols}] with n = {graph.n}, got {got}")
+        check_rows("csr_gat_conv: ", graph, name, t, cols)
     if u.shape[1] != heads or v.shape[1] != heads:
         raise ValueError(f"csr_gat_conv: u and v must be [n, heads] with heads = {heads}, got {tuple(u.shape)} and "
                          f"{tuple(v.shape)}")
@@ -1309,9 +1292,7 @@ def csr_gat_conv(z, u, v, graph, heads, negative_slope=0.2, concat=True):
     if width > _lib.CSR_GAT_CONV_MAX_WIDTH:
         raise ValueError(f"csr_gat_conv: z has {width} columns, more than the supported heads * C <= "
                          f"{_lib.CSR_GAT_CONV_MAX_WIDTH}")
-    slope = float(negative_slope)
-    if slope != slope or slope in (float("inf"), float("-inf")):
-        raise ValueError(f"csr_gat_conv: negative_slope must be finite, got {negative_slope!r}")
+    slope = finite_slope("csr_gat_conv", negative_slope)
     if graph.nnz == 0:                       # an edgeless container: every node gets a zero row, nothing launched
         return z.new_zeros((graph.n, width if concat else width // heads), dtype=torch.float32)
     for name, t in (("z", z), ("u", u), ("v", v)):
@@ -1331,9 +1312,8 @@ class _CsrSampleMeanFn(torch.autograd.Function):
         y = _f32(x, m, width)
         thr = torch.empty(m, device=x.device, dtype=torch.int64)
         cnt = torch.empty(m, device=x.device, dtype=torch.int32)
-        indices = g.indices if g.indices.numel() else g.indptr          # an edgeless CsrGraph: never read, never NULL
-        _call(lib, "dp_csr_sample_mean_fwd", x.data_ptr(), feat, g.indptr.data_ptr(), indices.data_ptr(), _lib.ptr(nodes),
-              y.data_ptr(), width, thr.data_ptr(), cnt.data_ptr(), m, n, feat, k, mode, seed, _lib.current_stream())
+        _call(lib, "dp_csr_sample_mean_fwd", x.data_ptr(), feat, *_csr_index_args(g)[0], _lib.ptr(nodes), y.data_ptr(),
+              width, thr.data_ptr(), cnt.data_ptr(), m, n, feat, k, mode, seed, _lib.current_stream())
         ctx.save_for_backward(thr, cnt)
         ctx.g, ctx.nodes, ctx.seed, ctx.mode, ctx.shape = g, nodes, seed, mode, (n, feat)
         ctx.mark_non_differentiable(thr, cnt)
@@ -1353,10 +1333,8 @@ class _CsrSampleMeanFn(torch.autograd.Function):
             slot = torch.full((n,), -1, device=dy.device, dtype=torch.int32)
             slot[nodes.long()] = torch.arange(nodes.numel(), device=dy.device, dtype=torch.int32)
         dx = _f32(dy, n, feat)
-        indices_t = g.indices_t if g.indices_t.numel() else g.indptr_t
-        _call(lib, "dp_csr_sample_mean_bwd", dy.data_ptr(), dy.shape[1], g.indptr_t.data_ptr(), indices_t.data_ptr(),
-              _lib.ptr(slot), thr.data_ptr(), cnt.data_ptr(), dx.data_ptr(), feat, n, feat, ctx.mode, ctx.seed,
-              _lib.current_stream())
+        _call(lib, "dp_csr_sample_mean_bwd", dy.data_ptr(), dy.shape[1], *_csr_index_args(g)[1], _lib.ptr(slot),
+              thr.data_ptr(), cnt.data_ptr(), dx.data_ptr(), feat, n, feat, ctx.mode, ctx.seed, _lib.current_stream())
         return dx, None, None, None, None, None
 
 
@@ -1393,9 +1371,7 @@ def csr_sample_mean_stats(x, graph, num_sample, seed, nodes=None, self_mode="non
     """`csr_sample_mean` with what it saves: (y, thr int64 [m], cnt int32 [m]).  thr holds the bits of each target row's
     64-bit threshold (-1: every neighbour taken), cnt the divisor; both are data."""
     k, seed64, mode = _sample_args("csr_sample_mean", num_sample, seed, self_mode)
-    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != graph.n:
-        got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
-        raise ValueError(f"csr_sample_mean: expected x [n, F] with n = {graph.n}, got {got}")
+    check_rows("csr_sample_mean: ", graph, "x", x, "F")
     if nodes is not None:
         if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int32 or nodes.dim() != 1:
             raise ValueError("csr_sample_mean: nodes must be None or an int32 tensor [m] of distinct node ids")
@@ -1490,13 +1466,11 @@ def csr_topk_pool_stats(x, score, graph, ratio=None, k=None, gate=None):
     """`csr_topk_pool` with what it computes on the way: (x_out, graph_out, perm, new_id int32 [n] (-1: dropped), thr
     int64 [B] (the bits of every graph's threshold key; 0 where everything is kept), edge_map int32 [nnz'], edge_map_t
     (the same tensor for an undirected container)).  All but x_out are data."""
-    batch = hasattr(graph, "indices_local")
+    batch = graph.is_batch
     sizes = np.asarray(graph.num_nodes if batch else [graph.n], dtype=np.int64)
     kb = topk_counts(sizes, ratio, k)
     n = graph.n
-    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != n:
-        got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
-        raise ValueError(f"csr_topk_pool: expected x [n, F] with n = {n}, got {got}")
+    check_rows("csr_topk_pool: ", graph, "x", x, "F")
     for name, t in (("score", score), ("gate", gate)):
         if t is None and name == "gate":
             continue
@@ -1526,19 +1500,18 @@ def csr_topk_pool_stats(x, score, graph, ratio=None, k=None, gate=None):
     wsb = lib.dp_csr_topk_workspace_bytes(n_out)
     ws = _workspace(wsb, x)
 
-    def induce(indptr, indices):
-        nnz = indices.numel()                                   # the stored entries, or the pad of an edgeless batch
+    def induce(adjacency, nnz):                                 # nnz: the stored entries, or the pad of an edgeless batch
         cap = max(nnz, 1)
         ip, ix, em = i32(n_out + 1), i32(cap), i32(cap)
         il = i32(cap) if batch else None
-        _call(lib, "dp_csr_topk_induce", indptr.data_ptr(), (indices if nnz else indptr).data_ptr(), new_id.data_ptr(),
-              perm.data_ptr(), new_off.data_ptr(), ip.data_ptr(), ix.data_ptr(), _lib.ptr(il), em.data_ptr(), n, n_out, nb,
-              nnz, cap, ws.data_ptr(), wsb, stream)
+        _call(lib, "dp_csr_topk_induce", *adjacency, new_id.data_ptr(), perm.data_ptr(), new_off.data_ptr(), ip.data_ptr(),
+              ix.data_ptr(), _lib.ptr(il), em.data_ptr(), n, n_out, nb, nnz, cap, ws.data_ptr(), wsb, stream)
         return ip, ix, il, em
 
-    directed = graph.indices_t is not graph.indices
-    fwd = induce(graph.indptr, graph.indices)
-    bwd = induce(graph.indptr_t, graph.indices_t) if directed else None
+    directed = not graph.undirected
+    a, at = _csr_index_args(graph)
+    fwd = induce(a, graph.indices.numel())
+    bwd = induce(at, graph.indices_t.numel()) if directed else None
 
     def narrowed(arrs):
         ip, ix, il, em = arrs
