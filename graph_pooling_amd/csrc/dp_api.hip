@@ -147,35 +147,6 @@ void ensure_dyn_lds(Seq& q, DynLdsOnce& st, const void* fn, int bytes, const cha
     if (dev >= 0 && dev < 64) st.done.fetch_or(1ull << dev, std::memory_order_release);
 }
 
-// dp_model.hip
-int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const float* x, const float* adj,
-                    const float* assign_x, const int* num_nodes, const float* dropout, float* ypred,
-                    float* assign_out, void* save, int mode, long long* labels_out, const PackedAdj* given = nullptr);
-int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const float* x, const float* adj,
-                     const float* assign_x, const int* num_nodes, const float* dropout, const float* d_ypred,
-                     const float* d_assign, float* grads, const void* save, int prezeroed,
-                     const PackedAdj* given = nullptr);
-size_t encoder_save_bytes(const dp_encoder_cfg& c);
-int encoder_validate(const dp_encoder_cfg* c);
-int encoder_save_locate(const dp_encoder_cfg& c, int level, int field, size_t* offset, size_t* count);
-// dp_set2set.hip
-void set2set_fwd(Seq& q, const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
-                 const float* b_hh, const float* Wp, const float* bp, float* out, int B, int n, int d, void* save);
-void set2set_bwd(Seq& q, const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
-                 const float* b_hh, const float* Wp, const float* bp, const float* out, const float* dout,
-                 float* demb, int ldde, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, float* dWp,
-                 float* dbp, int B, int n, int d, const void* save);
-size_t set2set_save_bytes(int B, int n, int d);
-int set2set_plan(int n, int d);
-// dp_csr_edge_grad.hip: out[e] = P_i . Q_indices[e] over the stored entries
-void csr_sddmm_identity(Seq& q, const float* P, int ldp, const float* Q, int ldq, const int* indptr, const int* indices,
-                        float* out, int n_rows, int F);
-// dp_meanagg.hip
-void mean_aggregate_fwd(Seq& q, const float* table, int ldt, const int* indptr, const int* indices, float* out,
-                        int ldo, int n_rows, int feat);
-void mean_aggregate_bwd(Seq& q, const float* dout, int ldo, const int* indptr, const int* indices, float* dtable,
-                        int ldt, int n_rows, int feat);
-
 namespace {
 
 RowGroups one_group(int w) {
@@ -350,16 +321,17 @@ size_t sized(F&& f) {
     f(q);
     return q.ws_off + 256;
 }
+// one workspace serves the forward and the backward: the larger of the two
+template <typename F, typename G>
+size_t sized(F&& fwd, G&& bwd) {
+    const size_t f = sized(fwd), b = sized(bwd);
+    return f > b ? f : b;
+}
 
 }  // namespace
 }  // namespace dp
 
 using namespace dp;
-
-#define STREAM(s) ((hipStream_t)(s))
-#define NONNEG(v) DP_CHECK_ARG((v) > 0, #v "=%d must be positive", (int)(v))
-#define NOTNULL(p) DP_CHECK_ARG((p) != nullptr, #p " is NULL")
-#define ALIGNED16(p) DP_CHECK_ARG(((uintptr_t)(p) & 15) == 0, #p " is not 16-byte aligned")
 
 extern "C" {
 
@@ -368,26 +340,22 @@ const char* dp_last_error_string(void) { return dp::last_error(); }
 int dp_device_error(int clear) { return device_error_take(clear != 0); }
 const char* dp_device_error_describe(int mask) { return device_error_text(mask); }
 int dp_level0_bwd_symmetric(int* verdicts, int capacity, int* count, int* rows_per_block) {
-    NOTNULL(count);
+    DP_NOTNULL(count);
     DP_CHECK_ARG(capacity >= 0 && (capacity == 0 || verdicts != nullptr), "verdicts is NULL with capacity=%d", capacity);
     return level0_verdicts_read(verdicts, capacity, count, rows_per_block);
 }
-#define DEVICE_GATE(name)                                     \
-    do {                                                      \
-        const int gate_rc_ = device_error_gate(name);         \
-        if (gate_rc_ != DP_OK) return gate_rc_;               \
-    } while (0)
+#define DEVICE_GATE(name) DP_TRY(device_error_gate(name))
 
 int dp_bgemm_f32(const float* A, const float* B, float* C, const float* bias, int batch, int M, int N, int K,
                  int lda, int ldb, int ldc, long strideA, long strideB, long strideC, int transA, int transB,
                  float alpha, float beta, int act, void* stream) {
-    NOTNULL(A); NOTNULL(B); NOTNULL(C);
-    NONNEG(batch); NONNEG(M); NONNEG(N);
+    DP_NOTNULL(A); DP_NOTNULL(B); DP_NOTNULL(C);
+    DP_POS(batch); DP_POS(M); DP_POS(N);
     DP_CHECK_ARG(K >= 0, "K=%d must be >= 0", K);
     DP_CHECK_ARG(lda >= (transA ? M : K), "lda=%d too small", lda);
     DP_CHECK_ARG(ldb >= (transB ? K : N), "ldb=%d too small", ldb);
     DP_CHECK_ARG(ldc >= N, "ldc=%d < N=%d", ldc, N);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     bgemm(q, A, B, C, bias, batch, M, N, K, lda, ldb, ldc, strideA, strideB, strideC, transA != 0, transB != 0, alpha,
           beta, act);
     return q.err;
@@ -410,7 +378,7 @@ GemmDesc gemm_desc_of(const dp_gemm_problem& p, float* fix_part, int* fix_cnt) {
     return d;
 }
 int gemm_group_check(const dp_gemm_problem* p, int count, int batch, int ksplit, bool pointers) {
-    NOTNULL(p);
+    DP_NOTNULL(p);
     DP_CHECK_ARG(count >= 1 && count <= GEMM_GROUP_MAX, "count=%d out of range [1,%d]", count, GEMM_GROUP_MAX);
     DP_CHECK_ARG(batch >= 1 && batch <= 65535, "batch=%d out of range [1,65535]", batch);
     DP_CHECK_ARG(ksplit >= 1 && ksplit <= DP_GEMM_MAX_KSPLIT, "ksplit=%d out of range [1,%d]", ksplit,
@@ -460,9 +428,8 @@ void gemm_group_seq(Seq& q, const dp_gemm_problem* p, int count, int batch, int 
 }  // namespace
 
 int dp_bgemm_plan(const dp_gemm_problem* p, int count, int batch, int ksplit, int* plan_out) {
-    NOTNULL(plan_out);
-    const int rc = gemm_group_check(p, count, batch, ksplit, false);
-    if (rc != DP_OK) return rc;
+    DP_NOTNULL(plan_out);
+    DP_TRY(gemm_group_check(p, count, batch, ksplit, false));
     GemmDesc d[GEMM_GROUP_MAX];
     float* const some = reinterpret_cast<float*>(sizeof(float));      // "has partials": never dereferenced
     for (int i = 0; i < count; ++i)
@@ -479,40 +446,41 @@ size_t dp_bgemm_group_workspace_bytes(const dp_gemm_problem* p, int count, int b
 
 int dp_bgemm_group_f32(const dp_gemm_problem* p, int count, int batch, int ksplit, void* workspace,
                        size_t workspace_bytes, void* stream) {
-    const int rc = gemm_group_check(p, count, batch, ksplit, true);
-    if (rc != DP_OK) return rc;
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_TRY(gemm_group_check(p, count, batch, ksplit, true));
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     gemm_group_seq(q, p, count, batch, ksplit);
     return q.err;
 }
 
 int dp_adj_aggregate(const float* adj, const float* V, int ldv, float* U, int ldu, int B, int n, int C, int trans,
                      float beta, void* stream) {
-    NOTNULL(adj); NOTNULL(V); NOTNULL(U);
-    NONNEG(B); NONNEG(n); NONNEG(C);
+    DP_NOTNULL(adj); DP_NOTNULL(V); DP_NOTNULL(U);
+    DP_POS(B); DP_POS(n); DP_POS(C);
     DP_CHECK_ARG(ldv >= C && ldu >= C, "ldv=%d/ldu=%d smaller than C=%d", ldv, ldu, C);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     aggregate(q, adj, V, ldv, U, ldu, B, n, C, trans != 0, beta);
     return q.err;
 }
 
 int dp_adj_pack_ld(int n) { return adj_pack_ld(n); }
 size_t dp_adj_pack_bytes(int B, int n) { return (size_t)B * n * adj_pack_ld(n) * sizeof(unsigned short); }
-int dp_adj_pack(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, void* stream) {
-    NOTNULL(adj); NOTNULL(packed); NOTNULL(packed_t); NOTNULL(flag);
-    NONNEG(B); NONNEG(n);
-    Seq q(STREAM(stream), nullptr, 0);
-    adj_pack(q, adj, (unsigned short*)packed, (unsigned short*)packed_t, flag, B, n, adj_pack_ld(n));
-    return q.err;
-}
-int dp_adj_pack_zero(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, void* zero_p,
-                     size_t zero_bytes, void* stream) {
-    NOTNULL(adj); NOTNULL(packed); NOTNULL(packed_t); NOTNULL(flag); NOTNULL(zero_p);
-    NONNEG(B); NONNEG(n);
-    Seq q(STREAM(stream), nullptr, 0);
+// zeroing: dp_adj_pack_zero, whose zero_p is required; the plain name passes NULL and 0
+static int adj_pack_entry(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, bool zeroing,
+                          void* zero_p, size_t zero_bytes, void* stream) {
+    DP_NOTNULL(adj); DP_NOTNULL(packed); DP_NOTNULL(packed_t); DP_NOTNULL(flag);
+    if (zeroing) DP_NOTNULL(zero_p);
+    DP_POS(B); DP_POS(n);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     adj_pack(q, adj, (unsigned short*)packed, (unsigned short*)packed_t, flag, B, n, adj_pack_ld(n), false, zero_p,
              zero_bytes);
     return q.err;
+}
+int dp_adj_pack(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, void* stream) {
+    return adj_pack_entry(adj, packed, packed_t, flag, B, n, false, nullptr, 0, stream);
+}
+int dp_adj_pack_zero(const float* adj, void* packed, void* packed_t, int* flag, int B, int n, void* zero_p,
+                     size_t zero_bytes, void* stream) {
+    return adj_pack_entry(adj, packed, packed_t, flag, B, n, true, zero_p, zero_bytes, stream);
 }
 size_t dp_adj_aggregate_packed_workspace_bytes(int B, int n, int C) {
     return split3_elems(B, n, C) * sizeof(unsigned short) + 512;
@@ -520,10 +488,10 @@ size_t dp_adj_aggregate_packed_workspace_bytes(int B, int n, int C) {
 int dp_adj_aggregate_packed(const float* adj, const void* packed, const void* packed_t, const int* flag,
                             const float* V, int ldv, float* U, int ldu, int B, int n, int C, int trans, float beta,
                             int presplit, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(adj); NOTNULL(packed); NOTNULL(packed_t); NOTNULL(flag); NOTNULL(V); NOTNULL(U);
-    NONNEG(B); NONNEG(n); NONNEG(C);
+    DP_NOTNULL(adj); DP_NOTNULL(packed); DP_NOTNULL(packed_t); DP_NOTNULL(flag); DP_NOTNULL(V); DP_NOTNULL(U);
+    DP_POS(B); DP_POS(n); DP_POS(C);
     DP_CHECK_ARG(ldv >= C && ldu >= C, "ldv=%d/ldu=%d smaller than C=%d", ldv, ldu, C);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     unsigned short* vs = q.alloc<unsigned short>(split3_elems(B, n, C));
     if (q.err) return q.err;
     PackedAdj pk{(const unsigned short*)packed, (const unsigned short*)packed_t, adj_pack_ld(n), flag};
@@ -533,8 +501,8 @@ int dp_adj_aggregate_packed(const float* adj, const void* packed, const void* pa
 
 int dp_adj_aggregate_plan(int B, int n, int C, int trans, int packed, int fused, int a_misalign, float beta,
                           int* plan_out) {
-    NOTNULL(plan_out);
-    NONNEG(B); NONNEG(n); NONNEG(C);
+    DP_NOTNULL(plan_out);
+    DP_POS(B); DP_POS(n); DP_POS(C);
     DP_CHECK_ARG(a_misalign >= 0 && a_misalign <= 15, "a_misalign=%d is not the low four bits of an address", a_misalign);
     const AggPick p = agg_pick(B, n, C, trans != 0, packed != 0, fused != 0, (unsigned)a_misalign, beta);
     const int out[DP_AGG_PLAN_INTS] = {p.form, p.ct, p.rt, p.tiles, p.grid, (int)p.lds, p.fallback, p.fb_ct, p.fb_rt,
@@ -544,19 +512,17 @@ int dp_adj_aggregate_plan(int B, int n, int C, int trans, int packed, int fused,
 }
 
 size_t dp_gcn_layer_workspace_bytes(int B, int n, int Fin, int Fout) {
-    size_t f = sized([&](Seq& q) { gcn_layer_fwd_seq(q, 0, Fin, 0, 0, 0, 0, Fout, 0, B, n, Fin, Fout, 0); });
-    size_t b = sized([&](Seq& q) {
+    return sized([&](Seq& q) { gcn_layer_fwd_seq(q, 0, Fin, 0, 0, 0, 0, Fout, 0, B, n, Fin, Fout, 0); }, [&](Seq& q) {
         gcn_layer_bwd_seq(q, 0, Fin, 0, 0, 0, Fout, 0, 0, Fout, 0, Fin, 0, 0, (float*)1, B, n, Fin, Fout, 0);
     });
-    return f > b ? f : b;
 }
 int dp_gcn_layer_fwd(const float* x, int ldx, const float* adj, const float* W, const float* bias, float* y, int ldy,
                      float* invnorm, int B, int n, int Fin, int Fout, int flags, void* workspace,
                      size_t workspace_bytes, void* stream) {
-    NOTNULL(x); NOTNULL(adj); NOTNULL(W); NOTNULL(y);
-    NONNEG(B); NONNEG(n); NONNEG(Fin); NONNEG(Fout);
+    DP_NOTNULL(x); DP_NOTNULL(adj); DP_NOTNULL(W); DP_NOTNULL(y);
+    DP_POS(B); DP_POS(n); DP_POS(Fin); DP_POS(Fout);
     DP_CHECK_ARG(ldx >= Fin && ldy >= Fout, "ldx=%d/ldy=%d smaller than the row width", ldx, ldy);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     gcn_layer_fwd_seq(q, x, ldx, adj, W, bias, y, ldy, invnorm, B, n, Fin, Fout, flags);
     return q.err;
 }
@@ -564,34 +530,33 @@ int dp_gcn_layer_bwd(const float* x, int ldx, const float* adj, const float* W, 
                      const float* invnorm, const float* dy, int lddy, float* dx, int lddx, float* dW, float* db,
                      float* dadj, int B, int n, int Fin, int Fout, int flags, void* workspace, size_t workspace_bytes,
                      void* stream) {
-    NOTNULL(x); NOTNULL(adj); NOTNULL(W); NOTNULL(y); NOTNULL(dy); NOTNULL(dW);
-    NONNEG(B); NONNEG(n); NONNEG(Fin); NONNEG(Fout);
+    DP_NOTNULL(x); DP_NOTNULL(adj); DP_NOTNULL(W); DP_NOTNULL(y); DP_NOTNULL(dy); DP_NOTNULL(dW);
+    DP_POS(B); DP_POS(n); DP_POS(Fin); DP_POS(Fout);
     DP_CHECK_ARG(!(flags & DP_F_NORMALIZE) || invnorm, "invnorm is NULL but DP_F_NORMALIZE is set");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     gcn_layer_bwd_seq(q, x, ldx, adj, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, dadj, B, n, Fin, Fout, flags);
     return q.err;
 }
 
 size_t dp_bn_node_workspace_bytes(int B, int n, int F) {
-    size_t f = sized([&](Seq& q) { bn_fwd_seq(q, 0, F, 0, F, 0, B, n, F, 1); });
-    size_t b = sized([&](Seq& q) { bn_bwd_seq(q, 0, F, 0, F, 0, 0, F, 0, F, B, n, F, 1); });
-    return f > b ? f : b;
+    return sized([&](Seq& q) { bn_fwd_seq(q, 0, F, 0, F, 0, B, n, F, 1); },
+                 [&](Seq& q) { bn_bwd_seq(q, 0, F, 0, F, 0, 0, F, 0, F, B, n, F, 1); });
 }
 int dp_bn_node_fwd(const float* x, int ldx, float* y, int ldy, float* stats, int B, int n, int F, int relu,
                    void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(x); NOTNULL(y); NOTNULL(stats);
-    NONNEG(B); NONNEG(n); NONNEG(F);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(x); DP_NOTNULL(y); DP_NOTNULL(stats);
+    DP_POS(B); DP_POS(n); DP_POS(F);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     bn_fwd_seq(q, x, ldx, y, ldy, stats, B, n, F, relu);
     return q.err;
 }
 int dp_bn_node_bwd(const float* x, int ldx, const float* y, int ldy, const float* stats, const float* dy, int lddy,
                    float* dx, int lddx, int B, int n, int F, int relu, void* workspace, size_t workspace_bytes,
                    void* stream) {
-    NOTNULL(y); NOTNULL(stats); NOTNULL(dy); NOTNULL(dx);
+    DP_NOTNULL(y); DP_NOTNULL(stats); DP_NOTNULL(dy); DP_NOTNULL(dx);
     DP_CHECK_ARG(!relu || x, "x is NULL but relu != 0");
-    NONNEG(B); NONNEG(n); NONNEG(F);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_POS(B); DP_POS(n); DP_POS(F);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     bn_bwd_seq(q, x, ldx, y, ldy, stats, dy, lddy, dx, lddx, B, n, F, relu);
     return q.err;
 }
@@ -602,27 +567,27 @@ size_t dp_assign_workspace_bytes(int B, int n, int Din, int K) {
 int dp_assign_softmax_mask_fwd(const float* z, int ldz, const float* Wp, const float* bp, const int* num_nodes,
                                float* S, int B, int n, int Din, int K, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    NOTNULL(z); NOTNULL(Wp); NOTNULL(S);
-    NONNEG(B); NONNEG(n); NONNEG(Din); NONNEG(K);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(z); DP_NOTNULL(Wp); DP_NOTNULL(S);
+    DP_POS(B); DP_POS(n); DP_POS(Din); DP_POS(K);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     assign_fwd_seq(q, z, ldz, Wp, bp, num_nodes, S, B, n, Din, K);
     return q.err;
 }
 int dp_assign_softmax_mask_bwd(const float* z, int ldz, const float* Wp, const float* S, const float* dS,
                                const int* num_nodes, float* dz, int lddz, float* dWp, float* dbp, int B, int n, int Din,
                                int K, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(z); NOTNULL(Wp); NOTNULL(S); NOTNULL(dS); NOTNULL(dWp);
-    NONNEG(B); NONNEG(n); NONNEG(Din); NONNEG(K);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(z); DP_NOTNULL(Wp); DP_NOTNULL(S); DP_NOTNULL(dS); DP_NOTNULL(dWp);
+    DP_POS(B); DP_POS(n); DP_POS(Din); DP_POS(K);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     assign_bwd_seq(q, z, ldz, Wp, S, dS, num_nodes, dz, lddz, dWp, dbp, B, n, Din, K);
     return q.err;
 }
 
 int dp_pool_fwd(const float* S, const float* Z, int ldz, const float* adj, float* Xp, float* Ap, float* T, int B, int n,
                 int K, int D, void* stream) {
-    NOTNULL(S); NOTNULL(Z); NOTNULL(adj); NOTNULL(Xp); NOTNULL(Ap); NOTNULL(T);
-    NONNEG(B); NONNEG(n); NONNEG(K); NONNEG(D);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(S); DP_NOTNULL(Z); DP_NOTNULL(adj); DP_NOTNULL(Xp); DP_NOTNULL(Ap); DP_NOTNULL(T);
+    DP_POS(B); DP_POS(n); DP_POS(K); DP_POS(D);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     pool_fwd_seq(q, S, Z, ldz, adj, Xp, Ap, T, B, n, K, D);
     return q.err;
 }
@@ -632,26 +597,27 @@ size_t dp_pool_bwd_workspace_bytes(int B, int n, int K, int D) {
 int dp_pool_bwd(const float* S, const float* Z, int ldz, const float* adj, const float* T, const float* dXp,
                 const float* dAp, float* dS, float* dZ, int lddz, float* dadj, int B, int n, int K, int D,
                 void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(Z); NOTNULL(adj); NOTNULL(T); NOTNULL(dXp); NOTNULL(dAp); NOTNULL(dS); NOTNULL(dZ);
-    NONNEG(B); NONNEG(n); NONNEG(K); NONNEG(D);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(S); DP_NOTNULL(Z); DP_NOTNULL(adj); DP_NOTNULL(T); DP_NOTNULL(dXp); DP_NOTNULL(dAp); DP_NOTNULL(dS);
+    DP_NOTNULL(dZ);
+    DP_POS(B); DP_POS(n); DP_POS(K); DP_POS(D);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     pool_bwd_seq(q, S, Z, ldz, adj, T, dXp, dAp, dS, dZ, lddz, dadj, B, n, K, D);
     return q.err;
 }
 
 int dp_masked_max_fwd(const float* Z, int ldz, const int* num_nodes, float* out, int ldo, int* argmax, int B, int n,
                       int F, void* stream) {
-    NOTNULL(Z); NOTNULL(out); NOTNULL(argmax);
-    NONNEG(B); NONNEG(n); NONNEG(F);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(Z); DP_NOTNULL(out); DP_NOTNULL(argmax);
+    DP_POS(B); DP_POS(n); DP_POS(F);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     masked_max_fwd(q, Z, ldz, num_nodes, out, ldo, argmax, F, B, n, F);
     return q.err;
 }
 int dp_masked_max_bwd(const float* dout, int ldo, const int* argmax, float* dZ, int lddz, int B, int n, int F,
                       void* stream) {
-    NOTNULL(dout); NOTNULL(argmax); NOTNULL(dZ);
-    NONNEG(B); NONNEG(n); NONNEG(F);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(dout); DP_NOTNULL(argmax); DP_NOTNULL(dZ);
+    DP_POS(B); DP_POS(n); DP_POS(F);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     masked_max_bwd(q, dout, ldo, argmax, F, dZ, lddz, B, n, F);
     return q.err;
 }
@@ -661,7 +627,7 @@ size_t dp_sizeof_row_groups(void) { return sizeof(dp_row_groups); }
 size_t dp_sizeof_group_ptrs(void) { return sizeof(dp_group_ptrs); }
 namespace {
 int row_groups_check(const dp_row_groups* g) {
-    NOTNULL(g);
+    DP_NOTNULL(g);
     DP_CHECK_ARG(g->G >= 1 && g->G <= 2, "G=%d out of range [1,2]", g->G);
     for (int i = 0; i < g->G; ++i) {
         DP_CHECK_ARG(g->w[i] >= 1, "group %d: width w=%d must be >= 1", i, g->w[i]);
@@ -709,23 +675,15 @@ GroupCPtrs gcptrs(const dp_row_groups& g, const dp_group_ptrs* p) {
 }
 int joint_width(const dp_row_groups& g) { return g.c0[g.G - 1] + g.w[g.G - 1]; }
 }  // namespace
-#define ROWS_OK(g)                                  \
-    do {                                            \
-        const int rg_rc_ = row_groups_check(g);     \
-        if (rg_rc_ != DP_OK) return rg_rc_;         \
-    } while (0)
-#define GROUP_PTRS(g, p, need)                                    \
-    do {                                                          \
-        const int gp_rc_ = group_ptrs_check(*(g), p, #p, need);   \
-        if (gp_rc_ != DP_OK) return gp_rc_;                       \
-    } while (0)
+#define ROWS_OK(g) DP_TRY(row_groups_check(g))
+#define GROUP_PTRS(g, p, need) DP_TRY(group_ptrs_check(*(g), p, #p, need))
 
 int dp_rowop_plan(int op, const dp_row_groups* g, int n, int B, int Bs, int flags, int* plan_out) {
-    NOTNULL(plan_out);
+    DP_NOTNULL(plan_out);
     DP_CHECK_ARG(op >= DP_ROWOP_ROWNORM_FWD && op <= DP_ROWOP_MASKED_MAX_FWD, "op=%d is no row operation", op);
     RowPick p{};
     if (op == DP_ROWOP_MASKED_MAX_FWD) {
-        NONNEG(n);
+        DP_POS(n);
         p = masked_max_fwd_pick(n);
     } else {
         ROWS_OK(g);
@@ -751,14 +709,14 @@ int dp_rownorm_fwd(const float* U, int ldu, const float* P, const dp_row_groups*
                    const dp_group_ptrs* yout, float* invn, float* part, long rows, int normalize, int stats_mode,
                    void* stream) {
     ROWS_OK(g);
-    NOTNULL(U);
+    DP_NOTNULL(U);
     GROUP_PTRS(g, yout, true);
     if (bias) GROUP_PTRS(g, bias, false);
-    NONNEG(rows);
+    DP_POS(rows);
     DP_CHECK_ARG(ldu >= joint_width(*g), "ldu=%d smaller than the joint width %d", ldu, joint_width(*g));
     DP_CHECK_ARG(stats_mode >= 0 && stats_mode <= 2, "stats_mode=%d (0 none, 1 of relu(y), 2 of y)", stats_mode);
     DP_CHECK_ARG(!stats_mode || part, "part is NULL but stats_mode=%d", stats_mode);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     rownorm_fwd(q, U, ldu, P, gcptrs(*g, bias), row_groups_of(*g), gptrs(*g, yout), invn, part, rows, normalize != 0,
                 stats_mode);
     return q.err;
@@ -769,12 +727,13 @@ int dp_adj_aggregate_rownorm(const float* adj, const void* packed, const void* p
                              const dp_group_ptrs* yout, float* invn, float* part, int B, int n, int normalize,
                              int stats_mode, int presplit, void* workspace, size_t workspace_bytes, void* stream) {
     ROWS_OK(g);
-    NOTNULL(adj); NOTNULL(V);
+    DP_NOTNULL(adj); DP_NOTNULL(V);
     GROUP_PTRS(g, yout, true);
     if (bias) GROUP_PTRS(g, bias, false);
-    NONNEG(B); NONNEG(n);
+    DP_POS(B); DP_POS(n);
     const int Cj = joint_width(*g);
-    // (the tail kernels take the groups as one run of columns: the wide forms norm every column below c0[1] with group 0)
+    // (the tail kernels take the groups as one run of columns: the wide forms norm every column below c0[1] with group
+    // 0)
     DP_CHECK_ARG(g->c0[0] == 0 && (g->G == 1 || g->c0[1] == g->w[0]),
                  "the groups must cover the joint width without a gap (c0 = %d, %d; w[0] = %d)", g->c0[0],
                  g->G == 2 ? g->c0[1] : 0, g->w[0]);
@@ -784,7 +743,7 @@ int dp_adj_aggregate_rownorm(const float* adj, const void* packed, const void* p
     const bool any = packed || packed_t || flag || workspace;
     DP_CHECK_ARG(!any || (packed && packed_t && flag && workspace),
                  "packed, packed_t, flag and workspace are given together or not at all");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     PackedAdj pk{(const unsigned short*)packed, (const unsigned short*)packed_t, adj_pack_ld(n), flag};
     unsigned short* vs = nullptr;
     if (any) {
@@ -800,13 +759,13 @@ int dp_adj_aggregate_rownorm(const float* adj, const void* packed, const void* p
 int dp_bn_apply_fwd(const float* Y, int ldy, const float* part, float* stats, const dp_row_groups* g,
                     const dp_group_ptrs* xout, int B, int n, int relu, int Bs, void* stream) {
     ROWS_OK(g);
-    NOTNULL(Y);
+    DP_NOTNULL(Y);
     GROUP_PTRS(g, xout, true);
-    NONNEG(B); NONNEG(n);
+    DP_POS(B); DP_POS(n);
     DP_CHECK_ARG(Bs >= 0, "Bs=%d must not be negative (0: B)", Bs);
     DP_CHECK_ARG(ldy >= joint_width(*g), "ldy=%d smaller than the joint width %d", ldy, joint_width(*g));
     DP_CHECK_ARG(!part || stats, "stats is NULL but part is given");
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     bn_apply_fwd(q, Y, ldy, part, stats, row_groups_of(*g), gptrs(*g, xout), B, n, relu != 0, Bs);
     return q.err;
 }
@@ -816,9 +775,9 @@ int dp_bn_bwd_partials(const dp_row_groups* g, const dp_group_ptrs* dx, const dp
     ROWS_OK(g);
     GROUP_PTRS(g, dx, true);
     GROUP_PTRS(g, xhat, true);
-    NOTNULL(part);
-    NONNEG(rows);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(part);
+    DP_POS(rows);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     bn_bwd_partials(q, gcptrs(*g, dx), gcptrs(*g, xhat), row_groups_of(*g), part, rows);
     return q.err;
 }
@@ -831,8 +790,8 @@ int dp_rownorm_bwd(const dp_row_groups* g, const dp_group_ptrs* dx, const dp_gro
     GROUP_PTRS(g, y, true);
     if (has_bn) GROUP_PTRS(g, xhat, true);
     if (dbias) GROUP_PTRS(g, dbias, false);
-    NOTNULL(dU);
-    NONNEG(B); NONNEG(n);
+    DP_NOTNULL(dU);
+    DP_POS(B); DP_POS(n);
     DP_CHECK_ARG(Bs >= 0, "Bs=%d must not be negative (0: B)", Bs);
     DP_CHECK_ARG(B <= 65535, "B=%d exceeds the grid's second dimension (65535)", B);
     DP_CHECK_ARG(ldu >= joint_width(*g), "ldu=%d smaller than the joint width %d", ldu, joint_width(*g));
@@ -847,9 +806,9 @@ int dp_rownorm_bwd(const dp_row_groups* g, const dp_group_ptrs* dx, const dp_gro
         DP_CHECK_ARG(!dbias->p[i] || B <= 1 || dbias->ld[i] >= g->w[i],
                      "dbias: ld=%d of group %d, the stride between graphs, smaller than its width %d", dbias->ld[i], i,
                      g->w[i]);
-    if (vs) ALIGNED16(vs);
+    if (vs) DP_ALIGNED16_P(vs);
     GroupPtrs db = gptrs(*g, dbias);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     rownorm_bwd(q, gcptrs(*g, dx), gcptrs(*g, has_bn ? xhat : nullptr), gcptrs(*g, y), invn, stats, part2,
                 row_groups_of(*g), dU, ldu, dbias ? &db : nullptr, B, n, has_relu != 0, has_bn != 0, normalize != 0,
                 (unsigned short*)vs, Bs);
@@ -858,16 +817,16 @@ int dp_rownorm_bwd(const dp_row_groups* g, const dp_group_ptrs* dx, const dp_gro
 
 int dp_softmax_mask_fwd(const float* logits, int ldl, float* S, int lds, const int* num_nodes, int B, int n, int K,
                         float* S2, void* vs, void* zero_p, size_t zero_bytes, void* stream) {
-    NOTNULL(logits); NOTNULL(S);
-    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_NOTNULL(logits); DP_NOTNULL(S);
+    DP_POS(B); DP_POS(n); DP_POS(K);
     DP_CHECK_ARG(B <= 65535, "B=%d exceeds the grid's second dimension (65535)", B);
     DP_CHECK_ARG(ldl >= K && lds >= K, "ldl=%d/lds=%d smaller than K=%d", ldl, lds, K);
     DP_CHECK_ARG(!vs || !softmax_mask_fwd_pick(K, true, false, true).generic(),
                  "vs: K=%d is past the plan forms (16 rows of K floats must fit 48 KiB), the generic kernel writes no split",
                  K);
     DP_CHECK_ARG(!zero_bytes || zero_p, "zero_p is NULL but zero_bytes=%zu", zero_bytes);
-    if (vs) ALIGNED16(vs);
-    Seq q(STREAM(stream), nullptr, 0);
+    if (vs) DP_ALIGNED16_P(vs);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     softmax_mask_fwd(q, logits, ldl, S, lds, num_nodes, B, n, K, S2, (unsigned short*)vs, zero_bytes ? zero_p : nullptr,
                      zero_bytes);
     return q.err;
@@ -875,36 +834,35 @@ int dp_softmax_mask_fwd(const float* logits, int ldl, float* S, int lds, const i
 
 int dp_softmax_mask_bwd(const float* S, int lds, float* dS, int ldds, const int* num_nodes, float* dlogits, int ldl,
                         int B, int n, int K, float* dbias, long dbias_stride, const float* dS2, void* stream) {
-    NOTNULL(S); NOTNULL(dS); NOTNULL(dlogits);
-    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_NOTNULL(S); DP_NOTNULL(dS); DP_NOTNULL(dlogits);
+    DP_POS(B); DP_POS(n); DP_POS(K);
     DP_CHECK_ARG(B <= 65535, "B=%d exceeds the grid's second dimension (65535)", B);
     DP_CHECK_ARG(lds >= K && ldds >= K && ldl >= K, "lds=%d/ldds=%d/ldl=%d smaller than K=%d", lds, ldds, ldl, K);
     DP_CHECK_ARG(!dbias || B == 1 || dbias_stride >= K, "dbias_stride=%ld smaller than K=%d", dbias_stride, K);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     softmax_mask_bwd(q, S, lds, dS, ldds, num_nodes, dlogits, ldl, B, n, K, dbias, dbias_stride, dS2);
     return q.err;
 }
 
 int dp_colsum_batched(const float* X, int ldx, long strideX, int rows, int cols, float* out, long strideOut, int batch,
                       int rowsplit, void* stream) {
-    NOTNULL(X); NOTNULL(out);
-    NONNEG(rows); NONNEG(cols); NONNEG(batch);
+    DP_NOTNULL(X); DP_NOTNULL(out);
+    DP_POS(rows); DP_POS(cols); DP_POS(batch);
     DP_CHECK_ARG(ldx >= cols, "ldx=%d smaller than cols=%d", ldx, cols);
     DP_CHECK_ARG(rowsplit >= 1 && rowsplit <= 65535, "rowsplit=%d out of range [1,65535]", rowsplit);
     DP_CHECK_ARG(batch <= 65535, "batch=%d exceeds the grid's second dimension (65535)", batch);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     colsum_batched(q, X, ldx, strideX, rows, cols, out, strideOut, batch, rowsplit);
     return q.err;
 }
 
 size_t dp_linkpred_workspace_bytes(int B, int n, int K) {
-    size_t f = sized([&](Seq& q) { linkpred_fwd(q, 0, K, 0, 0, 0, B, n, K); });
-    size_t b = sized([&](Seq& q) { linkpred_bwd(q, 0, K, 0, 0, 0, 0, K, B, n, K, 0); });
-    return f > b ? f : b;
+    return sized([&](Seq& q) { linkpred_fwd(q, 0, K, 0, 0, 0, B, n, K); },
+                 [&](Seq& q) { linkpred_bwd(q, 0, K, 0, 0, 0, 0, K, B, n, K, 0); });
 }
 int dp_linkpred_plan(int B, int n, int K, int* plan_out) {
-    NOTNULL(plan_out);
-    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_NOTNULL(plan_out);
+    DP_POS(B); DP_POS(n); DP_POS(K);
     LinkPlan p;
     if (!linkpred_plan(B, n, K, p)) {
         set_error("linkpred: K=%d clusters exceed the fused tile kernel (max 256)", K);
@@ -917,36 +875,36 @@ int dp_linkpred_plan(int B, int n, int K, int* plan_out) {
 }
 int dp_linkpred_loss_fwd(const float* S, const float* adj, const int* num_nodes, float* loss_out, int B, int n, int K,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(adj); NOTNULL(loss_out);
-    NONNEG(B); NONNEG(n); NONNEG(K);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(S); DP_NOTNULL(adj); DP_NOTNULL(loss_out);
+    DP_POS(B); DP_POS(n); DP_POS(K);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     linkpred_fwd(q, S, K, adj, num_nodes, loss_out, B, n, K);
     return q.err;
 }
 int dp_linkpred_loss_bwd(const float* S, const float* adj, const int* num_nodes, const float* dloss, float* dS,
                          int accumulate, int B, int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(adj); NOTNULL(dS);
-    NONNEG(B); NONNEG(n); NONNEG(K);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(S); DP_NOTNULL(adj); DP_NOTNULL(dS);
+    DP_POS(B); DP_POS(n); DP_POS(K);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     linkpred_bwd(q, S, K, adj, num_nodes, dloss, dS, K, B, n, K, accumulate);
     return q.err;
 }
 int dp_linkpred_loss_fwd_packed(const float* S, const void* adj_pk, const int* num_nodes, float* loss_out, int B,
                                 int n, int K, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(adj_pk); NOTNULL(loss_out);
-    NONNEG(B); NONNEG(n); NONNEG(K);
-    ALIGNED16(adj_pk);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(S); DP_NOTNULL(adj_pk); DP_NOTNULL(loss_out);
+    DP_POS(B); DP_POS(n); DP_POS(K);
+    DP_ALIGNED16_P(adj_pk);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     linkpred_fwd_packed(q, S, K, static_cast<const unsigned short*>(adj_pk), num_nodes, loss_out, B, n, K);
     return q.err;
 }
 int dp_linkpred_loss_bwd_packed(const float* S, const void* adj_pk, const void* adj_pkt, const int* num_nodes,
                                 const float* dloss, float* dS, int accumulate, int B, int n, int K, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    NOTNULL(S); NOTNULL(adj_pk); NOTNULL(adj_pkt); NOTNULL(dS);
-    NONNEG(B); NONNEG(n); NONNEG(K);
-    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DP_NOTNULL(S); DP_NOTNULL(adj_pk); DP_NOTNULL(adj_pkt); DP_NOTNULL(dS);
+    DP_POS(B); DP_POS(n); DP_POS(K);
+    DP_ALIGNED16_P(adj_pk); DP_ALIGNED16_P(adj_pkt);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     linkpred_bwd_packed(q, S, K, static_cast<const unsigned short*>(adj_pk),
                         static_cast<const unsigned short*>(adj_pkt), num_nodes, dloss, dS, K, B, n, K, accumulate);
     return q.err;
@@ -959,24 +917,24 @@ size_t dp_assign_entropy_workspace_bytes(int B, int n, int K) {
 int dp_assign_entropy_fwd(const float* S, int lds, const int* num_nodes, float weight, float* ent_out,
                           float* total_inout, int B, int n, int K, void* workspace, size_t workspace_bytes,
                           void* stream) {
-    NOTNULL(S); NOTNULL(ent_out);
-    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_NOTNULL(S); DP_NOTNULL(ent_out);
+    DP_POS(B); DP_POS(n); DP_POS(K);
     DP_CHECK_ARG(lds >= K, "dp_assign_entropy_fwd: lds=%d smaller than K=%d", lds, K);
-    NOTNULL(workspace);
+    DP_NOTNULL(workspace);
     DP_CHECK_ARG(workspace_bytes >= dp_assign_entropy_workspace_bytes(B, n, K),
                  "dp_assign_entropy_fwd: workspace too small: need >= %zu bytes, have %zu",
                  dp_assign_entropy_workspace_bytes(B, n, K), workspace_bytes);
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     assign_entropy_fwd(q, S, lds, num_nodes, weight, ent_out, total_inout, B, n, K);
     return q.err;
 }
 int dp_assign_entropy_bwd(const float* S, int lds, const int* num_nodes, const float* dloss, float weight, float* dS,
                           int ldds, int accumulate, int B, int n, int K, void* stream) {
-    NOTNULL(S); NOTNULL(dS);
-    NONNEG(B); NONNEG(n); NONNEG(K);
+    DP_NOTNULL(S); DP_NOTNULL(dS);
+    DP_POS(B); DP_POS(n); DP_POS(K);
     DP_CHECK_ARG(lds >= K, "dp_assign_entropy_bwd: lds=%d smaller than K=%d", lds, K);
     DP_CHECK_ARG(ldds >= K, "dp_assign_entropy_bwd: ldds=%d smaller than K=%d", ldds, K);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     assign_entropy_bwd(q, S, lds, num_nodes, dloss, weight, dS, ldds, accumulate, B, n, K);
     return q.err;
 }
@@ -1005,7 +963,7 @@ static int frob_link_fwd_dense(const char* fn, const float* S, int lds, const vo
     DP_CHECK(adj_pk != nullptr, DP_ERR_INVALID_ARG, "%s is NULL", packed ? "adj_pk" : "adj");
     if (packed) DP_NOTNULL(adj_pkt);
     DP_NOTNULL(W); DP_NOTNULL(G); DP_NOTNULL(loss_out);
-    NONNEG(B); NONNEG(N); NONNEG(K);
+    DP_POS(B); DP_POS(N); DP_POS(K);
     FROB_K_OK(fn);
     DP_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", fn, lds, K);
     if (packed) {
@@ -1013,7 +971,7 @@ static int frob_link_fwd_dense(const char* fn, const float* S, int lds, const vo
         DP_ALIGNED16(adj_pkt, true, "adj_pkt is not 16-byte aligned");
     }
     FROB_WS_OK(fn, dp_frob_link_workspace_bytes(B, N, K));
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     const int ld = packed ? adj_pack_ld(N) : N;
     frob_link_w_dense(q, S, lds, adj_pk, adj_pkt, packed, ld, num_nodes, W, B, N, K);
     frob_link_fwd(q, S, lds, W, adj_pk, packed ? 3 : 1, ld, num_nodes, nullptr, nullptr, link_norm, 1.f, G, loss_out,
@@ -1035,12 +993,12 @@ int dp_frob_link_fwd_packed(const float* S, int lds, const void* adj_pk, const v
 int dp_frob_link_bwd(const float* S, int lds, const float* W, const float* G, const int* num_nodes,
                      const float* link_norm, const float* dloss, float* dS, int ldds, int accumulate, int B, int N, int K,
                      void* stream) {
-    NOTNULL(S); NOTNULL(W); NOTNULL(G); NOTNULL(dS);
-    NONNEG(B); NONNEG(N); NONNEG(K);
+    DP_NOTNULL(S); DP_NOTNULL(W); DP_NOTNULL(G); DP_NOTNULL(dS);
+    DP_POS(B); DP_POS(N); DP_POS(K);
     FROB_K_OK("dp_frob_link_bwd");
     DP_CHECK_ARG(lds >= K, "dp_frob_link_bwd: lds=%d smaller than K=%d", lds, K);
     DP_CHECK_ARG(ldds >= K, "dp_frob_link_bwd: ldds=%d smaller than K=%d", ldds, K);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     frob_link_bwd(q, S, lds, W, G, num_nodes, nullptr, link_norm, dloss, 1.f, dS, ldds, accumulate, B, N,
                   (long long)B * N, K);
     return q.err;
@@ -1065,9 +1023,9 @@ static int csr_frob_link_fwd(const char* fn, bool batch, const float* S, int lds
     DP_VALUES((void)0, "values is NULL");
     if (batch) DP_NOTNULL(node_off);
     DP_NOTNULL(W); DP_NOTNULL(G); DP_NOTNULL(loss_out);
-    if (batch) NONNEG(B);
+    if (batch) DP_POS(B);
     DP_CHECK(n > 0, DP_ERR_INVALID_ARG, "%s=%d must be positive", batch ? "n_total" : "n", n);
-    NONNEG(K);
+    DP_POS(K);
     FROB_K_OK(fn);
     if (batch)
         DP_CHECK(B <= n, DP_ERR_INVALID_ARG, "%s: B=%d graphs over n_total=%d rows (every graph has >= 1 node)", fn, B, n);
@@ -1078,7 +1036,7 @@ static int csr_frob_link_fwd(const char* fn, bool batch, const float* S, int lds
     FROB_WS_OK(fn, dp_csr_frob_link_workspace_bytes(n, B, K));
     if (!weighted) values = nullptr;
     values_t = weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr;
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     const bool directed = indptr_t && indices_t && !(indptr_t == indptr && indices_t == indices);
     csr_aggregate_fwd(q, S, lds, indptr, indices, W, K, n, K, 0, 0.f, values);                       // W = A S
     if (directed) csr_aggregate_fwd(q, S, lds, indptr_t, indices_t, W, K, n, K, 0, 1.f, values_t);   // += A^T S
@@ -1096,13 +1054,13 @@ static int csr_frob_link_bwd(const char* fn, bool batch, const float* S, int lds
     DP_NOTNULL(S); DP_NOTNULL(W); DP_NOTNULL(G);
     if (batch) DP_NOTNULL(node_off);
     DP_NOTNULL(dS);
-    if (batch) NONNEG(B);
+    if (batch) DP_POS(B);
     DP_CHECK(n > 0, DP_ERR_INVALID_ARG, "%s=%d must be positive", batch ? "n_total" : "n", n);
-    NONNEG(K);
+    DP_POS(K);
     FROB_K_OK(fn);
     DP_CHECK(lds >= K, DP_ERR_INVALID_ARG, "%s: lds=%d smaller than K=%d", fn, lds, K);
     DP_CHECK(ldds >= K, DP_ERR_INVALID_ARG, "%s: ldds=%d smaller than K=%d", fn, ldds, K);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     frob_link_bwd(q, S, lds, W, G, nullptr, node_off, link_norm, dloss, symmetric ? 2.f : 1.f, dS, ldds, accumulate, B, n,
                   n, K);
     return q.err;
@@ -1155,17 +1113,17 @@ int dp_csr_frob_link_batch_bwd(const float* S, int lds, const float* W, const fl
 
 int dp_cross_entropy_fwd(const float* logits, const long long* label, float* loss_out, float* prob, int B, int C,
                          void* stream) {
-    NOTNULL(logits); NOTNULL(label); NOTNULL(loss_out);
-    NONNEG(B); NONNEG(C);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(logits); DP_NOTNULL(label); DP_NOTNULL(loss_out);
+    DP_POS(B); DP_POS(C);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     ce_fwd(q, logits, label, loss_out, prob, B, C);
     return q.err;
 }
 int dp_cross_entropy_bwd(const float* prob, const long long* label, const float* dloss, float* dlogits, int B, int C,
                          void* stream) {
-    NOTNULL(prob); NOTNULL(label); NOTNULL(dlogits);
-    NONNEG(B); NONNEG(C);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(prob); DP_NOTNULL(label); DP_NOTNULL(dlogits);
+    DP_POS(B); DP_POS(C);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     ce_bwd(q, prob, label, dloss, 1.f, dlogits, B, C);
     return q.err;
 }
@@ -1175,14 +1133,14 @@ int dp_set2set_plan(int n, int d) { return set2set_plan(n, d); }
 int dp_set2set_fwd(const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
                    const float* b_hh, const float* Wp, const float* bp, float* out, int B, int n, int d, void* save,
                    size_t save_bytes, void* stream) {
-    NOTNULL(emb); NOTNULL(w_ih); NOTNULL(w_hh); NOTNULL(b_ih); NOTNULL(b_hh); NOTNULL(Wp); NOTNULL(bp); NOTNULL(out);
-    NOTNULL(save);
+    DP_NOTNULL(emb); DP_NOTNULL(w_ih); DP_NOTNULL(w_hh); DP_NOTNULL(b_ih); DP_NOTNULL(b_hh); DP_NOTNULL(Wp);
+    DP_NOTNULL(bp); DP_NOTNULL(out); DP_NOTNULL(save);
     DP_CHECK_ARG(B >= 0, "B=%d must not be negative", B);      // B == 0: DP_OK, nothing is launched
-    NONNEG(n); NONNEG(d);
+    DP_POS(n); DP_POS(d);
     DP_CHECK_ARG(lde >= d, "lde=%d smaller than the row width d=%d", lde, d);
     DP_CHECK_ARG(save_bytes >= set2set_save_bytes(B, n, d), "set2set save buffer too small: %zu < %zu",
                  save_bytes, set2set_save_bytes(B, n, d));
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     set2set_fwd(q, emb, lde, w_ih, w_hh, b_ih, b_hh, Wp, bp, out, B, n, d, save);
     return q.err;
 }
@@ -1196,13 +1154,14 @@ int dp_set2set_bwd(const float* emb, int lde, const float* w_ih, const float* w_
                    float* demb, int ldde, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, float* dWp,
                    float* dbp, int B, int n, int d, const void* save, size_t save_bytes, void* workspace,
                    size_t workspace_bytes, void* stream) {
-    NOTNULL(emb); NOTNULL(w_ih); NOTNULL(w_hh); NOTNULL(Wp); NOTNULL(out); NOTNULL(dout); NOTNULL(demb);
-    NOTNULL(dw_ih); NOTNULL(dw_hh); NOTNULL(db_ih); NOTNULL(db_hh); NOTNULL(dWp); NOTNULL(dbp); NOTNULL(save);
+    DP_NOTNULL(emb); DP_NOTNULL(w_ih); DP_NOTNULL(w_hh); DP_NOTNULL(Wp); DP_NOTNULL(out); DP_NOTNULL(dout);
+    DP_NOTNULL(demb); DP_NOTNULL(dw_ih); DP_NOTNULL(dw_hh); DP_NOTNULL(db_ih); DP_NOTNULL(db_hh); DP_NOTNULL(dWp);
+    DP_NOTNULL(dbp); DP_NOTNULL(save);
     DP_CHECK_ARG(B >= 0, "B=%d must not be negative", B);      // B == 0: DP_OK, the parameter gradients are zeroed
-    NONNEG(n); NONNEG(d);
+    DP_POS(n); DP_POS(d);
     DP_CHECK_ARG(lde >= d && ldde >= d, "lde=%d / ldde=%d smaller than the row width d=%d", lde, ldde, d);
     DP_CHECK_ARG(save_bytes >= set2set_save_bytes(B, n, d), "set2set save buffer too small");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     set2set_bwd(q, emb, lde, w_ih, w_hh, b_ih, b_hh, Wp, bp, out, dout, demb, ldde, dw_ih, dw_hh, db_ih, db_hh, dWp,
                 dbp, B, n, d, save);
     return q.err;
@@ -1210,17 +1169,17 @@ int dp_set2set_bwd(const float* emb, int lde, const float* w_ih, const float* w_
 
 int dp_mean_aggregate_fwd(const float* table, int ldt, const int* indptr, const int* indices, float* out, int ldo,
                           int n_rows, int feat, void* stream) {
-    NOTNULL(table); NOTNULL(indptr); NOTNULL(indices); NOTNULL(out);
-    NONNEG(n_rows); NONNEG(feat);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(table); DP_NOTNULL(indptr); DP_NOTNULL(indices); DP_NOTNULL(out);
+    DP_POS(n_rows); DP_POS(feat);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     mean_aggregate_fwd(q, table, ldt, indptr, indices, out, ldo, n_rows, feat);
     return q.err;
 }
 int dp_mean_aggregate_bwd(const float* dout, int ldo, const int* indptr, const int* indices, float* dtable, int ldt,
                           int n_rows, int feat, void* stream) {
-    NOTNULL(dout); NOTNULL(indptr); NOTNULL(indices); NOTNULL(dtable);
-    NONNEG(n_rows); NONNEG(feat);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(dout); DP_NOTNULL(indptr); DP_NOTNULL(indices); DP_NOTNULL(dtable);
+    DP_POS(n_rows); DP_POS(feat);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     mean_aggregate_bwd(q, dout, ldo, indptr, indices, dtable, ldt, n_rows, feat);
     return q.err;
 }
@@ -1228,10 +1187,10 @@ int dp_mean_aggregate_bwd(const float* dout, int ldo, const int* indptr, const i
 int dp_bgemm_split_bf16(const float* A, const float* B, float* C, int batch, int M, int N, int K, int lda, int ldb,
                         int ldc, long strideA, long strideB, long strideC, int transA, int transB, float beta,
                         void* stream) {
-    NOTNULL(A); NOTNULL(B); NOTNULL(C);
-    NONNEG(batch); NONNEG(M); NONNEG(N); NONNEG(K);
+    DP_NOTNULL(A); DP_NOTNULL(B); DP_NOTNULL(C);
+    DP_POS(batch); DP_POS(M); DP_POS(N); DP_POS(K);
     DP_CHECK_ARG(beta == 0.f || beta == 1.f, "beta must be 0 or 1");
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     GemmDesc d{A, B, C, nullptr, M, N, K, lda, ldb, ldc, strideA, strideB, strideC, transA != 0, transB != 0, 1.f, beta,
                0, 0, 0, nullptr, 0, 0, 0};
     gemm_split_bf16(q, d, batch);
@@ -1245,8 +1204,8 @@ static int csr_aggregate_entry(const float* table, int ldt, const int* indptr, c
     DP_NOTNULL(table); DP_NOTNULL(indptr); DP_NOTNULL(indices);
     DP_VALUES((void)0, "values is NULL");
     DP_NOTNULL(out);
-    NONNEG(n_rows); NONNEG(feat);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_POS(n_rows); DP_POS(feat);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     csr_aggregate_fwd(q, table, ldt, indptr, indices, out, ldo, n_rows, feat, mean, beta, weighted ? values : nullptr);
     return q.err;
 }
@@ -1298,11 +1257,10 @@ void sparse_gcn_bwd_seq(Seq& q, const float* ax, const int* indptr, const int* i
 }
 }  // namespace
 size_t dp_sparse_gcn_layer_workspace_bytes(int n, int Fin, int Fout) {
-    size_t f = sized([&](Seq& q) { sparse_gcn_fwd_seq(q, 0, Fin, 0, 0, 0, 0, 0, Fout, 0, 0, n, Fin, Fout, 0); });
-    size_t b = sized([&](Seq& q) {
-        sparse_gcn_bwd_seq(q, 0, 0, 0, 0, 0, 0, 0, Fout, 0, 0, Fout, (float*)1, Fin, 0, 0, n, Fin, Fout, 0);
-    });
-    return f > b ? f : b;
+    return sized([&](Seq& q) { sparse_gcn_fwd_seq(q, 0, Fin, 0, 0, 0, 0, 0, Fout, 0, 0, n, Fin, Fout, 0); },
+                 [&](Seq& q) {
+                     sparse_gcn_bwd_seq(q, 0, 0, 0, 0, 0, 0, 0, Fout, 0, 0, Fout, (float*)1, Fin, 0, 0, n, Fin, Fout, 0);
+                 });
 }
 static int sparse_gcn_fwd_entry(const float* x, int ldx, const int* indptr, const int* indices, const float* values,
                                 bool weighted, const float* W, const float* bias, float* y, int ldy, float* ax,
@@ -1311,9 +1269,9 @@ static int sparse_gcn_fwd_entry(const float* x, int ldx, const int* indptr, cons
     DP_NOTNULL(x); DP_NOTNULL(indptr); DP_NOTNULL(indices);
     DP_VALUES((void)0, "values is NULL");
     DP_NOTNULL(W); DP_NOTNULL(y); DP_NOTNULL(ax); DP_NOTNULL(invnorm);
-    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
+    DP_POS(n); DP_POS(Fin); DP_POS(Fout);
     DP_CHECK_ARG(!(flags & DP_F_ADD_SELF) || ldx == Fin, "add_self needs a contiguous x (ldx == Fin)");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     sparse_gcn_fwd_seq(q, x, ldx, indptr, indices, W, bias, y, ldy, ax, invnorm, n, Fin, Fout, flags,
                        weighted ? values : nullptr);
     return q.err;
@@ -1328,7 +1286,7 @@ static int sparse_gcn_bwd_entry(const char* fn, const float* ax, const int* indp
     DP_NOTNULL(ax); DP_NOTNULL(indptr); DP_NOTNULL(indices);
     DP_VALUES((void)0, "values is NULL");
     DP_NOTNULL(W); DP_NOTNULL(y); DP_NOTNULL(invnorm); DP_NOTNULL(dy); DP_NOTNULL(dW);
-    NONNEG(n); NONNEG(Fin); NONNEG(Fout);
+    DP_POS(n); DP_POS(Fin); DP_POS(Fout);
     DP_CHECK_ARG((indptr_t == nullptr) == (indices_t == nullptr), "indptr_t and indices_t come together");
     DP_VALUES_T((void)0, "%s: values_t is NULL but indices_t is a CSR of its own", fn);
     DP_CHECK_ARG(!dx || lddx == Fin, "dx must be contiguous (lddx == Fin)");
@@ -1336,7 +1294,7 @@ static int sparse_gcn_bwd_entry(const char* fn, const float* ax, const int* indp
         DP_NOTNULL(x); DP_NOTNULL(dvalues);
         DP_CHECK_ARG(ldx >= Fin, "ldx=%d smaller than Fin=%d", ldx, Fin);
     }
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     sparse_gcn_bwd_seq(q, ax, indptr, indices, indptr_t, indices_t, W, y, ldy, invnorm, dy, lddy, dx, lddx, dW, db, n,
                        Fin, Fout, flags, weighted ? values : nullptr,
                        weighted ? values_t_of(indices, indices_t, values, values_t) : nullptr, want_dv ? x : nullptr, ldx,
@@ -1390,221 +1348,256 @@ size_t dp_encoder_save_bytes(const dp_encoder_cfg* cfg) {
 }
 size_t dp_encoder_workspace_bytes(const dp_encoder_cfg* cfg) {
     if (encoder_validate(cfg) != DP_OK) return 0;
-    size_t f = sized([&](Seq& q) { encoder_forward(q, *cfg, 0, 0, 0, 0, 0, 0, 0, 0, 0, DP_MODE_TRAIN, 0); });
-    size_t b = sized([&](Seq& q) { encoder_backward(q, *cfg, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0); });
-    return f > b ? f : b;
+    return sized([&](Seq& q) { encoder_forward(q, *cfg, 0, 0, 0, 0, 0, 0, 0, 0, 0, DP_MODE_TRAIN, 0); },
+                 [&](Seq& q) { encoder_backward(q, *cfg, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0); });
 }
 int dp_encoder_save_locate(const dp_encoder_cfg* cfg, int level, int field, size_t* offset, size_t* count) {
-    int rc = encoder_validate(cfg);
-    if (rc != DP_OK) return rc;
-    NOTNULL(offset); NOTNULL(count);
+    DP_TRY(encoder_validate(cfg));
+    DP_NOTNULL(offset); DP_NOTNULL(count);
     DP_CHECK_ARG(level >= 0 && level <= cfg->num_pooling, "level=%d out of range [0,%d]", level, cfg->num_pooling);
     return encoder_save_locate(*cfg, level, field, offset, count);
 }
-int dp_encoder_forward(const dp_encoder_cfg* cfg, const float* params, const float* x, const float* adj,
-                       const float* assign_x, const int* num_nodes, const float* dropout, float* ypred,
-                       float* assign_out, long long* labels_out, void* save, size_t save_bytes, void* workspace,
-                       size_t workspace_bytes, int mode, void* stream) {
-    int rc = encoder_validate(cfg);
-    if (rc != DP_OK) return rc;
-    NOTNULL(params); NOTNULL(x); NOTNULL(adj); NOTNULL(ypred); NOTNULL(save);
+// The dense and the packed name of each pass share one body.  packed: adj_pk / adj_pkt are the bf16 planes of A and
+// A^T; else adj_pk is the fp32 adjacency and adj_pkt NULL.  (Neither name checks the planes' alignment.)
+static int encoder_forward_entry(const char* fn, bool packed, const dp_encoder_cfg* cfg, const float* params,
+                                 const float* x, const void* adj_pk, const void* adj_pkt, const float* assign_x,
+                                 const int* num_nodes, const float* dropout, float* ypred, float* assign_out,
+                                 long long* labels_out, void* save, size_t save_bytes, void* workspace,
+                                 size_t workspace_bytes, int mode, void* stream) {
+    DP_TRY(encoder_validate(cfg));
+    DP_NOTNULL(params); DP_NOTNULL(x);
+    DP_CHECK_ARG(adj_pk != nullptr, "%s is NULL", packed ? "adj_pk" : "adj");
+    if (packed) DP_NOTNULL(adj_pkt);
+    DP_NOTNULL(ypred); DP_NOTNULL(save);
     DP_CHECK_ARG(cfg->num_pooling == 0 || assign_x, "assign_x is NULL");
     DP_CHECK_ARG(save_bytes >= encoder_save_bytes(*cfg), "save buffer too small: %zu < %zu", save_bytes,
                  encoder_save_bytes(*cfg));
-    DEVICE_GATE("dp_encoder_forward");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DEVICE_GATE(fn);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     DP_CHECK_ARG((mode & ~(DP_MODE_TRAIN)) == 0, "mode=%d: DP_MODE_EVAL or DP_MODE_TRAIN", mode);
-    return encoder_forward(q, *cfg, params, x, adj, assign_x, num_nodes, dropout, ypred, assign_out, save, mode,
-                           labels_out);
-}
-int dp_encoder_backward(const dp_encoder_cfg* cfg, const float* params, const float* x, const float* adj,
-                        const float* assign_x, const int* num_nodes, const float* dropout, const float* d_ypred,
-                        const float* d_assign, float* grads, const void* save, size_t save_bytes, void* workspace,
-                        size_t workspace_bytes, int prezeroed, void* stream) {
-    int rc = encoder_validate(cfg);
-    if (rc != DP_OK) return rc;
-    NOTNULL(params); NOTNULL(x); NOTNULL(adj); NOTNULL(d_ypred); NOTNULL(grads); NOTNULL(save);
-    DP_CHECK_ARG(save_bytes >= encoder_save_bytes(*cfg), "save buffer too small: %zu < %zu", save_bytes,
-                 encoder_save_bytes(*cfg));
-    DEVICE_GATE("dp_encoder_backward");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    return encoder_backward(q, *cfg, params, x, adj, assign_x, num_nodes, dropout, d_ypred, d_assign, grads, save,
-                            prezeroed);
-}
-
-int dp_encoder_forward_packed(const dp_encoder_cfg* cfg, const float* params, const float* x, const void* adj_pk,
-                              const void* adj_pkt,
-                       const float* assign_x, const int* num_nodes, const float* dropout, float* ypred,
-                       float* assign_out, long long* labels_out, void* save, size_t save_bytes, void* workspace,
-                       size_t workspace_bytes, int mode, void* stream) {
-    int rc = encoder_validate(cfg);
-    if (rc != DP_OK) return rc;
-    NOTNULL(params); NOTNULL(x); NOTNULL(adj_pk); NOTNULL(adj_pkt); NOTNULL(ypred); NOTNULL(save);
-    DP_CHECK_ARG(cfg->num_pooling == 0 || assign_x, "assign_x is NULL");
-    DP_CHECK_ARG(save_bytes >= encoder_save_bytes(*cfg), "save buffer too small: %zu < %zu", save_bytes,
-                 encoder_save_bytes(*cfg));
-    DEVICE_GATE("dp_encoder_forward_packed");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    DP_CHECK_ARG((mode & ~(DP_MODE_TRAIN)) == 0, "mode=%d: DP_MODE_EVAL or DP_MODE_TRAIN", mode);
+    if (!packed)
+        return encoder_forward(q, *cfg, params, x, static_cast<const float*>(adj_pk), assign_x, num_nodes, dropout,
+                               ypred, assign_out, save, mode, labels_out);
     const PackedAdj given{static_cast<const unsigned short*>(adj_pk), static_cast<const unsigned short*>(adj_pkt),
                           adj_pack_ld(cfg->N), nullptr};
     return encoder_forward(q, *cfg, params, x, nullptr, assign_x, num_nodes, dropout, ypred, assign_out, save, mode,
                            labels_out, &given);
 }
-
-int dp_encoder_backward_packed(const dp_encoder_cfg* cfg, const float* params, const float* x, const void* adj_pk,
-                               const void* adj_pkt,
-                        const float* assign_x, const int* num_nodes, const float* dropout, const float* d_ypred,
-                        const float* d_assign, float* grads, const void* save, size_t save_bytes, void* workspace,
-                        size_t workspace_bytes, int prezeroed, void* stream) {
-    int rc = encoder_validate(cfg);
-    if (rc != DP_OK) return rc;
-    NOTNULL(params); NOTNULL(x); NOTNULL(adj_pk); NOTNULL(adj_pkt); NOTNULL(d_ypred); NOTNULL(grads); NOTNULL(save);
+static int encoder_backward_entry(const char* fn, bool packed, const dp_encoder_cfg* cfg, const float* params,
+                                  const float* x, const void* adj_pk, const void* adj_pkt, const float* assign_x,
+                                  const int* num_nodes, const float* dropout, const float* d_ypred,
+                                  const float* d_assign, float* grads, const void* save, size_t save_bytes,
+                                  void* workspace, size_t workspace_bytes, int prezeroed, void* stream) {
+    DP_TRY(encoder_validate(cfg));
+    DP_NOTNULL(params); DP_NOTNULL(x);
+    DP_CHECK_ARG(adj_pk != nullptr, "%s is NULL", packed ? "adj_pk" : "adj");
+    if (packed) DP_NOTNULL(adj_pkt);
+    DP_NOTNULL(d_ypred); DP_NOTNULL(grads); DP_NOTNULL(save);
     DP_CHECK_ARG(save_bytes >= encoder_save_bytes(*cfg), "save buffer too small: %zu < %zu", save_bytes,
                  encoder_save_bytes(*cfg));
-    DEVICE_GATE("dp_encoder_backward_packed");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DEVICE_GATE(fn);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
+    if (!packed)
+        return encoder_backward(q, *cfg, params, x, static_cast<const float*>(adj_pk), assign_x, num_nodes, dropout,
+                                d_ypred, d_assign, grads, save, prezeroed);
     const PackedAdj given{static_cast<const unsigned short*>(adj_pk), static_cast<const unsigned short*>(adj_pkt),
                           adj_pack_ld(cfg->N), nullptr};
     return encoder_backward(q, *cfg, params, x, nullptr, assign_x, num_nodes, dropout, d_ypred, d_assign, grads, save,
                             prezeroed, &given);
 }
+int dp_encoder_forward(const dp_encoder_cfg* cfg, const float* params, const float* x, const float* adj,
+                       const float* assign_x, const int* num_nodes, const float* dropout, float* ypred,
+                       float* assign_out, long long* labels_out, void* save, size_t save_bytes, void* workspace,
+                       size_t workspace_bytes, int mode, void* stream) {
+    return encoder_forward_entry("dp_encoder_forward", false, cfg, params, x, adj, nullptr, assign_x, num_nodes,
+                                 dropout, ypred, assign_out, labels_out, save, save_bytes, workspace, workspace_bytes,
+                                 mode, stream);
+}
+int dp_encoder_forward_packed(const dp_encoder_cfg* cfg, const float* params, const float* x, const void* adj_pk,
+                              const void* adj_pkt, const float* assign_x, const int* num_nodes, const float* dropout,
+                              float* ypred, float* assign_out, long long* labels_out, void* save, size_t save_bytes,
+                              void* workspace, size_t workspace_bytes, int mode, void* stream) {
+    return encoder_forward_entry("dp_encoder_forward_packed", true, cfg, params, x, adj_pk, adj_pkt, assign_x,
+                                 num_nodes, dropout, ypred, assign_out, labels_out, save, save_bytes, workspace,
+                                 workspace_bytes, mode, stream);
+}
+int dp_encoder_backward(const dp_encoder_cfg* cfg, const float* params, const float* x, const float* adj,
+                        const float* assign_x, const int* num_nodes, const float* dropout, const float* d_ypred,
+                        const float* d_assign, float* grads, const void* save, size_t save_bytes, void* workspace,
+                        size_t workspace_bytes, int prezeroed, void* stream) {
+    return encoder_backward_entry("dp_encoder_backward", false, cfg, params, x, adj, nullptr, assign_x, num_nodes,
+                                  dropout, d_ypred, d_assign, grads, save, save_bytes, workspace, workspace_bytes,
+                                  prezeroed, stream);
+}
+int dp_encoder_backward_packed(const dp_encoder_cfg* cfg, const float* params, const float* x, const void* adj_pk,
+                               const void* adj_pkt, const float* assign_x, const int* num_nodes, const float* dropout,
+                               const float* d_ypred, const float* d_assign, float* grads, const void* save,
+                               size_t save_bytes, void* workspace, size_t workspace_bytes, int prezeroed,
+                               void* stream) {
+    return encoder_backward_entry("dp_encoder_backward_packed", true, cfg, params, x, adj_pk, adj_pkt, assign_x,
+                                  num_nodes, dropout, d_ypred, d_assign, grads, save, save_bytes, workspace,
+                                  workspace_bytes, prezeroed, stream);
+}
 
 size_t dp_loss_workspace_bytes(int B, int N, int K, int linkpred) {
-    size_t f = sized([&](Seq& q) { loss_fwd_seq(q, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, 1, N, K, linkpred); });
-    size_t b = sized([&](Seq& q) { loss_bwd_seq(q, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, 1, N, K, linkpred); });
-    return f > b ? f : b;
+    return sized([&](Seq& q) { loss_fwd_seq(q, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, 1, N, K, linkpred); },
+                 [&](Seq& q) { loss_bwd_seq(q, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, 1, N, K, linkpred); });
+}
+// packed: adj_pk / adj_pkt are the bf16 planes, 16-byte aligned whether or not linkpred reads them; else adj_pk is the
+// fp32 adjacency and adj_pkt NULL
+static int loss_forward_entry(const char* fn, bool packed, const float* ypred, const long long* label, const float* S,
+                              const void* adj_pk, const void* adj_pkt, const int* num_nodes, const float* link_norm,
+                              float* loss_out, float* prob, float* d_ypred_unit, int B, int C, int N, int K,
+                              int linkpred, void* workspace, size_t workspace_bytes, void* stream) {
+    DP_NOTNULL(ypred); DP_NOTNULL(label); DP_NOTNULL(loss_out); DP_NOTNULL(prob);
+    DP_POS(B); DP_POS(C);
+    DP_CHECK_ARG(!linkpred || (S && adj_pk && (adj_pkt || !packed) && N > 0 && K > 0), "linkpred needs S, %s, N, K",
+                 packed ? "adj_pk, adj_pkt" : "adj");
+    if (packed) {
+        DP_ALIGNED16_P(adj_pk); DP_ALIGNED16_P(adj_pkt);
+    }
+    DEVICE_GATE(fn);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
+    loss_fwd_seq(q, ypred, label, S, packed ? nullptr : static_cast<const float*>(adj_pk), num_nodes, link_norm,
+                 loss_out, prob, d_ypred_unit, B, C, N, K, linkpred,
+                 packed ? static_cast<const unsigned short*>(adj_pk) : nullptr);
+    return q.err;
+}
+static int loss_backward_entry(const char* fn, bool packed, const float* prob, const long long* label, const float* S,
+                               const void* adj_pk, const void* adj_pkt, const int* num_nodes, const float* link_norm,
+                               const float* dloss, float* d_ypred, float* dS, int B, int C, int N, int K, int linkpred,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    DP_NOTNULL(prob); DP_NOTNULL(label);
+    DP_POS(B); DP_POS(C);
+    DP_CHECK_ARG(!linkpred || (S && adj_pk && (adj_pkt || !packed) && dS && N > 0 && K > 0),
+                 "linkpred needs S, %s, dS, N, K", packed ? "adj_pk, adj_pkt" : "adj");
+    if (packed) {
+        DP_ALIGNED16_P(adj_pk); DP_ALIGNED16_P(adj_pkt);
+    }
+    DEVICE_GATE(fn);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
+    loss_bwd_seq(q, prob, label, S, packed ? nullptr : static_cast<const float*>(adj_pk), num_nodes, link_norm, dloss,
+                 d_ypred, dS, B, C, N, K, linkpred, packed ? static_cast<const unsigned short*>(adj_pk) : nullptr,
+                 static_cast<const unsigned short*>(adj_pkt));
+    return q.err;
 }
 int dp_loss_forward(const float* ypred, const long long* label, const float* S, const float* adj, const int* num_nodes,
-                    const float* link_norm, float* loss_out, float* prob, float* d_ypred_unit, int B, int C, int N, int K,
-                    int linkpred, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(ypred); NOTNULL(label); NOTNULL(loss_out); NOTNULL(prob);
-    NONNEG(B); NONNEG(C);
-    DP_CHECK_ARG(!linkpred || (S && adj && N > 0 && K > 0), "linkpred needs S, adj, N, K");
-    DEVICE_GATE("dp_loss_forward");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    loss_fwd_seq(q, ypred, label, S, adj, num_nodes, link_norm, loss_out, prob, d_ypred_unit, B, C, N, K, linkpred);
-    return q.err;
-}
-int dp_loss_backward(const float* prob, const long long* label, const float* S, const float* adj, const int* num_nodes,
-                     const float* link_norm, const float* dloss, float* d_ypred, float* dS, int B, int C, int N, int K,
-                     int linkpred, void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(prob); NOTNULL(label);
-    NONNEG(B); NONNEG(C);
-    DP_CHECK_ARG(!linkpred || (S && adj && dS && N > 0 && K > 0), "linkpred needs S, adj, dS, N, K");
-    DEVICE_GATE("dp_loss_backward");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    loss_bwd_seq(q, prob, label, S, adj, num_nodes, link_norm, dloss, d_ypred, dS, B, C, N, K, linkpred);
-    return q.err;
+                    const float* link_norm, float* loss_out, float* prob, float* d_ypred_unit, int B, int C, int N,
+                    int K, int linkpred, void* workspace, size_t workspace_bytes, void* stream) {
+    return loss_forward_entry("dp_loss_forward", false, ypred, label, S, adj, nullptr, num_nodes, link_norm, loss_out,
+                              prob, d_ypred_unit, B, C, N, K, linkpred, workspace, workspace_bytes, stream);
 }
 int dp_loss_forward_packed(const float* ypred, const long long* label, const float* S, const void* adj_pk,
                            const void* adj_pkt, const int* num_nodes, const float* link_norm, float* loss_out,
                            float* prob, float* d_ypred_unit, int B, int C, int N, int K, int linkpred, void* workspace,
                            size_t workspace_bytes, void* stream) {
-    NOTNULL(ypred); NOTNULL(label); NOTNULL(loss_out); NOTNULL(prob);
-    NONNEG(B); NONNEG(C);
-    DP_CHECK_ARG(!linkpred || (S && adj_pk && adj_pkt && N > 0 && K > 0), "linkpred needs S, adj_pk, adj_pkt, N, K");
-    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
-    DEVICE_GATE("dp_loss_forward_packed");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    loss_fwd_seq(q, ypred, label, S, nullptr, num_nodes, link_norm, loss_out, prob, d_ypred_unit, B, C, N, K, linkpred,
-                 static_cast<const unsigned short*>(adj_pk));
-    return q.err;
+    return loss_forward_entry("dp_loss_forward_packed", true, ypred, label, S, adj_pk, adj_pkt, num_nodes, link_norm,
+                              loss_out, prob, d_ypred_unit, B, C, N, K, linkpred, workspace, workspace_bytes, stream);
+}
+int dp_loss_backward(const float* prob, const long long* label, const float* S, const float* adj, const int* num_nodes,
+                     const float* link_norm, const float* dloss, float* d_ypred, float* dS, int B, int C, int N, int K,
+                     int linkpred, void* workspace, size_t workspace_bytes, void* stream) {
+    return loss_backward_entry("dp_loss_backward", false, prob, label, S, adj, nullptr, num_nodes, link_norm, dloss,
+                               d_ypred, dS, B, C, N, K, linkpred, workspace, workspace_bytes, stream);
 }
 int dp_loss_backward_packed(const float* prob, const long long* label, const float* S, const void* adj_pk,
                             const void* adj_pkt, const int* num_nodes, const float* link_norm, const float* dloss,
                             float* d_ypred, float* dS, int B, int C, int N, int K, int linkpred, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    NOTNULL(prob); NOTNULL(label);
-    NONNEG(B); NONNEG(C);
-    DP_CHECK_ARG(!linkpred || (S && adj_pk && adj_pkt && dS && N > 0 && K > 0),
-                 "linkpred needs S, adj_pk, adj_pkt, dS, N, K");
-    ALIGNED16(adj_pk); ALIGNED16(adj_pkt);
-    DEVICE_GATE("dp_loss_backward_packed");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    loss_bwd_seq(q, prob, label, S, nullptr, num_nodes, link_norm, dloss, d_ypred, dS, B, C, N, K, linkpred,
-                 static_cast<const unsigned short*>(adj_pk), static_cast<const unsigned short*>(adj_pkt));
-    return q.err;
+    return loss_backward_entry("dp_loss_backward_packed", true, prob, label, S, adj_pk, adj_pkt, num_nodes, link_norm,
+                               dloss, d_ypred, dS, B, C, N, K, linkpred, workspace, workspace_bytes, stream);
 }
 
-int dp_build_batch(const int* edge_src, const int* edge_dst, const int* edge_ptr, const int* node_label,
-                   const int* node_ptr, float* adj, float* feats, float* assign_feats, int* num_nodes, int* errors,
-                   int* degree, int B, int N, int F, int feature_mode, int symmetric, int max_edges_per_graph,
-                   void* stream) {
-    NOTNULL(edge_src); NOTNULL(edge_dst); NOTNULL(edge_ptr); NOTNULL(node_ptr); NOTNULL(adj); NOTNULL(num_nodes);
-    NOTNULL(errors);
-    NONNEG(B); NONNEG(N);
+// adj: the fp32 batch, or NULL beside the packed planes adj_pk / adj_pkt of dp_build_batch_packed
+static int build_batch_entry(const int* edge_src, const int* edge_dst, const int* edge_ptr, const int* node_label,
+                             const int* node_ptr, float* adj, void* adj_pk, void* adj_pkt, bool packed, float* feats,
+                             float* assign_feats, int* num_nodes, int* errors, int* degree, int B, int N, int F,
+                             int feature_mode, int symmetric, int max_edges_per_graph, void* stream) {
+    DP_NOTNULL(edge_src); DP_NOTNULL(edge_dst); DP_NOTNULL(edge_ptr); DP_NOTNULL(node_ptr);
+    if (packed) {
+        DP_NOTNULL(adj_pk); DP_NOTNULL(adj_pkt);
+    } else {
+        DP_NOTNULL(adj);
+    }
+    DP_NOTNULL(num_nodes); DP_NOTNULL(errors);
+    DP_POS(B); DP_POS(N);
     DP_CHECK_ARG(feature_mode >= 0 && feature_mode <= 3, "feature_mode=%d (0 default, 1 id, 2 deg-num, 3 deg)",
                  feature_mode);
+    if (packed)
+        DP_CHECK_ARG(adj_pk != adj_pkt || symmetric, "A and A^T may share one buffer only for a symmetric edge list");
     const bool labels = feature_mode == 0 || feature_mode == 3;
     DP_CHECK_ARG(!(feats || assign_feats) || !labels || (node_label && F > 0),
                  "label-based features need node labels and F > 0");
     DP_CHECK_ARG(feature_mode < 2 || degree, "deg / deg-num features need the degree workspace (B*N ints)");
-    Seq q(STREAM(stream), nullptr, 0);
-    build_batch(q, edge_src, edge_dst, edge_ptr, node_label, node_ptr, adj, nullptr, nullptr, feats, assign_feats,
-                num_nodes, errors, degree, B, N, F, feature_mode, symmetric, max_edges_per_graph);
-    return q.err;
-}
-
-int dp_build_batch_packed(const int* edge_src, const int* edge_dst, const int* edge_ptr, const int* node_label,
-                          const int* node_ptr, void* adj_pk, void* adj_pkt, float* feats, float* assign_feats,
-                          int* num_nodes, int* errors, int* degree, int B, int N, int F, int feature_mode, int symmetric,
-                          int max_edges_per_graph, void* stream) {
-    NOTNULL(edge_src); NOTNULL(edge_dst); NOTNULL(edge_ptr); NOTNULL(node_ptr); NOTNULL(adj_pk); NOTNULL(adj_pkt);
-    NOTNULL(num_nodes); NOTNULL(errors);
-    NONNEG(B); NONNEG(N);
-    DP_CHECK_ARG(feature_mode >= 0 && feature_mode <= 3, "feature_mode=%d (0 default, 1 id, 2 deg-num, 3 deg)",
-                 feature_mode);
-    DP_CHECK_ARG(adj_pk != adj_pkt || symmetric, "A and A^T may share one buffer only for a symmetric edge list");
-    const bool labels = feature_mode == 0 || feature_mode == 3;
-    DP_CHECK_ARG(!(feats || assign_feats) || !labels || (node_label && F > 0),
-                 "label-based features need node labels and F > 0");
-    DP_CHECK_ARG(feature_mode < 2 || degree, "deg / deg-num features need the degree workspace (B*N ints)");
-    Seq q(STREAM(stream), nullptr, 0);
-    build_batch(q, edge_src, edge_dst, edge_ptr, node_label, node_ptr, nullptr, static_cast<unsigned short*>(adj_pk),
+    Seq q(DP_STREAM(stream), nullptr, 0);
+    build_batch(q, edge_src, edge_dst, edge_ptr, node_label, node_ptr, adj, static_cast<unsigned short*>(adj_pk),
                 static_cast<unsigned short*>(adj_pkt), feats, assign_feats, num_nodes, errors, degree, B, N, F,
                 feature_mode, symmetric, max_edges_per_graph);
     return q.err;
 }
+int dp_build_batch(const int* edge_src, const int* edge_dst, const int* edge_ptr, const int* node_label,
+                   const int* node_ptr, float* adj, float* feats, float* assign_feats, int* num_nodes, int* errors,
+                   int* degree, int B, int N, int F, int feature_mode, int symmetric, int max_edges_per_graph,
+                   void* stream) {
+    return build_batch_entry(edge_src, edge_dst, edge_ptr, node_label, node_ptr, adj, nullptr, nullptr, false, feats,
+                             assign_feats, num_nodes, errors, degree, B, N, F, feature_mode, symmetric,
+                             max_edges_per_graph, stream);
+}
+int dp_build_batch_packed(const int* edge_src, const int* edge_dst, const int* edge_ptr, const int* node_label,
+                          const int* node_ptr, void* adj_pk, void* adj_pkt, float* feats, float* assign_feats,
+                          int* num_nodes, int* errors, int* degree, int B, int N, int F, int feature_mode,
+                          int symmetric, int max_edges_per_graph, void* stream) {
+    return build_batch_entry(edge_src, edge_dst, edge_ptr, node_label, node_ptr, nullptr, adj_pk, adj_pkt, true, feats,
+                             assign_feats, num_nodes, errors, degree, B, N, F, feature_mode, symmetric,
+                             max_edges_per_graph, stream);
+}
 
 int dp_gather_labels(const long long* graph_label, long long* label_out, int B, void* stream) {
-    NOTNULL(graph_label); NOTNULL(label_out);
-    NONNEG(B);
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_NOTNULL(graph_label); DP_NOTNULL(label_out);
+    DP_POS(B);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     gather_labels(q, graph_label, label_out, B);
     return q.err;
 }
 
 size_t dp_clip_adam_workspace_bytes(void) { return 4096; }
-int dp_clip_adam_step_counted(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, int* step_counter,
-                              float lr, float beta1, float beta2, float eps, float max_norm, float* total_norm_out,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-    NOTNULL(params); NOTNULL(grads); NOTNULL(exp_avg); NOTNULL(exp_avg_sq); NOTNULL(step_counter);
+// step_counter: the device counter of dp_clip_adam_step_counted, which needs no host step; NULL: `step` is this
+// update's 1-based count and the bias corrections come from the host
+static int clip_adam_entry(const char* fn, bool counted, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                           long n, int* step_counter, int step, float lr, float beta1, float beta2, float eps,
+                           float max_norm, float* total_norm_out, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    DP_NOTNULL(params); DP_NOTNULL(grads); DP_NOTNULL(exp_avg); DP_NOTNULL(exp_avg_sq);
+    if (counted) DP_NOTNULL(step_counter);
     DP_CHECK_ARG(n >= 0, "n=%ld must be >= 0", n);
+    if (!counted) DP_CHECK_ARG(step >= 1, "step=%d is the 1-based count of this update", step);
     DP_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "betas (%g, %g) must lie in [0, 1)",
                  (double)beta1, (double)beta2);
-    DEVICE_GATE("dp_clip_adam_step_counted");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
-    clip_adam_step(q, params, grads, exp_avg, exp_avg_sq, n, max_norm, beta1, beta2, eps, 0.f, 0.f, total_norm_out,
-                   step_counter, lr);
-    return q.err;
-}
-int dp_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, int step, float lr,
-                      float beta1, float beta2, float eps, float max_norm, float* total_norm_out, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-    NOTNULL(params); NOTNULL(grads); NOTNULL(exp_avg); NOTNULL(exp_avg_sq);
-    DP_CHECK_ARG(n >= 0, "n=%ld must be >= 0", n);
-    DP_CHECK_ARG(step >= 1, "step=%d is the 1-based count of this update", step);
-    DP_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "betas (%g, %g) must lie in [0, 1)",
-                 (double)beta1, (double)beta2);
-    DEVICE_GATE("dp_clip_adam_step");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    DEVICE_GATE(fn);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
+    if (counted) {
+        clip_adam_step(q, params, grads, exp_avg, exp_avg_sq, n, max_norm, beta1, beta2, eps, 0.f, 0.f, total_norm_out,
+                       step_counter, lr);
+        return q.err;
+    }
     // bias corrections in double on the host, exactly as torch.optim.Adam's single-tensor path computes them
     const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
     const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
     clip_adam_step(q, params, grads, exp_avg, exp_avg_sq, n, max_norm, beta1, beta2, eps, (float)((double)lr / bc1),
                    (float)(1.0 / std::sqrt(bc2)), total_norm_out);
     return q.err;
+}
+int dp_clip_adam_step_counted(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, int* step_counter,
+                              float lr, float beta1, float beta2, float eps, float max_norm, float* total_norm_out,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    return clip_adam_entry("dp_clip_adam_step_counted", true, params, grads, exp_avg, exp_avg_sq, n, step_counter, 0,
+                           lr, beta1, beta2, eps, max_norm, total_norm_out, workspace, workspace_bytes, stream);
+}
+int dp_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, int step, float lr,
+                      float beta1, float beta2, float eps, float max_norm, float* total_norm_out, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return clip_adam_entry("dp_clip_adam_step", false, params, grads, exp_avg, exp_avg_sq, n, nullptr, step, lr, beta1,
+                           beta2, eps, max_norm, total_norm_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -16,13 +16,15 @@ namespace dp {
 void set_error(const char* fmt, ...);
 const char* last_error();
 
-#define DP_CHECK_ARG(cond, ...)                      \
-    do {                                             \
-        if (!(cond)) {                               \
-            ::dp::set_error(__VA_ARGS__);            \
-            return DP_ERR_INVALID_ARG;               \
-        }                                            \
+// A refusal sets the error text and returns its code.  dp_entry.h builds the checks of the C entries on these two.
+#define DP_CHECK(cond, code, ...)         \
+    do {                                  \
+        if (!(cond)) {                    \
+            ::dp::set_error(__VA_ARGS__); \
+            return code;                  \
+        }                                 \
     } while (0)
+#define DP_CHECK_ARG(cond, ...) DP_CHECK(cond, DP_ERR_INVALID_ARG, __VA_ARGS__)
 
 // ----------------------------------------------------------------- device-side failures (see diffpool_hip.h)
 // Device-visible pointer to the current device's error word (pinned, mapped host memory; nullptr when it could not be
@@ -747,5 +749,34 @@ void frob_link_fwd(Seq& q, const float* S, int lds, const float* W, const void* 
 void frob_link_bwd(Seq& q, const float* S, int lds, const float* W, const float* G, const int* num_nodes,
                    const int* node_off, const float* link_norm, const float* dloss, float wscale, float* dS, int ldds,
                    int accumulate, int B, int N, long long rows, int K);
+
+// (dp_model.hip) the encoder; given: the caller's packed level-0 adjacency (adj is NULL then)
+int encoder_forward(Seq& q, const dp_encoder_cfg& c, const float* params, const float* x, const float* adj,
+                    const float* assign_x, const int* num_nodes, const float* dropout, float* ypred,
+                    float* assign_out, void* save, int mode, long long* labels_out, const PackedAdj* given = nullptr);
+int encoder_backward(Seq& q, const dp_encoder_cfg& c, const float* params, const float* x, const float* adj,
+                     const float* assign_x, const int* num_nodes, const float* dropout, const float* d_ypred,
+                     const float* d_assign, float* grads, const void* save, int prezeroed,
+                     const PackedAdj* given = nullptr);
+size_t encoder_save_bytes(const dp_encoder_cfg& c);
+int encoder_validate(const dp_encoder_cfg* c);
+int encoder_save_locate(const dp_encoder_cfg& c, int level, int field, size_t* offset, size_t* count);
+// (dp_set2set.hip)
+void set2set_fwd(Seq& q, const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
+                 const float* b_hh, const float* Wp, const float* bp, float* out, int B, int n, int d, void* save);
+void set2set_bwd(Seq& q, const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
+                 const float* b_hh, const float* Wp, const float* bp, const float* out, const float* dout,
+                 float* demb, int ldde, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, float* dWp,
+                 float* dbp, int B, int n, int d, const void* save);
+size_t set2set_save_bytes(int B, int n, int d);
+int set2set_plan(int n, int d);
+// (dp_csr_edge_grad.hip) out[e] = P_i . Q_indices[e] over the stored entries
+void csr_sddmm_identity(Seq& q, const float* P, int ldp, const float* Q, int ldq, const int* indptr, const int* indices,
+                        float* out, int n_rows, int F);
+// (dp_meanagg.hip)
+void mean_aggregate_fwd(Seq& q, const float* table, int ldt, const int* indptr, const int* indices, float* out,
+                        int ldo, int n_rows, int feat);
+void mean_aggregate_bwd(Seq& q, const float* dout, int ldo, const int* indptr, const int* indices, float* dtable,
+                        int ldt, int n_rows, int feat);
 
 }  // namespace dp

@@ -237,16 +237,13 @@ void csr_sddmm_identity(Seq& q, const float* P, int ldp, const float* Q, int ldq
 
 using namespace dp;
 
-#define STREAM(s) ((hipStream_t)(s))
-#define SD_NONNEG(v) DP_CHECK((v) >= 0, DP_ERR_INVALID_ARG, #v "=%d must not be negative", (int)(v))
-#define SD_POS(v) DP_CHECK((v) > 0, DP_ERR_INVALID_ARG, #v "=%d must be positive", (int)(v))
 #define SD_LD(ld, w) DP_CHECK((ld) >= (w), DP_ERR_INVALID_ARG, #ld "=%d smaller than " #w "=%d", (int)(ld), (int)(w))
 
 extern "C" {
 
 int dp_csr_sddmm_plan(int F, int ldp, int ldq, int p_misaligned, int q_misaligned, int* plan_out) {
     DP_NOTNULL(plan_out);
-    SD_POS(F);
+    DP_POS(F);
     SD_LD(ldp, F);
     SD_LD(ldq, F);
     const SddmmPick k = sddmm_pick(F, ldp, ldq, p_misaligned != 0, q_misaligned != 0);
@@ -259,11 +256,11 @@ int dp_csr_sddmm(const float* P, int ldp, const float* Q, int ldq, const int* in
                  int n_rows, int F, float alpha, const float* dscale, float beta, void* stream) {
     DP_PTR(P); DP_PTR(Q); DP_PTR(indptr); DP_PTR(indices); DP_PTR(out);
     DP_ALIGNED4(dscale);
-    SD_NONNEG(n_rows);
-    SD_NONNEG(F);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(F);
     SD_LD(ldp, F);
     SD_LD(ldq, F);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     csr_sddmm(q, SddmmArgs{P, ldp, Q, ldq, indptr, indices, nullptr, out, n_rows, F, alpha, dscale, beta}, EPI_ID);
     return q.err;
 }
@@ -274,12 +271,12 @@ int dp_csr_link_dvalues(const float* S, int lds, const int* indptr, const int* i
     DP_PTR(S); DP_PTR(indptr); DP_PTR(indices); DP_PTR(dvalues);
     DP_ALIGNED4(values);
     DP_ALIGNED4(dloss);
-    SD_NONNEG(n_rows);
-    SD_POS(K);
+    DP_NONNEG(n_rows);
+    DP_POS(K);
     SD_LD(lds, K);
     DP_CHECK(objective == 0 || objective == 1, DP_ERR_INVALID_ARG,
              "objective=%d: 0 (cross entropy) or 1 (frobenius)", objective);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     csr_sddmm(q, SddmmArgs{S, lds, S, lds, indptr, indices, values, dvalues, n_rows, K, inv_norm, dloss, 0.f},
               objective == 1 ? EPI_FROB : EPI_BCE);
     return q.err;
@@ -296,9 +293,9 @@ int dp_csr_pool_dvalues(const float* S, int lds, const int* indptr, const int* i
                         const int* node_off_host, int B, float* dvalues, int n_total, int K, void* workspace,
                         size_t workspace_bytes, void* stream) {
     DP_PTR(S); DP_PTR(indptr); DP_PTR(indices); DP_PTR(dAp); DP_PTR(dvalues);
-    SD_NONNEG(n_total);
-    SD_POS(K);
-    SD_POS(B);
+    DP_NONNEG(n_total);
+    DP_POS(K);
+    DP_POS(B);
     SD_LD(lds, K);
     if (node_off_host) {
         DP_CHECK(node_off_host[0] == 0 && node_off_host[B] == n_total, DP_ERR_INVALID_ARG,
@@ -313,7 +310,7 @@ int dp_csr_pool_dvalues(const float* S, int lds, const int* indptr, const int* i
              workspace_bytes);
     if (n_total == 0) return DP_OK;
     DP_ALIGNED16(workspace, false, "workspace is NULL or not 16-byte aligned");
-    Seq q(STREAM(stream), workspace, workspace_bytes);
+    Seq q(DP_STREAM(stream), workspace, workspace_bytes);
     pool_dvalues_seq(q, S, lds, indptr, indices, dAp, node_off_host, B, dvalues, n_total, K);
     return q.err;
 }

@@ -201,15 +201,12 @@ __global__ __launch_bounds__(EO_THREADS) void k_edge_sym_dvalues(const int* __re
 
 using namespace dp;
 
-#define STREAM(s) ((hipStream_t)(s))
-#define EO_NONNEG(v) DP_CHECK((v) >= 0, DP_ERR_INVALID_ARG, #v "=%d must not be negative", (int)(v))
-
 extern "C" {
 
 int dp_csr_edge_plan(int n_rows, int nnz, int* plan_out) {
     DP_NOTNULL(plan_out);
-    EO_NONNEG(n_rows);
-    EO_NONNEG(nnz);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(nnz);
     const EdgePick k = edge_pick(n_rows, nnz);
     const int plan[DP_CSR_EDGE_PLAN_INTS] = {k.lanes, k.regs, k.rows_per_wg, k.lanes * k.regs};
     memcpy(plan_out, plan, sizeof(plan));
@@ -218,10 +215,10 @@ int dp_csr_edge_plan(int n_rows, int nnz, int* plan_out) {
 
 int dp_csr_edge_softmax_fwd(const float* scores, const int* indptr, float* out, int n_rows, int nnz, void* stream) {
     DP_PTR(scores); DP_PTR(indptr); DP_PTR(out);
-    EO_NONNEG(n_rows);
-    EO_NONNEG(nnz);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(nnz);
     if (n_rows == 0 || nnz == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const EdgePick k = edge_pick(n_rows, nnz);
     EO_LAUNCH(q, k, n_rows, k_edge_softmax_fwd, scores, indptr, out, n_rows);
     return q.err;
@@ -230,10 +227,10 @@ int dp_csr_edge_softmax_fwd(const float* scores, const int* indptr, float* out, 
 int dp_csr_edge_softmax_bwd(const float* out, const float* dout, const int* indptr, float* dscores, int n_rows, int nnz,
                             void* stream) {
     DP_PTR(out); DP_PTR(dout); DP_PTR(indptr); DP_PTR(dscores);
-    EO_NONNEG(n_rows);
-    EO_NONNEG(nnz);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(nnz);
     if (n_rows == 0 || nnz == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const EdgePick k = edge_pick(n_rows, nnz);
     EO_LAUNCH(q, k, n_rows, k_edge_softmax_bwd, out, dout, indptr, dscores, n_rows);
     return q.err;
@@ -248,10 +245,10 @@ int dp_csr_sym_norm_fwd(const int* indptr, const int* indices, const float* valu
     DP_CHECK(mirror != nullptr || !own_transpose(indices, indices_t), DP_ERR_INVALID_ARG,
              "mirror is NULL beside a transposed CSR of its own (indices_t is not indices)");
     DP_PTR(rdeg); DP_PTR(out);
-    EO_NONNEG(n);
-    EO_NONNEG(nnz);
+    DP_NONNEG(n);
+    DP_NONNEG(nnz);
     if (n == 0 || nnz == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const EdgePick k = edge_pick(n, nnz);
     EO_LAUNCH(q, k, n, k_edge_sym_rdeg, indptr_t, mirror, values, rdeg, n);
     EO_LAUNCH(q, k, n, k_edge_sym_scale, indptr, indices, values, (const float*)rdeg, out, n);
@@ -265,10 +262,10 @@ int dp_csr_sym_norm_bwd(const int* indptr, const int* indices, const float* valu
     DP_ALIGNED4(values);
     DP_PTR(indptr_t); DP_PTR(indices_t);
     DP_PTR(mirror); DP_PTR(rdeg); DP_PTR(dout); DP_PTR(gdeg); DP_PTR(dvalues);
-    EO_NONNEG(n);
-    EO_NONNEG(nnz);
+    DP_NONNEG(n);
+    DP_NONNEG(nnz);
     if (n == 0 || nnz == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const EdgePick k = edge_pick(n, nnz);
     EO_LAUNCH(q, k, n, k_edge_sym_gdeg, indptr, indices, values, indptr_t, indices_t, mirror, rdeg, dout, gdeg, n);
     EO_LAUNCH(q, k, n, k_edge_sym_dvalues, indptr, indices, rdeg, (const float*)gdeg, dout, dvalues, n);

@@ -333,8 +333,6 @@ void gat_dispatch(int lanes, int H, int vec, F&& f) {
 
 using namespace dp;
 
-#define STREAM(s) ((hipStream_t)(s))
-#define GAT_NONNEG(v) DP_CHECK((v) >= 0, DP_ERR_INVALID_ARG, #v "=%d must not be negative", (int)(v))
 #define GAT_HEADS(H)                                                                                        \
     DP_CHECK((H) >= 1 && (H) <= DP_CSR_GAT_MAX_HEADS, DP_ERR_INVALID_ARG, "H=%d must be 1 .. %d", (int)(H), \
              DP_CSR_GAT_MAX_HEADS)
@@ -345,8 +343,8 @@ extern "C" {
 
 int dp_csr_gat_plan(int n_rows, int nnz, int H, int ldv, int v_misaligned, int* plan_out) {
     DP_NOTNULL(plan_out);
-    GAT_NONNEG(n_rows);
-    GAT_NONNEG(nnz);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(nnz);
     GAT_HEADS(H);
     GAT_LD(ldv, H);
     const GatPick k = gat_pick(n_rows, nnz, H, ldv, v_misaligned != 0);
@@ -358,14 +356,14 @@ int dp_csr_gat_plan(int n_rows, int nnz, int H, int ldv, int v_misaligned, int* 
 int dp_csr_gat_fwd(const float* u, int ldu, const float* v, int ldv, const int* indptr, const int* indices, float* out,
                    float* rowstat, int n_rows, int nnz, int H, float slope, void* stream) {
     DP_PTR(u); DP_PTR(v); DP_PTR(indptr); DP_PTR(indices); DP_PTR(out); DP_PTR(rowstat);
-    GAT_NONNEG(n_rows);
-    GAT_NONNEG(nnz);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(nnz);
     GAT_HEADS(H);
     GAT_LD(ldu, H);
     GAT_LD(ldv, H);
     GAT_SLOPE(slope);
     if (n_rows == 0 || nnz == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const GatPick k = gat_pick(n_rows, nnz, H, ldv, !aligned16(v));
     const dim3 grid(cdiv(n_rows, k.rows_per_wg)), block(EO_THREADS);
     gat_dispatch(k.lanes, H, k.vec, [&](auto lc, auto hc, auto vc) {
@@ -382,8 +380,8 @@ int dp_csr_gat_bwd(const float* u, int ldu, const float* v, int ldv, const int* 
                    float slope, void* stream) {
     DP_PTR(u); DP_PTR(v); DP_PTR(indptr); DP_PTR(indices); DP_PTR(indptr_t); DP_PTR(indices_t); DP_PTR(mirror);
     DP_PTR(rowstat); DP_PTR(dout); DP_PTR(tdot); DP_PTR(du); DP_PTR(dv);
-    GAT_NONNEG(n);
-    GAT_NONNEG(nnz);
+    DP_NONNEG(n);
+    DP_NONNEG(nnz);
     GAT_HEADS(H);
     GAT_LD(ldu, H);
     GAT_LD(ldv, H);
@@ -392,7 +390,7 @@ int dp_csr_gat_bwd(const float* u, int ldu, const float* v, int ldv, const int* 
     GAT_SLOPE(slope);
     if (n == 0) return DP_OK;
     // nnz == 0: every row and every column is empty, the two launches write the zero du, dv (indptr all zero)
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const GatPick k = gat_pick(n, nnz, H, ldv, !aligned16(v));
     const int vec_u = gat_vec_ok(H, ldu, !aligned16(u) || !aligned16(rowstat) || !aligned16(tdot)) ? 4 : 1;
     const dim3 grid(cdiv(n, k.rows_per_wg)), block(EO_THREADS);

@@ -439,14 +439,7 @@ int conv_shape(int H, int C) {
 
 using namespace dp;
 
-#define STREAM(s) ((hipStream_t)(s))
-#define GC_NONNEG(v) DP_CHECK((v) >= 0, DP_ERR_INVALID_ARG, #v "=%d must not be negative", (int)(v))
-#define GC_LD(ld, w) DP_CHECK((ld) >= (w), DP_ERR_INVALID_ARG, #ld "=%d smaller than its width %d", (int)(ld), (int)(w))
-#define GC_SHAPE(H, C)                           \
-    do {                                         \
-        const int rc_ = conv_shape(H, C);        \
-        if (rc_ != DP_OK) return rc_;            \
-    } while (0)
+#define GC_SHAPE(H, C) DP_TRY(conv_shape(H, C))
 #define GC_FLAGS(slope, mean_heads)                                                                      \
     do {                                                                                                 \
         DP_CHECK(isfinite(slope), DP_ERR_INVALID_ARG, "slope must be finite");                           \
@@ -458,10 +451,10 @@ extern "C" {
 
 int dp_csr_gat_conv_plan(int n_rows, int nnz, int H, int C, int ldz, int z_misaligned, int* plan_out) {
     DP_NOTNULL(plan_out);
-    GC_NONNEG(n_rows);
-    GC_NONNEG(nnz);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(nnz);
     GC_SHAPE(H, C);
-    GC_LD(ldz, H * C);
+    DP_LD(ldz, H * C);
     const ConvPick k = conv_pick(n_rows, nnz, H * C, C, ldz, z_misaligned != 0);
     const int plan[DP_CSR_GAT_CONV_PLAN_INTS] = {k.vec, k.nch, k.uni, GC_THREADS / 64, k.vec * k.nch, k.lanes};
     memcpy(plan_out, plan, sizeof(plan));
@@ -472,17 +465,17 @@ int dp_csr_gat_conv_fwd(const float* z, int ldz, const float* u, int ldu, const 
                         const int* indices, float* y, int ldy, float* rowstat, int n_rows, int nnz, int H, int C,
                         float slope, int mean_heads, void* stream) {
     DP_PTR(z); DP_PTR(u); DP_PTR(v); DP_PTR(indptr); DP_PTR(indices); DP_PTR(y); DP_PTR(rowstat);
-    GC_NONNEG(n_rows);
-    GC_NONNEG(nnz);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(nnz);
     GC_SHAPE(H, C);
     GC_FLAGS(slope, mean_heads);
-    GC_LD(ldz, H * C);
-    GC_LD(ldu, H);
-    GC_LD(ldv, H);
-    GC_LD(ldy, mean_heads ? C : H * C);
+    DP_LD(ldz, H * C);
+    DP_LD(ldu, H);
+    DP_LD(ldv, H);
+    DP_LD(ldy, mean_heads ? C : H * C);
     if (n_rows == 0) return DP_OK;
     // nnz == 0: every row is empty, the launches write the zero rowstat and y (indptr all zero)
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const ConvPick k = conv_pick(n_rows, nnz, H * C, C, ldz, !aligned16(z));
     const dim3 sgrid(cdiv(n_rows, EO_THREADS / k.lanes)), sblock(EO_THREADS);
     if (k.lanes == 4)
@@ -512,20 +505,20 @@ int dp_csr_gat_conv_bwd(const float* z, int ldz, const float* u, int ldu, const 
                         int lddz, int n, int nnz, int H, int C, float slope, int mean_heads, void* stream) {
     DP_PTR(z); DP_PTR(u); DP_PTR(v); DP_PTR(indptr); DP_PTR(indices); DP_PTR(indptr_t); DP_PTR(indices_t);
     DP_PTR(rowstat); DP_PTR(dy); DP_PTR(tdot); DP_PTR(du); DP_PTR(dv); DP_PTR(dz);
-    GC_NONNEG(n);
-    GC_NONNEG(nnz);
+    DP_NONNEG(n);
+    DP_NONNEG(nnz);
     GC_SHAPE(H, C);
     GC_FLAGS(slope, mean_heads);
-    GC_LD(ldz, H * C);
-    GC_LD(ldu, H);
-    GC_LD(ldv, H);
-    GC_LD(lddy, mean_heads ? C : H * C);
-    GC_LD(lddu, H);
-    GC_LD(lddv, H);
-    GC_LD(lddz, H * C);
+    DP_LD(ldz, H * C);
+    DP_LD(ldu, H);
+    DP_LD(ldv, H);
+    DP_LD(lddy, mean_heads ? C : H * C);
+    DP_LD(lddu, H);
+    DP_LD(lddv, H);
+    DP_LD(lddz, H * C);
     if (n == 0) return DP_OK;
     // nnz == 0: every row and every column is empty, the two launches write the zero t, du, dv, dz
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     // both passes gather with one form: z (rows) and dy (columns) must both allow the 16-byte loads, and a quad of the
     // mean's dy [n, C] must not straddle heads
     const ConvPick k =

@@ -338,24 +338,16 @@ int sample_shape(int k, int self_mode) {
 
 using namespace dp;
 
-#define STREAM(s) ((hipStream_t)(s))
-#define SM_NONNEG(v) DP_CHECK((v) >= 0, DP_ERR_INVALID_ARG, #v "=%d must not be negative", (int)(v))
-#define SM_LD(ld, w) DP_CHECK((ld) >= (w), DP_ERR_INVALID_ARG, #ld "=%d smaller than its width %d", (int)(ld), (int)(w))
-#define SM_ALIGNED8(p) DP_CHECK(((uintptr_t)(p) & 7) == 0, DP_ERR_INVALID_ARG, #p " is not 8-byte aligned")
-#define SM_SHAPE(k, self_mode)                    \
-    do {                                          \
-        const int rc_ = sample_shape(k, self_mode); \
-        if (rc_ != DP_OK) return rc_;             \
-    } while (0)
+#define SM_SHAPE(k, self_mode) DP_TRY(sample_shape(k, self_mode))
 
 extern "C" {
 
 int dp_csr_sample_mean_plan(int n_rows, int n, int F, int k, int self_mode, int d, int* plan_out) {
     DP_NOTNULL(plan_out);
-    SM_NONNEG(n_rows);
-    SM_NONNEG(n);
-    SM_NONNEG(F);
-    SM_NONNEG(d);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(n);
+    DP_NONNEG(F);
+    DP_NONNEG(d);
     SM_SHAPE(k, self_mode);
     DP_CHECK(n_rows <= n, DP_ERR_INVALID_ARG, "n_rows=%d exceeds n=%d", n_rows, n);
     const SamplePick p = sample_pick(n_rows, n, F, k, d);
@@ -369,18 +361,18 @@ int dp_csr_sample_mean_fwd(const float* x, int ldx, const int* indptr, const int
                            int ldy, unsigned long long* thr, int* cnt, int n_rows, int n, int F, int k, int self_mode,
                            long seed, void* stream) {
     DP_PTR(x); DP_PTR(indptr); DP_PTR(indices); DP_PTR(y); DP_PTR(thr); DP_PTR(cnt);
-    SM_ALIGNED8(thr);
+    DP_ALIGNED8(thr);
     if (nodes) DP_ALIGNED4(nodes);
-    SM_NONNEG(n_rows);
-    SM_NONNEG(n);
-    SM_NONNEG(F);
+    DP_NONNEG(n_rows);
+    DP_NONNEG(n);
+    DP_NONNEG(F);
     SM_SHAPE(k, self_mode);
     DP_CHECK(n_rows <= n, DP_ERR_INVALID_ARG, "n_rows=%d exceeds n=%d", n_rows, n);
     DP_CHECK(nodes || n_rows == n, DP_ERR_INVALID_ARG, "n_rows=%d differs from n=%d without nodes", n_rows, n);
-    SM_LD(ldx, F);
-    SM_LD(ldy, self_mode == DP_CSR_SAMPLE_SELF_CONCAT ? 2 * F : F);
+    DP_LD(ldx, F);
+    DP_LD(ldy, self_mode == DP_CSR_SAMPLE_SELF_CONCAT ? 2 * F : F);
     if (n_rows == 0 || F == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const SamplePick p = sample_pick(n_rows, n, F, k, 0);
     const unsigned long long s = (unsigned long long)seed;
     hipLaunchKernelGGL(k_csr_sample_mean_fwd, dim3(p.grid_fwd), dim3(SM_THREADS), 0, q.stream, x, ldx, indptr, indices,
@@ -393,15 +385,15 @@ int dp_csr_sample_mean_bwd(const float* dy, int lddy, const int* indptr_t, const
                            const unsigned long long* thr, const int* cnt, float* dx, int lddx, int n, int F,
                            int self_mode, long seed, void* stream) {
     DP_PTR(dy); DP_PTR(indptr_t); DP_PTR(indices_t); DP_PTR(thr); DP_PTR(cnt); DP_PTR(dx);
-    SM_ALIGNED8(thr);
+    DP_ALIGNED8(thr);
     if (slot) DP_ALIGNED4(slot);
-    SM_NONNEG(n);
-    SM_NONNEG(F);
+    DP_NONNEG(n);
+    DP_NONNEG(F);
     SM_SHAPE(DP_CSR_SAMPLE_ALL, self_mode);
-    SM_LD(lddy, self_mode == DP_CSR_SAMPLE_SELF_CONCAT ? 2 * F : F);
-    SM_LD(lddx, F);
+    DP_LD(lddy, self_mode == DP_CSR_SAMPLE_SELF_CONCAT ? 2 * F : F);
+    DP_LD(lddx, F);
     if (n == 0 || F == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     const SamplePick p = sample_pick(n, n, F, DP_CSR_SAMPLE_ALL, 0);
     const unsigned long long s = (unsigned long long)seed;
     hipLaunchKernelGGL(k_csr_sample_mean_bwd, dim3(p.grid_bwd), dim3(SM_THREADS), 0, q.stream, dy, lddy, indptr_t,

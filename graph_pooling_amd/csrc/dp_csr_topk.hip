@@ -374,20 +374,15 @@ int topk_tables(const int* node_off_host, const int* kb_host, int n, int n_out, 
 
 using namespace dp;
 
-#define STREAM(s) ((hipStream_t)(s))
-#define TK_NONNEG(v) DP_CHECK((v) >= 0, DP_ERR_INVALID_ARG, #v "=%d must not be negative", (int)(v))
-#define TK_LD(ld, w) DP_CHECK((ld) >= (w), DP_ERR_INVALID_ARG, #ld "=%d smaller than its width %d", (int)(ld), (int)(w))
-#define TK_ALIGNED8(p) DP_CHECK(((uintptr_t)(p) & 7) == 0, DP_ERR_INVALID_ARG, #p " is not 8-byte aligned")
-
 extern "C" {
 
 int dp_csr_topk_plan(int n, int n_out, int B, int max_n, int n_b, int k_b, int F, int* plan_out) {
     DP_NOTNULL(plan_out);
-    TK_NONNEG(n);
-    TK_NONNEG(n_out);
-    TK_NONNEG(B);
-    TK_NONNEG(max_n);
-    TK_NONNEG(F);
+    DP_NONNEG(n);
+    DP_NONNEG(n_out);
+    DP_NONNEG(B);
+    DP_NONNEG(max_n);
+    DP_NONNEG(F);
     DP_CHECK(n_b >= 1 && n_b <= (max_n > 0 ? max_n : 1), DP_ERR_INVALID_ARG, "n_b=%d must be 1 .. max_n=%d", n_b, max_n);
     DP_CHECK(k_b >= 1 && k_b <= n_b, DP_ERR_INVALID_ARG, "k_b=%d must be 1 .. n_b=%d", k_b, n_b);
     DP_CHECK(n_out <= n, DP_ERR_INVALID_ARG, "n_out=%d exceeds n=%d", n_out, n);
@@ -414,16 +409,15 @@ int dp_csr_topk_select(const float* score, const int* node_off, const int* new_o
     DP_PTR(score); DP_PTR(node_off); DP_PTR(new_off); DP_PTR(new_id); DP_PTR(perm); DP_PTR(thr);
     DP_NOTNULL(node_off_host);
     DP_NOTNULL(kb_host);
-    TK_ALIGNED8(thr);
-    TK_NONNEG(n);
-    TK_NONNEG(n_out);
-    TK_NONNEG(B);
+    DP_ALIGNED8(thr);
+    DP_NONNEG(n);
+    DP_NONNEG(n_out);
+    DP_NONNEG(B);
     if (n == 0 && B == 0 && n_out == 0) return DP_OK;
     DP_CHECK(B >= 1, DP_ERR_INVALID_ARG, "B=%d: %d nodes need at least one graph", B, n);
     int max_n = 0;
-    const int rc = topk_tables(node_off_host, kb_host, n, n_out, B, &max_n);
-    if (rc != DP_OK) return rc;
-    Seq q(STREAM(stream), nullptr, 0);
+    DP_TRY(topk_tables(node_off_host, kb_host, n, n_out, B, &max_n));
+    Seq q(DP_STREAM(stream), nullptr, 0);
     hipLaunchKernelGGL(k_csr_topk_select, dim3(B), dim3(tk_threads(max_n)), 0, q.stream, score, node_off, new_off, new_id,
                        perm, thr);
     q.check_launch("k_csr_topk_select");
@@ -439,17 +433,17 @@ int dp_csr_topk_induce(const int* indptr, const int* indices, const int* new_id,
         DP_ALIGNED4(indices_local_out);
         DP_PTR(new_off);
     }
-    TK_NONNEG(n);
-    TK_NONNEG(n_out);
-    TK_NONNEG(B);
-    TK_NONNEG(nnz);
+    DP_NONNEG(n);
+    DP_NONNEG(n_out);
+    DP_NONNEG(B);
+    DP_NONNEG(nnz);
     DP_CHECK(n_out <= n, DP_ERR_INVALID_ARG, "n_out=%d exceeds n=%d", n_out, n);
     DP_CHECK(cap >= nnz, DP_ERR_INVALID_ARG, "cap=%d is below the input's nnz=%d", cap, nnz);
     DP_CHECK(!indices_local_out || B >= 1 || n_out == 0, DP_ERR_INVALID_ARG, "B=%d: indices_local_out needs the graphs", B);
     DP_ALIGNED16(workspace, false, "workspace must be there and 16-byte aligned");
     DP_CHECK(workspace_bytes >= tk_ws_bytes(n_out), DP_ERR_WORKSPACE, "workspace too small: need >= %zu bytes, have %zu",
              tk_ws_bytes(n_out), workspace_bytes);
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     int* bsum = (int*)workspace;
     const int nblk = cdiv(n_out, TK_ROWS_PER_WG);
     if (nblk) {
@@ -472,14 +466,14 @@ int dp_csr_topk_gather_fwd(const float* x, int ldx, const float* gate, const int
                            int F, void* stream) {
     DP_PTR(x); DP_PTR(perm); DP_PTR(y);
     if (gate) DP_ALIGNED4(gate);
-    TK_NONNEG(n);
-    TK_NONNEG(n_out);
-    TK_NONNEG(F);
+    DP_NONNEG(n);
+    DP_NONNEG(n_out);
+    DP_NONNEG(F);
     DP_CHECK(n_out <= n, DP_ERR_INVALID_ARG, "n_out=%d exceeds n=%d", n_out, n);
-    TK_LD(ldx, F);
-    TK_LD(ldy, F);
+    DP_LD(ldx, F);
+    DP_LD(ldy, F);
     if (n_out == 0 || F == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     hipLaunchKernelGGL(k_csr_topk_gather_fwd, dim3(cdiv(n_out, TK_GATHER_THREADS / 64)), dim3(TK_GATHER_THREADS), 0,
                        q.stream, x, ldx, gate, perm, y, ldy, n, n_out, F);
     q.check_launch("k_csr_topk_gather_fwd");
@@ -496,15 +490,15 @@ int dp_csr_topk_gather_bwd(const float* dy, int lddy, const float* x, int ldx, c
         DP_PTR(x);
     }
     if (x) DP_ALIGNED4(x);
-    TK_NONNEG(n);
-    TK_NONNEG(n_out);
-    TK_NONNEG(F);
+    DP_NONNEG(n);
+    DP_NONNEG(n_out);
+    DP_NONNEG(F);
     DP_CHECK(n_out <= n, DP_ERR_INVALID_ARG, "n_out=%d exceeds n=%d", n_out, n);
-    TK_LD(lddy, F);
-    TK_LD(lddx, F);
-    if (dgate) TK_LD(ldx, F);
+    DP_LD(lddy, F);
+    DP_LD(lddx, F);
+    if (dgate) DP_LD(ldx, F);
     if (n == 0 || F == 0) return DP_OK;
-    Seq q(STREAM(stream), nullptr, 0);
+    Seq q(DP_STREAM(stream), nullptr, 0);
     hipLaunchKernelGGL(k_csr_topk_gather_bwd, dim3(cdiv(n, TK_GATHER_THREADS / 64)), dim3(TK_GATHER_THREADS), 0, q.stream,
                        dy, lddy, x, ldx, gate, new_id, dx, lddx, dgate, n, n_out, F);
     q.check_launch("k_csr_topk_gather_bwd");

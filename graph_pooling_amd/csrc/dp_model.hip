@@ -16,14 +16,6 @@
 
 namespace dp {
 
-void set2set_fwd(Seq& q, const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
-                 const float* b_hh, const float* Wp, const float* bp, float* out, int B, int n, int d, void* save);
-void set2set_bwd(Seq& q, const float* emb, int lde, const float* w_ih, const float* w_hh, const float* b_ih,
-                 const float* b_hh, const float* Wp, const float* bp, const float* out, const float* dout,
-                 float* demb, int ldde, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, float* dWp,
-                 float* dbp, int B, int n, int d, const void* save);
-size_t set2set_save_bytes(int B, int n, int d);
-
 namespace {
 
 struct LevelInfo {
