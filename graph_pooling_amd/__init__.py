@@ -6,6 +6,7 @@
     from graph_pooling_amd import EdgeAttention                # learned edge weights in front of the CSR encoders
     from graph_pooling_amd import GatConv                      # multi-head graph-attention layer on CSR graphs / batches
     from graph_pooling_amd import SageConv, SageEncoder        # GraphSAGE layer, the neighbour sample drawn on the device
+    from graph_pooling_amd import NestedSageEncoder            # a SageConv stack on nested mini-batches (sampled blocks)
     from graph_pooling_amd import TopKPooling                  # hard top-k (gPool / SAGPool) pooling, the induced CSR on the device
 
 The arithmetic lives in libdiffpool_hip.so (graph_pooling_amd/csrc, C ABI in include/diffpool_hip.h).
@@ -13,7 +14,7 @@ Importing this package does not load the library; the first forward does, and ra
 """
 __version__ = "0.1.0"
 
-__all__ = ["SparseGcnSet2SetEncoder", "EdgeAttention", "GatConv", "SageConv", "SageEncoder", "TopKPooling"]
+__all__ = ["SparseGcnSet2SetEncoder", "EdgeAttention", "GatConv", "SageConv", "SageEncoder", "TopKPooling", "NestedSageEncoder"]
 
 
 def __getattr__(name):
@@ -27,7 +28,7 @@ def __getattr__(name):
     if name == "GatConv":
         from .sparse import GatConv
         return GatConv
-    if name in ("SageConv", "SageEncoder", "TopKPooling"):
+    if name in ("SageConv", "SageEncoder", "TopKPooling", "NestedSageEncoder"):
         from . import sparse
         return getattr(sparse, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

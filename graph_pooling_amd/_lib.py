@@ -118,6 +118,10 @@ CSR_SAMPLE_SELF = {"none": 0, "gcn": 1, "concat": 2}      # DP_CSR_SAMPLE_SELF_*
 # registers / 2 keys recomputed), its keys per thread, its radix passes, the chunks of its prefix count, workgroups of the
 # select, of an induce count / fill launch, chunks of the scan, workgroups of the gather forward, of the backward)
 CSR_TOPK_PLAN_INTS = 10
+# dp_csr_block_plan: (flags per compaction chunk, chunks, scan steps, the smallest capacity of src (min(n, n_rows (k + 1));
+# n for every neighbour), workgroups of the mark, count and fill launches, of the forward, of the backward at n_src = that
+# capacity, 64-column forward passes, 256-column backward passes)
+CSR_BLOCK_PLAN_INTS = 11
 
 GEMM_GROUP_MAX = 4
 GEMM_WHOLE_K, GEMM_ATOMIC, GEMM_SLABS, GEMM_TICKETS = 0, 1, 2, 3      # dp_gemm_problem.split
@@ -315,6 +319,13 @@ _PROTOS = {
     "dp_csr_topk_induce": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "dp_csr_topk_gather_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dp_csr_topk_gather_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    # sampled frontier blocks for nested GraphSAGE mini-batches: src / slot built on the device, the sampled mean on
+    # compact rows
+    "dp_csr_block_plan": (_I, [_I, _I, _I, _I, C.POINTER(_I)]),
+    "dp_csr_block_workspace_bytes": (_Z, [_I]),
+    "dp_csr_block_build": (_I, [_P, _P, _P, _I, _I, _I, _L, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "dp_csr_block_mean_fwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _L, _P]),
+    "dp_csr_block_mean_bwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _L, _P]),
     "dp_encoder_save_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderCfg)]),
     "dp_encoder_save_locate": (_I, [C.POINTER(EncoderCfg), _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -4,7 +4,8 @@ Mirrors the public surface of the reference's `SupervisedGraphSage` (graphsage.p
 `(num_classes, enc)`, `forward(nodes) -> scores [len(nodes), num_classes]`, `loss(nodes, labels)`, one parameter named
 `weight` of shape `[enc.embed_dim, num_classes]` — on top of an encoder that produces node embeddings (here
 `graph_pooling_amd.aggregators.MeanAggregator`-based encoders, whose mean aggregation runs in `dp_mean_aggregate_*`, or
-`graph_pooling_amd.sparse.SageEncoder`, whose neighbour sample is drawn on the device in `dp_csr_sample_mean_*`).
+`graph_pooling_amd.sparse.SageEncoder`, whose neighbour sample is drawn on the device in `dp_csr_sample_mean_*`, or
+`graph_pooling_amd.sparse.NestedSageEncoder`, a stack of such layers on nested mini-batches, `dp_csr_block_*`).
 
 The reference file cannot run as written: it calls an `init` module it never imports and a
 non-existent `nn.softmax`.  Decisions: Xavier-uniform initialisation of `weight` (what `init.xavier_uniform` meant),

@@ -1415,6 +1415,155 @@ def csr_sample_mean(x, graph, num_sample, seed, nodes=None, self_mode="none", no
     return csr_sample_mean_stats(x, graph, num_sample, seed, nodes, self_mode, nodes_checked)[0]
 
 
+# ----------------------------------------------------------------------------- sampled frontier blocks
+class SampledBlock:
+    """One layer's sampled block of a nested GraphSAGE mini-batch (`csr_sample_block`): for the targets T and the sample
+    S(i) of `csr_sample_mean` at (k, seed),
+
+    graph   the container;   k  the sample size as the C entries take it (0: every neighbour);   seed  in [0, 2^64)
+    nodes   the targets: an int32 device tensor [m] of distinct ids, None (every node), or — the nested form — the
+            SampledBlock whose `src` they are
+    src     int32 [n_src], the ascending, duplicate-free ids of T u U_{i in T} S(i);   n_src  a Python int
+    slot    int32 [n], slot[src[s]] = s and -1 elsewhere
+    thr, cnt  int64 / int32 [m]: each target row's threshold bits (-1: every neighbour taken) and |S(i)|
+
+    All of it is data (no autograd history)."""
+
+    __slots__ = ("graph", "nodes", "src", "slot", "n_src", "thr", "cnt", "k", "seed")
+
+    def __init__(self, graph, nodes, src, slot, n_src, thr, cnt, k, seed):
+        self.graph, self.nodes, self.src, self.slot, self.n_src = graph, nodes, src, slot, n_src
+        self.thr, self.cnt, self.k, self.seed = thr, cnt, k, seed
+
+    @property
+    def targets(self):
+        """The target ids as the kernels read them: an int32 tensor [m], or None for every node."""
+        return self.nodes.src if isinstance(self.nodes, SampledBlock) else self.nodes
+
+    @property
+    def m(self):
+        t = self.targets
+        return self.graph.n if t is None else t.numel()
+
+
+def _seed_word(seed):
+    """A seed in [0, 2^64) as the signed 64-bit word the C entries take."""
+    return seed - (1 << 64) if seed >= 1 << 63 else seed
+
+
+def csr_sample_block(graph, nodes, num_sample, seed, nodes_checked=False):
+    """The sampled block of one GraphSAGE layer, built on the device (dp_csr_block_build; the `unique_nodes_list` of
+    MeanAggregator.forward, aggregators.py:30-63): a `SampledBlock` whose `src` holds, ascending and without duplicates,
+    the targets and every node that `csr_sample_mean(.., num_sample, seed, nodes)` would gather for them — the sample is
+    the same pure function of (seed, i, j).
+
+    `nodes`: an int32 device tensor [m] of DISTINCT node ids (range and distinctness are checked on the host as in
+    `csr_sample_mean`, unless nodes_checked=True), None for every node, or ANOTHER SampledBlock of the same container:
+    the targets are then that block's `src` — the layer below in a nested mini-batch — and its `slot` serves the
+    backward; nothing is scattered and nothing is read back for it.  Five launches whatever m and n, and ONE 4-byte
+    read-back (n_src).  An empty target set returns an empty block without a launch.  Not for hipGraph capture (the
+    read-back; the seed is a kernel argument); weighted sampling, num_sample > 64 and a `src` order with the targets
+    first are out of scope."""
+    k, seed64, _ = _sample_args("csr_sample_block", num_sample, seed, "none")
+    if not hasattr(graph, "indptr") or not hasattr(graph, "n"):
+        raise TypeError(f"csr_sample_block: graph must be a CsrGraph or CsrBatch, got {type(graph).__name__}")
+    n = graph.n
+    if isinstance(nodes, SampledBlock):
+        if nodes.graph is not graph:
+            raise ValueError("csr_sample_block: the block passed as nodes belongs to another container")
+        targets = nodes.src
+    elif nodes is None:
+        targets = None
+    else:
+        if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int32 or nodes.dim() != 1:
+            raise ValueError("csr_sample_block: nodes must be an int32 tensor [m] of distinct node ids, None or a "
+                             "SampledBlock")
+        if not nodes_checked:
+            check_target_nodes("csr_sample_block", nodes, n)
+        nodes = targets = nodes.contiguous()
+    m = n if targets is None else targets.numel()
+    dev = graph.indptr.device
+    if m == 0 or n == 0:                                          # nothing to sample: nothing launched
+        return SampledBlock(graph, nodes, torch.zeros(0, device=dev, dtype=torch.int32),
+                            torch.full((n,), -1, device=dev, dtype=torch.int32), 0,
+                            torch.full((m,), -1, device=dev, dtype=torch.int64),
+                            torch.zeros(m, device=dev, dtype=torch.int32), k, seed)
+    _lib.require_gpu_tensor(graph.indptr, "the container's index arrays")
+    if targets is not None:
+        _lib.require_gpu_tensor(targets, "nodes")
+    lib = _lib.load()
+    cap = n if k == _lib.CSR_SAMPLE_ALL else min(n, m * (k + 1))
+    i32 = lambda count: torch.empty(count, device=dev, dtype=torch.int32)
+    slot, src, count, cnt = i32(n), i32(cap), i32(1), i32(m)
+    thr = torch.empty(m, device=dev, dtype=torch.int64)
+    wsb = lib.dp_csr_block_workspace_bytes(n)
+    ws = _workspace(wsb, slot)
+    _call(lib, "dp_csr_block_build", *_csr_index_args(graph)[0], _lib.ptr(targets), m, n, k, seed64, slot.data_ptr(),
+          src.data_ptr(), cap, count.data_ptr(), thr.data_ptr(), cnt.data_ptr(), ws.data_ptr(), wsb, _lib.current_stream())
+    n_src = int(count.item())                                     # the one read-back of a block: 4 bytes
+    return SampledBlock(graph, nodes, src[:n_src], slot, n_src, thr, cnt, k, seed)
+
+
+class _CsrBlockMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x_src, block, mode):
+        lib = _lib.load()
+        x_src = x_src.contiguous().float()
+        feat = x_src.shape[1]
+        g, targets, m = block.graph, block.targets, block.m
+        width = 2 * feat if mode == _lib.CSR_SAMPLE_SELF["concat"] else feat
+        y = _f32(x_src, m, width)
+        thr = torch.empty(m, device=x_src.device, dtype=torch.int64)
+        cnt = torch.empty(m, device=x_src.device, dtype=torch.int32)
+        _call(lib, "dp_csr_block_mean_fwd", x_src.data_ptr(), feat, *_csr_index_args(g)[0], _lib.ptr(targets),
+              block.slot.data_ptr(), block.n_src, y.data_ptr(), width, thr.data_ptr(), cnt.data_ptr(), m, g.n, feat,
+              block.k, mode, _seed_word(block.seed), _lib.current_stream())
+        ctx.save_for_backward(thr, cnt)
+        ctx.block, ctx.mode, ctx.feat = block, mode, feat
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        thr, cnt = ctx.saved_tensors
+        block, feat = ctx.block, ctx.feat
+        g, dy = block.graph, dy.contiguous()
+        if isinstance(block.nodes, SampledBlock):                        # nested: the outer block's slot IS the targets'
+            tslot = block.nodes.slot
+        elif block.nodes is None:
+            tslot = None
+        else:                                                            # plumbing: one scatter
+            tslot = torch.full((g.n,), -1, device=dy.device, dtype=torch.int32)
+            tslot[block.nodes.long()] = torch.arange(block.m, device=dy.device, dtype=torch.int32)
+        dx = _f32(dy, block.n_src, feat)
+        _call(lib, "dp_csr_block_mean_bwd", dy.data_ptr(), dy.shape[1], *_csr_index_args(g)[1], _lib.ptr(tslot),
+              block.src.data_ptr(), block.n_src, thr.data_ptr(), cnt.data_ptr(), dx.data_ptr(), feat, g.n, feat, ctx.mode,
+              _seed_word(block.seed), _lib.current_stream())
+        return dx, None, None
+
+
+def csr_block_mean(x_src, block, self_mode="none"):
+    """`csr_sample_mean` on the compact rows of a `SampledBlock` (dp_csr_block_mean_fwd / _bwd; MeanAggregator.forward on
+    its unique_nodes_list, aggregators.py:30-63): x_src fp32 [n_src, F] holds the features of `block.src`, the result is
+    [m, F] ('none', 'gcn') or [m, 2F] ('concat'), row r for the block's r-th target, and autograd reaches x_src as
+    [n_src, F].  With x_src = x[block.src] the result has the bits of `csr_sample_mean(x, graph, k, seed, targets)`, and
+    the gradient is the rows `block.src` of that op's (whose other rows are zero): the selection and the order of every
+    sum are the same device code.  A block without targets (or F == 0) returns zeros without a launch.  Not for hipGraph
+    capture: the seed is a kernel argument and would be frozen."""
+    if not isinstance(block, SampledBlock):
+        raise TypeError(f"csr_block_mean: block must be a SampledBlock, got {type(block).__name__}")
+    if self_mode not in _lib.CSR_SAMPLE_SELF:
+        raise ValueError(f"csr_block_mean: self_mode must be 'none', 'gcn' or 'concat', got {self_mode!r}")
+    if not isinstance(x_src, torch.Tensor) or x_src.dim() != 2 or x_src.shape[0] != block.n_src:
+        got = tuple(x_src.shape) if isinstance(x_src, torch.Tensor) else type(x_src).__name__
+        raise ValueError(f"csr_block_mean: expected x_src [n_src, F] with n_src = {block.n_src}, got {got}")
+    feat = x_src.shape[1]
+    if block.m == 0 or feat == 0:
+        return x_src.new_zeros((block.m, 2 * feat if self_mode == "concat" else feat), dtype=torch.float32)
+    _lib.require_gpu_tensor(x_src, "x_src")
+    return _CsrBlockMeanFn.apply(x_src, block, _lib.CSR_SAMPLE_SELF[self_mode])
+
+
 # ----------------------------------------------------------------------------- top-k pooling (DESIGN §4.11)
 class _CsrTopkGatherFn(torch.autograd.Function):
     """x_out = x[perm] * gate[perm] and its gradients to x and gate (dp_csr_topk_gather_fwd / _bwd): one launch each."""

@@ -40,7 +40,9 @@ behind a CsrGraph.
 (dp_csr_gat_*) — and hands the three encoders a weighted container through which its projections train.
 
 `SageConv` / `SageEncoder` are GraphSAGE's mean-aggregator layer and the encoder `SupervisedGraphSage` expects, on either
-container, with the neighbour sample drawn on the device in the launch that takes its mean (dp_csr_sample_mean_*).
+container, with the neighbour sample drawn on the device in the launch that takes its mean (dp_csr_sample_mean_*);
+`NestedSageEncoder` stacks the layers on nested mini-batches, each on the sampled frontier of the one above
+(dp_csr_block_*).
 
 `TopKPooling` is the hard pooling next to DiffPool's soft one (gPool / SAGPool): it keeps the best-scored nodes of every
 graph and returns the induced subgraph as a container of the input's class, built on the device (dp_csr_topk_*) and
@@ -574,9 +576,14 @@ class SageConv(torch.nn.Module):
     `seed`: a Python int in [0, 2^64) fixes the sample; None draws one from torch's CPU generator (no device sync,
     reproducible under `torch.manual_seed`).  The layer samples in training AND in evaluation, as the reference does.
     `nodes`: None for every node (layers stack on the whole graph), or an int32 device tensor of distinct node ids —
-    the last layer of a stack may take the mini-batch.  Nested mini-batch sampling across layers (a sample of the
-    sample's neighbourhood) is out of scope, as are weighted sampling, num_sample > 64 and hipGraph capture of the op
-    (the seed is a kernel argument and would be frozen).  A node without neighbours gets a zero mean, not NaN."""
+    the last layer of a stack may take the mini-batch.
+
+    Nested mini-batches: `block(graph, nodes, seed)` builds the layer's `ops.SampledBlock` on the device —
+    `src`, the targets and everything their samples reach — and `forward_block(x_src, block)` is the same layer on the
+    COMPACT rows x_src [n_src, input_dim], with the bits of forward(x, graph, nodes, seed) at x_src = x[block.src];
+    `nodes` may be the block of the layer above (`NestedSageEncoder` stacks them).  Out of scope: weighted sampling,
+    num_sample > 64, a `src` order with the targets first, and hipGraph capture of either form (the seed is a kernel
+    argument and would be frozen; a block costs one read-back).  A node without neighbours gets a zero mean, not NaN."""
 
     def __init__(self, input_dim, out_dim, num_sample=10, gcn=False, bias=False):
         super().__init__()
@@ -602,6 +609,97 @@ class SageConv(torch.nn.Module):
         h = ops.csr_sample_mean(x, graph, self.num_sample, seed, nodes, "gcn" if self.gcn else "concat",
                                 nodes_checked)
         return torch.relu(hip_linear(h, self.weight, self.bias))
+
+    def _k(self):
+        return _lib.CSR_SAMPLE_ALL if self.num_sample is None else self.num_sample
+
+    def block(self, graph, nodes, seed=None, nodes_checked=False):
+        """The layer's sampled block for the targets `nodes` (an int32 device tensor of distinct ids, None, or the
+        `SampledBlock` of the layer above): `ops.csr_sample_block` at this layer's num_sample."""
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError(f"SageConv.block(graph: CsrGraph or CsrBatch, nodes), got {type(graph).__name__}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # the CPU generator: no device sync
+        return ops.csr_sample_block(graph, nodes, self.num_sample, seed, nodes_checked)
+
+    def forward_block(self, x_src, block):
+        """relu(W [x_i | mean] ) (or the gcn form) for the block's targets from the compact rows x_src
+        [block.n_src, input_dim] -> [m, out_dim]."""
+        if not isinstance(block, ops.SampledBlock):
+            raise TypeError(f"SageConv.forward_block(x_src, block: SampledBlock), got {type(block).__name__}")
+        if block.k != self._k():
+            raise ValueError(f"SageConv.forward_block: the block was sampled with k = {block.k}, the layer has num_sample = "
+                             f"{self.num_sample} (k = {self._k()})")
+        if not isinstance(x_src, torch.Tensor) or x_src.dim() != 2 or tuple(x_src.shape) != (block.n_src, self.input_dim):
+            got = tuple(x_src.shape) if isinstance(x_src, torch.Tensor) else type(x_src).__name__
+            raise ValueError(f"SageConv.forward_block: expected x_src [{block.n_src}, {self.input_dim}], got {got}")
+        if block.m == 0:
+            return x_src.new_zeros((0, self.out_dim), dtype=torch.float32)
+        h = ops.csr_block_mean(x_src, block, "gcn" if self.gcn else "concat")
+        return torch.relu(hip_linear(h, self.weight, self.bias))
+
+
+LAYER_SEED_STEP = 0x9E3779B97F4A7C15                      # layer l samples with (seed + l * this) mod 2^64
+
+
+class NestedSageEncoder(torch.nn.Module):
+    """A stack of `SageConv` layers on nested mini-batches, the reference's Encoder over Encoder for
+    `SupervisedGraphSage`: forward(nodes) -> [len(nodes), embed_dim], every layer evaluated on the sampled frontier of
+    the layer above only, as MeanAggregator.forward calls `features` on its unique_nodes_list (aggregators.py:30-63).
+
+    convs[0] is the innermost layer (it reads `features`), convs[-1] the one whose targets are `nodes`.  forward builds
+    the blocks from the last layer inwards — the block of layer l - 1 has the `src` of layer l's block as its targets —
+    evaluates `features` at the innermost `src` ONLY (a tensor by index_select; an `nn.Embedding` or a callable is called
+    with the LongTensor of ids), then runs the layers outwards with `SageConv.forward_block`.  Layer l samples with
+    (seed + l * 0x9E3779B97F4A7C15) mod 2^64, so the layers draw independently; seed=None draws one from torch's CPU
+    generator.  One 4-byte read-back per layer; no hipGraph capture.  `blocks(nodes, seed)` returns the list
+    (innermost first) for inspection."""
+
+    def __init__(self, features, graph, convs):
+        super().__init__()
+        convs = list(convs)
+        if not convs or not all(isinstance(c, SageConv) for c in convs):
+            raise TypeError("NestedSageEncoder: convs must be a non-empty sequence of SageConv layers")
+        for a, b in zip(convs, convs[1:]):
+            if b.input_dim != a.out_dim:
+                raise ValueError(f"NestedSageEncoder: a layer of input_dim {b.input_dim} follows one of out_dim {a.out_dim}")
+        if not isinstance(graph, (CsrGraph, CsrBatch)):
+            raise TypeError(f"NestedSageEncoder: graph must be a CsrGraph or CsrBatch, got {type(graph).__name__}")
+        if isinstance(features, torch.Tensor) and not isinstance(features, torch.nn.Parameter):
+            self.register_buffer("features", features, persistent=False)
+        elif isinstance(features, (torch.nn.Module, torch.nn.Parameter)) or callable(features):
+            self.features = features
+        else:
+            raise TypeError(f"NestedSageEncoder: features must be a tensor, an nn.Embedding or a callable, got "
+                            f"{type(features).__name__}")
+        self.graph, self.convs, self.embed_dim = graph, torch.nn.ModuleList(convs), convs[-1].out_dim
+
+    @staticmethod
+    def layer_seed(seed, layer):
+        return (seed + layer * LAYER_SEED_STEP) % (1 << 64)
+
+    def blocks(self, nodes, seed):
+        """The layers' blocks, innermost first: blocks[-1] has the targets `nodes`, blocks[l - 1] the targets blocks[l]."""
+        ids = ops.check_target_nodes("NestedSageEncoder", nodes, self.graph.n)
+        if not isinstance(seed, int) or isinstance(seed, bool) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"NestedSageEncoder: seed must be a Python int in [0, 2^64), got {seed!r}")
+        targets = ids.to(device=self.graph.indptr.device, dtype=torch.int32)
+        out = []
+        for layer in range(len(self.convs) - 1, -1, -1):
+            targets = self.convs[layer].block(self.graph, targets, self.layer_seed(seed, layer), nodes_checked=True)
+            out.append(targets)
+        return out[::-1]
+
+    def forward(self, nodes, seed=None):
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # the CPU generator: no device sync
+        blocks = self.blocks(nodes, seed)
+        ids = blocks[0].src.long()
+        f = self.features
+        h = f.index_select(0, ids) if isinstance(f, torch.Tensor) else f(ids)
+        for conv, block in zip(self.convs, blocks):
+            h = conv.forward_block(h, block)
+        return h
 
 
 class SageEncoder(torch.nn.Module):

@@ -1335,6 +1335,59 @@ int dp_csr_topk_gather_fwd(const float* x, int ldx, const float* gate, const int
 int dp_csr_topk_gather_bwd(const float* dy, int lddy, const float* x, int ldx, const float* gate, const int* new_id,
                            float* dx, int lddx, float* dgate, int n, int n_out, int F, void* stream);
 
+/* ------------------------------------------------------------------ N10  sampled frontier blocks: nested GraphSAGE mini-batches
+ * (DESIGN §4.12): MeanAggregator.forward, aggregators.py:30-63, evaluates the layer below on `unique_nodes_list` only,
+ * the union of the sampled neighbourhoods (its lines 48-61).  For the target nodes T = nodes [n_rows] (int32, distinct,
+ * in 0 .. n - 1; NULL with n_rows == n: every node), k and seed, with S(i) EXACTLY the sample of N8:
+ *     src   int32 [n_src]  the ascending, duplicate-free ids of T u U_{i in T} S(i)  (T itself always, in every self mode)
+ *     slot  int32 [n]      slot[src[s]] = s, -1 elsewhere
+ *     thr [n_rows] (64-bit), cnt [n_rows]: as dp_csr_sample_mean_fwd writes them with DP_CSR_SAMPLE_SELF_NONE
+ *     n_src int32 [1] ON THE DEVICE (the host reads it back once, 4 bytes)
+ * The sampled mean then runs on COMPACT rows: x_src [n_src, F] holds the rows src of x, dx_src [n_src, F] their
+ * gradients.  The selection, the compaction and the order of every sum are the code of N8 (dp_csr_sample_body.h), so with
+ * x_src = x[src] the forward gives the bits of dp_csr_sample_mean_fwd(x, nodes = T), and the backward the rows src of
+ * dp_csr_sample_mean_bwd's dx (whose other rows are zero).  The targets may be another block's src: that is the nested
+ * form, and that block's slot then serves as tslot.
+ * Indices built on the device are compared before they are used: a target id and a stored column against n, a slot
+ * against n_src before x_src is read through it (out of range: the term is 0), src[s] against n, a fill position
+ * against cap.  tslot's values index thr, cnt and dy and are the caller's (dp_csr_block_build's slot is below its n_src
+ * by construction).  Every refusal (a NULL or misaligned pointer — thr 8-byte, the workspace 16-byte —, an ld below its
+ * width, a negative count, n_rows > n, n_src > n, n_rows != n without nodes, k outside 1 .. DP_CSR_SAMPLE_MAX_K and not
+ * DP_CSR_SAMPLE_ALL, a self_mode that is none of the three, cap or the workspace too small) comes before any launch;
+ * n_rows == 0 (n_src == 0 in the backward), n == 0 or F == 0 returns without one.  No atomics; a second run gives the
+ * same bits.
+ *
+ * dp_csr_block_plan (host only, aggregators.py:30-63): plan_out[DP_CSR_BLOCK_PLAN_INTS] = { flags per compaction chunk
+ * (256), chunks of n nodes, steps of the one-workgroup scan (256 chunks each, a carry between them), the smallest cap
+ * (min(n, n_rows (k + 1)); n under DP_CSR_SAMPLE_ALL), workgroups of the mark launch (4 target rows each), of the count
+ * and of the fill launch (one per chunk), of the forward (4 rows each), of the backward at n_src = the smallest cap (4
+ * rows each), 64-column passes of the forward, 256-column passes of the backward }, answered by the function the
+ * launchers act on. */
+#define DP_CSR_BLOCK_PLAN_INTS 11
+int dp_csr_block_plan(int n_rows, int n, int F, int k, int* plan_out);
+/* Workspace of dp_csr_block_build on n nodes (aggregators.py:30-63): one int per chunk of 256 nodes, and the total. */
+size_t dp_csr_block_workspace_bytes(int n);
+/* The block of MeanAggregator.forward's unique_nodes_list, aggregators.py:30-63.  FIVE launches whatever n_rows and n:
+ * zero the flags (they live in slot); mark (one wavefront per target row runs N8's selection and stores 1 at the node and
+ * at every selected column); count per chunk; one workgroup scans the counts; fill (src ascending, the flags turned into
+ * slot in place).  slot [n], src [cap], n_src [1], thr [n_rows], cnt [n_rows] OVERWRITTEN; cap >= min(n, n_rows (k + 1)),
+ * or n under DP_CSR_SAMPLE_ALL (n_src arrives as min(count, cap)).  No workgroup waits for another. */
+int dp_csr_block_build(const int* indptr, const int* indices, const int* nodes, int n_rows, int n, int k, long seed,
+                       int* slot, int* src, int cap, int* n_src, unsigned long long* thr, int* cnt, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* MeanAggregator.forward on the block's rows, aggregators.py:30-63: dp_csr_sample_mean_fwd with every gathered id, the
+ * self row included, sent through slot.  x_src [n_src, F] at ldx >= F; y [n_rows, F | 2F], thr, cnt OVERWRITTEN (cnt by
+ * self_mode's rule).  One launch. */
+int dp_csr_block_mean_fwd(const float* x_src, int ldx, const int* indptr, const int* indices, const int* nodes,
+                          const int* slot, int n_src, float* y, int ldy, unsigned long long* thr, int* cnt, int n_rows,
+                          int n, int F, int k, int self_mode, long seed, void* stream);
+/* Its backward, aggregators.py:30-63: one wavefront per src row s walks the transposed list of j = src[s] exactly as
+ * dp_csr_sample_mean_bwd does.  tslot int32 [n]: the TARGETS' slot (tslot[nodes[r]] = r, -1 elsewhere; NULL: every node
+ * its own target row).  EVERY row of dx_src [n_src, F] at lddx >= F OVERWRITTEN.  One launch. */
+int dp_csr_block_mean_bwd(const float* dy, int lddy, const int* indptr_t, const int* indices_t, const int* tslot,
+                          const int* src, int n_src, const unsigned long long* thr, const int* cnt, float* dx_src,
+                          int lddx, int n, int F, int self_mode, long seed, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
